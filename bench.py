@@ -9,15 +9,21 @@ slice is block-matched instead of the reference's PROCESS_EVENT_NUM = 10000):
     block matching -> LM refinement + culling -> window policy -> fusion -> clean -> regularisation.
 All events are staged in HBM before the timed region starts.  The stream is STATIONARY (SURVEY.md section 8(d):
 20 Mev/s per camera = 200 k events per tick, whatever --steps is): a periodic scene seen from a rig in uniform motion.
+Up to LOOP_TICKS warm-up + timed ticks are generated; a longer one-GPU run loops a LOOP_TICKS segment of that stream
+(benchlib/points.py looped_workload, as the `sustained` point does), so set-up time does not grow with --steps.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 With N GPUs the job maps N x K ticks of one stream, K per GPU (weak scaling): ticks are dealt round-robin and the
 ranks all-gather their frames (esvo_amd/dist.py), or, with ESVO_SHARD_MODE=band, every tick is split over the GPUs.
 
-Prints ONE JSON line on rank 0 (see the task contract), including `roofline` for the dominant
-kernel and `cpu_baseline` (the CPU oracle timed on the host cores, N=1 only).
+Prints ONE JSON line on rank 0 (see the task contract).  A plain run sets up, warms up, times K ticks and prints the
+headline (`value`, `ms_per_step`, per-kernel means and the `roofline` of the dominant kernel from the committed profile).
+--full adds the legs that take runs of their own: `sustained`, the reference-faithful ticks, `band_share`, `tick_share`,
+`cpu_baseline`, `parity` (N=1) and `band_mode` (N>1); --extras (implies --full) the heavy secondary points.
+--dump-outputs DIR writes the DepthMap after the last timed tick (and, on one GPU, that tick's new depth points) as
+float64 .npy files: the same arguments give the same inputs, so two builds can be compared output for output.
 """
 import argparse
 import json
@@ -35,26 +41,35 @@ from esvo_amd import lib  # noqa: E402
 # (re-exported: tools/ and tests/ address these through `bench.`)
 from benchlib.baselines import check_against_oracle, cpu_baseline, cpu_baseline_reference, parity_vs_reference_node  # noqa: E402,F401
 from benchlib.multigpu import band_share, selftest, self_launch, tick_share  # noqa: E402,F401
-from benchlib.points import extra_operating_points, reference_faithful_points, sustained_point  # noqa: E402,F401
+from benchlib.points import extra_operating_points, looped_workload, reference_faithful_points, sustained_point  # noqa: E402,F401
 from benchlib.roofline import (TRAFFIC_NOTE, algorithmic_bytes, attach_measured_clock, committed_profile, profile_figures,  # noqa: E402,F401
                                roofline_rows, whole_tick_valu)
-from benchlib.workload import (HBM_PEAK_GBS, HIST_S, KERNEL_NAMES, KERNEL_SYMBOLS, TICK_S, VALU_PEAK_INST_S, WORKLOADS, make_workload,  # noqa: E402,F401
-                               map_sha1, run_single, shift_events)
+from benchlib.workload import (HBM_PEAK_GBS, HIST_S, KERNEL_NAMES, KERNEL_SYMBOLS, TICK_S, VALU_PEAK_INST_S, WORKLOADS, dump_outputs,  # noqa: E402,F401
+                               make_workload, map_sha1, run_single, shift_events)
+
+# ticks of synthetic stream every run generates at least (a seeded stream's noise events are drawn over its whole duration:
+# every run up to this length sees the same events) and a one-GPU run at most: a longer one loops a segment this long
+LOOP_TICKS = 40
 
 
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=20)
+    ap.add_argument("--steps", type=int, default=20, help="timed ticks (per GPU in the weak-scaling mode)")
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--workload", default="dsec640x480", choices=sorted(WORKLOADS))
     ap.add_argument("--events-per-tick", type=int, default=0, help="cap on block-matched events per tick (0 = all)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also every leg beside the headline (sustained point, reference-faithful ticks, band / tick-share projections, "
+                         "CPU baselines, parity; the band mode at N > 1): about a minute; a plain run times the headline only")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write the DepthMap after the last timed tick (and the tick's new depth points) to DIR/<name>.npy, float64")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: no cpu_baseline block")
     ap.add_argument("--no-extras", action="store_true",
-                    help="the headline line only: no sustained point, no reference-faithful ticks, no band-share projection")
+                    help="with --full: no sustained point, no reference-faithful ticks, no band / tick-share projection, no band mode")
     ap.add_argument("--extras", action="store_true",
-                    help="also the heavy secondary points (346x260 throughput, closed loop, 1280x720 stress stream, PCIe-inclusive "
-                         "ingest): minutes; the default run keeps to what the driver's time budget allows")
+                    help="--full and also the heavy secondary points (346x260 throughput, closed loop, 1280x720 stress stream, "
+                         "PCIe-inclusive ingest): minutes")
     ap.add_argument("--no-band-share", action="store_true", help="skip the band-mode projection block (8 and 16 logical shards on this GPU)")
     ap.add_argument("--no-tick-share", action="store_true",
                     help="skip the tick-interleaved projection block (rank 0 of a world-8 run on this GPU, the other ranks' frames pre-recorded)")
@@ -68,10 +83,15 @@ def main():
                     help="N-GPU plumbing check in < 30 s instead of the benchmark: who is there (rank, device, bus id), the RCCL the library "
                          "resolved, one all-gather round trip, and the DepthMap SHA-1 of both N-GPU modes against the one-GPU run")
     ap.add_argument("--no-parity", action="store_true",
-                    help="skip the `parity` block of the line (oracle equality of the first timed tick; IoU / RMSE against the reference node)")
+                    help="with --full: skip the `parity` block of the line (oracle equality of the first timed tick; IoU / RMSE against "
+                         "the reference node)")
     ap.add_argument("--sustained-ticks", type=int, default=1600,
-                    help="ticks of the sustained operating point (the headline workload looped for >= 2 s of wall time); 0 skips it")
+                    help="with --full: ticks of the sustained operating point (the headline workload looped for >= 2 s of wall time); "
+                         "0 skips it")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    args.full = args.full or args.extras
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         raise SystemExit(self_launch(args.gpus))
@@ -124,10 +144,15 @@ def main():
         # weak scaling: K timed (and Wm warm-up) ticks PER GPU in the tick-interleaved mode; the band mode splits every tick
         per_gpu = world if (world > 1 and shard_mode == "tick" and not strong) else 1
         n_ticks = (K + Wm) * per_gpu
-        # (at least 40 ticks whatever N is: the seeded stream -- its noise events are drawn over the whole duration -- is then the
-        #  same for an N-rank run and the one-rank run it is compared with, and serves the sustained point's 40-tick segment too)
-        rig, stream, p, ticks = make_workload(args.workload, max(n_ticks, 40), args.events_per_tick,
-                                              r01_scene=args.r01_scene, share=(rank, dist.barrier) if dist else None)
+        # (at least LOOP_TICKS ticks whatever N is: the seeded stream -- its noise events are drawn over the whole duration -- is then
+        #  the same for an N-rank run and the one-rank run it is compared with, and serves the sustained point's segment too)
+        looped, passes = None, None
+        if world == 1 and n_ticks > LOOP_TICKS and not args.timed_ingest and not args.r01_scene:
+            # generating n_ticks x 10 ms of stream costs ~0.1 s of numpy per tick: loop the first LOOP_TICKS instead
+            rig, stream, p, ticks, looped, passes = looped_workload(args.workload, n_ticks, args.events_per_tick, base_ticks=LOOP_TICKS)
+        else:
+            rig, stream, p, ticks = make_workload(args.workload, max(n_ticks, LOOP_TICKS), args.events_per_tick,
+                                                  r01_scene=args.r01_scene, share=(rank, dist.barrier) if dist else None)
         duration = (stream.t1_ns - stream.t0_ns) * 1e-9
 
         native = (world > 1 and os.environ.get("ESVO_DIST_BACKEND", "nccl") == "nccl"
@@ -160,6 +185,8 @@ def main():
             if args.timed_ingest:
                 r.ts_push_events(0, stream.slice(0, stream.t0_ns, t_first))
                 r.ts_push_events(1, stream.slice(1, stream.t0_ns, t_first))
+            elif looped:
+                looped(r)
             else:
                 r.ts_push_events(0, stream.ev_left)
                 r.ts_push_events(1, stream.ev_right)
@@ -250,7 +277,8 @@ def main():
             ev_rank, mt_rank = n_events, n_matches
         return dict(per_gpu=per_gpu, rig=rig, stream=stream, p=p, ticks=ticks, duration=duration, native=native, comm_note=comm_note,
                     runner=runner, dt=dt, st=st, base=base, n_events=n_events, n_points=n_points, n_matches=n_matches, ksum=ksum,
-                    launches=launches, timed=timed if timed > 0 else launches, ev_rank=ev_rank, mt_rank=mt_rank, shard_mode=shard_mode)
+                    launches=launches, timed=timed if timed > 0 else launches, ev_rank=ev_rank, mt_rank=mt_rank, shard_mode=shard_mode,
+                    loop_passes=passes)
 
     if args.selftest:
         res = selftest(rank, world, local_rank, dist, ranks_seen, rccl)
@@ -273,6 +301,14 @@ def main():
     lap("stream_generation_warmup_timed_region")
     per_gpu, rig, stream, p, ticks, duration = M["per_gpu"], M["rig"], M["stream"], M["p"], M["ticks"], M["duration"]
     native, comm_note, runner, dt, st = M["native"], M["comm_note"], M["runner"], M["dt"], M["st"]
+    if args.dump_outputs:
+        # what a caller of the timed path receives after its last tick: the DepthMap (a collective at N > 1) and the tick's frame
+        arrays = {"depth_map": runner.get_map()}
+        if hasattr(runner, "get_last_frame"):
+            arrays["last_frame"] = runner.get_last_frame()
+        if rank == 0:
+            dump_outputs(args.dump_outputs, arrays)
+        lap("dump_outputs")
     n_events, n_points, n_matches, ksum, launches = M["n_events"], M["n_points"], M["n_matches"], M["ksum"], M["launches"]
     ev_rank, mt_rank = M["ev_rank"], M["mt_rank"]
     nd = p.bm_max_disparity - p.bm_min_disparity + 1
@@ -322,6 +358,8 @@ def main():
                                                         if shard_mode == "tick" else f"{world} GPUs, slots + image row bands")
                                                        + (" (esvo_comm_*: RCCL inside the C library)" if native else " (torch.distributed)")
                                                        + (f"; {comm_note}" if comm_note else "")),
+            "stream": (f"the first {LOOP_TICKS} ticks looped {M['loop_passes']} times (time stamps advanced, trajectory continued)"
+                       if M["loop_passes"] else "generated for the whole run"),
         },
         "kernel_ms": {KERNEL_NAMES[i]: round(float(kavg[i]), 4) for i in range(7)},
         "roofline": {
@@ -371,7 +409,7 @@ def main():
         attach_measured_clock(valu, sclk)
         if "whole_tick" in valu:
             attach_measured_clock(valu["whole_tick"], sclk)
-    if rank == 0 and world == 1 and not args.timed_ingest and args.sustained_ticks > 0 and not args.no_extras:
+    if rank == 0 and world == 1 and args.full and not args.timed_ingest and args.sustained_ticks > 0 and not args.no_extras:
         runner.close()
         runner = None
         try:
@@ -381,7 +419,7 @@ def main():
         except Exception as e:  # noqa: BLE001  (an extra: never takes the headline down with it)
             out["sustained"] = {"error": f"{type(e).__name__}: {e}"}
         lap("sustained")
-    if rank == 0 and world == 1 and not args.no_extras:
+    if rank == 0 and world == 1 and args.full and not args.no_extras:
         try:
             out["other_operating_points"] = reference_faithful_points(local_rank)
             if args.extras:
@@ -389,7 +427,7 @@ def main():
         except Exception as e:  # noqa: BLE001  (extras: the headline line is printed whatever happens here)
             out["other_operating_points"] = {"error": f"{type(e).__name__}: {e}"}
         lap("other_operating_points")
-    if rank == 0 and world == 1 and not args.no_extras and not args.no_band_share and not args.timed_ingest:
+    if rank == 0 and world == 1 and args.full and not args.no_extras and not args.no_band_share and not args.timed_ingest:
         # SURVEY 8(e) on one GPU: what one rank of an 8-GPU band-mode run computes per tick (a projection, labelled as such)
         try:
             if runner is not None:
@@ -399,7 +437,7 @@ def main():
         except Exception as e:  # noqa: BLE001
             out["band_share"] = {"error": f"{type(e).__name__}: {e}"}
         lap("band_share")
-    if rank == 0 and world == 1 and not args.no_extras and not args.no_tick_share and not args.timed_ingest:
+    if rank == 0 and world == 1 and args.full and not args.no_extras and not args.no_tick_share and not args.timed_ingest:
         # the mode whose number lands on the N-GPU line (`value` at --gpus N): what one rank of a world-8 run does per round
         try:
             if runner is not None:
@@ -412,7 +450,7 @@ def main():
             out["tick_share"] = {"error": f"{type(e).__name__}: {e}"}
         lap("tick_share")
     ref_maps = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         try:
             port = cpu_baseline(rig, stream, p, ticks)
         except Exception as e:  # noqa: BLE001  (the line is printed whatever happens to a baseline leg)
@@ -434,7 +472,7 @@ def main():
             ratios[f"gpu_over_port_{pv.get('cores')}_threads"] = out["value"] / pv["value"]
         cb["ratios"] = ratios
         lap("cpu_baseline")
-    if rank == 0 and world == 1 and not args.no_parity:
+    if rank == 0 and world == 1 and args.full and not args.no_parity:
         # parity evidence ON the line: (a) the DepthMap of the first timed tick of THIS workload against the CPU oracle in its
         # GPU-comparable arithmetic, element for element (what --check does); (b) the device against the REFERENCE's own node
         # object (oracle/_ref: esvo_Mapping.cpp compiled unmodified) on the reference-faithful ticks the CPU baseline just ran
@@ -460,7 +498,7 @@ def main():
             par["reference_node"] = None
         out["parity"] = par
         lap("parity")
-    if world > 1 and "ESVO_SHARD_MODE" not in os.environ and not args.strong and not args.check and not args.no_extras:
+    if world > 1 and args.full and "ESVO_SHARD_MODE" not in os.environ and not args.strong and not args.check and not args.no_extras:
         # the OTHER way of using N GPUs, on the same line: every tick of ONE stream split over the ranks -- per-event work
         # by slot, per-cell work by image row band (north_star's image-tile partition), two ncclAllGather per tick (own-slot bytes; [count | kept points]) and the
         # all-gather of the DepthMap bands at read-out.  Strong scaling: K ticks in total, shorter ticks.

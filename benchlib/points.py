@@ -15,7 +15,7 @@ if ROOT not in sys.path:
 
 from esvo_amd import calib, lib, params, rostime, synth  # noqa: E402,F401
 from .roofline import attach_measured_clock, committed_profile, roofline_rows, whole_tick_valu  # noqa: E402
-from .workload import HIST_S, KERNEL_NAMES, TICK_S, WORKLOADS, make_workload, run_single, shift_events  # noqa: E402
+from .workload import HIST_S, KERNEL_NAMES, TICK_S, WORKLOADS, advance_events, make_workload, run_single  # noqa: E402
 
 
 def looped_workload(name, n_ticks, events_cap=0, base_ticks=40):
@@ -44,8 +44,11 @@ def looped_workload(name, n_ticks, events_cap=0, base_ticks=40):
     def stage(dev):
         for cam in (0, 1):
             dev.ts_push_events(cam, hist[cam])
+            buf = np.ascontiguousarray(seg[cam]).copy()
             for k in range(loops):
-                dev.ts_push_events(cam, shift_events(seg[cam], k * T_b) if k else seg[cam])
+                if k:
+                    advance_events(buf, T_b)   # = shift_events(seg[cam], k * T_b); the push has copied the previous pass
+                dev.ts_push_events(cam, buf)
 
     ticks = []
     for k in range(n_ticks):

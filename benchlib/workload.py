@@ -132,3 +132,30 @@ def shift_events(ev, dt_ns):
     return out
 
 
+def advance_events(ev, dt_ns):
+    """shift_events in place, for a contiguous EVENT_DTYPE array (nsec < 1e9): whole seconds plus a carry, no copy and no
+    64-bit division per event -- a long looped bench run stages hundreds of millions of events this way"""
+    ds, dn = divmod(int(dt_ns), 1_000_000_000)
+    words = ev.view(np.uint32).reshape(-1, 4)    # x|y, sec, nsec, polarity|pad
+    sec, nsec = words[:, 1], words[:, 2]
+    nsec += np.uint32(dn)                        # < 2e9: no u32 overflow
+    carry = nsec >= np.uint32(1_000_000_000)
+    np.subtract(nsec, np.uint32(1_000_000_000), out=nsec, where=carry)
+    np.add(sec, np.uint32(ds) + carry, out=sec)
+
+
+DUMP_LIMIT_BYTES = 60 << 20   # (under 64 MB however a megabyte is counted, .npy headers included)
+
+
+def dump_outputs(out_dir, arrays, seed=20250418):
+    """bench.py --dump-outputs: every numeric field of each DepthPoint array as out_dir/<array>_<field>.npy, float64 (vector
+    fields as (n, k) columns).  Over DUMP_LIMIT_BYTES in all, every array keeps the same seeded sample of its rows."""
+    os.makedirs(out_dir, exist_ok=True)
+    row_bytes = {name: 8 * sum(int(np.prod(a.dtype[f].shape or (1,))) for f in a.dtype.names) for name, a in arrays.items()}
+    total = sum(len(a) * row_bytes[name] for name, a in arrays.items())
+    for name, a in arrays.items():
+        if total > DUMP_LIMIT_BYTES:
+            keep = int(len(a) * DUMP_LIMIT_BYTES / total)
+            a = a[np.sort(np.random.default_rng(seed).choice(len(a), keep, replace=False))]
+        for f in a.dtype.names:
+            np.save(os.path.join(out_dir, f"{name}_{f}.npy"), np.ascontiguousarray(a[f], dtype=np.float64))

@@ -15,7 +15,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 def _bench(extra_env, launcher, n, strong=True, check=True, extras=False):
     env = dict(os.environ, **extra_env)
     cmd = launcher + [os.path.join(ROOT, "bench.py"), "--gpus", str(n), "--workload", "upenn346x260", "--steps", "5", "--warmup", "2",
-                      "--no-cpu-baseline"] + ([] if extras else ["--no-extras"]) + (["--check"] if check else []) + (["--strong"] if strong else [])
+                      "--no-cpu-baseline"] + (["--full"] if extras else ["--no-extras"]) + (["--check"] if check else []) + (["--strong"] if strong else [])
     out = subprocess.run(cmd, env=env, cwd=ROOT, capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-2000:]
     line = [l for l in out.stdout.splitlines() if l.startswith("{")][-1]

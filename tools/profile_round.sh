@@ -10,7 +10,7 @@ out=$root/gpurun_out
 mkdir -p $out
 cd /tmp && export TMPDIR=/tmp
 export ESVO_BENCH_STREAM_CACHE=/tmp/esvo_streams   # the seeded stream is generated once for the five runs below
-cmd="python $root/bench.py --steps 20 --warmup 3 --workload $wl --sustained-ticks 0 --no-parity"
+cmd="python $root/bench.py --full --steps 20 --warmup 3 --workload $wl --sustained-ticks 0 --no-parity"
 $cmd --no-extras > $out/${tag}_bench.json 2> $out/${tag}_bench.err
 echo "{\"workload\": \"$wl\", \"bench_cmd\": \"bench.py --steps 20 --warmup 3 (kernel stats), --steps 5 --warmup 2 (counter passes)\"}" > $out/${tag}_meta.json
 rocprofv3 --kernel-trace --stats -d $out/prof_$tag -o ks -- $cmd --no-cpu-baseline --no-extras > /dev/null 2>&1
