@@ -197,3 +197,30 @@ def serialize_event_array(ev, width, height, seq=0, stamp_ns=0, frame_id=""):
         wire[f] = ev[f]
     assert wire.dtype.itemsize == 13
     return head + wire.tobytes()
+
+
+# ---- event-to-event matching (esvo_em_* of include/esvo_hip.h)
+class EmParamsStruct(C.Structure):
+    _fields_ = [
+        ("slice_thickness", C.c_double), ("time_threshold", C.c_double), ("epipolar_threshold", C.c_double),
+        ("ncc_threshold", C.c_double), ("num_event_matching", C.c_int32), ("patch_intensity_threshold", C.c_int32),
+        ("patch_valid_ratio", C.c_double),
+    ]
+
+
+class EmSelectionStruct(C.Structure):
+    _fields_ = [
+        ("t_low_ns", C.c_uint64), ("t_up_ns", C.c_uint64), ("left_first", C.c_uint64), ("right_first", C.c_uint64),
+        ("left_count", C.c_uint32), ("right_count", C.c_uint32), ("n_slices", C.c_uint32), ("pad_", C.c_uint32),
+    ]
+
+
+class EmStatsStruct(C.Structure):
+    _fields_ = [
+        ("events", C.c_uint64), ("right_events", C.c_uint64), ("time_polarity", C.c_uint64), ("epipolar", C.c_uint64),
+        ("patch_ok", C.c_uint64), ("matches", C.c_uint64), ("slices", C.c_uint64), ("ms_match", C.c_float), ("pad_", C.c_float),
+    ]
+
+
+# the pose callback of esvo_map_tick_em: int (*)(void* user, uint64_t t_ns, double T_world_cam[16])
+EM_POSE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_uint64, C.POINTER(C.c_double))

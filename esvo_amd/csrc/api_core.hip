@@ -399,6 +399,7 @@ int esvo_destroy(esvo_handle h) {
   if (h->stream_l1) hipStreamSynchronize(h->stream_l1);
   if (h->stream_b) hipStreamSynchronize(h->stream_b);
   comm_release(h);
+  em_release(h);
   void* ptrs[] = {h->d_lut, h->d_mask, h->d_fixmap[0], h->d_fixmap[1], h->d_sae[0], h->d_sae[1], h->d_raw, h->d_raw1, h->d_fwd_lut[0], h->d_fwd_lut[1], h->d_fwd_off[0], h->d_fwd_off[1],
                   h->d_fwd_src[0], h->d_fwd_src[1], h->d_fwd_val, h->d_ts[0],
                   h->d_ts[1], h->d_ring[0], h->d_ring[1], h->d_obs2[0][0], h->d_obs2[0][1], h->d_obs2[1][0], h->d_obs2[1][1], h->d_obs_tmp,

@@ -230,6 +230,7 @@ int push_begin(esvo_context* h, int cam, size_t n, u64 t_first, PushTicket& tk) 
       const u64 sel_lo = std::min(h->sh_first, h->sh_first_prev);
       oldest_read = std::min(oldest_read, sel_lo > (u64)h->max_ev ? sel_lo - (u64)h->max_ev : 0);
     }
+    oldest_read = std::min(oldest_read, h->em_guard_lo[cam]);  // an event-matching tick's gather (api_em.hip)
     tk.drain = evict_end > oldest_read;
     tk.seq = h->scatter_seq;
   }

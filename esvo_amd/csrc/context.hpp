@@ -147,6 +147,7 @@ struct esvo_context {
   bool back_pending[2] = {false, false};  // back-stage timings / counters of that parity not collected yet
   u32 back_frames[2] = {0, 0};
   double baseline = 0;
+  struct EmState* em = nullptr;  // event-to-event matching (api_em.hip): buffers, last selection and counts; created on first use
 
   // ---- threading contract (include/esvo_hip.h, "Threads"): three groups of calls may run concurrently on one handle --
   // INGEST (esvo_ts_push_events / _event_array / _bag: the ROS spinner's eventsCallback), TRACKER (esvo_track_*) and
@@ -385,6 +386,7 @@ struct esvo_context {
   static constexpr u64 TSQ_ROUND = 1ull << 20;  // events per insertion round = capacity of the overflow list
   u64 sh_first = 0;
   u64 sh_first_prev = 0;  // the selection before it (two ticks may be in flight)
+  u64 em_guard_lo[2] = {~0ull, ~0ull};  // oldest ring event an esvo_map_tick_em gather may still read, per camera (api_em.hip)
   double2* d_reg_ab = nullptr;
   double2* d_reg_cd = nullptr;
   double T_world_frame[16];
@@ -457,6 +459,9 @@ void resident_write_begin(esvo_context* h, int cam);
 int ts_render_pair(esvo_context* h, uint64_t t_ns, uint8_t* const obs_out[2]);
 // api_map.hip
 int flush_pending_tick(esvo_context* h);  // completes a lazily finished tick (see esvo_context::TickState)
+void em_release(esvo_context* h);  // frees the event-matching state of api_em.hip (esvo_destroy)
+u64 lower_bound_sec(const esvo_context* h, int cam, double t);
+u64 ros_time_from_sec(double t);
 int finalize_tick_stats(esvo_context* h);
 int run_bm(esvo_context* h, const esvo_event_t* d_ev, u64 first, u64 cap, int reverse, u32 n, const u32* sel = nullptr);
 int run_order_points(esvo_context* h, u32 max_matches, DevPoint* dst, hipStream_t st = nullptr);

@@ -10,13 +10,13 @@ import subprocess
 
 import numpy as np
 
-from .abi import (DEPTH_POINT_DTYPE, EVENT_DTYPE, MATCH_DTYPE, CalibStruct, ParamsStruct,
-                  StatsStruct)
+from .abi import (DEPTH_POINT_DTYPE, EM_POSE_FN, EVENT_DTYPE, MATCH_DTYPE, CalibStruct, EmSelectionStruct,
+                  EmStatsStruct, ParamsStruct, StatsStruct)
 
 _CSRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc")
 # ESVO_HIP_LIB: another build of the same library (A/B measurements of kernel variants, tools/ab_build.py); never a fallback
 _LIB_PATH = os.environ.get("ESVO_HIP_LIB") or os.path.join(_CSRC, "libesvo_hip.so")
-_SOURCES = ["api_core.hip", "api_ts.hip", "api_map.hip", "api_comm.hip", "api_bag.hip", "api_track.hip", "scan.hip", "kernels_ts.hip", "kernels_bm.hip", "kernels_lm.hip", "kernels_lm_any.hip", "kernels_fuse.hip", "kernels_shard.hip", "kernels_track.hip", "kernels_viz.hip", "kernels_sgm.hip"]
+_SOURCES = ["api_core.hip", "api_ts.hip", "api_map.hip", "api_comm.hip", "api_bag.hip", "api_track.hip", "scan.hip", "kernels_ts.hip", "kernels_bm.hip", "kernels_lm.hip", "kernels_lm_any.hip", "kernels_fuse.hip", "kernels_shard.hip", "kernels_track.hip", "kernels_viz.hip", "kernels_sgm.hip", "api_em.hip", "kernels_em.hip"]
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared",
                "-Wno-unused-value", "-Wno-unused-result", "-ldl"]
 
@@ -34,6 +34,7 @@ SYMBOLS = [
     "esvo_map_get_debug_images", "esvo_map_get_pointcloud_near_xyz", "esvo_voxel_filter_xyz", "esvo_map_save_depth_map",
     "esvo_comm_unique_id", "esvo_comm_rccl_info", "esvo_comm_init", "esvo_comm_init_callbacks", "esvo_comm_destroy", "esvo_comm_owns_next_tick",
     "esvo_comm_tick", "esvo_comm_tick_resident", "esvo_comm_get_stats", "esvo_comm_flush", "esvo_comm_newest_map", "esvo_comm_shard_tick", "esvo_comm_gather_map", "esvo_comm_gather_pointcloud_xyz", "esvo_comm_gather_ts",
+    "esvo_map_match_em", "esvo_map_tick_em", "esvo_map_em_get_selection", "esvo_map_em_stats", "esvo_em_sizes",
 ]
 
 ALL_GATHER_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p)
@@ -201,8 +202,14 @@ def load():
     lib.esvo_comm_gather_map.argtypes = [vp, vp, sz, psz]
     lib.esvo_comm_gather_pointcloud_xyz.argtypes = [vp, vp, sz, psz]
     lib.esvo_comm_gather_ts.argtypes = [vp, i32]
+    lib.esvo_map_match_em.argtypes = [vp, vp, vp, sz, vp, vp, vp, sz, vp, sz, vp, sz, psz]
+    lib.esvo_map_tick_em.argtypes = [vp, vp, i32, u64, u64, EM_POSE_FN, vp]
+    lib.esvo_map_em_get_selection.argtypes = [vp, vp, vp, vp, vp, vp, sz]
+    lib.esvo_map_em_stats.argtypes = [vp, vp]
+    lib.esvo_em_sizes.argtypes = [vp]
+    lib.esvo_em_sizes.restype = None
     for s in SYMBOLS:
-        if s not in ("esvo_default_params", "esvo_last_error", "esvo_abi_sizes", "esvo_bag_last_error"):
+        if s not in ("esvo_default_params", "esvo_last_error", "esvo_abi_sizes", "esvo_bag_last_error", "esvo_em_sizes"):
             getattr(lib, s).restype = C.c_int
     lib.esvo_abi_sizes.argtypes = [vp]
     lib.esvo_abi_sizes.restype = None
@@ -305,6 +312,13 @@ class PinnedEvents:
 def abi_sizes():
     out = (C.c_size_t * 8)()
     load().esvo_abi_sizes(out)
+    return list(out)
+
+
+def em_sizes():
+    """sizeof() of esvo_em_params_t, esvo_em_selection_t, esvo_em_stats_t (esvo_em_sizes)"""
+    out = (C.c_size_t * 4)()
+    load().esvo_em_sizes(out)
     return list(out)
 
 
@@ -461,6 +475,60 @@ class Esvo:
         mt = np.ascontiguousarray(matches, dtype=MATCH_DTYPE)
         T = self._poses if poses is None else np.ascontiguousarray(poses, np.float64).reshape(-1, 16)
         self._ck(self.lib.esvo_map_fuse_matches_naive(self.h, mt.ctypes.data, mt.shape[0], T.ctypes.data, T.shape[0]))
+
+    # ---- event-to-event matching: esvo_MVStereo modes 0 / 2 (EventMatcher)
+    def match_em(self, em, left, slice_begin, slice_count, slice_T, right):
+        """EventMatcher::createMatchProblem + match_all_HyperThread on host arrays (esvo_map_match_em): the matches in the
+        reference's stride-N order.  em: abi.EmParamsStruct; slice_T: (n_slices, 4, 4) T_world of each slice."""
+        l = np.ascontiguousarray(left, dtype=EVENT_DTYPE)
+        r = np.ascontiguousarray(right, dtype=EVENT_DTYPE)
+        b = np.ascontiguousarray(slice_begin, np.uint32)
+        c = np.ascontiguousarray(slice_count, np.uint32)
+        T = np.ascontiguousarray(slice_T, np.float64).reshape(-1, 16)
+        assert len(b) == len(c) == len(T)
+        out = np.zeros(max(int(c.sum()), 1), MATCH_DTYPE)
+        n = C.c_size_t(0)
+        self._ck(self.lib.esvo_map_match_em(self.h, C.addressof(em), l.ctypes.data, l.shape[0], b.ctypes.data, c.ctypes.data,
+                                            T.ctypes.data, len(b), r.ctypes.data, r.shape[0], out.ctypes.data, out.shape[0],
+                                            C.byref(n)))
+        return out[: n.value].copy()
+
+    def tick_em(self, em, mode, t_low_ns, t_up_ns, pose_fn=None):
+        """esvo_MVStereo::MappingAtTime in MVStereoMode 0 (PURE_EVENT_MATCHING) or 2 (EM_PLUS_ESTIMATION) on the staged events
+        (esvo_map_tick_em).  pose_fn(t_ns) -> 4x4 T_world_cam, or None where no pose is known (the slice keeps the identity)."""
+        def trampoline(user, t_ns, out):  # an exception must not unwind through the C frames: report it, use no pose
+            try:
+                T = None if pose_fn is None else pose_fn(int(t_ns))
+                if T is None:
+                    return 0
+                T = np.asarray(T, np.float64).reshape(16)
+                for k in range(16):
+                    out[k] = float(T[k])
+                return 1
+            except BaseException:  # noqa: BLE001
+                import traceback
+                traceback.print_exc()
+                return 0
+        cb = EM_POSE_FN(trampoline)
+        self._ck(self.lib.esvo_map_tick_em(self.h, C.addressof(em), int(mode), int(t_low_ns), int(t_up_ns), cb, None))
+
+    def em_selection(self):
+        """the last tick_em's selection: dict of the esvo_em_selection_t fields + slice table (begin, count, t_ns, T)"""
+        sel = EmSelectionStruct()
+        self._ck(self.lib.esvo_map_em_get_selection(self.h, C.byref(sel), None, None, None, None, 0))
+        ns = int(sel.n_slices)
+        b, c = np.zeros(max(ns, 1), np.uint32), np.zeros(max(ns, 1), np.uint32)
+        t, T = np.zeros(max(ns, 1), np.uint64), np.zeros((max(ns, 1), 16), np.float64)
+        self._ck(self.lib.esvo_map_em_get_selection(self.h, C.byref(sel), b.ctypes.data, c.ctypes.data, t.ctypes.data,
+                                                    T.ctypes.data, max(ns, 1)))
+        d = {k: int(getattr(sel, k)) for k, _ in EmSelectionStruct._fields_ if k != "pad_"}
+        d.update(slice_begin=b[:ns], slice_count=c[:ns], slice_t_ns=t[:ns], slice_T=T[:ns].reshape(-1, 4, 4))
+        return d
+
+    def em_stats(self):
+        s = EmStatsStruct()
+        self._ck(self.lib.esvo_map_em_stats(self.h, C.byref(s)))
+        return s
 
     def tick_resident(self, t_ns, T_world_cam, stamps, poses):
         """render both Time Surfaces at t_ns, take them as the observation, tick: one call"""

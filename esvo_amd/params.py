@@ -25,6 +25,9 @@ CODE_DEFAULTS = dict(
     # esvo_time_surface (ts_parameters.yaml / TimeSurface.cpp:23-30)
     decay_ms=30.0, median_blur_kernel_size=1, ignore_polarity=True, time_surface_mode=0,
     max_event_queue_len=20,
+    # esvo_MVStereo's event matcher (esvo_MVStereo.cpp:81-89) and mode (MVStereoMode, esvo_MVStereo.h:43-50)
+    EM_Slice_Thickness=1e-3, EM_Time_THRESHOLD=5e-5, EM_EPIPOLAR_THRESHOLD=0.5, EM_TS_NCC_THRESHOLD=0.1,
+    EM_NUM_EVENT_MATCHING=3000, EM_PATCH_INTENSITY_THRESHOLD=125, EM_PATCH_VALID_RATIO=0.1, MVStereoMode=3,
 )
 
 # values of the shipped yaml files (esvo_core/cfg/{mapping,mvstereo}/*.yaml), Appendix C
@@ -35,7 +38,9 @@ PRESETS = {
         age_max_range=10, age_vis_threshold=1, fusion_radius=0, FUSION_STRATEGY="CONST_POINTS",
         maxNumFusionFrames=40, maxNumFusionPoints=3000, Denoising=False, SmoothTimeSurface=False,
         Regularization=False, PROCESS_EVENT_NUM=1000, BM_min_disparity=1, BM_max_disparity=40, BM_step=1,
-        BM_ZNCC_Threshold=0.1, node="mvstereo"),
+        BM_ZNCC_Threshold=0.1, EM_Slice_Thickness=0.001, EM_Time_THRESHOLD=0.0005, EM_EPIPOLAR_THRESHOLD=1.0,
+        EM_TS_NCC_THRESHOLD=0.1, EM_NUM_EVENT_MATCHING=3000, EM_PATCH_INTENSITY_THRESHOLD=10, EM_PATCH_VALID_RATIO=0.75,
+        MVStereoMode=3, node="mvstereo"),
     "mapping_upenn": dict(
         patch_size_X=15, patch_size_Y=7, LSnorm="Tdist", Tdist_nu=2.182, Tdist_scale=17.277,
         invDepth_min_range=0.16, invDepth_max_range=1.0, residual_vis_threshold=20, stdVar_vis_threshold=0.15,
@@ -50,7 +55,9 @@ PRESETS = {
         maxNumFusionFrames=40, maxNumFusionPoints=5000, Denoising=True, SmoothTimeSurface=False,
         Regularization=True, RegularizationRadius=5, RegularizationMinNeighbours=8,
         RegularizationMinCloseNeighbours=8, PROCESS_EVENT_NUM=1000, BM_min_disparity=1, BM_max_disparity=40,
-        BM_step=1, BM_ZNCC_Threshold=0.1, node="mvstereo"),
+        BM_step=1, BM_ZNCC_Threshold=0.1, EM_Slice_Thickness=0.001, EM_Time_THRESHOLD=0.0005, EM_EPIPOLAR_THRESHOLD=1.0,
+        EM_TS_NCC_THRESHOLD=0.1, EM_NUM_EVENT_MATCHING=3000, EM_PATCH_INTENSITY_THRESHOLD=10, EM_PATCH_VALID_RATIO=0.75,
+        MVStereoMode=3, node="mvstereo"),
     "mapping_rpg": dict(  # cfg/mapping/mapping_rpg.yaml (`Lnorm` is misspelt there -> code default Tdist)
         patch_size_X=15, patch_size_Y=7, LSnorm="Tdist", Tdist_nu=2.1897, Tdist_scale=16.6397,
         invDepth_min_range=0.2, invDepth_max_range=2.0, residual_vis_threshold=20, stdVar_vis_threshold=0.015,
@@ -150,6 +157,27 @@ def make_params(cfg, rig, node=None, throughput_events=None, **overrides):
             raise KeyError(k)
         setattr(p, k, v)
     return p, bool(c["Denoising"])
+
+
+def make_em_params(cfg, **overrides):
+    """esvo_em_params_t from the EM_* yaml keys (esvo_MVStereo.cpp:81-89; code defaults where a key is absent).
+    EM_PATCH_INTENSITY_THRESHOLD / EM_PATCH_VALID_RATIO are carried but never read, as in the reference."""
+    from .abi import EmParamsStruct
+    c = dict(CODE_DEFAULTS)
+    c.update(cfg)
+    e = EmParamsStruct()
+    e.slice_thickness = float(c["EM_Slice_Thickness"])
+    e.time_threshold = float(c["EM_Time_THRESHOLD"])
+    e.epipolar_threshold = float(c["EM_EPIPOLAR_THRESHOLD"])
+    e.ncc_threshold = float(c["EM_TS_NCC_THRESHOLD"])
+    e.num_event_matching = int(c["EM_NUM_EVENT_MATCHING"])
+    e.patch_intensity_threshold = int(c["EM_PATCH_INTENSITY_THRESHOLD"])
+    e.patch_valid_ratio = float(c["EM_PATCH_VALID_RATIO"])
+    for k, v in overrides.items():
+        if not hasattr(e, k):
+            raise KeyError(k)
+        setattr(e, k, v)
+    return e
 
 
 def load_yaml_cfg(path):

@@ -409,6 +409,99 @@ int esvo_map_push_frame_device(esvo_handle h, const esvo_depth_point_t* d_pts, s
                                size_t m);
 int esvo_map_fuse_async(esvo_handle h);
 
+/* ---- Mapper: event-to-event matching, esvo_MVStereo modes 0 and 2 ------------------------------------------------
+ *
+ * EventMatcher (EventMatcher.cpp), the generalised-time-surface stereo method of [26] (Ieng et al. 2018) that esvo_MVStereo runs
+ * in MVStereoMode 0 (PURE_EVENT_MATCHING) and 2 (EM_PLUS_ESTIMATION).  For every left event: the right events within
+ * +-EM_Time_THRESHOLD / 2 (two std::lower_bound over the right selection, ros::Time roundings included) with the same polarity,
+ * rectified rows within EM_EPIPOLAR_THRESHOLD and x_right < x_left; per survivor depth = b f / (x_left - x_right), warping2 into the
+ * observation pair with T_left_rv = T_obs^-1 T_slice, patchInterpolation2 of a patch_size_X x patch_size_Y patch on each UN-smoothed
+ * Time Surface and zncc_cost; the first candidate with the smallest cost below 1.0 wins; costs above EM_TS_NCC_THRESHOLD are
+ * rejected.  Output order: match_all_HyperThread's NUM_THREAD_MAPPING threads (esvo_params_t.num_threads), event i to thread
+ * i % N, per-thread lists concatenated.  Results are restated in tests/em_restated.py and pinned to it bit for bit; they are not
+ * pinned to the compiled reference.
+ * esvo_match_t of a match: x_left, inv_depth = 1.0 / best_depth (the reference's two roundings), cost = the ZNCC cost, disp =
+ * x_left - x_right of the chosen candidate, event_idx = position in the left array handed in, pose_idx = slice index.
+ * Edge case kept from the reference: with ncc_threshold >= 1 and no candidate below cost 1, candidate 0 is emitted with cost 1.0 and
+ * inv_depth = +inf.
+ * Events off the sensor (x >= width or y >= height) have no rectified coordinate: as in block matching they are skipped -- a left
+ * one keeps its position (event_idx) but gets no candidate, a right one is never a candidate and is not counted in the stats.
+ * More than 2^32 - 1 (event, candidate) pairs past the epipolar test in one call: ESVO_ERR_CAPACITY.
+ * The Time Surfaces are the observation's (esvo_map_set_observation); with SmoothTimeSurface set the handle holds only the smoothed
+ * pair, so these calls return ESVO_ERR_UNSUPPORTED (the reference's EventMatcher reads TS_left_ / TS_right_ un-smoothed). */
+typedef struct esvo_em_params_t {
+  double slice_thickness;             /* EM_Slice_Thickness [s] (code default 1e-3) */
+  double time_threshold;              /* EM_Time_THRESHOLD [s] (5e-5; shipped yaml 5e-4) */
+  double epipolar_threshold;          /* EM_EPIPOLAR_THRESHOLD [px] (0.5; shipped yaml 1.0) */
+  double ncc_threshold;               /* EM_TS_NCC_THRESHOLD (0.1) */
+  int32_t num_event_matching;         /* EM_NUM_EVENT_MATCHING (3000): at most this + 1 events per camera and tick */
+  int32_t patch_intensity_threshold;  /* EM_PATCH_INTENSITY_THRESHOLD: stored by the reference, never read; ignored */
+  double patch_valid_ratio;           /* EM_PATCH_VALID_RATIO: stored by the reference, never read; ignored */
+} esvo_em_params_t;
+
+/* The selection and the slice table of the last esvo_map_tick_em (esvo_map_em_get_selection). */
+typedef struct esvo_em_selection_t {
+  uint64_t t_low_ns, t_up_ns;         /* the bounds handed in */
+  uint64_t left_first, right_first;   /* absolute index of the first selected event in the camera's staged stream */
+  uint32_t left_count, right_count;   /* selected events per camera (0: no tick) */
+  uint32_t n_slices;
+  uint32_t pad_;
+} esvo_em_selection_t;
+
+/* Counts of the last esvo_map_match_em / esvo_map_tick_em at each filter stage (pairs = (left event, right candidate)). */
+typedef struct esvo_em_stats_t {
+  uint64_t events;          /* left events matched (those of the slices) */
+  uint64_t right_events;    /* length of the candidate queue */
+  uint64_t time_polarity;   /* pairs inside the time window with equal polarity */
+  uint64_t epipolar;        /* ... that pass the epipolar test: the pairs whose warp + ZNCC is evaluated */
+  uint64_t patch_ok;        /* ... whose two projections and patches lie inside the images */
+  uint64_t matches;         /* events with a match */
+  uint64_t slices;
+  float ms_match;           /* HIP-event time from the first matching kernel to the last (candidates, scans, pair costs, argmin,
+                               compaction); it includes the host read-back of the pair count between the two candidate passes */
+  float pad_;
+} esvo_em_stats_t;
+
+/* Replaces EventMatcher::createMatchProblem + match_all_HyperThread (EventMatcher.cpp:49-58,184-246) -- the host-array seam a ROS
+ * node calls after its own dataTransferring (esvo_MVStereo.cpp:579-609) and eventSlicingForEM (:1096-1125).
+ * left_ev[n_left]: vEventsPtr_left_; slice s covers slice_count[s] events from slice_begin[s] with the pose slice_T[16 s] (row-major
+ * T_world, the slice's transf_).  As match_all_HyperThread does, the events matched are the sum of the slice counts taken
+ * contiguously from slice_begin[0] (slices of eventSlicingForEM are contiguous).  right_ev[n_right]: vEventsPtr_right_, time-sorted.
+ * The observation (pose and Time Surfaces) is the one set by esvo_map_set_observation; em->time_threshold,
+ * epipolar_threshold, ncc_threshold are read, patch size and num_threads come from esvo_params_t. */
+int esvo_map_match_em(esvo_handle h, const esvo_em_params_t* em, const esvo_event_t* left_ev, size_t n_left,
+                      const uint32_t* slice_begin, const uint32_t* slice_count, const double* slice_T, size_t n_slices,
+                      const esvo_event_t* right_ev, size_t n_right, esvo_match_t* out, size_t cap, size_t* n_out);
+/* The pose of a slice: return 1 and fill T_world_cam (row-major) when a pose is known at t_ns, 0 otherwise (identity is used:
+ * the reference's getPoseAt failure leaves EventSlice::transf_ at its default). */
+typedef int (*esvo_em_pose_fn)(void* user, uint64_t t_ns, double T_world_cam[16]);
+/* Replaces esvo_MVStereo::MappingAtTime in MVStereoMode 0 / 2 on the events staged by esvo_ts_push_events and the current
+ * observation.  Synchronous.
+ *   selection (dataTransferring, esvo_MVStereo.cpp:579-609): t_low_ns / t_up_ns are the oldest / newest stamps of the TS
+ *     history.  Per camera lo = lower_bound(t_low), up = lower_bound(t_up) - 1; events from lo while it != up and fewer than
+ *     num_event_matching + 1 are taken, oldest first (the last event before t_up is never taken).  A camera with no such event
+ *     (up <= lo) means no tick: ESVO_OK, nothing changes.
+ *   slicing (eventSlicingForEM, :1096-1125): floor((t_up - t_low) / slice_thickness) slices at most; a slice runs from its first
+ *     event to lower_bound(ts + thickness) INCLUSIVE (the last event if that is end()); its pose is pose_fn at the stamp of its
+ *     element count / 2; the next slice starts behind it.  More slices than max_poses_per_tick: ESVO_ERR_CAPACITY, no state change.
+ *   matching on the device (esvo_map_match_em).  No match: ESVO_OK and nothing changes (the reference returns, :268-271).
+ *   mode 0 (:273-305): esvo_map_fuse_matches_naive of the matches with the slice poses.
+ *   mode 2 (:445-503): esvo_map_set_poses (slice medians, slice poses), esvo_map_refine with culling, esvo_map_push_frame,
+ *     esvo_map_fuse -- the calls and policies of the BM mapper behind block matching.
+ * The left selection must fit max_events_per_tick (ESVO_ERR_CAPACITY otherwise).  Not on sharded handles.
+ * Ingest may run concurrently (the threading contract above): the selected ranges of both cameras are protected against eviction by
+ * a concurrent push until they have been copied; events inside [t_low, t_up) staged while the call selects them make it fail with
+ * ESVO_ERR_STATE (stage the events up to t_up first). */
+int esvo_map_tick_em(esvo_handle h, const esvo_em_params_t* em, int mode, uint64_t t_low_ns, uint64_t t_up_ns,
+                     esvo_em_pose_fn pose_fn, void* user);
+/* The last tick's selection and slice table: slice s = slice_count[s] events from slice_begin[s] of the left selection, pose
+ * stamp slice_t_ns[s], pose slice_T[16 s].  Each array may be NULL; non-NULL arrays need cap >= sel->n_slices. */
+int esvo_map_em_get_selection(esvo_handle h, esvo_em_selection_t* sel, uint32_t* slice_begin, uint32_t* slice_count,
+                              uint64_t* slice_t_ns, double* slice_T, size_t cap);
+int esvo_map_em_stats(esvo_handle h, esvo_em_stats_t* out);
+/* sizeof() of {esvo_em_params_t, esvo_em_selection_t, esvo_em_stats_t}, 0. */
+void esvo_em_sizes(size_t out[4]);
+
 /* ---- Outputs ------------------------------------------------------------------------ */
 
 /* DepthMap iteration (SmartGrid.h:346-358) as consumed by the publishers

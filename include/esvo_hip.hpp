@@ -6,6 +6,8 @@
 //                                     (esvo_time_surface/src/TimeSurface.cpp:403-425, :52-152)
 //   esvo_core::core::EventBM::resetParameters / createMatchProblem / match_all_HyperThread
 //                                     (esvo_core/src/core/EventBM.cpp:34-78, :269-315)
+//   esvo_core::core::EventMatcher::resetParameters / createMatchProblem / match_all_HyperThread
+//                                     (esvo_core/src/core/EventMatcher.cpp:33-58, :184-246)
 //   esvo_core::core::DepthProblemSolver::solve / pointCulling
 //                                     (esvo_core/src/core/DepthProblemSolver.cpp:28-78, :216-244)
 //   esvo_core::core::DepthFusion (window push + update loop) / DepthMap::clean /
@@ -140,6 +142,67 @@ class EventBM {
   const StampedTimeSurfaceObs* obs_ = nullptr;
   const StampTransformationMap* st_map_ = nullptr;
   const std::vector<Event>* events_ = nullptr;
+};
+
+// esvo_core::core::EventSlice (EventMatcher.h:17-28): indices into the left event vector instead of iterators; the slice
+// covers numEvents events from begin, transf is its row-major T_world pose
+struct EventSlice {
+  size_t begin = 0, numEvents = 0;
+  uint64_t t_median_ns = 0;
+  double transf[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
+};
+
+// esvo_core::core::EventMatcher (EventMatcher.cpp), the [26] matcher of esvo_MVStereo modes 0 and 2, over esvo_map_match_em.
+// patch_size_X / patch_size_Y and NUM_THREAD_MAPPING are the handle's esvo_params_t (patch_size_x/_y, num_threads);
+// patch_intensity_threshold and patch_valid_ratio are kept, as the reference keeps them, and never read.
+class EventMatcher {
+ public:
+  explicit EventMatcher(ContextPtr ctx, double Time_THRESHOLD = 10e-5, double EPIPOLAR_THRESHOLD = 0.5, double TS_NCC_THRESHOLD = 0.1,
+                        size_t patch_intensity_threshold = 125, double patch_valid_ratio = 0.1)
+      : ctx_(std::move(ctx)) {
+    resetParameters(Time_THRESHOLD, EPIPOLAR_THRESHOLD, TS_NCC_THRESHOLD, patch_intensity_threshold, patch_valid_ratio);
+  }
+  void resetParameters(double Time_THRESHOLD, double EPIPOLAR_THRESHOLD, double TS_NCC_THRESHOLD, size_t patch_intensity_threshold,
+                       double patch_valid_ratio) {
+    em_.time_threshold = Time_THRESHOLD;
+    em_.epipolar_threshold = EPIPOLAR_THRESHOLD;
+    em_.ncc_threshold = TS_NCC_THRESHOLD;
+    em_.patch_intensity_threshold = (int32_t)patch_intensity_threshold;
+    em_.patch_valid_ratio = patch_valid_ratio;
+  }
+  const esvo_em_params_t& params() const { return em_; }
+  // vEventPtr_left: the events the slices index (vEventsPtr_left_); vEventPtr_cand: the right selection (vEventsPtr_right_)
+  void createMatchProblem(const StampedTimeSurfaceObs* pTS_obs, const std::vector<EventSlice>* vEventSlice_ptr,
+                          const std::vector<Event>* vEventPtr_left, const std::vector<Event>* vEventPtr_cand) {
+    slices_ = vEventSlice_ptr; left_ = vEventPtr_left; cand_ = vEventPtr_cand;
+    ctx_->check(esvo_map_set_observation(ctx_->handle(), pTS_obs->t_ns, pTS_obs->TS_left, pTS_obs->TS_right, pTS_obs->T_world_cam),
+                "esvo_map_set_observation");
+  }
+  void match_all_HyperThread(std::vector<EventMatchPair>& vEMP) {
+    const size_t ns = slices_->size();
+    std::vector<uint32_t> begin(ns), count(ns);
+    std::vector<double> T(16 * ns);
+    size_t total = 0;
+    for (size_t s = 0; s < ns; ++s) {
+      begin[s] = (uint32_t)(*slices_)[s].begin;
+      count[s] = (uint32_t)(*slices_)[s].numEvents;
+      std::copy((*slices_)[s].transf, (*slices_)[s].transf + 16, T.begin() + 16 * s);
+      total += count[s];
+    }
+    vEMP.resize(total);
+    size_t n = 0;
+    ctx_->check(esvo_map_match_em(ctx_->handle(), &em_, left_->data(), left_->size(), begin.data(), count.data(), T.data(), ns,
+                                  cand_->data(), cand_->size(), vEMP.data(), vEMP.size(), &n),
+                "esvo_map_match_em");
+    vEMP.resize(n);
+  }
+
+ private:
+  ContextPtr ctx_;
+  esvo_em_params_t em_{1e-3, 10e-5, 0.5, 0.1, 3000, 125, 0.1};
+  const std::vector<EventSlice>* slices_ = nullptr;
+  const std::vector<Event>* left_ = nullptr;
+  const std::vector<Event>* cand_ = nullptr;
 };
 
 // esvo_core::core::DepthProblemSolver (NUMERICAL problem type, Tdist norm)

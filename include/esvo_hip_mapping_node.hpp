@@ -47,6 +47,7 @@ class MappingNodeHip {
     obs_.TS_left = ts_[0].data();
     obs_.TS_right = ts_[1].data();
     row_major(node_.TS_obs_.second.tr_.getTransformationMatrix(), obs_.T_world_cam);
+    if (eventMatching(node_, 0)) return;  // esvo_MVStereo in MVStereoMode 0 / 2; every other mode continues below unchanged
     // st_map_: the virtual views of the slice (:585-599)
     st_map_.clear();
     for (auto& kv : node_.st_map_) {
@@ -102,6 +103,64 @@ class MappingNodeHip {
   // msm_ == PURE_BLOCK_MATCHING where the node class has that member (esvo_MVStereo.h:43-50,155); esvo_Mapping has none
   template <class N> static auto pureBlockMatching(const N& n, int) -> decltype((void)n.msm_, bool()) { return (int)n.msm_ == 1; }
   template <class N> static bool pureBlockMatching(const N&, long) { return false; }
+  // MVStereoMode 0 (PURE_EVENT_MATCHING) and 2 (EM_PLUS_ESTIMATION), esvo_MVStereo.cpp:257-305 and :445-503: the node's own
+  // EM selection (dataTransferring, :579-609, fills vEventsPtr_left_ / vEventsPtr_right_) and its eventSlicingForEM
+  // (:1096-1125, getPoseAt per slice), then EventMatcher on the device and, for mode 0, vEMP2vDP + naive propagation of the
+  // window, for mode 2 the refinement, culling, window and fusion of the BM mapper with the slice poses as the pose table.
+  // Only instantiated for a node class with the EM members (esvo_MVStereo).  This branch is compile-checked only: the
+  // harness that runs the reference node (oracle/ref_harness_node.cpp) stages left events alone, so it cannot drive modes
+  // 0 / 2; tests/test_gpu_em.py covers the calls it makes (esvo_map_match_em, esvo_map_tick_em's stage-wise equivalents).
+  template <class N, class S> static S slice_vector(void (N::*)(S&));
+  template <class N>
+  auto eventMatching(N& n, int) -> decltype((void)n.msm_, (void)n.vEventsPtr_right_, (void)n.EM_Time_THRESHOLD_,
+                                            (void)slice_vector(&N::eventSlicingForEM), bool()) {
+    const int msm = (int)n.msm_;
+    if (msm != 0 && msm != 2) return false;
+    decltype(slice_vector(&N::eventSlicingForEM)) slices;
+    n.eventSlicingForEM(slices);
+    auto& L = n.vEventsPtr_left_;
+    auto& Rq = n.vEventsPtr_right_;
+    auto convert = [](const decltype(L)& src, std::vector<Event>& dst) {
+      dst.resize(src.size());
+      for (size_t i = 0; i < src.size(); ++i) {
+        Event& e = dst[i];
+        e.x = src[i]->x; e.y = src[i]->y;
+        e.sec = src[i]->ts.sec; e.nsec = src[i]->ts.nsec;
+        e.polarity = src[i]->polarity ? 1 : 0;
+        e._pad[0] = e._pad[1] = e._pad[2] = 0;
+      }
+    };
+    convert(L, events_);
+    convert(Rq, right_);
+    em_slices_.resize(slices.size());
+    st_map_.clear();
+    for (size_t s = 0; s < slices.size(); ++s) {
+      em_slices_[s].begin = (size_t)(slices[s].it_begin_ - L.begin());
+      em_slices_[s].numEvents = slices[s].numEvents_;
+      em_slices_[s].t_median_ns = slices[s].t_median_.toNSec();
+      row_major(slices[s].transf_.getTransformationMatrix(), em_slices_[s].transf);
+      st_map_.emplace(em_slices_[s].t_median_ns, em_slices_[s].transf);
+    }
+    EventMatcher em(ctx_, n.EM_Time_THRESHOLD_, n.EM_EPIPOLAR_THRESHOLD_, n.EM_TS_NCC_THRESHOLD_, n.EM_patch_intensity_threshold_,
+                    n.EM_patch_valid_ratio_);
+    em.createMatchProblem(&obs_, &em_slices_, &events_, &right_);
+    em.match_all_HyperThread(vEMP_);
+    vdp_.clear();
+    numFusionCount_ = 0;
+    if (vEMP_.empty()) return true;  // :268-271
+    if (msm == 0) {
+      fusion_.naivePropagation(vEMP_, st_map_);
+      return true;
+    }
+    ctx_->check(esvo_map_set_poses(ctx_->handle(), st_map_.stamps_ns.data(), st_map_.T_world_virtual.data(), st_map_.size()),
+                "esvo_map_set_poses");
+    solver_.solve(&vEMP_, &obs_, vdp_);
+    solver_.pointCulling(vdp_, n.stdVar_vis_threshold_, n.cost_vis_threshold_, n.invDepth_min_range_, n.invDepth_max_range_);
+    fusion_.pushFrame(vdp_, st_map_);
+    numFusionCount_ = fusion_.update();
+    return true;
+  }
+  template <class N> static bool eventMatching(const N&, long) { return false; }
   template <class M> static void row_major(const M& T, double out[16]) {
     for (int i = 0; i < 4; ++i)
       for (int j = 0; j < 4; ++j) out[i * 4 + j] = T(i, j);
@@ -116,6 +175,8 @@ class MappingNodeHip {
   StampTransformationMap st_map_;
   std::vector<uint8_t> ts_[2];
   std::vector<Event> events_;
+  std::vector<Event> right_;            // EM: vEventsPtr_right_
+  std::vector<EventSlice> em_slices_;   // EM: the node's slices as indices
   std::vector<EventMatchPair> vEMP_;
   std::vector<DepthPoint> vdp_;
   size_t numFusionCount_ = 0;
