@@ -497,7 +497,7 @@ int own_front(esvo_context* h, uint64_t t_ns, const double T_world_cam[16], cons
   }
   // the LM launch on its own queue (as in the lazy single-GPU tick): the front stages of the next rounds, enqueued while this
   // launch runs, overlap it
-  h->split_now = h->lm_split && !h->prm.denoising;
+  h->split_now = !h->prm.denoising;
   rc = tick_phase0(h, t_ns, pose_t_ns, pose_T, m);
   const bool split = h->split_now;
   h->split_now = false;
@@ -507,7 +507,7 @@ int own_front(esvo_context* h, uint64_t t_ns, const double T_world_cam[16], cons
   // one directly on its queue), behind the LM kernel
   hipStream_t sl = tk.n ? tk.lm_stream : h->stream;
   hipStream_t sn = sl;
-  if (tk.n && split && h->collect_aside && !h->lm_two_now && (sl == h->stream_l || sl == h->stream_l1)) {
+  if (tk.n && split && !h->lm_two_now && (sl == h->stream_l || sl == h->stream_l1)) {
     sn = sl == h->stream_l ? h->stream_l1 : h->stream_l;
     HIPCHK(hipStreamWaitEvent(sn, h->evt[EV_LM1 + h->fpar * EV_FRONT_STRIDE], 0));
   }
@@ -536,8 +536,7 @@ int comm_tick(esvo_context* h, uint64_t t_ns, const double T_world_cam[16], cons
     rc = own_front(h, t_ns, T_world_cam, pose_t_ns, pose_T, m, render);
     if (rc) return rc;
   } else {
-    static const bool ahead = !(esvo_dev_switch("ESVO_COMM_SCATTER_AHEAD") && std::atoi(esvo_dev_switch("ESVO_COMM_SCATTER_AHEAD")) == 0);
-    if (ahead) rc = ts_scatter_ahead(h, t_ns);  // the tick's events reach the SAE now (front stream, idle beside the own tick's LM launch)
+    rc = ts_scatter_ahead(h, t_ns);  // the tick's events reach the SAE now (front stream, idle beside the own tick's LM launch)
     if (rc) return rc;
   }
   RoundTick rt;

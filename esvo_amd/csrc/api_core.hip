@@ -157,29 +157,13 @@ int esvo_create(const esvo_params_t* params, const esvo_calib_t* left, const esv
     CK(hipStreamCreateWithPriority(&h->stream_l1, hipStreamNonBlocking, prio_lo));
     if (const char* ep = esvo_dev_switch("ESVO_LM_PAIR")) h->lm_pair_forced = std::atoi(ep) == 1 ? 1 : (std::atoi(ep) == 0 ? 0 : -1);
     if (const char* eq = esvo_dev_switch("ESVO_LM_QUEUES")) h->lm_queues = std::atoi(eq) == 1 ? 1 : (std::atoi(eq) == 2 ? 2 : 0);
-    if (const char* em = esvo_dev_switch("ESVO_LM_QUEUES_MAX_EVENTS")) h->lm_two_max = (u32)std::strtoul(em, nullptr, 10);  // A/B only
-    const char* e = esvo_dev_switch("ESVO_LM_STREAM");
-    h->lm_split = !(e && std::atoi(e) == 0);
   }
-  if (const char* ef = esvo_dev_switch("ESVO_FRONT_THROTTLE")) h->front_throttle = std::atoi(ef) != 0;
-  if (const char* ea = esvo_dev_switch("ESVO_RESYNC")) h->resync_on = std::atoi(ea) != 0;
-  if (const char* ea = esvo_dev_switch("ESVO_COLLECT_ASIDE")) h->collect_aside = std::atoi(ea) != 0;
   if (const char* et = esvo_dev_switch("ESVO_TIMELINE")) h->tl_on = std::atoi(et) != 0;
   if (const char* el = esvo_dev_switch("ESVO_LOWLAT")) h->lat_mode = std::atoi(el) != 0;
   if (const char* el = esvo_dev_switch("ESVO_LOWLAT_TIMED_EVERY")) h->lat_timed_every = std::max(1, std::atoi(el));
-  if (const char* el = esvo_dev_switch("ESVO_PIPE_BIG_TIMED_EVERY")) h->pipe_big_every = std::max(1, std::atoi(el));
   if (const char* el = esvo_dev_switch("ESVO_REG_SPARSE")) h->reg_sparse_forced = std::atoi(el) != 0 ? 1 : 0;
-  if (const char* el = esvo_dev_switch("ESVO_BACK_PROLOGUE")) h->pro_always = std::atoi(el) != 0;
   if (const char* el = esvo_dev_switch("ESVO_PIPE_TIMED_EVERY")) h->pipe_timed_every = std::max(1, std::atoi(el));
   if (const char* el = esvo_dev_switch("ESVO_LOWLAT_MAX_EVENTS")) h->lat_max_events = (u32)std::strtoul(el, nullptr, 10);
-  if (const char* e1 = esvo_dev_switch("ESVO_ONE_STREAM")) {  // A/B only: the three stages in one queue (no cross-queue hand-offs)
-    if (std::atoi(e1) == 1) {
-      hipStreamDestroy(h->stream_b);
-      h->stream_b = h->stream;
-      h->one_stream = true;
-      h->lm_split = false;
-    }
-  }
   CK(hipStreamCreateWithFlags(&h->stream_t, hipStreamNonBlocking));
   CK(hipStreamCreateWithFlags(&h->stream_i, hipStreamNonBlocking));
   // calibration -> device
@@ -257,20 +241,13 @@ int esvo_create(const esvo_params_t* params, const esvo_calib_t* left, const esv
   CK(dalloc(&h->d_matches2[0], E));
   CK(dalloc(&h->d_matches2[1], E));
   h->d_matches = h->d_matches2[0];
-  {
-    const char* es0 = esvo_dev_switch("ESVO_LM_SPLIT");
-    h->lm_split_mode = es0 ? (std::atoi(es0) == 1 ? 1 : 0) : -1;
-  }
   // (scratch of the split launch: 7 x 16 doubles per match -- only where the launch can be used)
-  if (E > LM_SPLIT_MIN_EVENTS && (h->lm_split_mode == 1 || (h->lm_split_mode < 0 && E >= 400000u))) {
+  if (E >= LM_SPLIT_MIN_EVENTS) {
     // The split LM launch (kernels_lm.hip, LmSplit) executes 10 % fewer vector instructions (3.47e8 against 3.85e8 per launch
     // of the bench workload) but does not shorten the tick (1.40 against 1.38 ms): what it removes are the partially masked
     // instructions of lockstep execution, and the tick is bound by the chip's throughput at its sustained f64 clock.  It is
     // On the 1280x720 stress stream (4.9e5 events, 2.3e5 matches per tick: five times the waves) it does pay: 7.7 against
-    // 8.4 ms per tick (profiles/r03_split_launch_other_workloads.txt).  So: used for launches bounded by >= 400 000 events,
-    // ESVO_LM_SPLIT=0 / 1 forces it off / on.
-    const char* es = esvo_dev_switch("ESVO_LM_SPLIT");
-    h->lm_split_mode = es ? (std::atoi(es) == 1 ? 1 : 0) : -1;
+    // 8.4 ms per tick (profiles/r03_split_launch_other_workloads.txt).  So: used for launches bounded by >= 400 000 events.
     CK(dalloc(&h->d_lm_fvec0, E * 7 * 16));
     CK(dalloc(&h->d_lm_fnorm0, E));
     CK(dalloc(&h->d_lm_meta, E));
@@ -283,12 +260,6 @@ int esvo_create(const esvo_params_t* params, const esvo_calib_t* left, const esv
   CK(dalloc(&h->d_clk, 2 * clk_words(h->max_ev)));
   CK(hipMemset(h->d_clk, 0, sizeof(u64) * 2 * clk_words(h->max_ev)));
   if (const char* ec = esvo_dev_switch("ESVO_CLK_PROBE")) h->clk_probe = std::atoi(ec) != 0;
-  if (const char* ep = esvo_dev_switch("ESVO_LM_PERSIST")) h->lm_persist = std::atoi(ep) != 0;
-  {
-    int cus = 0;
-    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device) == hipSuccess && cus > 0) h->lm_persist_blocks = (u32)cus * 4u * 2u;
-    if (const char* eb = esvo_dev_switch("ESVO_LM_PERSIST_BLOCKS")) h->lm_persist_blocks = (u32)std::max(1, std::atoi(eb));
-  }
   {
     int khz = 0;  // rate of s_memrealtime (wall_clock64): the constant reference clock the probe divides by
     if (hipDeviceGetAttribute(&khz, hipDeviceAttributeWallClockRate, device) != hipSuccess || khz <= 0) khz = 100000;
@@ -430,7 +401,7 @@ int esvo_destroy(esvo_handle h) {
                   (void*)h->sgm.d2key, (void*)h->d_sgm_img[0], (void*)h->d_sgm_img[1], (void*)h->d_sgm_disp, (void*)h->d_sgm_pair, (void*)h->d_sgm_T})
     if (q) hipFree(q);
   if (h->own_stream && h->stream) hipStreamDestroy(h->stream);
-  if (h->stream_b && !h->one_stream) hipStreamDestroy(h->stream_b);
+  if (h->stream_b) hipStreamDestroy(h->stream_b);
   if (h->stream_l) { hipStreamSynchronize(h->stream_l); hipStreamDestroy(h->stream_l); }
   if (h->stream_l1) { hipStreamSynchronize(h->stream_l1); hipStreamDestroy(h->stream_l1); }
   if (h->stream_t) { hipStreamSynchronize(h->stream_t); hipStreamDestroy(h->stream_t); }
@@ -555,7 +526,6 @@ int esvo_set_stream(esvo_handle h, void* hip_stream) {
   HIPCHK(hipStreamSynchronize(h->stream_b));
   if (h->own_stream && h->stream) hipStreamDestroy(h->stream);
   h->stream = reinterpret_cast<hipStream_t>(hip_stream);
-  if (h->one_stream) h->stream_b = h->stream;
   h->own_stream = false;
   return ESVO_OK;
 }

@@ -125,19 +125,16 @@ int run_lm(esvo_context* h, u32 max_matches, int cull, bool dense, hipStream_t s
   a.tsL = h->d_obs[0]; a.tsR = h->d_obs[1];
   a.pose_T = h->d_pose_T; std::memcpy(a.T_world_obs, h->T_world_obs, sizeof(double) * 16);
   a.out_slots = h->d_pt_slots; a.out_flags = flags; a.cull = cull; a.dense = dense ? 1 : 0;
-  const bool split = h->d_lm_fvec0 != nullptr && (h->lm_split_mode == 1 || (h->lm_split_mode < 0 && max_matches >= 400000u));
+  const bool split = h->d_lm_fvec0 != nullptr && max_matches >= esvo::LM_SPLIT_MIN_EVENTS;
   a.split_fvec0 = split ? h->d_lm_fvec0 : nullptr; a.split_fnorm0 = h->d_lm_fnorm0; a.split_meta = h->d_lm_meta;
   a.split_order = h->d_lm_order; a.split_hist = h->d_lm_hist;
   a.pair = pair >= 0 ? pair : (h->lm_pair_forced == 1 && max_matches <= esvo::LM_PAIR_MAX_EVENTS ? 1 : 0);
   a.clk = h->clk_probe ? h->d_clk + (size_t)h->fpar * clk_words(h->max_ev) : nullptr;  // (a block per front parity: api_core.hip)
   if (h->routed && dense) { a.halo_viol = h->d_counters + 10; a.vy0 = h->oband_y0; a.vy1 = h->oband_y1; }
-  // launches of the throughput layout: persistent groups that pull matches from a counter (kernels_lm.hip); counters[11] is
-  // zero at this point (a tick clears its counter row with the pose upload, run_refine clears it itself)
-  if (h->lm_persist && !dense) { a.persist_next = h->d_counters + 11; a.persist_blocks = h->lm_persist_blocks; }
   const bool timed_lm = h->stage_events_on || h->tk[h->fpar].timed_lm;
   if (timed_lm) hipEventRecord(h->evt[EV_LM0 + h->fpar * EV_FRONT_STRIDE], st);
   launch_lm_refine(a, h->dp, h->d_counters + 2, st);
-  // (EV_LM1 is also what the point compaction waits for when it runs on the other LM queue -- collect_aside)
+  // (EV_LM1 is also what the point compaction waits for when it runs on the other LM queue: tick_phase0)
   if (timed_lm || h->tk[h->fpar].cnt_stream != st) hipEventRecord(h->evt[EV_LM1 + h->fpar * EV_FRONT_STRIDE], st);
   HIPCHK(hipGetLastError());
   return ESVO_OK;
@@ -161,7 +158,6 @@ int run_order_points(esvo_context* h, u32 max_matches, DevPoint* dst, hipStream_
 }
 int run_refine(esvo_context* h, u32 max_matches, int cull, DevPoint* dst) {
   HIPCHK(hipMemsetAsync(h->d_counters + 2, 0, sizeof(u32), h->stream));  // n_solved (a tick zeroes all counters at once)
-  HIPCHK(hipMemsetAsync(h->d_counters + 11, 0, sizeof(u32), h->stream));  // the persistent LM layout's work counter
   int rc = run_lm(h, max_matches, cull, false);
   if (rc) return rc;
   return run_order_points(h, max_matches, dst);
@@ -395,8 +391,7 @@ int run_fuse(esvo_context* h, int par, const double* T_world_obs, bool naive) {
     // "staging buffer / pose table free again": recorded at the END of this back stage, not here between two dependent launches
     // (~5 us each); who waits for them -- the front stage two ticks on -- comes long after either point
     tail_ev[0] = d.ev_a;
-    if (d.tail_b) tail_ev[1] = d.ev_b;
-    else if (d.ev_b >= 0) HIPCHK(hipEventRecord(h->evt[d.ev_b], sb));
+    tail_ev[1] = d.ev_b;
   } else {
     launch_upload_words(host, dtab, sizeof(u32) * (3 * (size_t)nf + 1), sb);
   }
@@ -863,9 +858,6 @@ int tick_phase0(esvo_context* h, uint64_t t_ns, const uint64_t* pose_t_ns, const
     // a small tick that overlaps the previous one (esvo_map_tick's lazy path): host-paced -- one tick in pipe_timed_every is timed
     tk.timed = h->pipe_seq % h->pipe_timed_every == 0u;
     h->pipe_seq++;
-  } else if (h->pipe_now && !h->sharded && !h->comm && !h->tl_on && n > h->lat_max_events) {
-    tk.timed = h->pipe_big_seq % h->pipe_big_every == 0u;
-    h->pipe_big_seq++;
   }
   tk.timed_lm = tk.timed;
   h->stage_events_on = tk.timed;  // (esvo_map_tick's scope switches it back on)
@@ -876,9 +868,9 @@ int tick_phase0(esvo_context* h, uint64_t t_ns, const uint64_t* pose_t_ns, const
   // table buffer) was last read by the back stage two ticks ago.
   // (For the ordinary tick this device-side wait is only a throttle: the tick writes parity buffers that are released by events of
   // their own -- EV_STG, EV_POSE, the collected EV_CNT -- and the host never runs more than two back stages ahead.  Off since
-  // round 5 (ESVO_FRONT_THROTTLE=1 restores it): it ties every front stage to the END of a back stage, which is what makes a
-  // lagging back chain stay behind -- see pipeline_resync.  Sharded ticks keep it: their frame goes straight into the ring.)
-  if (h->sharded || h->front_throttle) HIPCHK(hipStreamWaitEvent(h->stream, h->evt[EV_RG1 + h->par * EV_BACK_STRIDE], 0));
+  // round 5: it ties every front stage to the END of a back stage, which is what makes a lagging back chain stay behind -- see
+  // pipeline_resync.  Sharded ticks keep it: their frame goes straight into the ring.)
+  if (h->sharded) HIPCHK(hipStreamWaitEvent(h->stream, h->evt[EV_RG1 + h->par * EV_BACK_STRIDE], 0));
   if (tk.timed) hipEventRecord(h->evt[EV_T0 + h->fpar * EV_FRONT_STRIDE], h->stream);
   const u32* sel = nullptr;
   if (h->prm.denoising && n && !h->routed) {
@@ -907,10 +899,10 @@ int tick_phase0(esvo_context* h, uint64_t t_ns, const uint64_t* pose_t_ns, const
       HIPCHK(hipEventRecord(h->evt[EV_A1 + h->fpar * EV_FRONT_STRIDE], h->stream));
       // launches in the latency-bound (wide) layout alternate between the two LM queues; the split launch's scratch and
       // the throughput layout (which fills the chip by itself) stay on one
-      const bool split_scratch = h->d_lm_fvec0 != nullptr && (h->lm_split_mode == 1 || (h->lm_split_mode < 0 && n >= 400000u));
+      const bool split_scratch = h->d_lm_fvec0 != nullptr && n >= esvo::LM_SPLIT_MIN_EVENTS;
       if (h->ema_lm_ms > 0.f && h->ema_back_ms > 0.f)
         h->lm_two_on = h->ema_lm_ms > (h->lm_two_on ? 0.7f : 0.9f) * h->ema_back_ms;  // (context.hpp: round 6's thresholds)
-      const bool two = (h->lm_queues == 2 || (h->lm_queues == 0 && h->lm_two_on)) && n <= h->lm_two_max && !split_scratch;
+      const bool two = (h->lm_queues == 2 || (h->lm_queues == 0 && h->lm_two_on)) && n <= esvo::LM_TWO_QUEUES_MAX_EVENTS && !split_scratch;
       h->lm_two_now = two;
       sl = (two && h->fpar) ? h->stream_l1 : h->stream_l;
       HIPCHK(hipStreamWaitEvent(sl, h->evt[EV_A1 + h->fpar * EV_FRONT_STRIDE], 0));
@@ -925,7 +917,7 @@ int tick_phase0(esvo_context* h, uint64_t t_ns, const uint64_t* pose_t_ns, const
     // ~40 us of small dependent launches at the head of the stream that paces the pipeline.
     // (only while ticks overlap -- the previous one is still pending: a tick that is waited for gains nothing from it and would pay
     //  one more cross-queue hand-off)
-    if (h->collect_aside && h->split_now && !tk.lat && h->tick_pending && (sl == h->stream_l || sl == h->stream_l1) && !h->lm_two_now)
+    if (h->split_now && !tk.lat && h->tick_pending && (sl == h->stream_l || sl == h->stream_l1) && !h->lm_two_now)
       tk.cnt_stream = sl == h->stream_l ? h->stream_l1 : h->stream_l;
     tk.lm_pair = lm_pair_policy(h, n);
     // (the layout policy's feedback is the LM launch time: sampled ticks aside, whenever it explores or tries the other layout)
@@ -1109,7 +1101,6 @@ static int pipeline_resync(esvo_context* h, float wait_ms, double now_ms) {
   esvo_context::Resync& r = h->resync;
   if (r.last_ms > 0.0) { const float dt = (float)(now_ms - r.last_ms); r.period_ema = r.period_ema > 0.f ? 0.8f * r.period_ema + 0.2f * dt : dt; }
   r.last_ms = now_ms;
-  if (!h->resync_on) return ESVO_OK;
   if (r.check_in > 0 && --r.check_in == 0)   // did the last attempt shorten the tick?  if not, the back chain IS the pace: stop trying
     r.cooldown = (r.period_ema > 0.93f * r.period_before) ? 5000u : 50u;
   if (r.cooldown > 0) { --r.cooldown; r.streak = 0; return ESVO_OK; }
@@ -1158,10 +1149,9 @@ int tick_phase2(esvo_context* h, int fp) {
   if (!h->sharded) {  // now that the size is known: exact ring space, frame copied behind the fusion that may still read it
     rc = window_reserve(h, tk.points, &tk.off);
     if (rc) return rc;
-    if (tk.lat || h->pro_always) {  // the copy rides on run_fuse's first launch (context.hpp, DeferredCopies)
+    if (tk.lat) {  // the copy rides on run_fuse's first launch (context.hpp, DeferredCopies)
       h->pro = esvo_context::DeferredCopies();
       h->pro.active = true;
-      h->pro.tail_b = tk.lat;
       h->pro.a_src = h->d_stage[fp]; h->pro.a_dst = h->d_win + tk.off; h->pro.a_bytes = sizeof(DevPoint) * tk.points;
       h->pro.ev_a = EV_STG + fp * EV_FRONT_STRIDE;
       if (tk.gather && tk.points) {
@@ -1255,7 +1245,7 @@ extern "C" int esvo_map_tick(esvo_handle h, uint64_t t_ns, const uint64_t* pose_
   }
   const bool prev = h->tick_pending;
   const int prev_fp = h->fpar;
-  h->split_now = h->lm_split && !h->prm.denoising;
+  h->split_now = !h->prm.denoising;
   h->lat_now = h->lat_mode && !prev;
   h->pipe_now = h->lat_mode && prev;
   int rc = tick_phase0(h, t_ns, pose_t_ns, pose_T, m);

@@ -12,8 +12,10 @@
 
 #define ESVO_WAVE 64
 
-// A/B and test switches (ESVO_LM_PAIR, ESVO_FUSE_TILE_CAP, ...; tools/README.md lists them) are read from the environment ONLY
-// when ESVO_DEV_SWITCHES=1 is set as well: a deployed library ignores stray variables.  tests/conftest.py and the tools set it.
+// Test and measurement switches -- they force a choice the default policy makes at run time (ESVO_LM_PAIR), a small capacity
+// that exercises an overflow path (ESVO_FUSE_TILE_CAP) or a measurement (ESVO_TIMELINE); tools/README.md lists them -- are read
+// from the environment ONLY when ESVO_DEV_SWITCHES=1 is set as well: a deployed library ignores stray variables.
+// tests/conftest.py and the tools set it.
 #include <cstdlib>
 #include <cstring>
 inline const char* esvo_dev_switch(const char* name) {
@@ -348,16 +350,12 @@ struct LmArgs {
   // (non-null selects the guarded kernels)
   u32* halo_viol = nullptr;
   int vy0 = 0, vy1 = 0;
-  // the persistent narrow layout (kernels_lm.hip, lm_refine_persist_kernel): a zeroed work counter (non-null selects it for
-  // launches of the throughput layout) and the number of workgroups the chip holds
-  u32* persist_next = nullptr;
-  u32 persist_blocks = 0;
 };
 constexpr u32 CLK_XCDS = 8, CLK_SAMPLES = 16, CLK_SCRATCH = 32, CLK_STRIDE = 65;
 inline size_t clk_words(u32 max_ev) { return CLK_SCRATCH + 2 * ((size_t)max_ev / 64 + 2); }
 constexpr u32 LM_PAIR_MAX_EVENTS = 10000u;       // launches bounded by more events never use the pair layout (2 waves per match)
 constexpr u32 LM_TWO_QUEUES_MAX_EVENTS = 40000u;  // = LM_WIDE_MAX (kernels_lm.hip): launches that use the wide layout
-constexpr u32 LM_SPLIT_MIN_EVENTS = 40000u;  // launches bounded by fewer events use the wide layout (LM_WIDE_MAX), never the split
+constexpr u32 LM_SPLIT_MIN_EVENTS = 400000u;  // launches bounded by at least this many events use the split launch (kernels_lm.hip, LmSplit)
 void launch_lm_refine(const LmArgs& a, const DevParams& p, u32* n_solved, hipStream_t s);
 void launch_compact_points(const DevPoint* slots, const u32* flags, const u32* prefix, const u32* n_in,
                            u32 max_n, DevPoint* out, hipStream_t s);

@@ -60,7 +60,6 @@ struct esvo_context {
   // long dependent chains -- drains.  Used for launches in the latency-bound (wide) layout; everything the stage writes
   // (d_pt_slots / d_pt_flags / d_pt_prefix / the scan scratch, besides the buffers listed above) exists once per parity.
   hipStream_t stream_l1 = nullptr;
-  bool collect_aside = true;   // one LM queue in use: a tick's compaction + counters go to the other one (api_map.hip, tick_phase0)
   bool lm_two_now = false;     // this tick's LM launch alternates between the two queues
   // Whether the second queue pays depends on what else the tick holds: where the LM launch is much longer than the fusion
   // stage (346x260, no regulariser: 0.37 ms against 0.12) two launches in flight raise the rate by 18 %; where the two are
@@ -74,18 +73,13 @@ struct esvo_context {
   int lm_queues = 0;              // 0 auto, 1 never, 2 always
   float ema_lm_ms = 0.f, ema_back_ms = 0.f;
   bool lm_two_on = false;
-  u32 lm_two_max = esvo::LM_TWO_QUEUES_MAX_EVENTS;  // launches bounded by more events stay on one queue
-  bool lm_split = true;           // ESVO_LM_STREAM=0: everything of the front stage on `stream`
-  bool one_stream = false;       // ESVO_ONE_STREAM=1 (A/B): stream_b aliases stream
   // ESVO_TIMELINE=1 (tools/regime_probe.py): when every stage of every tick ran, collected from the HIP events as they complete
   bool tl_on = false;
   hipEvent_t tl_ref = nullptr;
   std::vector<std::array<float, 8>> tl_front;
   std::vector<std::array<float, 4>> tl_back;
-  // the pipeline's way back from its slow operating point (api_map.hip, pipeline_resync); ESVO_RESYNC=0 (A/B) switches it off
-  bool resync_on = true;
+  // the pipeline's way back from its slow operating point (api_map.hip, pipeline_resync)
   struct Resync { double last_ms = 0; float period_ema = 0, period_before = 0; u32 streak = 0, cooldown = 0, check_in = 0; bool lm_wait_back = false; } resync;
-  bool front_throttle = false;   // ESVO_FRONT_THROTTLE=1 (A/B): an unsharded tick's front stage waits for the back stage two ticks ago (api_map.hip; the default until round 4)
   bool split_now = false;         // set by esvo_map_tick around its front stage: only the lazy tick path splits
   // Latency mode (round 6, api_map.hip): a tick that arrives while nothing of the previous one is pending -- the caller reads every
   // tick's result before it hands in the next, as the ROS node does -- has nothing to overlap with.  Its LM launch stays in the
@@ -107,19 +101,14 @@ struct esvo_context {
                                   // phase of such a tick is waited for by the exchange that follows it)
   // Overlapping SMALL ticks (at most lat_max_events events; two in flight, nobody waits) are paced by the host: ~45 runtime calls per
   // tick, a third of them event records.  They sample their stage timings one tick in pipe_timed_every; the throughput path (larger
-  // ticks, paced by the LM kernel) keeps recording every tick.
+  // ticks, paced by the LM kernel) keeps recording every tick: sampling one in four measured -0.5 % on one box and +0.3 % on
+  // another, a four-way A/B with the one-launch back prologue nothing at all (profiles/r06_throughput_ab.txt).
   u32 pipe_seq = 0;
   u32 pipe_timed_every = 4;       // ESVO_PIPE_TIMED_EVERY (A/B; 1 = every tick)
-  u32 pipe_big_seq = 0;
-  u32 pipe_big_every = 1;         // ESVO_PIPE_BIG_TIMED_EVERY (A/B): the same for large overlapping ticks -- the throughput path, paced by the LM
-                                  // queue.  One in four measured -0.5 % on one box and +0.3 % on another, a four-way A/B with the prologue
-                                  // switch nothing at all (profiles/r06_throughput_ab.txt): every tick stays timed there
   u32 lat_timed_every = 31;       // ESVO_LOWLAT_TIMED_EVERY (A/B; 1 = every tick)
   u32* cnt_row_host = nullptr;    // latency mode: where the tick's point compaction leaves the counter row (null: a copy follows)
   bool cnt_row_sent = false;
   int reg_sparse_forced = -1;     // ESVO_REG_SPARSE (A/B): the regulariser's sparse-map layout never (0) / always (1); -1: by the element count
-  bool pro_always = false;        // ESVO_BACK_PROLOGUE=1 (A/B): overlapping ticks open their back stage with the one-launch prologue too (neutral:
-                                  // profiles/r06_throughput_ab.txt; the path that has run for four rounds stays)
   bool match_by_index = false;    // latency mode: this tick's match list is d_own_w (indices into d_match_slots), not d_matches
   bool gather_guard[2] = {false, false};  // the solver-slot buffers of that parity are read by a back stage's first launch (EV_STG releases them)
   bool stage_events_on = true;    // false while a tick whose stage timings are not sampled is being enqueued (api_map.hip)
@@ -131,8 +120,6 @@ struct esvo_context {
     bool active = false;
     const void* a_src = nullptr; void* a_dst = nullptr; size_t a_bytes = 0; int ev_a = -1;  // frame points; event recorded behind it
     const u32* a_flags = nullptr; const u32* a_prefix = nullptr; u32 a_slots = 0;          // gather mode: a_src = the solver slots
-    bool tail_b = false;  // ev_b recorded at the end of the back stage too (a tick that runs alone); else right behind the launch:
-                          // the front stage two ticks on, which overlaps this back stage, waits for the pose table's copy
     const void* b_src = nullptr; void* b_dst = nullptr; size_t b_bytes = 0; int ev_b = -1;  // pose table
   } pro;
   uint8_t* d_obs2[2][2] = {{nullptr, nullptr}, {nullptr, nullptr}};
@@ -230,13 +217,6 @@ struct esvo_context {
   u32* d_lm_hist = nullptr;
   u64* d_clk = nullptr;           // in-run shader-clock probe of the LM kernel (LmArgs::clk, common.hpp); read by esvo_get_stats
   bool clk_probe = true;          // ESVO_CLK_PROBE=0 (A/B only) launches the LM kernel without it
-  // ESVO_LM_PERSIST=1 (A/B): launches of the throughput layout use lm_refine_persist_kernel (kernels_lm.hip).  Bit-identical and
-  // 13 % shorter as a launch (1.24 -> 1.075 ms beside the other stages), but OFF by default: a persistent grid has no draining
-  // tail, and the regulariser -- which runs beside that tail in the pipelined tick -- then takes 0.87 instead of 0.60 ms, so the
-  // back chain paces the tick at 1.6 ms (1.31 at best with a smaller grid; profiles/r05_ab_lm_persist.txt)
-  bool lm_persist = false;
-  u32 lm_persist_blocks = 2048;   // workgroups (= waves) of the persistent layout: two per SIMD
-  int lm_split_mode = -1;         // the split launch: -1 by launch size (>= 400 000 events), 0 never, 1 always (ESVO_LM_SPLIT)
   DevPoint* d_pt_slots = nullptr;   // LM output by slot + keep flags + their scan: alias one of two sets (front parity)
   u32* d_pt_flags = nullptr;
   u32* d_pt_prefix = nullptr;
@@ -534,9 +514,9 @@ struct StageEventsScope {  // stage-timing events off (or on) for the calls of o
 // whether the operations enqueued NOW (renders, a tick's stages) record their stage-timing events (context.hpp, lat_ticks)
 inline bool esvo_stage_timed(const esvo_context* h) {
   if (!h->lat_mode || h->tl_on || (h->comm && !h->sharded)) return true;  // (tick-interleaved ranks: every tick)
-  if (h->tick_pending) {  // overlapping ticks: the small ones are paced by the HOST's enqueueing (pipe_seq); the large ones: pipe_big_*
+  if (h->tick_pending) {  // overlapping ticks: the small ones are paced by the HOST's enqueueing (pipe_seq); the large ones: every tick
     if (h->tk[h->fpar].n && h->tk[h->fpar].n <= h->lat_max_events) return h->pipe_seq % h->pipe_timed_every == 0u;
-    return h->pipe_big_seq % h->pipe_big_every == 0u;
+    return true;
   }
   return h->lat_ticks < 8u || h->lat_ticks % h->lat_timed_every == 0u;
 }

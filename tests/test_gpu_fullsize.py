@@ -154,21 +154,16 @@ def test_hd_tick_equals_oracle():
 
 
 _SWITCH_SETS = [
-    {"ESVO_LM_PERSIST": "1"},                                                       # persistent narrow LM layout
-    {"ESVO_LM_PERSIST": "1", "ESVO_LM_PERSIST_BLOCKS": "300"},                      # ... with fewer groups than matches per pass
-    {"ESVO_COLLECT_ASIDE": "0", "ESVO_RESYNC": "0", "ESVO_FRONT_THROTTLE": "1"},    # round 4's queue discipline
-    {"ESVO_LM_QUEUES": "2"},                                                        # two LM queues whatever the launch size
-    {"ESVO_ONE_STREAM": "1"},                                                       # every stage in one queue
-    {"ESVO_REG_SPARSE": "1", "ESVO_BACK_PROLOGUE": "1", "ESVO_PIPE_BIG_TIMED_EVERY": "4"},   # round 6: the regulariser's sparse-map layout on a
-                                                                                    # dense map, the one-launch back prologue, sampled stage events
+    {"ESVO_REG_SPARSE": "1"},   # the regulariser's sparse-map layout on a dense map
 ]
 
 
 @pytest.mark.parametrize("env_set", _SWITCH_SETS, ids=lambda e: "+".join(f"{k[5:]}={v}" for k, v in e.items()))
 def test_scheduling_switches_change_no_bit(full, env_set):
     """`Scheduling is the library's business and never changes a result` (include/esvo_hip.h): six lazily completed (pipelined)
-    ticks of the benchmarked configuration under the experiment switches that move work between queues or pick another LM layout
-    -- read at esvo_create, only with ESVO_DEV_SWITCHES=1 -- give the DepthMap of the default handle, SHA-1 for SHA-1."""
+    ticks of the benchmarked configuration under the test switches that pick a layout the default policy would not pick here
+    -- read at esvo_create, only with ESVO_DEV_SWITCHES=1 -- give the DepthMap of the default handle, SHA-1 for SHA-1.
+    (The switches that move work between queues take effect on smaller ticks: test_gpu_latency_mode.py.)"""
     import os, subprocess, sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     _, maps = _run(full, eager=False)
@@ -176,7 +171,7 @@ def test_scheduling_switches_change_no_bit(full, env_set):
     code = ("import bench, sys; sys.path.insert(0, 'tests'); import test_gpu_fullsize as T; "
             "full = bench.make_workload('dsec640x480', 6); d, m = T._run(full, eager=False); "
             "print('SHA1', bench.map_sha1(m[-1]), len(m[-1]))")
-    env = dict(os.environ, ESVO_DEV_SWITCHES="1", ESVO_BENCH_STREAM_CACHE="/tmp/esvo_streams_test", **env_set)  # (one generation for the five)
+    env = dict(os.environ, ESVO_DEV_SWITCHES="1", ESVO_BENCH_STREAM_CACHE="/tmp/esvo_streams_test", **env_set)  # (one generation for every set)
     r = subprocess.run([sys.executable, "-c", code], cwd=root, env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
     got = [l.split() for l in r.stdout.splitlines() if l.startswith("SHA1")][-1]

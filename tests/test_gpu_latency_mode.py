@@ -77,14 +77,15 @@ def _sub(env_extra, events):
 def test_latency_path_changes_no_bit():
     """the same call sequence -- ticks waited for and ticks that overlap, mixed -- with the latency path off, on (default), with every
     tick recording its stage events, with the path's event bound below the tick size (lone ticks then keep the three queues and only
-    sample their events) and with the throughput path's A/B switches on top of that: every map read is the same, SHA-1 for SHA-1"""
+    sample their events), with the second LM queue forced on top of that, and with it forced on the default path (the overlapping
+    ticks take it there, small ticks paced by the host): every map read is the same, SHA-1 for SHA-1"""
     events = 3000
     want = _sub({"ESVO_LOWLAT": "0"}, events)
     assert len(set(want[0])) > 4 and want[1] == 24    # the maps do differ from tick to tick; 24 ticks were mapped
     on = _sub({}, events)
     assert on[0] == want[0] and on[1] == want[1]
     for env in ({"ESVO_LOWLAT_TIMED_EVERY": "1", "ESVO_PIPE_TIMED_EVERY": "1", "ESVO_REG_SPARSE": "0"}, {"ESVO_LOWLAT_MAX_EVENTS": "100"},
-                {"ESVO_LOWLAT_MAX_EVENTS": "100", "ESVO_PIPE_BIG_TIMED_EVERY": "4", "ESVO_BACK_PROLOGUE": "1"}):
+                {"ESVO_LOWLAT_MAX_EVENTS": "100", "ESVO_LM_QUEUES": "2"}, {"ESVO_LM_QUEUES": "2"}):
         got = _sub(env, events)
         assert got[0] == want[0] and got[1] == want[1], env
     # with the path off every tick that mapped something is a sample; with it on they are sampled

@@ -1,6 +1,6 @@
 #!/usr/bin/env python
 """What bounds the tick?  One stream, one process, a list of VARIANTS of the headline workload that each remove a known share of
-one stage's work (fewer LM iterations, no regulariser, 2x2 fusion, ...) or change only the scheduling (environment switches
+one stage's work (fewer LM iterations, no regulariser, 2x2 fusion, ...) or drop the in-run clock probe (an environment switch
 read at esvo_create); per variant: ms per tick (median / min of R repeats of N ticks), the per-stage HIP-event times, matches /
 points per tick and the shader clock measured inside the run (esvo_stats_t::clk_*).  The tick's sensitivity to each stage's
 work says which stage(s) it waits for.  usage: python tools/bound_probe.py [workload] [ticks] [repeats] > gpurun_out/bound.json"""
@@ -31,21 +31,7 @@ VARIANTS = [
     ("fusion_2x2", {"fusion_radius": 0}, {}),
     ("no_reg_fusion_2x2", {"regularization": 0, "fusion_radius": 0}, {}),
     ("no_reg_lm_iter5", {"regularization": 0, "lm_max_iteration": 5}, {}),
-    ("lm_stream_off", {}, {"ESVO_LM_STREAM": "0"}),
-    ("one_stream", {}, {"ESVO_ONE_STREAM": "1"}),
-    ("lm_split", {}, {"ESVO_LM_SPLIT": "1"}),
     ("base_again", {}, {}),
-    # two LM launches in flight (the head of tick k+1's fills the tail of tick k's).  (Round 4 also ran it with the fusion stage's
-    # stream confined to compute units of its own -- hipExtStreamCreateWithCUMask, 1.5-4 ms per tick: profiles/r04_bound_probe_*.txt;
-    # that switch is gone from the library.)
-    ("two_lm", {}, {"ESVO_LM_QUEUES": "2", "ESVO_LM_QUEUES_MAX_EVENTS": "100000000"}),
-    ("base_third", {}, {}),
-    # round 6: is the back chain what keeps the persistent LM layout from paying?
-    ("persist", {}, {"ESVO_LM_PERSIST": "1"}),
-    ("persist_no_reg", {"regularization": 0}, {"ESVO_LM_PERSIST": "1"}),
-    ("persist_no_reg_fusion_2x2", {"regularization": 0, "fusion_radius": 0}, {"ESVO_LM_PERSIST": "1"}),
-    ("persist_1536", {}, {"ESVO_LM_PERSIST": "1", "ESVO_LM_PERSIST_BLOCKS": "1536"}),
-    ("base_fourth", {}, {}),
 ]
 
 rig, stream, p, ticks = bench.make_workload(name, N + 6)

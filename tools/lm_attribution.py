@@ -41,7 +41,7 @@ MARKS = [  # (region, first line = the line holding this text); a region lasts u
     ("solver: phase 2 (trust-region test)", "    } else {  // phase 2: trust-region trial at xnew"),
     ("solver: outer loop (DepthProblemSolver.cpp:161-188)", "    if (phase == 0) {\n"),
     ("kernel epilogue (point, culling, store)", "  if (!active || !lead) return;\n  if constexpr (BAND) { if (viol) atomicAdd(a.halo_viol, 1u); }"),
-    ("(other kernels / host)", "// ---- the persistent narrow layout (round 5)"),
+    ("(other kernels / host)", "// counting sort of the slots by the cost of F(x0)"),
 ]
 
 
