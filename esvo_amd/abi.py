@@ -222,5 +222,14 @@ class EmStatsStruct(C.Structure):
     ]
 
 
+# ---- semi-global matching per tick (esvo_sgm_* of include/esvo_hip.h)
+class SgmStatsStruct(C.Structure):
+    _fields_ = [
+        ("events", C.c_uint64), ("on_image", C.c_uint64), ("matched_columns", C.c_uint64), ("disp_ok", C.c_uint64),
+        ("points", C.c_uint64), ("zero_disp", C.c_uint64), ("ms_sgbm", C.c_float), ("ms_points", C.c_float),
+        ("ms_propagate", C.c_float), ("pad_", C.c_float),
+    ]
+
+
 # the pose callback of esvo_map_tick_em: int (*)(void* user, uint64_t t_ns, double T_world_cam[16])
 EM_POSE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_uint64, C.POINTER(C.c_double))

@@ -400,6 +400,7 @@ int esvo_destroy(esvo_handle h) {
                   (void*)h->sgm.vol[2], (void*)h->sgm.vol[3], (void*)h->sgm.vol[4], (void*)h->sgm.vol[5], (void*)h->sgm.d1, (void*)h->sgm.d1b,
                   (void*)h->sgm.d2key, (void*)h->d_sgm_img[0], (void*)h->d_sgm_img[1], (void*)h->d_sgm_disp, (void*)h->d_sgm_pair, (void*)h->d_sgm_T})
     if (q) hipFree(q);
+  for (hipEvent_t e : h->evt_sgm) if (e) hipEventDestroy(e);
   if (h->own_stream && h->stream) hipStreamDestroy(h->stream);
   if (h->stream_b) hipStreamDestroy(h->stream_b);
   if (h->stream_l) { hipStreamSynchronize(h->stream_l); hipStreamDestroy(h->stream_l); }
@@ -457,6 +458,8 @@ int esvo_reset(esvo_handle h) {
   h->lm_pair_n[0] = h->lm_pair_n[1] = 0u;
   h->lm_pair_decisions = 0;
   h->lm_pair_current = -1;
+  h->sgm_disp_valid = false;
+  h->sgm_stats = esvo_sgm_stats_t{};
   h->frames.clear();
   h->n_window_frames = 0;
   std::fill(h->slot_used.begin(), h->slot_used.end(), 0);

@@ -1422,6 +1422,53 @@ extern "C" int esvo_map_fuse_matches_naive(esvo_handle h, const esvo_match_t* ma
   return ESVO_OK;
 }
 
+namespace esvo_host {
+// scratch of the SGM chain and of the SGM modes: allocated on first use, released by esvo_destroy
+static int sgm_alloc(esvo_context* h) {
+  const size_t npx = (size_t)h->W * h->H;
+  if (!h->sgm_ok) {
+    const size_t nvol = (size_t)h->H * (h->W - 48) * 48;
+    uint8_t** planes[4] = {&h->sgm.sobL, &h->sgm.rawL, &h->sgm.sobR, &h->sgm.rawR};
+    for (auto pp : planes) HIPCHK(hipMalloc(reinterpret_cast<void**>(pp), npx));
+    for (int i = 0; i < 6; ++i) HIPCHK(hipMalloc(reinterpret_cast<void**>(&h->sgm.vol[i]), nvol * sizeof(int16_t)));
+    HIPCHK(hipMalloc(reinterpret_cast<void**>(&h->sgm.d1), npx * sizeof(int16_t)));
+    HIPCHK(hipMalloc(reinterpret_cast<void**>(&h->sgm.d1b), npx * sizeof(int16_t)));
+    HIPCHK(hipMalloc(reinterpret_cast<void**>(&h->sgm.d2key), npx * sizeof(u32)));
+    HIPCHK(hipMalloc(reinterpret_cast<void**>(&h->d_sgm_img[0]), npx));
+    HIPCHK(hipMalloc(reinterpret_cast<void**>(&h->d_sgm_img[1]), npx));
+    HIPCHK(hipMalloc(reinterpret_cast<void**>(&h->d_sgm_disp), npx * sizeof(int16_t)));
+    HIPCHK(hipMalloc(reinterpret_cast<void**>(&h->d_sgm_pair), sizeof(u32) * 8 * (size_t)h->max_ev));
+    HIPCHK(hipMalloc(reinterpret_cast<void**>(&h->d_sgm_T), sizeof(double) * 16));
+    for (hipEvent_t& e : h->evt_sgm) HIPCHK(hipEventCreate(&e));
+    h->sgm_ok = true;
+  }
+  return ESVO_OK;
+}
+// the SGM event selection (esvo_Mapping.cpp:541-551, esvo_MVStereo.cpp:612-625): newest first from lower_bound(t), 2 *
+// BM_half_slice_thickness back, at most PROCESS_EVENT_NUM + 1; a refusal changes nothing
+static int sgm_select(esvo_context* h, u64* first_out, u32* n_out) {
+  u64 first = 0;
+  u32 n = 0;
+  std::lock_guard<std::mutex> lr(h->mu_ring);
+  ingest_fence(h, 0);
+  const double t_end = ns_to_sec(h->obs_t_ns);
+  const double t_begin = ns_to_sec(ros_time_from_sec(std::max(0.0, t_end - 2 * h->prm.bm_half_slice_thickness)));
+  const u64 it_end = lower_bound_sec(h, 0, t_end), it_begin = lower_bound_sec(h, 0, t_begin);
+  const u64 staged_end = h->ring_base[0] + h->ts_host[0].size();
+  u64 avail = it_end - it_begin;
+  first = it_end;
+  if (it_end == staged_end && avail > 0) { first = it_end - 1; avail -= 1; }  // end() is skipped (oracle definition)
+  n = (u32)std::min<u64>(avail, (u64)h->prm.process_event_num + 1);
+  if (n > h->max_ev) FAIL(ESVO_ERR_CAPACITY, "more events than max_events_per_tick");
+  if (n && first - (n - 1) < h->ring_reserved[0] - std::min<u64>(h->ring_reserved[0], h->ring_cap))
+    FAIL(ESVO_ERR_STATE, "selected events were already overwritten in the event ring");
+  if (n) { h->sh_first_prev = h->sh_first; h->sh_first = first; }  // the ingest thread's overwrite guard protects this selection like a tick's
+  *first_out = first;
+  *n_out = n;
+  return ESVO_OK;
+}
+}  // namespace esvo_host
+
 // ---- SGM initialisation -----------------------------------------------------------------------
 // Replaces esvo_Mapping::InitializationAtTime (esvo_Mapping.cpp:433-492) with the SGM branch of dataTransferring (:537-552):
 // cv::StereoSGBM on the UN-smoothed Time-Surface pair, the rectified pixels of the newest <= PROCESS_EVENT_NUM + 1 left
@@ -1439,21 +1486,8 @@ extern "C" int esvo_map_init_sgm(esvo_handle h, const uint8_t* ts_left, const ui
   int rc = flush_pending_tick(h);
   if (rc) return rc;
   const size_t npx = (size_t)h->W * h->H;
-  if (!h->sgm_ok) {
-    const size_t nvol = (size_t)h->H * (h->W - 48) * 48;
-    uint8_t** planes[4] = {&h->sgm.sobL, &h->sgm.rawL, &h->sgm.sobR, &h->sgm.rawR};
-    for (auto pp : planes) HIPCHK(hipMalloc(reinterpret_cast<void**>(pp), npx));
-    for (int i = 0; i < 6; ++i) HIPCHK(hipMalloc(reinterpret_cast<void**>(&h->sgm.vol[i]), nvol * sizeof(int16_t)));
-    HIPCHK(hipMalloc(reinterpret_cast<void**>(&h->sgm.d1), npx * sizeof(int16_t)));
-    HIPCHK(hipMalloc(reinterpret_cast<void**>(&h->sgm.d1b), npx * sizeof(int16_t)));
-    HIPCHK(hipMalloc(reinterpret_cast<void**>(&h->sgm.d2key), npx * sizeof(u32)));
-    HIPCHK(hipMalloc(reinterpret_cast<void**>(&h->d_sgm_img[0]), npx));
-    HIPCHK(hipMalloc(reinterpret_cast<void**>(&h->d_sgm_img[1]), npx));
-    HIPCHK(hipMalloc(reinterpret_cast<void**>(&h->d_sgm_disp), npx * sizeof(int16_t)));
-    HIPCHK(hipMalloc(reinterpret_cast<void**>(&h->d_sgm_pair), sizeof(u32) * 8 * (size_t)h->max_ev));
-    HIPCHK(hipMalloc(reinterpret_cast<void**>(&h->d_sgm_T), sizeof(double) * 16));
-    h->sgm_ok = true;
-  }
+  rc = sgm_alloc(h);
+  if (rc) return rc;
   const uint8_t* src[2] = {ts_left, ts_right};
   const uint8_t* img[2];
   for (int cam = 0; cam < 2; ++cam) {
@@ -1469,25 +1503,12 @@ extern "C" int esvo_map_init_sgm(esvo_handle h, const uint8_t* ts_left, const ui
   HIPCHK(hipStreamSynchronize(h->stream_b));  // the DepthMap and the window are rebuilt below
   launch_sgbm(img[0], img[1], h->sgm, h->d_sgm_disp, h->W, h->H, h->stream);
   HIPCHK(hipGetLastError());
+  h->sgm_disp_valid = true;
   // the SGM event selection (esvo_Mapping.cpp:541-551): newest first from lower_bound(t), 2 * BM_half_slice_thickness back
   u64 first = 0;
   u32 n = 0;
-  {
-    std::lock_guard<std::mutex> lr(h->mu_ring);
-    ingest_fence(h, 0);
-    const double t_end = ns_to_sec(h->obs_t_ns);
-    const double t_begin = ns_to_sec(ros_time_from_sec(std::max(0.0, t_end - 2 * h->prm.bm_half_slice_thickness)));
-    const u64 it_end = lower_bound_sec(h, 0, t_end), it_begin = lower_bound_sec(h, 0, t_begin);
-    const u64 staged_end = h->ring_base[0] + h->ts_host[0].size();
-    u64 avail = it_end - it_begin;
-    first = it_end;
-    if (it_end == staged_end && avail > 0) { first = it_end - 1; avail -= 1; }  // end() is skipped (oracle definition)
-    n = (u32)std::min<u64>(avail, (u64)h->prm.process_event_num + 1);
-    if (n > h->max_ev) FAIL(ESVO_ERR_CAPACITY, "more events than max_events_per_tick");
-    if (n && first - (n - 1) < h->ring_reserved[0] - std::min<u64>(h->ring_reserved[0], h->ring_cap))
-      FAIL(ESVO_ERR_STATE, "selected events were already overwritten in the event ring");
-    if (n) { h->sh_first_prev = h->sh_first; h->sh_first = first; }  // the ingest thread's overwrite guard protects this selection like a tick's
-  }
+  rc = sgm_select(h, &first, &n);
+  if (rc) return rc;
   HIPCHK(hipMemsetAsync(h->d_counters, 0, sizeof(u32) * CNT_ROW, h->stream));
   u32 count = 0;
   if (n) {
@@ -1531,6 +1552,177 @@ extern "C" int esvo_map_init_sgm(esvo_handle h, const uint8_t* ts_left, const ui
   h->stats.last_window_frames = (u32)h->n_window_frames;
   *n_points = count;
   return ESVO_OK;
+}
+
+// ---- esvo_MVStereo's PURE_SEMI_GLOBAL_MATCHING mode (MVStereoMode 4, esvo_MVStereo.cpp:311-376) ------------------------------
+namespace esvo_host {
+// Everything behind sgbm_->compute, on h->d_sgm_disp and the n events ev[(first -/+ k) % cap]: the mode's DepthPoints (:329-353),
+// dqvDepthPoints_.push_back + pop to maxNumFusionFrames_ (:357-359), naive_propagation of every frame, newest first, into a new
+// DepthFrame at the observation's pose (:360-361).  The caller has drained the other streams and probed the window ring for n points.
+static int sgm_frame_and_propagate(esvo_context* h, const esvo_event_t* d_ev, u64 first, u64 cap, int reverse, u32 n, u32* count_out) {
+  u32* cnt = h->d_counters + 10;  // four free words of the counter row (common.hpp)
+  HIPCHK(hipMemsetAsync(h->d_counters, 0, sizeof(u32) * CNT_ROW, h->stream));
+  HIPCHK(hipEventRecord(h->evt_sgm[1], h->stream));
+  u32 count = 0;
+  esvo_sgm_stats_t& g = h->sgm_stats;
+  g.events = n; g.on_image = g.matched_columns = g.disp_ok = g.points = g.zero_disp = 0;
+  int rc;
+  if (n) {
+    launch_sgm_tick_points(d_ev, first, cap, reverse, n, h->d_lut, h->d_sgm_disp, h->d_pt_slots, h->d_pt_flags, cnt, h->dp, h->stream);
+    launch_exclusive_scan_u32(h->d_pt_flags, h->d_pt_prefix, h->d_counters + 1, h->d_scan_tmp, n, h->stream);
+    HIPCHK(hipMemcpyAsync(h->d_counters + 0, &n, sizeof(u32), hipMemcpyHostToDevice, h->stream));  // compaction bound (n_in of compact_points), behind the memset above
+    launch_compact_points(h->d_pt_slots, h->d_pt_flags, h->d_pt_prefix, h->d_counters + 0, n, h->d_pts_tmp, h->stream);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(h->evt_sgm[2], h->stream));
+    rc = read_counters(h);  // the one host read of the tick
+    if (rc) return rc;
+    count = h->h_counters[1];
+    g.on_image = h->h_counters[10]; g.matched_columns = h->h_counters[11]; g.disp_ok = h->h_counters[12]; g.zero_disp = h->h_counters[13];
+    g.points = count;
+  } else {
+    HIPCHK(hipEventRecord(h->evt_sgm[2], h->stream));
+  }
+  rc = back_after_front(h);
+  if (rc) return rc;
+  // the frame that leaves at this tick leaves first (push_back + pop_front while size > max == pop while size >= max, then push);
+  // count <= n, for which the caller probed the ring
+  const size_t keep_below = (size_t)std::max(1, h->prm.max_fusion_frames);
+  while (h->n_window_frames && h->n_window_frames >= keep_below) pop_front_frame(h);
+  u32 off;
+  rc = window_reserve(h, count, &off);
+  if (rc) return rc;
+  if (count) HIPCHK(hipMemcpyAsync(h->d_win + off, h->d_pts_tmp, sizeof(DevPoint) * count, hipMemcpyDeviceToDevice, h->stream_b));
+  rc = commit_frame(h, off, count, h->T_world_obs, 1, 0, false);  // dp.updatePose(T_world_cam) of the observation: one pose per frame
+  if (rc) return rc;
+  while (h->n_window_frames > (size_t)h->prm.max_fusion_frames) pop_front_frame(h);
+  const int par = h->par;
+  h->par ^= 1;
+  HIPCHK(hipEventSynchronize(h->evt[EV_RG1 + par * EV_BACK_STRIDE]));
+  collect_back(h, par);
+  rc = run_fuse(h, par, h->T_world_obs, true);
+  if (rc) return rc;
+  HIPCHK(hipStreamSynchronize(h->stream_b));
+  const bool timed = h->back_timed[par];
+  collect_back(h, par);
+  h->committed_t_ns = h->obs_t_ns;
+  g.ms_points = g.ms_propagate = 0.f;
+  if (hipEventElapsedTime(&g.ms_points, h->evt_sgm[1], h->evt_sgm[2]) != hipSuccess) (void)hipGetLastError();
+  if (timed) g.ms_propagate = h->stats.ms_kernel[4];
+  esvo_stats_t& s = h->stats;
+  s.last_events_in = n; s.last_matches = 0; s.last_solved = 0; s.last_points = count;
+  s.total_events_in += n; s.total_points += count;
+  s.last_window_frames = (u32)h->n_window_frames;
+  u32 np = 0;
+  for (auto& f : h->frames) np += f.count;
+  s.last_window_points = np;
+  *count_out = count;
+  return ESVO_OK;
+}
+// the refusals the two calls share; W <= 50: the SGM chain matches the columns x >= numDisparities only
+static int sgm_mode_checks(esvo_context* h) {
+  if (!h->obs_set) FAIL(ESVO_ERR_STATE, "esvo_map_set_observation has not been called (time stamp and pose of the Time-Surface pair)");
+  if (h->sharded) FAIL(ESVO_ERR_STATE, "handle is sharded");
+  if (h->W <= 48 + 2) FAIL(ESVO_ERR_UNSUPPORTED, "image narrower than numDisparities");
+  return ESVO_OK;
+}
+}  // namespace esvo_host
+
+extern "C" int esvo_map_tick_sgm(esvo_handle h, const uint8_t* ts_left, const uint8_t* ts_right, size_t* n_points, int16_t* disp_out) {
+  if (!h) return ESVO_ERR_INVALID_ARG;
+  API_LOCK(h);
+  int rc = sgm_mode_checks(h);
+  if (rc) return rc;
+  const uint8_t* src[2] = {ts_left, ts_right};
+  for (int cam = 0; cam < 2; ++cam)
+    if (!src[cam] && !h->ts_valid[cam]) FAIL(ESVO_ERR_STATE, "no device-resident Time Surface: call esvo_ts_render first");
+  HIPCHK(hipSetDevice(h->device));
+  rc = flush_pending_tick(h);
+  if (rc) return rc;
+  rc = sgm_alloc(h);
+  if (rc) return rc;
+  const u64 sh_first = h->sh_first, sh_first_prev = h->sh_first_prev;
+  u64 first = 0;
+  u32 n = 0;
+  rc = sgm_select(h, &first, &n);
+  if (rc) return rc;
+  // maxNumFusionFrames frames of up to PROCESS_EVENT_NUM + 1 points whatever the fusion strategy: found out HERE whether the ring
+  // takes them (on a copy of the window), before anything changes -- as esvo_map_tick_bm_only does
+  if (window_probe_after_pops(h, (size_t)std::max(1, h->prm.max_fusion_frames), n) != ESVO_OK) {
+    std::lock_guard<std::mutex> lr(h->mu_ring);
+    h->sh_first = sh_first; h->sh_first_prev = sh_first_prev;
+    FAIL(ESVO_ERR_CAPACITY, "PURE_SEMI_GLOBAL_MATCHING window (maxNumFusionFrames frames of up to PROCESS_EVENT_NUM + 1 points) "
+                            "does not fit the fusion window ring: raise max_window_points");
+  }
+  const size_t npx = (size_t)h->W * h->H;
+  const uint8_t* img[2];
+  for (int cam = 0; cam < 2; ++cam) {
+    if (src[cam]) {
+      HIPCHK(hipMemcpyAsync(h->d_sgm_img[cam], src[cam], npx, hipMemcpyHostToDevice, h->stream));
+      img[cam] = h->d_sgm_img[cam];
+    } else {
+      img[cam] = h->d_ts[cam];
+    }
+  }
+  HIPCHK(hipStreamSynchronize(h->stream_l)); HIPCHK(hipStreamSynchronize(h->stream_l1));
+  HIPCHK(hipStreamSynchronize(h->stream_b));  // the DepthMap and the window are rebuilt below
+  HIPCHK(hipEventRecord(h->evt_sgm[0], h->stream));
+  launch_sgbm(img[0], img[1], h->sgm, h->d_sgm_disp, h->W, h->H, h->stream);
+  HIPCHK(hipGetLastError());
+  h->sgm_disp_valid = true;
+  if (disp_out) HIPCHK(hipMemcpyAsync(disp_out, h->d_sgm_disp, npx * sizeof(int16_t), hipMemcpyDeviceToHost, h->stream));
+  u32 count = 0;
+  rc = sgm_frame_and_propagate(h, h->d_ring[0], first, h->ring_cap, 1, n, &count);
+  if (rc) { (void)hipStreamSynchronize(h->stream); return rc; }  // (disp_out and the images are borrowed)
+  HIPCHK(hipStreamSynchronize(h->stream));  // disp_out / the borrowed images (n == 0: nothing else waited for the front stream)
+  h->sgm_stats.ms_sgbm = 0.f;
+  if (hipEventElapsedTime(&h->sgm_stats.ms_sgbm, h->evt_sgm[0], h->evt_sgm[1]) != hipSuccess) (void)hipGetLastError();
+  h->stats.ticks++;
+  if (n_points) *n_points = count;
+  return ESVO_OK;
+}
+
+extern "C" int esvo_map_push_disparity_frame(esvo_handle h, const int16_t* disp16, const esvo_event_t* ev, size_t n, size_t* n_points) {
+  if (!h || (n && !ev)) return ESVO_ERR_INVALID_ARG;
+  API_LOCK(h);
+  int rc = sgm_mode_checks(h);
+  if (rc) return rc;
+  if (n > h->max_ev) FAIL(ESVO_ERR_CAPACITY, "more events than max_events_per_tick");
+  if (!disp16 && !h->sgm_disp_valid) FAIL(ESVO_ERR_STATE, "no disparity image on the device: hand one in, or call esvo_map_tick_sgm / esvo_map_init_sgm first");
+  HIPCHK(hipSetDevice(h->device));
+  rc = flush_pending_tick(h);
+  if (rc) return rc;
+  rc = sgm_alloc(h);
+  if (rc) return rc;
+  const u32 n32 = (u32)n;
+  rc = window_probe_after_pops(h, (size_t)std::max(1, h->prm.max_fusion_frames), n32);
+  if (rc) return rc;
+  HIPCHK(hipStreamSynchronize(h->stream_l)); HIPCHK(hipStreamSynchronize(h->stream_l1));
+  HIPCHK(hipStreamSynchronize(h->stream_b));  // the staging buffers and the ring may still be read by work in flight
+  if (disp16) {
+    HIPCHK(hipMemcpyAsync(h->d_sgm_disp, disp16, (size_t)h->W * h->H * sizeof(int16_t), hipMemcpyHostToDevice, h->stream));
+    h->sgm_disp_valid = true;
+  }
+  if (n) HIPCHK(hipMemcpyAsync(h->d_tick_ev, ev, sizeof(esvo_event_t) * n, hipMemcpyHostToDevice, h->stream));
+  HIPCHK(hipStreamSynchronize(h->stream));  // disp16 / ev are borrowed
+  u32 count = 0;
+  rc = sgm_frame_and_propagate(h, h->d_tick_ev, 0, (u64)h->max_ev, 0, n32, &count);
+  if (rc) return rc;
+  h->sgm_stats.ms_sgbm = 0.f;
+  if (n_points) *n_points = count;
+  return ESVO_OK;
+}
+
+extern "C" int esvo_map_sgm_stats(esvo_handle h, esvo_sgm_stats_t* out) {
+  if (!h || !out) return ESVO_ERR_INVALID_ARG;
+  API_LOCK(h);
+  *out = h->sgm_stats;
+  return ESVO_OK;
+}
+
+extern "C" void esvo_sgm_sizes(size_t out[4]) {
+  out[0] = sizeof(esvo_sgm_stats_t);
+  out[1] = 48;
+  out[2] = out[3] = 0;
 }
 
 // ---- device-resident stage calls: the building blocks of tick-interleaved multi-GPU operation ---------------------

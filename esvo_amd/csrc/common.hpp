@@ -417,6 +417,8 @@ struct SgmScratch {
 void launch_sgbm(const uint8_t* left, const uint8_t* right, const SgmScratch& s, int16_t* disp, int W, int H, hipStream_t st);
 void launch_sgm_points(const esvo_event_t* ring, u64 first, u64 cap, u32 n, const float2* lut, const int16_t* disp, DevPoint* slots,
                        u32* flags, const DevParams& p, hipStream_t st);
+void launch_sgm_tick_points(const esvo_event_t* ev, u64 first, u64 cap, int reverse, u32 n, const float2* lut, const int16_t* disp,
+                            DevPoint* slots, u32* flags, u32* cnt, const DevParams& p, hipStream_t st);
 void launch_sgm_naive(const DevPoint* pts, u32 n, const double* d_T_frame_obs, u32* owner, u32* pair_flags, u32* pair_rank, u32* d_total,
                       u32* scan_tmp, MapCell* map, const DevParams& p, hipStream_t st);
 // kernels_viz.hip

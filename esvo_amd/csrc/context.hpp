@@ -408,6 +408,10 @@ struct esvo_context {
   int16_t* d_sgm_disp = nullptr;
   u32* d_sgm_pair = nullptr;      // [2][4 * max_ev] winner flags / ranks of naive_propagation
   double* d_sgm_T = nullptr;
+  // the per-tick SGM mode (esvo_map_tick_sgm / esvo_map_push_disparity_frame)
+  bool sgm_disp_valid = false;    // d_sgm_disp holds a disparity image
+  hipEvent_t evt_sgm[3] = {nullptr, nullptr, nullptr};  // before / behind the SGM chain, behind the point stage
+  esvo_sgm_stats_t sgm_stats = {};
 
   // debug images (kernels_viz.hip): allocated on first use
   uint8_t* d_viz_bgr = nullptr;

@@ -350,6 +350,68 @@ __global__ void __launch_bounds__(256) sgm_naive_create_kernel(const DevPoint* _
   map_flags(map, p.W * p.H)[cell] = CELL_ALIVE | CELL_GRID;
 }
 
+// ---- esvo_MVStereo's PURE_SEMI_GLOBAL_MATCHING mode (MVStereoMode 4, esvo_MVStereo.cpp:311-376) -------------------------------
+// createEdgeMask(..., true, 0) (:1127-1170) + the DepthPoint loop (:329-353).  NOT the bootstrap's rules: the columns below
+// numDisparities are skipped, there is no inverse-depth range test, and a disparity of exactly 0 is kept (inv_depth 0, p_cam
+// not finite).  Event k of the list = ev[(first -/+ k) % cap] (reverse: the ring, newest first; else a plain array in the
+// caller's order); flags + points in that order (the caller compacts them).
+// cnt[0..3]: events on the image, of those with x >= numDisparities, of those with disp >= 0 (= points), points with disp == 0.
+__global__ void __launch_bounds__(256) sgm_tick_points_kernel(const esvo_event_t* __restrict__ ev, u64 first, u64 cap, int reverse, u32 n,
+                                                              const float2* __restrict__ lut, const int16_t* __restrict__ disp,
+                                                              DevPoint* __restrict__ slots, u32* __restrict__ flags, u32* __restrict__ cnt,
+                                                              int num_disp, DevParams p) {
+  const u32 k = blockIdx.x * blockDim.x + threadIdx.x;
+  bool on_img = false, col_ok = false, keep = false, zero = false;
+  if (k < n) {
+    const esvo_event_t e = ev[(reverse ? first - k : first + k) % cap];
+    if (e.x < p.W && e.y < p.H) {  // an event off the sensor has no rectified coordinate
+      const float2 c = lut[(size_t)e.y * p.W + e.x];
+      const int xc = (int)floor((double)c.x), yc = (int)floor((double)c.y);
+      on_img = xc >= 0 && xc < p.W && yc >= 0 && yc < p.H;
+      col_ok = on_img && xc >= num_disp;  // `if (x < num_disparities_) continue` (:333)
+      if (col_ok) {
+        const double dsp = disp[(size_t)yc * p.W + xc] / 16.0;
+        keep = !(dsp < 0);
+        if (keep) {
+          zero = dsp == 0;
+          const double inv = dsp / p.baseline_f;  // disp / (P(0,0) * baseline), :341
+          DevPoint o;
+          o.row = (u32)xc;  // DepthPoint dp(x, y): the constructor takes (row, col) -- as the reference wrote it (:338)
+          o.col = (u32)yc;
+          o.x[0] = xc * 1.0;
+          o.x[1] = yc * 1.0;
+          cam2World(p.camL, o.x[0], o.x[1], inv, o.p_cam);
+          o.inv_depth = inv;
+          o.scale2 = 0;  // uninitialised memory in the reference (Appendix A-8): zero here, as in the bootstrap
+          o.nu = 0;
+          o.variance = 1e-6;  // update(invDepth, 0) + boundVariance
+          o.residual = 0;
+          o.age = (u64)p.age_thr;
+          o.pose_idx = 0;
+          o.seq = k;
+          slots[k] = o;
+        }
+      }
+    }
+    flags[k] = keep ? 1u : 0u;
+  }
+  // one atomic per wave and counter
+  const unsigned long long b0 = __ballot(on_img), b1 = __ballot(col_ok), b2 = __ballot(keep), b3 = __ballot(zero);
+  if ((threadIdx.x & 63) == 0) {
+    if (b0) atomicAdd(cnt + 0, (u32)__popcll(b0));
+    if (b1) atomicAdd(cnt + 1, (u32)__popcll(b1));
+    if (b2) atomicAdd(cnt + 2, (u32)__popcll(b2));
+    if (b3) atomicAdd(cnt + 3, (u32)__popcll(b3));
+  }
+}
+
+void launch_sgm_tick_points(const esvo_event_t* ev, u64 first, u64 cap, int reverse, u32 n, const float2* lut, const int16_t* disp,
+                            DevPoint* slots, u32* flags, u32* cnt, const DevParams& p, hipStream_t st) {
+  if (!n) return;
+  hipLaunchKernelGGL(sgm_tick_points_kernel, dim3((n + 255) / 256), dim3(256), 0, st, ev, first, cap, reverse, n, lut, disp, slots, flags, cnt,
+                     48, p);
+}
+
 void launch_sgm_points(const esvo_event_t* ring, u64 first, u64 cap, u32 n, const float2* lut, const int16_t* disp, DevPoint* slots,
                        u32* flags, const DevParams& p, hipStream_t st) {
   if (!n) return;

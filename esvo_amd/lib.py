@@ -11,7 +11,7 @@ import subprocess
 import numpy as np
 
 from .abi import (DEPTH_POINT_DTYPE, EM_POSE_FN, EVENT_DTYPE, MATCH_DTYPE, CalibStruct, EmSelectionStruct,
-                  EmStatsStruct, ParamsStruct, StatsStruct)
+                  EmStatsStruct, ParamsStruct, SgmStatsStruct, StatsStruct)
 
 _CSRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc")
 # ESVO_HIP_LIB: another build of the same library (A/B measurements of kernel variants, tools/ab_build.py); never a fallback
@@ -35,6 +35,7 @@ SYMBOLS = [
     "esvo_comm_unique_id", "esvo_comm_rccl_info", "esvo_comm_init", "esvo_comm_init_callbacks", "esvo_comm_destroy", "esvo_comm_owns_next_tick",
     "esvo_comm_tick", "esvo_comm_tick_resident", "esvo_comm_get_stats", "esvo_comm_flush", "esvo_comm_newest_map", "esvo_comm_shard_tick", "esvo_comm_gather_map", "esvo_comm_gather_pointcloud_xyz", "esvo_comm_gather_ts",
     "esvo_map_match_em", "esvo_map_tick_em", "esvo_map_em_get_selection", "esvo_map_em_stats", "esvo_em_sizes",
+    "esvo_map_tick_sgm", "esvo_map_push_disparity_frame", "esvo_map_sgm_stats", "esvo_sgm_sizes",
 ]
 
 ALL_GATHER_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p)
@@ -208,8 +209,13 @@ def load():
     lib.esvo_map_em_stats.argtypes = [vp, vp]
     lib.esvo_em_sizes.argtypes = [vp]
     lib.esvo_em_sizes.restype = None
+    lib.esvo_map_tick_sgm.argtypes = [vp, vp, vp, psz, vp]
+    lib.esvo_map_push_disparity_frame.argtypes = [vp, vp, vp, sz, psz]
+    lib.esvo_map_sgm_stats.argtypes = [vp, vp]
+    lib.esvo_sgm_sizes.argtypes = [vp]
+    lib.esvo_sgm_sizes.restype = None
     for s in SYMBOLS:
-        if s not in ("esvo_default_params", "esvo_last_error", "esvo_abi_sizes", "esvo_bag_last_error", "esvo_em_sizes"):
+        if s not in ("esvo_default_params", "esvo_last_error", "esvo_abi_sizes", "esvo_bag_last_error", "esvo_em_sizes", "esvo_sgm_sizes"):
             getattr(lib, s).restype = C.c_int
     lib.esvo_abi_sizes.argtypes = [vp]
     lib.esvo_abi_sizes.restype = None
@@ -319,6 +325,13 @@ def em_sizes():
     """sizeof() of esvo_em_params_t, esvo_em_selection_t, esvo_em_stats_t (esvo_em_sizes)"""
     out = (C.c_size_t * 4)()
     load().esvo_em_sizes(out)
+    return list(out)
+
+
+def sgm_sizes():
+    """sizeof(esvo_sgm_stats_t), numDisparities, 0, 0 (esvo_sgm_sizes)"""
+    out = (C.c_size_t * 4)()
+    load().esvo_sgm_sizes(out)
     return list(out)
 
 
@@ -528,6 +541,32 @@ class Esvo:
     def em_stats(self):
         s = EmStatsStruct()
         self._ck(self.lib.esvo_map_em_stats(self.h, C.byref(s)))
+        return s
+
+    # ---- semi-global matching per tick: esvo_MVStereo mode 4
+    def tick_sgm(self, ts_left=None, ts_right=None, want_disp=True):
+        """esvo_MVStereo::MappingAtTime in MVStereoMode 4 (PURE_SEMI_GLOBAL_MATCHING) on the staged events and the observation set
+        last (esvo_map_tick_sgm); None = the device-resident Time Surfaces.  Returns (#points, disparity*16 image or None)"""
+        l = None if ts_left is None else np.ascontiguousarray(ts_left, np.uint8)
+        r = None if ts_right is None else np.ascontiguousarray(ts_right, np.uint8)
+        disp = np.empty((self.H, self.W), np.int16) if want_disp else None
+        n = C.c_size_t()
+        self._ck(self.lib.esvo_map_tick_sgm(self.h, _p(l), _p(r), C.byref(n), _p(disp)))
+        return int(n.value), disp
+
+    def push_disparity_frame(self, disp16, ev):
+        """the mode-4 seam behind a node's own StereoSGBM (esvo_map_push_disparity_frame): disp16 (H, W) int16 or None for the
+        device's last SGM result, ev = vEventsPtr_left_SGM_ in the node's order.  Returns the number of points of the frame"""
+        d = None if disp16 is None else np.ascontiguousarray(disp16, np.int16)
+        assert d is None or d.shape == (self.H, self.W)
+        ev = np.ascontiguousarray(ev, dtype=EVENT_DTYPE)
+        n = C.c_size_t()
+        self._ck(self.lib.esvo_map_push_disparity_frame(self.h, _p(d), ev.ctypes.data if len(ev) else None, ev.shape[0], C.byref(n)))
+        return int(n.value)
+
+    def sgm_stats(self):
+        s = SgmStatsStruct()
+        self._ck(self.lib.esvo_map_sgm_stats(self.h, C.byref(s)))
         return s
 
     def tick_resident(self, t_ns, T_world_cam, stamps, poses):

@@ -502,6 +502,59 @@ int esvo_map_em_stats(esvo_handle h, esvo_em_stats_t* out);
 /* sizeof() of {esvo_em_params_t, esvo_em_selection_t, esvo_em_stats_t}, 0. */
 void esvo_em_sizes(size_t out[4]);
 
+/* ---- Mapper: semi-global matching per tick, esvo_MVStereo mode 4 -------------------------------------------------
+ *
+ * esvo_MVStereo::MappingAtTime in MVStereoMode 4, PURE_SEMI_GLOBAL_MATCHING (esvo_MVStereo.cpp:311-376).  It is not the
+ * bootstrap (esvo_map_init_sgm): the two share StereoSGBM and the event selection, and differ in every rule that decides which
+ * points exist.  Per selected event, in the selection's order (createEdgeMask(..., true, 0), :1127-1170, and the loop :329-353):
+ *   (x, y) = floor of the event's rectified coordinate; skipped when that pixel is off the image (an event off the sensor has no
+ *   rectified coordinate and is skipped too); events on the same pixel are NOT merged; skipped when x < 48 (numDisparities);
+ *   disp = D(y, x) / 16.0, skipped when disp < 0.  No inverse-depth range test, no minimum point count; a disparity of exactly 0
+ *   is kept (inv_depth 0, p_cam not finite).
+ * The DepthPoint of a kept event: row = x, col = y (`DepthPoint dp(x, y)`, the reference's own argument order), x = (x, y),
+ * inv_depth = disp / (P(0,0) * baseline), p_cam = cam2World(x, inv_depth), variance 1e-6 (update(inv_depth, 0) + boundVariance),
+ * residual 0, age = age_vis_threshold, the observation's pose; scale2 = nu = 0 (uninitialised memory in the reference).
+ * The frame enters the window even when it is empty, frames leave from the front while there are more than max_fusion_frames,
+ * and DepthFusion::naive_propagation (DepthFusion.cpp:234-327) of every frame, newest first, fills a new DepthFrame at the
+ * observation's pose: every residual is 0, so a cell belongs to the first point that touches it.  A point whose propagated
+ * coordinate is not finite touches no cell.  Nothing is cleaned or regularised.
+ * Checked against the reference's own compiled mode-4 branch through tests/sgm_tick_restated.py. */
+
+/* Counts of the last esvo_map_tick_sgm / esvo_map_push_disparity_frame at each filter, and HIP-event times of its stages. */
+typedef struct esvo_sgm_stats_t {
+  uint64_t events;          /* selected events (the seam: events handed in) */
+  uint64_t on_image;        /* ... on the sensor, with their rectified pixel on the image */
+  uint64_t matched_columns; /* ... with x >= 48 */
+  uint64_t disp_ok;         /* ... with disparity >= 0 */
+  uint64_t points;          /* DepthPoints of the frame (no further test: == disp_ok) */
+  uint64_t zero_disp;       /* points with a disparity of exactly 0 */
+  float ms_sgbm;            /* the StereoSGBM chain (0 for the seam) */
+  float ms_points;          /* point kernel, scan, compaction */
+  float ms_propagate;       /* naive propagation of the window */
+  float pad_;
+} esvo_sgm_stats_t;
+
+/* The whole mode-4 tick on the events staged by esvo_ts_push_events and the observation set last (its stamp and pose:
+ * esvo_map_set_observation).  Selection: dataTransferring's mode-4 branch (esvo_MVStereo.cpp:612-625) -- the walk of
+ * esvo_map_init_sgm: newest first from lower_bound(t_obs) over the last 2 * BM_half_slice_thickness, at most
+ * PROCESS_EVENT_NUM + 1 events.  StereoSGBM (0, 48, 11, 8*11*11, 32*11*11, -1, 0, 11) on the UN-smoothed Time-Surface pair --
+ * ts_left / ts_right: host mono8 W*H, or NULL for the device-resident frames of esvo_ts_render.  n_points (nullable): points of
+ * the new frame.  disp_out (nullable): the W*H int16 disparity image (x16, -16 = none).  Synchronous; one host read-back (the
+ * point count); nothing is allocated after the first call.  esvo_stats_t: ticks, last_events_in, last_points,
+ * last_window_frames, last_window_points as esvo_map_tick_bm_only fills them.
+ * Refused without any change of state: no observation / sharded handle (ESVO_ERR_STATE), W <= 50 (ESVO_ERR_UNSUPPORTED), more
+ * selected events than max_events_per_tick or a window that does not fit the ring (ESVO_ERR_CAPACITY), selected events already
+ * overwritten in the event ring (ESVO_ERR_STATE). */
+int esvo_map_tick_sgm(esvo_handle h, const uint8_t* ts_left, const uint8_t* ts_right, size_t* n_points, int16_t* disp_out);
+/* The seam of that mode for a node that keeps its own StereoSGBM and dataTransferring: everything behind sgbm_->compute.
+ * disp16: the disparity x 16 image (host W*H int16), or NULL for the device's last SGM result (esvo_map_tick_sgm,
+ * esvo_map_init_sgm); ev[n]: vEventsPtr_left_SGM_ in the node's order.  Builds the points, pushes the frame, applies the window
+ * policy and runs the naive propagation at the observation set last.  esvo_map_tick_sgm == selection + StereoSGBM + this. */
+int esvo_map_push_disparity_frame(esvo_handle h, const int16_t* disp16, const esvo_event_t* ev, size_t n, size_t* n_points);
+int esvo_map_sgm_stats(esvo_handle h, esvo_sgm_stats_t* out);
+/* sizeof() of {esvo_sgm_stats_t}, numDisparities (48), 0, 0. */
+void esvo_sgm_sizes(size_t out[4]);
+
 /* ---- Outputs ------------------------------------------------------------------------ */
 
 /* DepthMap iteration (SmartGrid.h:346-358) as consumed by the publishers

@@ -249,6 +249,16 @@ class DepthFusion {
     ctx_->check(esvo_map_fuse_matches_naive(ctx_->handle(), vEMP.data(), vEMP.size(), st_map.T_world_virtual.data(), st_map.size()),
                 "esvo_map_fuse_matches_naive");
   }
+  // esvo_MVStereo's PURE_SEMI_GLOBAL_MATCHING branch behind sgbm_->compute (esvo_MVStereo.cpp:320-361): createEdgeMask + the
+  // DepthPoint loop on vEventsPtr_left_SGM_, the window of maxNumFusionFrames_ frames and naive_propagation of every frame, at the
+  // observation set last.  dispMap: the W*H disparity x 16 image (CV_16S), or nullptr for the device's last SGM result.
+  // Returns the number of points of the new frame.
+  size_t pushDisparityFrame(const int16_t* dispMap, const std::vector<Event>& vEventsSGM) {
+    size_t n = 0;
+    ctx_->check(esvo_map_push_disparity_frame(ctx_->handle(), dispMap, vEventsSGM.data(), vEventsSGM.size(), &n),
+                "esvo_map_push_disparity_frame");
+    return n;
+  }
   // returns numFusionCount
   size_t update() {
     size_t n = 0;
@@ -311,6 +321,17 @@ inline void MappingAtTimePureBlockMatching(Context& ctx, const StampedTimeSurfac
             "esvo_map_set_observation");
   ctx.check(esvo_map_tick_bm_only(ctx.handle(), obs.t_ns, st_map.stamps_ns.data(), st_map.T_world_virtual.data(), st_map.size()),
             "esvo_map_tick_bm_only");
+}
+
+// esvo_MVStereo::MappingAtTime in MVStereoMode 4, PURE_SEMI_GLOBAL_MATCHING (esvo_MVStereo.cpp:311-376): StereoSGBM on the
+// observation's Time-Surface pair (obs.TS_left / TS_right: host images, or nullptr for the device-resident frames), the mode's
+// DepthPoints on the staged events and naive_propagation of the window.  Returns the number of points of the new frame.
+inline size_t MappingAtTimeSemiGlobalMatching(Context& ctx, const StampedTimeSurfaceObs& obs) {
+  ctx.check(esvo_map_set_observation(ctx.handle(), obs.t_ns, obs.TS_left, obs.TS_right, obs.T_world_cam),
+            "esvo_map_set_observation");
+  size_t n = 0;
+  ctx.check(esvo_map_tick_sgm(ctx.handle(), obs.TS_left, obs.TS_right, &n, nullptr), "esvo_map_tick_sgm");
+  return n;
 }
 
 // ---- the tracker's optimiser: host C++ over the device's normal equations ----------------------------------------------------
