@@ -231,5 +231,33 @@ class SgmStatsStruct(C.Structure):
     ]
 
 
+# ---- the tracker's registration loop (esvo_track_solve of include/esvo_hip.h)
+TRACK_SOLVE_MAX_ITERATIONS = 64
+
+
+class TrackSolveParamsStruct(C.Structure):
+    _fields_ = [
+        ("n_points", C.c_uint64), ("batch_size", C.c_uint64), ("ls_norm", C.c_int32), ("max_iterations", C.c_int32),
+        ("on_device", C.c_int32), ("reserved", C.c_int32), ("huber_threshold", C.c_double), ("damping", C.c_double),
+    ]
+
+
+class TrackIterStruct(C.Structure):
+    _fields_ = [
+        ("cost", C.c_double), ("lambda_", C.c_double), ("step_norm", C.c_double), ("n", C.c_uint32), ("offset", C.c_uint32),
+        ("pick", C.c_int32), ("trials", C.c_int32),
+    ]
+
+
+class TrackSolveInfoStruct(C.Structure):
+    _fields_ = [("rms", C.c_double), ("iterations", C.c_int32), ("ok", C.c_int32), ("stop", C.c_int32), ("launches", C.c_int32)]
+
+
+# esvo_track_iter_t as a record array: what Esvo.track_solve returns its trace in
+TRACK_ITER_DTYPE = np.dtype([("cost", "<f8"), ("lambda", "<f8"), ("step_norm", "<f8"), ("n", "<u4"), ("offset", "<u4"),
+                             ("pick", "<i4"), ("trials", "<i4")])
+assert TRACK_ITER_DTYPE.itemsize == C.sizeof(TrackIterStruct) == 40
+
+
 # the pose callback of esvo_map_tick_em: int (*)(void* user, uint64_t t_ns, double T_world_cam[16])
 EM_POSE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_uint64, C.POINTER(C.c_double))

@@ -33,9 +33,14 @@ def orth(R):
     return U @ Vt
 
 
-def register(dev, n_points, R_, t_, iters=12):
+def register(dev, n_points, R_, t_, iters=12, device_register=False):
     """The registration of one frame: the library's driver (esvo_track_register: host C++ over esvo_track_normal_equations,
-    the three trial dampings of an iteration in one launch, 224 bytes back per trial)."""
+    the three trial dampings of an iteration in one launch, 224 bytes back per trial).  device_register: the same loop in one
+    kernel launch (esvo_track_solve, on_device) -- the same bits, without the host between dependent launches."""
+    if device_register:
+        R, t, info, _ = dev.track_solve(n_points, R_, t_, batch_size=0, huber=True, huber_threshold=50.0, max_iterations=iters,
+                                        damping=1e-3, on_device=True)
+        return R, t, info.rms
     R, t, rms, _ = dev.track_register(n_points, R_, t_, huber=True, huber_threshold=50.0, max_iterations=iters, damping=1e-3)
     return R, t, rms
 
@@ -121,7 +126,7 @@ class _Band:
         return self.dev.comm_gather_map()
 
 
-def _loop(rig, st, p, ops, t0, T0, xyz0, n_ticks, reref, verbose=False):
+def _loop(rig, st, p, ops, t0, T0, xyz0, n_ticks, reref, verbose=False, device_register=False):
     """tracker -> mapper for n_ticks ticks after the bootstrap at t0 (pose T0, reference cloud xyz0); `ops`: _OneGpu / _Band"""
     dev = ops.dev
     T_est = {t0: T0}
@@ -142,7 +147,7 @@ def _loop(rig, st, p, ops, t0, T0, xyz0, n_ticks, reref, verbose=False):
             R_, t_ = np.eye(3), np.zeros(3)
         dev.track_set_current(None, 5)
         dev.track_set_reference(xyz[sel], T_est[t_ref])
-        R_, t_, rms = register(dev, len(sel), R_, t_)
+        R_, t_, rms = register(dev, len(sel), R_, t_, device_register=device_register)
         Tw = np.eye(4)
         Tw[:3, :3] = T_est[t_ref][:3, :3] @ R_
         Tw[:3, 3] = T_est[t_ref][:3, :3] @ t_ + T_est[t_ref][:3, 3]
@@ -196,7 +201,7 @@ def _scene(seed, speed):
     return rig, st, p, st.t0_ns + int(0.08e9)
 
 
-def run(n_ticks=15, reref=10**9, speed=1.0, seed=20250419, verbose=False):
+def run(n_ticks=15, reref=10**9, speed=1.0, seed=20250419, verbose=False, device_register=False):
     rig, st, p, t0 = _scene(seed, speed)
     dev = lib.Esvo(p, rig)
     dev.ts_push_events(0, st.ev_left)
@@ -206,13 +211,13 @@ def run(n_ticks=15, reref=10**9, speed=1.0, seed=20250419, verbose=False):
     T0 = st.pose(t0)                      # bootstrap pose given, as the reference's identity at start-up
     dev.set_observation(t0, None, None, T0)
     n_sgm, _ = dev.init_sgm(None, None, min_points=100)
-    out = _loop(rig, st, p, _OneGpu(dev), t0, T0, None, n_ticks, reref, verbose)
+    out = _loop(rig, st, p, _OneGpu(dev), t0, T0, None, n_ticks, reref, verbose, device_register)
     out["sgm_points"] = n_sgm
     dev.close()
     return out
 
 
-def run_bands(G, routing="y_rect", n_ticks=15, reref=10**9, speed=1.0, seed=20250419, transport=None):
+def run_bands(G, routing="y_rect", n_ticks=15, reref=10**9, speed=1.0, seed=20250419, transport=None, device_register=False):
     """The same loop with the mapper split over G row bands (BASELINE configs[2] on configs[3]'s partition): G ranks -- handles on
     ONE GPU here, driven from G threads through the library's collective calls with an in-process all-gather (`transport`:
     tests/test_gpu_comm.LocalTransport's interface) -- each ingesting its rows, rendering its band of the Time Surfaces, matching
@@ -246,7 +251,7 @@ def run_bands(G, routing="y_rect", n_ticks=15, reref=10**9, speed=1.0, seed=2025
             dev.ts_push_events(0, st.ev_left)   # every rank is handed the whole stream; a routed handle keeps its rows
             dev.ts_push_events(1, st.ev_right)
             dev.push_frame(frame0, T0.reshape(1, 16))
-            outs[r] = _loop(rig, st, p, _Band(dev), t0, T0, xyz0, n_ticks, reref)
+            outs[r] = _loop(rig, st, p, _Band(dev), t0, T0, xyz0, n_ticks, reref, device_register=device_register)
             outs[r]["halo_violations"] = int(dev.stats().halo_violations)
             outs[r]["events_staged"] = [int(x) for x in dev.stats().events_staged]
             dev.close()

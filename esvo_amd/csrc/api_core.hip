@@ -389,6 +389,7 @@ int esvo_destroy(esvo_handle h) {
   if (h->pool_ok) for (int i = 0; i < esvo_context::POSE_POOL; ++i) hipEventDestroy(h->pool_evt[i]);
   if (h->h_pose_pool) hipHostFree(h->h_pose_pool);
   if (h->h_trk_ne) hipHostFree(h->h_trk_ne);
+  if (h->h_trk_solve) hipHostFree(h->h_trk_solve);
   if (h->h_trk_xyz) hipHostFree(h->h_trk_xyz);
   release_routing(h);
   for (int cam = 0; cam < 2; ++cam) if (h->d_wire[cam]) hipFree(h->d_wire[cam]);

@@ -154,6 +154,7 @@ int esvo_track_jacobian(esvo_handle h, const double R[9], const double t[3], siz
 }
 
 static_assert(ESVO_TRACK_MAX_POSES == TRK_NE_MAX_POSES, "the ABI's pose limit is the kernel's");
+static_assert(ESVO_TRACK_SOLVE_MAX_ITERATIONS == TRK_SOLVE_MAX_ITERATIONS, "the ABI's iteration limit is the kernel's");
 // f = operator()(0), J = df(0) and their products in one launch: H = J^T J (6 x 6, row-major, symmetric), b = J^T f, cost = |f|^2;
 // n_poses of them (one workgroup each) share the launch and the read-back
 int esvo_track_normal_equations_batch(esvo_handle h, int n_poses, const double* R, const double* t, size_t offset, size_t count,
@@ -226,5 +227,75 @@ int esvo_track_register(esvo_handle h, size_t n_points, double R[9], double t[3]
   if (rms) *rms = res.rms;
   if (iterations) *iterations = res.iterations;
   return ESVO_OK;
+}
+// esvo_track_register with the batch schedule, a trace, and -- on_device -- the whole loop in one launch (kernels_track.hip)
+int esvo_track_solve(esvo_handle h, const esvo_track_solve_params_t* prm, double R[9], double t[3], esvo_track_solve_info_t* info,
+                     esvo_track_iter_t* trace, size_t trace_cap) {
+  if (!h || !prm || !R || !t || (prm->ls_norm != ESVO_TRACK_L2 && prm->ls_norm != ESVO_TRACK_HUBER) || prm->max_iterations < 1 ||
+      prm->max_iterations > ESVO_TRACK_SOLVE_MAX_ITERATIONS)
+    return ESVO_ERR_INVALID_ARG;
+  if (!trace) trace_cap = 0;
+  size_t N = 0;
+  {
+    std::lock_guard<std::mutex> _trk_lock(h->mu_track);
+    if (!h->trk_cur) FAIL(ESVO_ERR_STATE, "esvo_track_set_current has not been called");
+    N = std::min<size_t>(prm->n_points, h->trk_n);
+  }
+  const size_t B = prm->batch_size;
+  const bool batches = B != 0 && B < N;
+  const size_t n_batches = batches ? std::max<size_t>(N / B, 1) : 1;
+  if (!prm->on_device) {  // today's path: the host loop over one launch per evaluation, plus the recorder
+    int rc = ESVO_OK, launches = 0;
+    auto ne = [&](int it, int k, const double* Rc, const double* tc, double* H, double* b, double* cost, size_t* n) {
+      rc = esvo_track_normal_equations_batch(h, k, Rc, tc, batches ? ((size_t)it % n_batches) * B : 0, batches ? B : N, prm->ls_norm,
+                                             prm->huber_threshold, H, b, cost, n);
+      if (rc == ESVO_OK && *n) ++launches;
+      return rc == ESVO_OK;
+    };
+    esvo_track_iter_t rec[ESVO_TRACK_SOLVE_MAX_ITERATIONS];
+    esvo_hip::RegistrationTrace tr;
+    tr.rec = rec; tr.cap = ESVO_TRACK_SOLVE_MAX_ITERATIONS;
+    const esvo_hip::Registration res = esvo_hip::gauss_newton_register(ne, R, t, prm->max_iterations, prm->damping, !batches, &tr);
+    if (rc) return rc;
+    std::memcpy(R, res.R, sizeof(res.R));
+    std::memcpy(t, res.t, sizeof(res.t));
+    if (info) { info->rms = res.rms; info->iterations = res.iterations; info->ok = res.ok ? 1 : 0; info->stop = tr.stop; info->launches = launches; }
+    for (size_t it = 0; it < std::min<size_t>(trace_cap, (size_t)res.iterations); ++it) {
+      trace[it] = rec[it];
+      trace[it].offset = batches ? (uint32_t)((it % n_batches) * B) : 0u;
+    }
+    return ESVO_OK;
+  }
+  std::lock_guard<std::mutex> _trk_lock(h->mu_track);
+  if (!h->trk_cur) FAIL(ESVO_ERR_STATE, "esvo_track_set_current has not been called");
+  HIPCHK(hipSetDevice(h->device));
+  N = std::min<size_t>(prm->n_points, h->trk_n);  // (a reference set between the two locks)
+  if (!h->h_trk_solve) HIPCHK(hipHostMalloc(reinterpret_cast<void**>(&h->h_trk_solve), sizeof(TrackSolveOut)));
+  TrackArgs a;
+  fill_track_args(h, a);
+  TrackSolveArgs s;
+  std::memcpy(s.R0, R, sizeof(s.R0));
+  std::memcpy(s.t0, t, sizeof(s.t0));
+  s.huber_threshold = prm->huber_threshold; s.damping = prm->damping;
+  s.n_points = (u32)N; s.batch = (u32)std::min<size_t>(B, N);  // (>= N: one batch, as 0)
+  s.huber = prm->ls_norm == ESVO_TRACK_HUBER; s.max_iterations = prm->max_iterations;
+  // one launch, one write phase into the pinned block, and the host polls for the end of the launch as the per-evaluation path does
+  launch_track_solve(a, s, h->h_trk_solve, h->stream_t);
+  HIPCHK(hipGetLastError());
+  HIPCHK(esvo_wait_stream(h->stream_t, true));
+  h->trk_xyz_inflight = false;
+  const TrackSolveOut& o = *h->h_trk_solve;
+  std::memcpy(R, o.R, sizeof(o.R));
+  std::memcpy(t, o.t, sizeof(o.t));
+  if (info) *info = o.info;
+  for (size_t it = 0; it < std::min<size_t>(trace_cap, (size_t)o.info.iterations); ++it) trace[it] = o.trace[it];
+  return ESVO_OK;
+}
+
+void esvo_track_sizes(size_t out[4]) {
+  out[0] = sizeof(esvo_track_solve_params_t);
+  out[1] = sizeof(esvo_track_iter_t);
+  out[2] = sizeof(esvo_track_solve_info_t);
+  out[3] = ESVO_TRACK_SOLVE_MAX_ITERATIONS;
 }
 }  // extern "C"

@@ -299,6 +299,21 @@ void launch_track_jacobian(const TrackArgs& a, const TrackPose& pose, u32 offset
 #define TRK_NE_TERMS 28   // 21 upper-triangle entries of J^T J, 6 of J^T f, |f|^2
 void launch_track_normal(const TrackArgs& a, const TrackPoseSet& poses, int n_poses, u32 offset, u32 count, int huber, double thr,
                          double* out28_per_pose, hipStream_t s);
+// esvo_track_solve, on_device = 1: the registration loop in one launch of one workgroup (track_solve_kernel)
+#define TRK_SOLVE_MAX_ITERATIONS 64
+#define TRK_SOLVE_THREADS 1024  // the one workgroup: 256 owners of the sums, all of them computing points (kernels_track.hip)
+struct TrackSolveArgs {
+  double R0[9], t0[3];
+  double huber_threshold, damping;
+  u32 n_points, batch;   // batch: 0 = all points in every iteration
+  int huber, max_iterations;
+};
+struct TrackSolveOut {   // the pinned block the kernel writes once: results, info, one record per iteration
+  double R[9], t[3];
+  esvo_track_solve_info_t info;
+  esvo_track_iter_t trace[TRK_SOLVE_MAX_ITERATIONS];
+};
+void launch_track_solve(const TrackArgs& a, const TrackSolveArgs& s, TrackSolveOut* out, hipStream_t st);
 
 // kernels_shard.hip: ordering of a tick's frame from the ranks' (matched, kept) bits
 void launch_shard_codes(const u32* own_w, const u32* keep, const u32* n_local, u32 max_local, u32 N, uint8_t* block, hipStream_t s);

@@ -386,6 +386,7 @@ struct esvo_context {
   double* d_trk_pts = nullptr;
   double* d_trk_out = nullptr;
   double* h_trk_ne = nullptr;     // pinned: the 28 sums of esvo_track_normal_equations
+  TrackSolveOut* h_trk_solve = nullptr;  // pinned: what track_solve_kernel writes (esvo_track_solve, on_device)
   float* h_trk_xyz = nullptr;     // pinned staging of esvo_track_set_reference's point cloud
   bool trk_xyz_inflight = false;  // an upload out of it has been enqueued and no call has waited for the tracker stream since
   size_t trk_cap = 0, trk_n = 0;

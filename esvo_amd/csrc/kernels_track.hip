@@ -10,6 +10,7 @@
 // 2x2 fetch per image.  One thread per point; every f64 operation is written in the order of the reference's
 // expressions (no contraction), so results equal the CPU restatement bit for bit.
 #include "common.hpp"
+#include "../../include/esvo_hip.hpp"  // the step of esvo_hip::gauss_newton_register, compiled for the device too (track_solve_kernel)
 
 namespace esvo {
 
@@ -209,6 +210,208 @@ __global__ void __launch_bounds__(TRK_NE_THREADS) track_normal_kernel(TrackArgs 
 void launch_track_normal(const TrackArgs& a, const TrackPoseSet& poses, int n_poses, u32 offset, u32 count, int huber, double thr,
                          double* out, hipStream_t s) {
   hipLaunchKernelGGL(track_normal_kernel, dim3(n_poses), dim3(TRK_NE_THREADS), 0, s, a, poses, offset, count, huber, thr, out);
+}
+
+// ---- the whole registration in ONE launch --------------------------------------------------------------------------------
+// esvo_hip::gauss_newton_register (include/esvo_hip.hpp) with the batch schedule of RegProblemLM::solve, inside one workgroup:
+// the normal equations by the whole workgroup in track_normal_kernel's summation order (trk_normal_sums_wide), everything between two evaluations -- the
+// damped 6 x 6 solve, the Cayley update, the polar factor, the accept test, the damping schedule -- by lane 0, through the very
+// functions the host loop is made of (ESVO_HD in esvo_hip.hpp; no contraction on either side), so the launch returns the host
+// loop's bits.  What differs is the schedule only: the host evaluates the three trial dampings of a round speculatively in one
+// launch and takes the first acceptable one in rising order; here an evaluation costs no round trip, so the trials are taken one
+// after the other in that order and the first acceptable one ends the iteration.
+// Every loop is bounded (<= 64 iterations x 6 trials, orthonormalize3 <= 20 steps) and nothing waits for another workgroup.
+// Lane 0's state lives in LDS (TrkSolveState); its decisions reach the other lanes through one flag per barrier (go_*), each
+// written before and read after its own barrier, so no flag is rewritten while a slow wave still has to read it.
+// track_normal_kernel's sums of one pose, left in red[n][0], by a workgroup of TRK_SOLVE_THREADS > 256 threads.  The order of
+// the additions is that kernel's -- owner t < 256 adds the terms of points t, t + 256, t + 512, ... in that order, then the same
+// tree -- but the expensive part of a point, its residual and its Jacobian row (the reprojection, three bilinear fetches, a
+// dozen divisions), is computed by whichever thread the point falls to: TRK_SOLVE_THREADS points at a time, 7 doubles each
+// through LDS (the staging area IS the reduction scratch, free until the sums are complete), the owner forming the 28 products
+// from those values exactly as the kernel's thread does from its own.  Every thread of the workgroup calls it (barriers inside).
+// Kept apart from track_normal_kernel so that its code stays what it was; the bit-for-bit test of the two paths of
+// esvo_track_solve holds the two together.
+__device__ __forceinline__ void trk_normal_sums_wide(const TrackArgs& a, const TrackPose& pose, u32 offset, u32 count, int huber,
+                                                     double huber_threshold, double (*red)[TRK_NE_THREADS]) {
+  static_assert(TRK_SOLVE_THREADS % TRK_NE_THREADS == 0 && 7 * TRK_SOLVE_THREADS <= TRK_NE_TERMS * TRK_NE_THREADS, "staging fits the scratch");
+  double* stage = &red[0][0];  // [7][TRK_SOLVE_THREADS]: row[0..5], f
+  const u32 tid = threadIdx.x;
+  double acc[TRK_NE_TERMS];
+#pragma unroll
+  for (int n = 0; n < TRK_NE_TERMS; ++n) acc[n] = 0.0;
+  for (u32 base = 0; base < count; base += TRK_SOLVE_THREADS) {
+    if (base + tid < count) {
+      const double* pq = a.pts + 3 * (size_t)(offset + base + tid);
+      const double p[3] = {pq[0], pq[1], pq[2]};
+      const double f = trk_residual(a, pose.T, p, huber, huber_threshold);
+      double row[6];
+      trk_jacobian_row(a, pose, p, row);
+#pragma unroll
+      for (int i = 0; i < 6; ++i) stage[i * TRK_SOLVE_THREADS + tid] = row[i];
+      stage[6 * TRK_SOLVE_THREADS + tid] = f;
+    }
+    __syncthreads();
+    if (tid < TRK_NE_THREADS) {
+      for (u32 q = tid; q < TRK_SOLVE_THREADS && base + q < count; q += TRK_NE_THREADS) {
+        double row[6];
+#pragma unroll
+        for (int i = 0; i < 6; ++i) row[i] = stage[i * TRK_SOLVE_THREADS + q];
+        const double f = stage[6 * TRK_SOLVE_THREADS + q];
+        int n = 0;
+#pragma unroll
+        for (int i = 0; i < 6; ++i)
+#pragma unroll
+          for (int j = i; j < 6; ++j) { acc[n] = acc[n] + row[i] * row[j]; ++n; }
+#pragma unroll
+        for (int i = 0; i < 6; ++i) acc[21 + i] = acc[21 + i] + row[i] * f;
+        acc[27] = acc[27] + f * f;
+      }
+    }
+    __syncthreads();
+  }
+  if (tid < TRK_NE_THREADS) {
+#pragma unroll
+    for (int n = 0; n < TRK_NE_TERMS; ++n) red[n][tid] = acc[n];
+  }
+  for (u32 s = TRK_NE_THREADS / 2; s > 0; s >>= 1) {
+    __syncthreads();
+    if (tid < s)
+      for (int n = 0; n < TRK_NE_TERMS; ++n) red[n][tid] = red[n][tid] + red[n][tid + s];
+  }
+  __syncthreads();
+}
+enum { TRK_GO_NEXT = 0, TRK_GO_ACCEPT = 1, TRK_GO_FAIL = 2, TRK_GO_STOP = 3 };
+struct TrkSolveState {
+  double R[9], t[3];    // the last accepted pose
+  double Rn[9], tn[3];  // the trial pose
+  double H[36], b[6], dx[6];
+  double cost, lambda;
+  int go_trial, go_eval, go_iter;
+};
+// T_left_ref = [R^T | -R^T t] (RegProblemLM.cpp:203-205), J_constPart (:189-194): api_track.hip's pose set-up
+__device__ inline void trk_pose_of(const double* R, const double* t, double iP11, double iP22, TrackPose& pose) {
+#pragma unroll
+  for (int i = 0; i < 16; ++i) pose.T[i] = 0.0;
+#pragma unroll
+  for (int r = 0; r < 3; ++r) {
+#pragma unroll
+    for (int c = 0; c < 3; ++c) pose.T[r * 4 + c] = R[c * 3 + r];
+    pose.T[r * 4 + 3] = (-R[0 * 3 + r] * t[0] + -R[1 * 3 + r] * t[1]) + -R[2 * 3 + r] * t[2];
+  }
+  pose.T[15] = 1.0;
+#pragma unroll
+  for (int r = 0; r < 3; ++r) { pose.Jc[r * 2 + 0] = R[0 * 3 + r] * iP11; pose.Jc[r * 2 + 1] = R[1 * 3 + r] * iP22; }
+}
+__device__ inline void trk_unpack_sums(const double (*red)[TRK_NE_THREADS], double* H, double* b, double* cost) {
+  int n = 0;
+  for (int i = 0; i < 6; ++i)
+    for (int j = i; j < 6; ++j) { H[i * 6 + j] = H[j * 6 + i] = red[n][0]; ++n; }
+  for (int i = 0; i < 6; ++i) b[i] = red[21 + i][0];
+  *cost = red[27][0];
+}
+__global__ void __launch_bounds__(TRK_SOLVE_THREADS) track_solve_kernel(TrackArgs a, TrackSolveArgs s, TrackSolveOut* __restrict__ out) {
+  __shared__ double red[TRK_NE_TERMS][TRK_NE_THREADS];
+  __shared__ TrkSolveState S;
+  __shared__ TrackSolveOut O;
+  const bool lane0 = threadIdx.x == 0;
+  const double iP11 = 1.0 / a.P[0], iP22 = 1.0 / a.P[5];
+  const bool batches = s.batch != 0 && s.batch < s.n_points;
+  const u32 n_batches = batches ? (s.n_points / s.batch > 1u ? s.n_points / s.batch : 1u) : 1u;
+  const int max_it = s.max_iterations < TRK_SOLVE_MAX_ITERATIONS ? s.max_iterations : TRK_SOLVE_MAX_ITERATIONS;
+  if (lane0) {
+    for (int i = 0; i < 9; ++i) S.R[i] = s.R0[i];
+    for (int i = 0; i < 3; ++i) S.t[i] = s.t0[i];
+    S.cost = 0; S.lambda = s.damping;
+    O.info.rms = 0; O.info.iterations = 0; O.info.ok = 1; O.info.stop = 0; O.info.launches = 1;
+  }
+  __syncthreads();
+  TrackPose pose;
+  bool have = false;
+  for (int it = 0; it < max_it; ++it) {
+    const u32 off = batches ? ((u32)it % n_batches) * s.batch : 0u, cnt = batches ? s.batch : s.n_points;
+    if (!have) {
+      trk_pose_of(S.R, S.t, iP11, iP22, pose);
+      trk_normal_sums_wide(a, pose, off, cnt, s.huber, s.huber_threshold, red);
+      if (lane0) trk_unpack_sums(red, S.H, S.b, &S.cost);
+    }
+    have = false;
+    double lam = 0, lam_tried = 0;  // lane 0's
+    int tried = 0, go = TRK_GO_NEXT;
+    esvo_track_iter_t* rec = &O.trace[it];
+    if (lane0) {
+      O.info.iterations = it + 1;
+      O.info.rms = cnt ? sqrt(S.cost / (double)cnt) : 0.0;
+      rec->cost = S.cost; rec->n = cnt; rec->offset = off; rec->step_norm = 0.0; rec->pick = -1;
+      lam_tried = S.lambda;
+    }
+    for (int trial = 0; trial < 2 * esvo_hip::kRegisterTrials; ++trial) {  // dampings lambda 10^0..2, then lambda 10^3..5
+      if (lane0) {
+        if (trial % esvo_hip::kRegisterTrials == 0) lam = S.lambda;
+        lam_tried = lam;
+        S.go_trial = esvo_hip::gn_trial_step(S.H, S.b, lam, S.R, S.t, S.dx, S.Rn, S.tn) ? TRK_GO_NEXT : TRK_GO_FAIL;
+      }
+      __syncthreads();
+      go = S.go_trial;
+      if (go == TRK_GO_FAIL) break;  // a singular damped system, none before it acceptable
+      trk_pose_of(S.Rn, S.tn, iP11, iP22, pose);
+      trk_normal_sums_wide(a, pose, off, cnt, s.huber, s.huber_threshold, red);
+      if (lane0) {
+        const double pred = esvo_hip::gn_predicted_reduction(S.H, S.b, S.dx);
+        ++tried;
+        if (esvo_hip::gn_accept(pred, S.cost, red[27][0])) {
+          rec->pick = trial; S.lambda = lam; S.go_eval = TRK_GO_ACCEPT;
+        } else {
+          lam *= 10.0;
+          if (trial % esvo_hip::kRegisterTrials == esvo_hip::kRegisterTrials - 1) S.lambda = lam;  // lambda x 10 x 10 x 10
+          S.go_eval = TRK_GO_NEXT;
+        }
+      }
+      __syncthreads();
+      go = S.go_eval;
+      if (go == TRK_GO_ACCEPT) break;
+    }
+    if (go != TRK_GO_ACCEPT) {  // failed, or no step pays any more: (R, t) stays the last accepted pose
+      if (lane0) {
+        if (go == TRK_GO_FAIL) O.info.ok = 0;
+        O.info.stop = go == TRK_GO_FAIL ? 3 : 2;
+        rec->lambda = lam_tried; rec->trials = tried;
+      }
+      break;
+    }
+    if (lane0) {
+      for (int i = 0; i < 9; ++i) S.R[i] = S.Rn[i];
+      for (int i = 0; i < 3; ++i) S.t[i] = S.tn[i];
+      rec->lambda = S.lambda; rec->trials = tried;
+      S.lambda = S.lambda / 10.0 > s.damping ? S.lambda / 10.0 : s.damping;
+      if (!batches) {  // same batch: the evaluation at the accepted pose IS the next iteration's linearisation
+        trk_unpack_sums(red, S.H, S.b, &S.cost);
+        O.info.rms = cnt ? sqrt(S.cost / (double)cnt) : 0.0;
+      }
+      const double step = esvo_hip::gn_step_norm(S.dx);
+      rec->step_norm = step;
+      S.go_iter = step < 1e-6 ? TRK_GO_STOP : TRK_GO_NEXT;
+      if (step < 1e-6) O.info.stop = 1;
+    }
+    have = !batches;
+    __syncthreads();
+    if (S.go_iter == TRK_GO_STOP) break;
+  }
+  __syncthreads();
+  if (lane0) {
+    for (int i = 0; i < 9; ++i) O.R[i] = S.R[i];
+    for (int i = 0; i < 3; ++i) O.t[i] = S.t[i];
+  }
+  __syncthreads();
+  // one write phase: the header and the records of the iterations that ran, as 8-byte words, into the pinned block the host reads
+  static_assert(sizeof(esvo_track_iter_t) % 8 == 0 && offsetof(TrackSolveOut, trace) % 8 == 0, "copied as 8-byte words");
+  const u32 words = (u32)((offsetof(TrackSolveOut, trace) + (size_t)O.info.iterations * sizeof(esvo_track_iter_t)) / 8);
+  const unsigned long long* src = reinterpret_cast<const unsigned long long*>(&O);
+  unsigned long long* dst = reinterpret_cast<unsigned long long*>(out);
+  for (u32 w = threadIdx.x; w < words; w += TRK_SOLVE_THREADS) dst[w] = src[w];
+  __threadfence_system();
+}
+void launch_track_solve(const TrackArgs& a, const TrackSolveArgs& s, TrackSolveOut* out, hipStream_t st) {
+  hipLaunchKernelGGL(track_solve_kernel, dim3(1), dim3(TRK_SOLVE_THREADS), 0, st, a, s, out);
 }
 
 }  // namespace esvo

@@ -11,7 +11,8 @@ import subprocess
 import numpy as np
 
 from .abi import (DEPTH_POINT_DTYPE, EM_POSE_FN, EVENT_DTYPE, MATCH_DTYPE, CalibStruct, EmSelectionStruct,
-                  EmStatsStruct, ParamsStruct, SgmStatsStruct, StatsStruct)
+                  EmStatsStruct, ParamsStruct, SgmStatsStruct, StatsStruct, TRACK_ITER_DTYPE, TRACK_SOLVE_MAX_ITERATIONS,
+                  TrackSolveInfoStruct, TrackSolveParamsStruct)
 
 _CSRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc")
 # ESVO_HIP_LIB: another build of the same library (A/B measurements of kernel variants, tools/ab_build.py); never a fallback
@@ -28,7 +29,7 @@ SYMBOLS = [
     "esvo_get_stats", "esvo_shard_set_band", "esvo_shard_set_routing", "esvo_shard_get_rows", "esvo_shard_exchange", "esvo_shard_tick_phase", "esvo_abi_sizes",
     "esvo_map_front", "esvo_map_front_frame", "esvo_map_push_frame_device", "esvo_map_fuse_async",
     "esvo_track_set_current", "esvo_track_get_images", "esvo_track_set_reference", "esvo_track_residuals", "esvo_track_jacobian",
-    "esvo_track_normal_equations", "esvo_track_normal_equations_batch", "esvo_track_register",
+    "esvo_track_normal_equations", "esvo_track_normal_equations_batch", "esvo_track_register", "esvo_track_solve", "esvo_track_sizes",
     "esvo_map_init_sgm",
     "esvo_bag_open", "esvo_bag_close", "esvo_bag_last_error", "esvo_bag_next_event_array", "esvo_ts_push_bag",
     "esvo_map_get_debug_images", "esvo_map_get_pointcloud_near_xyz", "esvo_voxel_filter_xyz", "esvo_map_save_depth_map",
@@ -178,6 +179,9 @@ def load():
     lib.esvo_track_normal_equations.argtypes = [vp, vp, vp, sz, sz, i32, C.c_double, vp, vp, C.POINTER(C.c_double), psz]
     lib.esvo_track_normal_equations_batch.argtypes = [vp, i32, vp, vp, sz, sz, i32, C.c_double, vp, vp, vp, psz]
     lib.esvo_track_register.argtypes = [vp, sz, vp, vp, i32, C.c_double, i32, C.c_double, C.POINTER(C.c_double), C.POINTER(C.c_int)]
+    lib.esvo_track_solve.argtypes = [vp, vp, vp, vp, vp, vp, sz]
+    lib.esvo_track_sizes.argtypes = [vp]
+    lib.esvo_track_sizes.restype = None
     lib.esvo_map_init_sgm.argtypes = [vp, vp, vp, sz, psz, vp]
     lib.esvo_bag_open.argtypes = [C.c_char_p, C.POINTER(vp)]
     lib.esvo_bag_close.argtypes = [vp]
@@ -215,7 +219,8 @@ def load():
     lib.esvo_sgm_sizes.argtypes = [vp]
     lib.esvo_sgm_sizes.restype = None
     for s in SYMBOLS:
-        if s not in ("esvo_default_params", "esvo_last_error", "esvo_abi_sizes", "esvo_bag_last_error", "esvo_em_sizes", "esvo_sgm_sizes"):
+        if s not in ("esvo_default_params", "esvo_last_error", "esvo_abi_sizes", "esvo_bag_last_error", "esvo_em_sizes", "esvo_sgm_sizes",
+                     "esvo_track_sizes"):
             getattr(lib, s).restype = C.c_int
     lib.esvo_abi_sizes.argtypes = [vp]
     lib.esvo_abi_sizes.restype = None
@@ -332,6 +337,13 @@ def sgm_sizes():
     """sizeof(esvo_sgm_stats_t), numDisparities, 0, 0 (esvo_sgm_sizes)"""
     out = (C.c_size_t * 4)()
     load().esvo_sgm_sizes(out)
+    return list(out)
+
+
+def track_sizes():
+    """sizeof() of esvo_track_solve_params_t, esvo_track_iter_t, esvo_track_solve_info_t, and the iteration limit (esvo_track_sizes)"""
+    out = (C.c_size_t * 4)()
+    load().esvo_track_sizes(out)
     return list(out)
 
 
@@ -708,6 +720,22 @@ class Esvo:
         self._ck(self.lib.esvo_track_register(self.h, int(n_points), R.ctypes.data, t.ctypes.data, 1 if huber else 0, float(huber_threshold),
                                               int(max_iterations), float(damping), C.byref(rms), C.byref(it)))
         return R.reshape(3, 3), t, rms.value, it.value
+
+    def track_solve(self, n_points, R, t, batch_size=0, huber=True, huber_threshold=50.0, max_iterations=12, damping=1e-3,
+                    on_device=True):
+        """esvo_track_solve: the registration with the shipped configs' batch schedule (batch_size 0: all points in every
+        iteration, what track_register does) and a record of what it did.  on_device: the whole loop in one kernel launch,
+        bit for bit what the host loop (on_device=False: one launch per evaluation) returns.
+        -> (R 3x3, t, info: abi.TrackSolveInfoStruct, trace: one abi.TRACK_ITER_DTYPE record per iteration)"""
+        R = np.ascontiguousarray(R, np.float64).reshape(9).copy()
+        t = np.ascontiguousarray(t, np.float64).reshape(3).copy()
+        prm = TrackSolveParamsStruct(int(n_points), int(batch_size), 1 if huber else 0, int(max_iterations), 1 if on_device else 0, 0,
+                                     float(huber_threshold), float(damping))
+        info = TrackSolveInfoStruct()
+        trace = np.zeros(TRACK_SOLVE_MAX_ITERATIONS, TRACK_ITER_DTYPE)
+        self._ck(self.lib.esvo_track_solve(self.h, C.addressof(prm), R.ctypes.data, t.ctypes.data, C.addressof(info), trace.ctypes.data,
+                                           len(trace)))
+        return R.reshape(3, 3), t, info, trace[:info.iterations].copy()
 
     # ---- multi-GPU exchange behind the C-ABI (api_comm.hip): RCCL, or the two collectives as callbacks ----
     def comm_init(self, unique_id, rank, world):

@@ -783,6 +783,52 @@ int esvo_track_normal_equations_batch(esvo_handle h, int n_poses, const double* 
 int esvo_track_register(esvo_handle h, size_t n_points, double R[9], double t[3], int ls_norm, double huber_threshold,
                         int max_iterations, double damping, double* rms, int* iterations);
 
+/* The same registration with the batch schedule of the shipped configs, a record of what it did, and -- on_device = 1 -- the
+ * whole loop in ONE kernel launch and one read-back: normal equations, the damped 6 x 6 solves, the Cayley update, the polar
+ * factor and the accept test all run inside track_solve_kernel (one workgroup), in the host loop's expression order, so both
+ * paths return the same bits.  The device path evaluates the trial dampings of an iteration lazily, in rising order: the
+ * result is defined as the first acceptable one in that order, which is what the host's speculative launch of three returns. */
+#define ESVO_TRACK_SOLVE_MAX_ITERATIONS 64
+typedef struct esvo_track_solve_params_t {
+  uint64_t n_points;        /* first n_points of the reference cloud (clamped to what esvo_track_set_reference holds) */
+  uint64_t batch_size;      /* 0 or >= n_points: every iteration on all points (what esvo_track_register does);
+                               else RegProblemLM::solve's schedule: offset = (it % max(n_points / batch_size, 1)) * batch_size */
+  int32_t  ls_norm;         /* ESVO_TRACK_L2 / ESVO_TRACK_HUBER */
+  int32_t  max_iterations;  /* 1 .. ESVO_TRACK_SOLVE_MAX_ITERATIONS */
+  int32_t  on_device;       /* 0: gauss_newton_register on the host over esvo_track_normal_equations_batch
+                               1: the whole loop in one kernel launch */
+  int32_t  reserved;
+  double   huber_threshold;
+  double   damping;
+} esvo_track_solve_params_t;
+
+typedef struct esvo_track_iter_t {   /* one record per outer iteration */
+  double   cost;        /* |f|^2 at the linearisation point of this iteration */
+  double   lambda;      /* damping of the accepted trial, or the last one tried when none was accepted */
+  double   step_norm;   /* |dx| of the accepted trial, 0 when none */
+  uint32_t n;           /* points in this iteration's batch */
+  uint32_t offset;      /* first point of the batch */
+  int32_t  pick;        /* index 0..5 of the accepted trial in rising damping order (3..5 = second round), -1 none */
+  int32_t  trials;      /* trial poses whose cost was needed to decide (1..6; in an iteration that ends on a singular damped
+                           system: the trials before it, 0..5, and lambda is the singular system's damping) */
+} esvo_track_iter_t;
+
+typedef struct esvo_track_solve_info_t {
+  double  rms;
+  int32_t iterations;
+  int32_t ok;           /* Registration::ok */
+  int32_t stop;         /* 0 max_iterations, 1 step < 1e-6, 2 no trial acceptable, 3 failed (singular trial / evaluation) */
+  int32_t launches;     /* kernel launches this call made (1 when on_device) */
+} esvo_track_solve_info_t;
+
+/* R, t: in = the start, out = what gauss_newton_register returns (its last accepted pose also when ok is 0).  info and trace may
+ * be NULL; at most trace_cap records are written (info->iterations of them exist).  ESVO_ERR_STATE before
+ * esvo_track_set_current, ESVO_ERR_INVALID_ARG for an unknown norm or max_iterations outside 1..64. */
+int esvo_track_solve(esvo_handle h, const esvo_track_solve_params_t* prm, double R[9], double t[3],
+                     esvo_track_solve_info_t* info, esvo_track_iter_t* trace, size_t trace_cap);
+/* sizeof of esvo_track_solve_params_t, esvo_track_iter_t, esvo_track_solve_info_t, and ESVO_TRACK_SOLVE_MAX_ITERATIONS */
+void esvo_track_sizes(size_t out[4]);
+
 #ifdef __cplusplus
 }
 #endif

@@ -335,8 +335,17 @@ inline size_t MappingAtTimeSemiGlobalMatching(Context& ctx, const StampedTimeSur
 }
 
 // ---- the tracker's optimiser: host C++ over the device's normal equations ----------------------------------------------------
+// The pieces of a step (ESVO_HD) are compiled for the device as well: track_solve_kernel (esvo_track_solve, on_device = 1) runs
+// the same expressions in the same order inside one launch, and returns the host loop's bits.
+#if defined(__HIPCC__)
+#define ESVO_HD __host__ __device__
+#define ESVO_UNROLL _Pragma("unroll")
+#else
+#define ESVO_HD
+#define ESVO_UNROLL
+#endif
 // tools::cayley2rot (esvo_core/src/tools/cayley.cpp), row-major
-inline void cayley2rot(const double c[3], double R[9]) {
+ESVO_HD inline void cayley2rot(const double c[3], double R[9]) {
   const double c0 = c[0], c1 = c[1], c2 = c[2];
   const double s = 1.0 + ((c0 * c0 + c1 * c1) + c2 * c2);
   const double M[9] = {1 + c0 * c0 - c1 * c1 - c2 * c2, 2 * (c0 * c1 - c2), 2 * (c0 * c2 + c1),
@@ -346,7 +355,7 @@ inline void cayley2rot(const double c[3], double R[9]) {
 }
 // U V^T of the SVD of a (nearly orthonormal) 3x3 matrix = its orthogonal polar factor -- what addMotionUpdate's JacobiSVD
 // re-orthonormalisation (RegProblemLM.cpp:355-357) returns; Newton's iteration X <- (X + X^-T) / 2 converges quadratically
-inline void orthonormalize3(double X[9]) {
+ESVO_HD inline void orthonormalize3(double X[9]) {
   for (int it = 0; it < 20; ++it) {
     const double* a = X;
     const double c00 = a[4] * a[8] - a[5] * a[7], c01 = a[5] * a[6] - a[3] * a[8], c02 = a[3] * a[7] - a[4] * a[6];
@@ -359,28 +368,93 @@ inline void orthonormalize3(double X[9]) {
     if (d < 1e-16) break;
   }
 }
-// solves A x = rhs (6 x 6, row-major) by Gaussian elimination with partial pivoting; false if singular
-inline bool solve6(const double A_in[36], const double rhs[6], double x[6]) {
+// solves A x = rhs (6 x 6, row-major) by Gaussian elimination with partial pivoting; false if singular.  Every index is a
+// loop counter (the pivot row is found and swapped by comparing counters, not by indexing with it), so that the device
+// compiler, with the loops unrolled, keeps the 6 x 7 tableau in registers.
+ESVO_HD inline bool solve6(const double A_in[36], const double rhs[6], double x[6]) {
   double A[6][7];
-  for (int i = 0; i < 6; ++i) { for (int j = 0; j < 6; ++j) A[i][j] = A_in[i * 6 + j]; A[i][6] = rhs[i]; }
+  ESVO_UNROLL
+  for (int i = 0; i < 6; ++i) {
+    ESVO_UNROLL
+    for (int j = 0; j < 6; ++j) A[i][j] = A_in[i * 6 + j];
+    A[i][6] = rhs[i];
+  }
+  ESVO_UNROLL
   for (int c = 0; c < 6; ++c) {
     int piv = c;
-    for (int r = c + 1; r < 6; ++r) if (std::fabs(A[r][c]) > std::fabs(A[piv][c])) piv = r;
-    if (A[piv][c] == 0.0 || !std::isfinite(A[piv][c])) return false;
-    if (piv != c) for (int j = 0; j < 7; ++j) std::swap(A[piv][j], A[c][j]);
+    double pv = A[c][c];  // A[piv][c]
+    ESVO_UNROLL
+    for (int r = c + 1; r < 6; ++r) if (std::fabs(A[r][c]) > std::fabs(pv)) { piv = r; pv = A[r][c]; }
+    if (pv == 0.0 || !std::isfinite(pv)) return false;
+    ESVO_UNROLL
+    for (int r = c + 1; r < 6; ++r)
+      if (r == piv) {
+        ESVO_UNROLL
+        for (int j = 0; j < 7; ++j) { const double v = A[r][j]; A[r][j] = A[c][j]; A[c][j] = v; }
+      }
+    ESVO_UNROLL
     for (int r = c + 1; r < 6; ++r) {
       const double f = A[r][c] / A[c][c];
+      ESVO_UNROLL
       for (int j = c; j < 7; ++j) A[r][j] -= f * A[c][j];
     }
   }
+  ESVO_UNROLL
   for (int i = 5; i >= 0; --i) {
     double s = A[i][6];
+    ESVO_UNROLL
     for (int j = i + 1; j < 6; ++j) s -= A[i][j] * x[j];
     x[i] = s / A[i][i];
   }
   return true;
 }
+// one trial of an iteration: (H + lam diag(H) + 1e-9 I) dx = -b, then addMotionUpdate's pose Rn = orth(cayley2rot(dx_c) R),
+// tn = dx_t + cayley2rot(dx_c) t; false if the damped system is singular
+ESVO_HD inline bool gn_trial_step(const double H[36], const double b[6], double lam, const double R[9], const double t[3], double dx[6],
+                                  double Rn[9], double tn[3]) {
+  double A[36], rhs[6];
+  for (int i = 0; i < 36; ++i) A[i] = H[i];
+  for (int i = 0; i < 6; ++i) { A[i * 6 + i] = (H[i * 6 + i] + lam * H[i * 6 + i]) + 1e-9; rhs[i] = -b[i]; }
+  if (!solve6(A, rhs, dx)) return false;
+  double dR[9];
+  cayley2rot(dx, dR);
+  for (int r = 0; r < 3; ++r)
+    for (int c = 0; c < 3; ++c)
+      Rn[r * 3 + c] = (dR[r * 3 + 0] * R[0 * 3 + c] + dR[r * 3 + 1] * R[1 * 3 + c]) + dR[r * 3 + 2] * R[2 * 3 + c];
+  orthonormalize3(Rn);
+  for (int r = 0; r < 3; ++r) tn[r] = dx[3 + r] + ((dR[r * 3 + 0] * t[0] + dR[r * 3 + 1] * t[1]) + dR[r * 3 + 2] * t[2]);
+  return true;
+}
+// the reduction the linear model predicts for the step: |f|^2 - |f + J dx|^2 = -(2 b.dx + dx.H dx)
+ESVO_HD inline double gn_predicted_reduction(const double H[36], const double b[6], const double dx[6]) {
+  double pred = 0;
+  for (int i = 0; i < 6; ++i) {
+    double hd = 0;
+    for (int j = 0; j < 6; ++j) hd += H[i * 6 + j] * dx[j];
+    pred -= dx[i] * (2.0 * b[i] + hd);
+  }
+  return pred;
+}
+ESVO_HD inline bool gn_accept(double pred, double cost, double cost_t) { return pred > 0 && (cost - cost_t) >= 1e-4 * pred; }
+ESVO_HD inline double gn_step_norm(const double dx[6]) {
+  double nrm = 0;
+  for (int i = 0; i < 6; ++i) nrm += dx[i] * dx[i];
+  return std::sqrt(nrm);
+}
 struct Registration { double R[9]; double t[3]; double rms = 0; int iterations = 0; bool ok = true; };
+// What a registration did, for a caller who asks (esvo_track_solve): one esvo_track_iter_t per outer iteration (at most `cap`;
+// `offset` is the caller's to fill -- the batch schedule lives in its normal_eq) and the reason it stopped
+// (esvo_track_solve_info_t::stop).  A recorder only: no value it stores feeds back into the loop.
+struct RegistrationTrace {
+  esvo_track_iter_t* rec = nullptr;
+  size_t cap = 0;
+  int stop = 0;
+  void put(int it, double cost, double lambda, double step_norm, size_t n, int pick, int trials) {
+    if (!rec || (size_t)it >= cap) return;
+    esvo_track_iter_t& r = rec[it];
+    r.cost = cost; r.lambda = lambda; r.step_norm = step_norm; r.n = (uint32_t)n; r.offset = 0; r.pick = pick; r.trials = trials;
+  }
+};
 // Levenberg-damped Gauss-Newton on x = (Cayley parameters, translation), linearised at x = 0 in every iteration exactly as
 // RegProblemSolverLM::solve_analytical does (RegProblemSolverLM.cpp:160-183: x.fill(0), minimizeInit, ONE minimizeOneStep,
 // addMotionUpdate):
@@ -404,62 +478,65 @@ struct Registration { double R[9]; double t[3]; double rms = 0; int iterations =
 // `normal_eq(it, k, R[k][9], t[k][3], H[k][36], b[k][6], cost[k], &n)` evaluates H = J^T J, b = J^T f, cost = |f|^2 at k poses
 // (1 <= k <= 3) on the batch of outer iteration `it`: esvo_track_normal_equations_batch on the device, or the CPU oracle's
 // restatement in the tests.  same_batch: the batch does not depend on `it`, so the evaluation at an accepted trial pose IS
-// the next iteration's linearisation.
+// the next iteration's linearisation.  trace (optional): a recorder of what each iteration did (RegistrationTrace).
 constexpr int kRegisterTrials = 3;
 template <class NormalEq>
 Registration gauss_newton_register(NormalEq&& normal_eq, const double R0[9], const double t0[3], int max_iterations = 12,
-                                   double damping = 1e-3, bool same_batch = true) {
+                                   double damping = 1e-3, bool same_batch = true, RegistrationTrace* trace = nullptr) {
   constexpr int K = kRegisterTrials;
   Registration g;
+  RegistrationTrace none;
+  RegistrationTrace& tr = trace ? *trace : none;
+  tr.stop = 0;
   for (int i = 0; i < 9; ++i) g.R[i] = R0[i];
   for (int i = 0; i < 3; ++i) g.t[i] = t0[i];
   double H[36], b[6], cost = 0, lambda = damping;
   size_t n = 0;
   bool have = false;
   for (int it = 0; it < max_iterations; ++it) {
-    if (!have && !normal_eq(it, 1, g.R, g.t, H, b, &cost, &n)) { g.ok = false; return g; }
+    if (!have && !normal_eq(it, 1, g.R, g.t, H, b, &cost, &n)) { g.ok = false; tr.stop = 3; return g; }
     have = false;
     g.iterations = it + 1;
     g.rms = n ? std::sqrt(cost / (double)n) : 0.0;
+    const double cost_it = cost;
+    const size_t n_it = n;
     double dx[K][6], Rn[K][9], tn[K][3], Ht[K][36], bt[K][6], cost_t[K];
     size_t nt = 0;
-    int pick = -1;
+    int pick = -1, pick_at = -1, tried = 0;
+    double lam_tried = lambda;  // the damping of the last system set up: the singular one, or the third of the round
     for (int round = 0; round < 2 && pick < 0; ++round) {  // dampings lambda 10^0..2, then lambda 10^3..5
       int k_eff = 0;
       double lam = lambda;
       for (int k = 0; k < K; ++k, lam *= 10.0) {
-        double A[36], rhs[6];
-        for (int i = 0; i < 36; ++i) A[i] = H[i];
-        for (int i = 0; i < 6; ++i) { A[i * 6 + i] = (H[i * 6 + i] + lam * H[i * 6 + i]) + 1e-9; rhs[i] = -b[i]; }
-        if (!solve6(A, rhs, dx[k])) break;
-        double dR[9];
-        cayley2rot(dx[k], dR);
-        for (int r = 0; r < 3; ++r)
-          for (int c = 0; c < 3; ++c)
-            Rn[k][r * 3 + c] = (dR[r * 3 + 0] * g.R[0 * 3 + c] + dR[r * 3 + 1] * g.R[1 * 3 + c]) + dR[r * 3 + 2] * g.R[2 * 3 + c];
-        orthonormalize3(Rn[k]);
-        for (int r = 0; r < 3; ++r) tn[k][r] = dx[k][3 + r] + ((dR[r * 3 + 0] * g.t[0] + dR[r * 3 + 1] * g.t[1]) + dR[r * 3 + 2] * g.t[2]);
+        lam_tried = lam;
+        if (!gn_trial_step(H, b, lam, g.R, g.t, dx[k], Rn[k], tn[k])) break;
         k_eff = k + 1;
       }
-      if (k_eff == 0 || !normal_eq(it, k_eff, &Rn[0][0], &tn[0][0], &Ht[0][0], &bt[0][0], cost_t, &nt)) { g.ok = false; return g; }
+      if (k_eff == 0 || !normal_eq(it, k_eff, &Rn[0][0], &tn[0][0], &Ht[0][0], &bt[0][0], cost_t, &nt)) {
+        g.ok = false; tr.stop = 3; tr.put(it, cost_it, lam_tried, 0.0, n_it, -1, tried);
+        return g;
+      }
       lam = lambda;
       for (int k = 0; k < k_eff && pick < 0; ++k, lam *= 10.0) {
-        double pred = 0;  // -(2 b.dx + dx.H dx)
-        for (int i = 0; i < 6; ++i) {
-          double hd = 0;
-          for (int j = 0; j < 6; ++j) hd += H[i * 6 + j] * dx[k][j];
-          pred -= dx[k][i] * (2.0 * b[i] + hd);
-        }
-        if (pred > 0 && (cost - cost_t[k]) >= 1e-4 * pred) { pick = k; lambda = lam; }
+        const double pred = gn_predicted_reduction(H, b, dx[k]);
+        ++tried;
+        if (gn_accept(pred, cost, cost_t[k])) { pick = k; pick_at = round * K + k; lambda = lam; }
       }
       if (pick < 0) {
-        if (k_eff < K) { g.ok = false; return g; }  // a singular damped system among the trials, none before it acceptable
+        if (k_eff < K) {  // a singular damped system among the trials, none before it acceptable
+          g.ok = false; tr.stop = 3; tr.put(it, cost_it, lam_tried, 0.0, n_it, -1, tried);
+          return g;
+        }
         lambda = lam;  // = lambda x 10 x 10 x 10, the product a one-by-one loop arrives at
       }
     }
-    if (pick < 0) break;  // no step pays any more: (R, t) stays the last accepted pose
+    if (pick < 0) {  // no step pays any more: (R, t) stays the last accepted pose
+      tr.stop = 2; tr.put(it, cost_it, lam_tried, 0.0, n_it, -1, tried);
+      break;
+    }
     for (int i = 0; i < 9; ++i) g.R[i] = Rn[pick][i];
     for (int i = 0; i < 3; ++i) g.t[i] = tn[pick][i];
+    const double lam_pick = lambda;
     lambda = lambda / 10.0 > damping ? lambda / 10.0 : damping;
     if (same_batch) {
       for (int i = 0; i < 36; ++i) H[i] = Ht[pick][i];
@@ -467,9 +544,9 @@ Registration gauss_newton_register(NormalEq&& normal_eq, const double R0[9], con
       cost = cost_t[pick]; n = nt; have = true;
       g.rms = n ? std::sqrt(cost / (double)n) : 0.0;
     }
-    double nrm = 0;
-    for (int i = 0; i < 6; ++i) nrm += dx[pick][i] * dx[pick][i];
-    if (std::sqrt(nrm) < 1e-6) break;
+    const double step = gn_step_norm(dx[pick]);
+    tr.put(it, cost_it, lam_pick, step, n_it, pick_at, tried);
+    if (step < 1e-6) { tr.stop = 1; break; }
   }
   return g;
 }
@@ -531,8 +608,22 @@ class RegProblemLM {
   }
   // RegProblemSolverLM::solve_analytical's loop (RegProblemSolverLM.cpp:148-215) with gauss_newton_register as the step:
   // the batch advances with the iteration as setStochasticSampling does there (:167-168)
-  Registration solve(const double R0[9], const double t0[3], int MAX_ITERATION = 12, double damping = 1e-3) {
+  // on_device: the same loop, the same schedule and the same bits in ONE kernel launch (esvo_track_solve)
+  Registration solve(const double R0[9], const double t0[3], int MAX_ITERATION = 12, double damping = 1e-3, bool on_device = false) {
     const bool batches = cfg_.BATCH_SIZE < numPoints_;
+    if (on_device) {
+      esvo_track_solve_params_t prm = {};
+      prm.n_points = numPoints_; prm.batch_size = cfg_.BATCH_SIZE;
+      prm.ls_norm = cfg_.huber ? ESVO_TRACK_HUBER : ESVO_TRACK_L2; prm.max_iterations = MAX_ITERATION; prm.on_device = 1;
+      prm.huber_threshold = cfg_.huber_threshold; prm.damping = damping;
+      Registration g;
+      for (int i = 0; i < 9; ++i) g.R[i] = R0[i];
+      for (int i = 0; i < 3; ++i) g.t[i] = t0[i];
+      esvo_track_solve_info_t info;
+      ctx_->check(esvo_track_solve(ctx_->handle(), &prm, g.R, g.t, &info, nullptr, 0), "esvo_track_solve");
+      g.rms = info.rms; g.iterations = info.iterations; g.ok = info.ok != 0;
+      return g;
+    }
     auto ne = [&](int it, int k, const double* R, const double* t, double* H, double* b, double* cost, size_t* n) {
       if (batches) setStochasticSampling(((size_t)it % numBatches_) * cfg_.BATCH_SIZE, cfg_.BATCH_SIZE);
       *n = normalEquations(k, R, t, H, b, cost);
