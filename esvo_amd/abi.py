@@ -25,6 +25,9 @@ DEPTH_POINT_DTYPE = np.dtype(
 )
 assert DEPTH_POINT_DTYPE.itemsize == 104
 
+# esvo_status_t values the bindings and the tests name (include/esvo_hip.h)
+ERR_INVALID_ARG, ERR_CAPACITY, ERR_STATE = -1, -4, -6
+
 CAM_LEFT, CAM_RIGHT = 0, 1
 FUSION_CONST_FRAMES, FUSION_CONST_POINTS = 0, 1
 LSNORM_TDIST, LSNORM_L2 = 0, 1

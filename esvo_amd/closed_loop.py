@@ -126,8 +126,12 @@ class _Band:
         return self.dev.comm_gather_map()
 
 
-def _loop(rig, st, p, ops, t0, T0, xyz0, n_ticks, reref, verbose=False, device_register=False):
-    """tracker -> mapper for n_ticks ticks after the bootstrap at t0 (pose T0, reference cloud xyz0); `ops`: _OneGpu / _Band"""
+def _loop(rig, st, p, ops, t0, T0, xyz0, n_ticks, reref, verbose=False, device_register=False, device_reference=False):
+    """tracker -> mapper for n_ticks ticks after the bootstrap at t0 (pose T0, reference cloud xyz0); `ops`: _OneGpu / _Band.
+    device_reference (one plain handle): a re-reference builds the map's cloud on the device (map_cloud_build) and the tracker
+    gathers its 2000 points out of it (track_set_reference_from_cloud) -- the same rng.permutation(n)[:2000] indices as the
+    host route takes out of the downloaded cloud, so both routes register against the same points, bit for bit."""
+    assert not device_reference or (xyz0 is None and isinstance(ops, _OneGpu)), "the device-resident cloud is a one-GPU handle's"
     dev = ops.dev
     T_est = {t0: T0}
     out = {"pos_err": [], "rot_err_deg": [], "cos": [], "est_len": [], "gt_len": [], "points": [],
@@ -140,13 +144,19 @@ def _loop(rig, st, p, ops, t0, T0, xyz0, n_ticks, reref, verbose=False, device_r
         dev.ts_render(0, t, download=False)
         dev.ts_render(1, t, download=False)
         ops.full_left_ts()
-        if xyz is None or (k - 1) % reref == 0:
-            xyz = xyz0 if (xyz is None and xyz0 is not None) else ops.pointcloud()
-            sel = rng.permutation(len(xyz))[:2000]
+        if sel is None or (k - 1) % reref == 0:
+            if device_reference:
+                sel = rng.permutation(dev.map_cloud_build())[:2000]
+            else:
+                xyz = xyz0 if (xyz is None and xyz0 is not None) else ops.pointcloud()
+                sel = rng.permutation(len(xyz))[:2000]
             t_ref = t - TICK_NS
             R_, t_ = np.eye(3), np.zeros(3)
         dev.track_set_current(None, 5)
-        dev.track_set_reference(xyz[sel], T_est[t_ref])
+        if device_reference:
+            dev.track_set_reference_from_cloud(sel, T_est[t_ref])
+        else:
+            dev.track_set_reference(xyz[sel], T_est[t_ref])
         R_, t_, rms = register(dev, len(sel), R_, t_, device_register=device_register)
         Tw = np.eye(4)
         Tw[:3, :3] = T_est[t_ref][:3, :3] @ R_
@@ -201,7 +211,7 @@ def _scene(seed, speed):
     return rig, st, p, st.t0_ns + int(0.08e9)
 
 
-def run(n_ticks=15, reref=10**9, speed=1.0, seed=20250419, verbose=False, device_register=False):
+def run(n_ticks=15, reref=10**9, speed=1.0, seed=20250419, verbose=False, device_register=False, device_reference=False):
     rig, st, p, t0 = _scene(seed, speed)
     dev = lib.Esvo(p, rig)
     dev.ts_push_events(0, st.ev_left)
@@ -211,7 +221,7 @@ def run(n_ticks=15, reref=10**9, speed=1.0, seed=20250419, verbose=False, device
     T0 = st.pose(t0)                      # bootstrap pose given, as the reference's identity at start-up
     dev.set_observation(t0, None, None, T0)
     n_sgm, _ = dev.init_sgm(None, None, min_points=100)
-    out = _loop(rig, st, p, _OneGpu(dev), t0, T0, None, n_ticks, reref, verbose, device_register)
+    out = _loop(rig, st, p, _OneGpu(dev), t0, T0, None, n_ticks, reref, verbose, device_register, device_reference)
     out["sgm_points"] = n_sgm
     dev.close()
     return out

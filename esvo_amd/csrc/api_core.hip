@@ -394,6 +394,12 @@ int esvo_destroy(esvo_handle h) {
   release_routing(h);
   for (int cam = 0; cam < 2; ++cam) if (h->d_wire[cam]) hipFree(h->d_wire[cam]);
   if (h->evt_trk_read) hipEventDestroy(h->evt_trk_read);
+  for (void* q : {(void*)h->d_cloud_xyz[0], (void*)h->d_cloud_xyz[1], (void*)h->d_cloud_ids, (void*)h->d_cloud_scan, (void*)h->d_cloud_cnt}) if (q) hipFree(q);
+  if (h->h_cloud_cnt) hipHostFree(h->h_cloud_cnt);
+  for (int k = 0; k < 2; ++k) {
+    if (h->evt_cloud_built[k]) hipEventDestroy(h->evt_cloud_built[k]);
+    if (h->evt_cloud_read[k]) hipEventDestroy(h->evt_cloud_read[k]);
+  }
   if (h->tl_ref) hipEventDestroy(h->tl_ref);
   for (int cam = 0; cam < 2; ++cam) if (h->evt_ingest[cam]) hipEventDestroy(h->evt_ingest[cam]);
   for (void* q : {(void*)h->d_viz_bgr, (void*)h->d_viz_jet, (void*)h->d_viz_owner}) if (q) hipFree(q);
@@ -419,7 +425,7 @@ int esvo_reset(esvo_handle h) {
   if (!h) return ESVO_ERR_INVALID_ARG;
   API_LOCK(h);
   // a reset excludes the other two groups as well: pushers in flight finish first, the tracker's images go
-  std::lock_guard<std::mutex> lp0(h->mu_push[0]), lp1(h->mu_push[1]), ltk(h->mu_track), lts(h->mu_ts), lr(h->mu_ring);
+  std::lock_guard<std::mutex> lp0(h->mu_push[0]), lp1(h->mu_push[1]), ltk(h->mu_track), lts(h->mu_ts), lr(h->mu_ring), lcl(h->mu_cloud);
   HIPCHK(hipSetDevice(h->device));
   { int rcp = flush_pending_tick(h); if (rcp) return rcp; }
   const size_t npx = (size_t)h->W * h->H;
@@ -470,6 +476,11 @@ int esvo_reset(esvo_handle h) {
   HIPCHK(hipMemsetAsync(h->d_fuse_ctr, 0, sizeof(u32) * 2112, h->stream));
   if (h->d_rank_kept) HIPCHK(hipMemsetAsync(h->d_rank_kept, 0, sizeof(u32) * esvo_context::SHARD_MAX_RANKS, h->stream));
   h->d_map_cur = h->d_map;
+  h->map_id_bound = 0;
+  h->cloud_cur = -1;  // the device-resident cloud is emptied (every stream was drained above: no gather is in flight)
+  h->cloud_n = 0;
+  h->cloud_t_ns = 0;
+  h->cloud_read_pending[0] = h->cloud_read_pending[1] = false;
   h->obs_set = false;
   h->n_pose = 0;
   HIPCHK(hipStreamSynchronize(h->stream));

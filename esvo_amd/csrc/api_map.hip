@@ -425,6 +425,8 @@ int run_fuse(esvo_context* h, int par, const double* T_world_obs, bool naive) {
   launch_fuse(a, h->dp, sb);
   if (timed) hipEventRecord(h->evt[EV_FU1 + o], sb);
   h->d_map_cur = h->d_map;
+  // the ids this fusion numbered (kernels_fuse.hip: record id q K + k, launch_fuse's K): what esvo_map_cloud_build scans over
+  h->map_id_bound = total * ((naive || h->dp.fusion_radius == 0) ? 4u : 9u);
   // (naive propagation, esvo_MVStereo.cpp:416-428: the map is published as it is, neither cleaned nor regularised)
   const bool do_clean = naive ? false : (h->prm.clean_requires_full_window ? (h->n_window_frames >= (size_t)h->prm.max_fusion_frames) : true);
   if (do_clean) launch_clean(h->d_map, h->dp, sb);
@@ -1547,6 +1549,7 @@ extern "C" int esvo_map_init_sgm(esvo_handle h, const uint8_t* ts_left, const ui
   HIPCHK(hipStreamSynchronize(h->stream_l)); HIPCHK(hipStreamSynchronize(h->stream_l1));
   HIPCHK(hipStreamSynchronize(h->stream_b));
   h->d_map_cur = h->d_map;
+  h->map_id_bound = 4u * count;  // (creation ids: ranks of the winning (point, k) pairs, kernels_sgm.hip)
   h->committed_t_ns = h->obs_t_ns;
   h->stats.last_points = count;
   h->stats.last_window_frames = (u32)h->n_window_frames;
@@ -1877,6 +1880,86 @@ int esvo_map_get_pointcloud_xyz(esvo_handle h, float* out_xyz, size_t cap_points
       for (int r = 0; r < 3; ++r)
         out_xyz[3 * i + r] = (float)(((T[r * 4 + 0] * v[i].p_cam[0] + T[r * 4 + 1] * v[i].p_cam[1]) + T[r * 4 + 2] * v[i].p_cam[2]) + T[r * 4 + 3]);
   }
+  return ESVO_OK;
+}
+
+// The same cloud built and kept on the device (kernels_cloud.hip; context.hpp: cloud_*): no element leaves the device, the
+// host reads two counters.
+int esvo_map_cloud_build(esvo_handle h, size_t* n) {
+  if (!h) return ESVO_ERR_INVALID_ARG;
+  API_LOCK(h);
+  if (h->sharded) FAIL(ESVO_ERR_STATE, "handle is sharded");
+  HIPCHK(hipSetDevice(h->device));
+  { int rcp = flush_pending_tick(h); if (rcp) return rcp; }
+  const size_t npx = (size_t)h->W * h->H;
+  if (!h->d_cloud_xyz[1]) {  // first build: nothing of this state is in use yet
+    for (int k = 0; k < 2; ++k) {
+      if (!h->d_cloud_xyz[k]) HIPCHK(hipMalloc(reinterpret_cast<void**>(&h->d_cloud_xyz[k]), npx * 3 * sizeof(float)));
+      if (!h->evt_cloud_built[k]) HIPCHK(hipEventCreateWithFlags(&h->evt_cloud_built[k], hipEventDisableTiming));
+      if (!h->evt_cloud_read[k]) HIPCHK(hipEventCreateWithFlags(&h->evt_cloud_read[k], hipEventDisableTiming));
+    }
+    if (!h->d_cloud_cnt) HIPCHK(hipMalloc(reinterpret_cast<void**>(&h->d_cloud_cnt), sizeof(u32) * 2));
+    if (!h->h_cloud_cnt) HIPCHK(hipHostMalloc(reinterpret_cast<void**>(&h->h_cloud_cnt), sizeof(u32) * 2));
+  }
+  const u32 id_n = h->map_id_bound;
+  if (id_n > h->cloud_id_cap) {  // (the id arrays are read on the back stream only, by earlier builds: all complete -- every build waits for its count)
+    if (h->d_cloud_ids) hipFree(h->d_cloud_ids);
+    if (h->d_cloud_scan) hipFree(h->d_cloud_scan);
+    h->d_cloud_ids = h->d_cloud_scan = nullptr;
+    h->cloud_id_cap = 0;
+    const size_t cap = std::max<size_t>((size_t)id_n + id_n / 4, 4096);
+    HIPCHK(hipMalloc(reinterpret_cast<void**>(&h->d_cloud_ids), sizeof(u32) * 3 * cap));
+    HIPCHK(hipMalloc(reinterpret_cast<void**>(&h->d_cloud_scan), sizeof(u32) * (scan_scratch_elems(cap) + 8)));
+    h->cloud_id_cap = cap;
+  }
+  int w;
+  {
+    std::lock_guard<std::mutex> lc(h->mu_cloud);
+    w = h->cloud_cur < 0 ? 0 : h->cloud_cur ^ 1;  // not the current one: the tracker may be gathering out of that right now
+    if (h->cloud_read_pending[w]) {  // its last gather out of this buffer (two builds ago): waited for on the device
+      HIPCHK(hipStreamWaitEvent(h->stream_b, h->evt_cloud_read[w], 0));
+      h->cloud_read_pending[w] = false;
+    }
+  }
+  u32* present = h->d_cloud_ids;
+  launch_map_cloud(h->d_map_cur, id_n, present, present + h->cloud_id_cap, present + 2 * h->cloud_id_cap, h->d_cloud_cnt, h->d_cloud_scan,
+                   h->T_world_frame, h->d_cloud_xyz[w], (u32)npx, h->dp, h->stream_b);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipMemcpyAsync(h->h_cloud_cnt, h->d_cloud_cnt, sizeof(u32) * 2, hipMemcpyDeviceToHost, h->stream_b));
+  HIPCHK(hipEventRecord(h->evt_cloud_built[w], h->stream_b));
+  HIPCHK(esvo_wait_stream(h->stream_b, true));
+  if (h->h_cloud_cnt[1]) FAIL(ESVO_ERR_STATE, "DepthMap elements carry creation ids beyond the bound of the last fusion (internal error)");
+  const size_t cnt = h->h_cloud_cnt[0];
+  {
+    std::lock_guard<std::mutex> lc(h->mu_cloud);
+    h->cloud_cur = w;
+    h->cloud_n = cnt;
+    h->cloud_t_ns = h->committed_t_ns;
+  }
+  h->stats.last_map_size = (u32)cnt;  // (as the host read-out does)
+  if (n) *n = cnt;
+  return ESVO_OK;
+}
+
+int esvo_map_cloud_get(esvo_handle h, float* out_xyz, size_t cap_points, size_t* n) {
+  if (!h || !n) return ESVO_ERR_INVALID_ARG;
+  API_LOCK(h);  // (no build meanwhile: the snapshot is complete and stays where it is)
+  HIPCHK(hipSetDevice(h->device));
+  const size_t cnt = h->cloud_cur < 0 ? 0 : h->cloud_n;
+  *n = cnt;
+  if (!out_xyz || !cnt) return ESVO_OK;
+  if (cnt > cap_points) FAIL(ESVO_ERR_CAPACITY, "output array too small for the point cloud");
+  HIPCHK(hipMemcpy(out_xyz, h->d_cloud_xyz[h->cloud_cur], cnt * 3 * sizeof(float), hipMemcpyDeviceToHost));
+  return ESVO_OK;
+}
+
+int esvo_map_cloud_device(esvo_handle h, const float** d_xyz, size_t* n, uint64_t* t_ns) {
+  if (!h || !d_xyz || !n) return ESVO_ERR_INVALID_ARG;
+  API_LOCK(h);
+  const bool have = h->cloud_cur >= 0;
+  *d_xyz = have ? h->d_cloud_xyz[h->cloud_cur] : nullptr;
+  *n = have ? h->cloud_n : 0;
+  if (t_ns) *t_ns = have ? h->cloud_t_ns : 0;
   return ESVO_OK;
 }
 

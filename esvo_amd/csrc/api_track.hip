@@ -58,15 +58,14 @@ int esvo_track_get_images(esvo_handle h, uint8_t* neg, int16_t* du, int16_t* dv)
   return ESVO_OK;
 }
 
-int esvo_track_set_reference(esvo_handle h, const float* xyz_world, size_t n, const double T_world_ref[16]) {
-  if (!h || (n && !xyz_world) || !T_world_ref) return ESVO_ERR_INVALID_ARG;
-  std::lock_guard<std::mutex> _trk_lock(h->mu_track);
-  HIPCHK(hipSetDevice(h->device));
+// room for a reference of n points (caller holds mu_track)
+static int track_reserve(esvo_context* h, size_t n) {
   if (n > h->trk_cap) {
     HIPCHK(hipStreamSynchronize(h->stream_t));
     for (void* q : {(void*)h->d_trk_xyz, (void*)h->d_trk_pts, (void*)h->d_trk_out}) if (q) hipFree(q);
     if (h->h_trk_xyz) hipHostFree(h->h_trk_xyz);
     h->d_trk_xyz = nullptr; h->d_trk_pts = nullptr; h->d_trk_out = nullptr; h->h_trk_xyz = nullptr;
+    h->trk_cap = 0; h->trk_n = 0;
     const size_t cap = std::max<size_t>(n, 4096);
     HIPCHK(hipHostMalloc(reinterpret_cast<void**>(&h->h_trk_xyz), cap * 3 * sizeof(float)));
     HIPCHK(hipMalloc(reinterpret_cast<void**>(&h->d_trk_xyz), cap * 3 * sizeof(float)));
@@ -74,6 +73,14 @@ int esvo_track_set_reference(esvo_handle h, const float* xyz_world, size_t n, co
     HIPCHK(hipMalloc(reinterpret_cast<void**>(&h->d_trk_out), cap * 6 * sizeof(double)));
     h->trk_cap = cap;
   }
+  return ESVO_OK;
+}
+
+int esvo_track_set_reference(esvo_handle h, const float* xyz_world, size_t n, const double T_world_ref[16]) {
+  if (!h || (n && !xyz_world) || !T_world_ref) return ESVO_ERR_INVALID_ARG;
+  std::lock_guard<std::mutex> _trk_lock(h->mu_track);
+  HIPCHK(hipSetDevice(h->device));
+  { int rc = track_reserve(h, n); if (rc) return rc; }
   h->trk_n = n;
   if (n) {
     TrackRef r;
@@ -88,6 +95,72 @@ int esvo_track_set_reference(esvo_handle h, const float* xyz_world, size_t n, co
     launch_track_reference(h->d_trk_xyz, (u32)n, r, h->d_trk_pts, h->stream_t);
     HIPCHK(hipGetLastError());
   }
+  return ESVO_OK;
+}
+
+// setProblem's point loop on the device-resident cloud of esvo_map_cloud_build: nothing but the indices travels
+int esvo_track_set_reference_from_cloud(esvo_handle h, const uint32_t* order, size_t n, const double T_world_ref[16]) {
+  if (!h || !T_world_ref) return ESVO_ERR_INVALID_ARG;
+  std::lock_guard<std::mutex> _trk_lock(h->mu_track);
+  HIPCHK(hipSetDevice(h->device));
+  // The snapshot cannot change under this call's feet: a build fills the OTHER buffer, and the one after it -- the first that
+  // writes this one again -- queues behind evt_cloud_read.  cloud_cur / cloud_n are re-read under mu_cloud where the gather is
+  // enqueued; a build that has published meanwhile only makes this call gather out of the newer snapshot, so the indices are
+  // checked there, against the count of the buffer that is read.
+  size_t cloud_n = 0;
+  {
+    std::lock_guard<std::mutex> lc(h->mu_cloud);
+    if (h->cloud_cur < 0) FAIL(ESVO_ERR_STATE, "no device-resident point cloud: call esvo_map_cloud_build first");
+    cloud_n = h->cloud_n;
+  }
+  if (!order) n = std::min(n, cloud_n);  // numPoints_ = min(size, MAX_REGISTRATION_POINTS_), :38-40
+  if (n > 0xffffffffull) FAIL(ESVO_ERR_CAPACITY, "more reference points than 32-bit indices address");
+  if (n > h->trk_cap) {  // (before anything else changes: the reserve drops the previous reference's buffers)
+    if (order)
+      for (size_t i = 0; i < n; ++i)
+        if (order[i] >= cloud_n) FAIL(ESVO_ERR_INVALID_ARG, "order holds an index beyond the cloud's point count");
+    int rc = track_reserve(h, n);
+    if (rc) return rc;
+  }
+  if (order && n) {
+    // the indices go through the pinned staging buffer the xyz take on the host route (4 of its 12 bytes per point) into
+    // d_trk_xyz, which this route does not otherwise use
+    if (h->trk_xyz_inflight) HIPCHK(hipStreamSynchronize(h->stream_t));
+  }
+  TrackRef r;
+  std::memcpy(r.T, T_world_ref, sizeof(r.T));
+  std::lock_guard<std::mutex> lc(h->mu_cloud);
+  if (h->cloud_cur < 0) FAIL(ESVO_ERR_STATE, "no device-resident point cloud: call esvo_map_cloud_build first");
+  const int cb = h->cloud_cur;
+  cloud_n = h->cloud_n;
+  if (!order) n = std::min(n, cloud_n);
+  else
+    for (size_t i = 0; i < n; ++i)
+      if (order[i] >= cloud_n) FAIL(ESVO_ERR_INVALID_ARG, "order holds an index beyond the cloud's point count");
+  h->trk_n = n;
+  if (n == 0) return ESVO_OK;
+  const u32* d_order = nullptr;
+  if (order) {
+    std::memcpy(h->h_trk_xyz, order, n * sizeof(u32));
+    h->trk_xyz_inflight = true;
+    HIPCHK(hipMemcpyAsync(h->d_trk_xyz, h->h_trk_xyz, n * sizeof(u32), hipMemcpyHostToDevice, h->stream_t));
+    d_order = reinterpret_cast<const u32*>(h->d_trk_xyz);
+  }
+  HIPCHK(hipStreamWaitEvent(h->stream_t, h->evt_cloud_built[cb], 0));
+  launch_track_reference_gather(h->d_cloud_xyz[cb], d_order, (u32)n, r, h->d_trk_pts, h->stream_t);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipEventRecord(h->evt_cloud_read[cb], h->stream_t));
+  h->cloud_read_pending[cb] = true;
+  return ESVO_OK;
+}
+
+// the order the stochastic swaps of RegProblemLM::setProblem (:48-49) leave, from the draws alone (host code, no handle)
+int esvo_track_stochastic_order(size_t n_cloud, size_t n_take, const uint32_t* draws, uint32_t* order) {
+  esvo_context* h = nullptr;
+  n_take = std::min(n_take, n_cloud);
+  if (n_take && (!draws || !order)) return ESVO_ERR_INVALID_ARG;
+  if (n_cloud > 0xffffffffull) FAIL(ESVO_ERR_CAPACITY, "more cloud points than 32-bit indices address");
+  esvo_hip::stochastic_order(n_cloud, n_take, draws, order);
   return ESVO_OK;
 }
 }  // extern "C"

@@ -292,6 +292,8 @@ struct TrackArgs {
 };
 void launch_track_images(const uint8_t* blurred, uint8_t* neg, int16_t* du, int16_t* dv, int W, int H, hipStream_t s);
 void launch_track_reference(const float* xyz, u32 n, const TrackRef& r, double* pts, hipStream_t s);
+// the same on the points cloud_xyz[order[i]] (order == nullptr: cloud_xyz[i]) of a device-resident cloud: gather + transform in one launch
+void launch_track_reference_gather(const float* cloud_xyz, const u32* order, u32 n, const TrackRef& r, double* pts, hipStream_t s);
 void launch_track_residuals(const TrackArgs& a, const TrackPose& pose, u32 offset, u32 count, int huber, double thr, double* fvec,
                             hipStream_t s);
 void launch_track_jacobian(const TrackArgs& a, const TrackPose& pose, u32 offset, u32 count, double* fjac, hipStream_t s);
@@ -441,5 +443,8 @@ void launch_debug_image(const MapCell* map, u32* owner, uint8_t* bgr, const uint
                         double min_range, double thr1, double thr2, const DevParams& p, hipStream_t s);
 void launch_map_compact(const MapCell* map, u32* flags, u32* prefix, u32* d_total, u32* scan_tmp,
                         esvo_depth_point_t* out, u32* out_cell, const DevParams& p, hipStream_t s);
+// kernels_cloud.hip: the map's point cloud in list order, on the device (present | prefix | where: id_n words each; counts: 2 words)
+void launch_map_cloud(const MapCell* map, u32 id_n, u32* present, u32* prefix, u32* where, u32* counts, u32* scan_tmp, const double* T_world_frame,
+                      float* xyz, u32 cap_points, const DevParams& p, hipStream_t s);
 
 }  // namespace esvo

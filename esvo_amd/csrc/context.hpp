@@ -146,6 +146,14 @@ struct esvo_context {
   std::mutex mu_track;          // tracker-group calls
   std::mutex mu_ts;             // the resident left Time Surface (d_ts[0], ts_valid[0], EV_R1) between a render and a
                                 // tracker read (esvo_track_set_current without a host image)
+  std::mutex mu_cloud;          // the device-resident point cloud between a build (mapper group) and a tracker gather
+                                // (esvo_track_set_reference_from_cloud): cloud_cur, cloud_n, cloud_t_ns, evt_cloud_built,
+                                // evt_cloud_read and cloud_read_pending.  Held only while those change or while work that reads
+                                // or writes a buffer is ENQUEUED -- never across a host wait, so neither group waits on the host
+                                // for the other: the build fills the buffer that is NOT current and publishes it afterwards.
+  // Lock order: mu_api (API_LOCK) comes before mu_track, never after it -- esvo_reset takes mu_api, mu_push[0..1], mu_track,
+  // mu_ts, mu_ring in that order, and no tracker-group call takes mu_api.  mu_cloud is innermost for both groups (mapper:
+  // mu_api -> mu_cloud; tracker: mu_track -> mu_cloud; esvo_reset holds all of them) and nothing is locked under it.
 
   // calibration
   float2* d_lut = nullptr;
@@ -375,6 +383,26 @@ struct esvo_context {
   u32* d_exp_prefix = nullptr;
   esvo_depth_point_t* d_export = nullptr;
   u32* d_export_cell = nullptr;
+  // The map's point cloud kept on the device (esvo_map_cloud_build; kernels_cloud.hip): a SNAPSHOT in one of two buffers of W*H
+  // points (allocated by the first build).  A build fills the buffer that is not current, on the back stream and behind the
+  // event of the tracker's last gather out of it (evt_cloud_read), records evt_cloud_built, reads the count -- its one host
+  // read -- and only then makes the buffer current, under mu_cloud.  The tracker's gather runs on its own stream behind
+  // evt_cloud_built.  Ticks never touch the buffers; esvo_reset empties them (cloud_cur = -1).
+  u32 map_id_bound = 0;           // creation ids of d_map_cur are below this: what the fusion that built it numbered (run_fuse:
+                                  // points x records per point; esvo_map_init_sgm: 4 x points).  Recorded where the ids are
+                                  // assigned: the window may shrink afterwards without a fusion (esvo_map_push_frame).
+  float* d_cloud_xyz[2] = {nullptr, nullptr};
+  int cloud_cur = -1;             // the buffer that holds the snapshot (-1: none -- before the first build, after a reset)
+  size_t cloud_n = 0;
+  u64 cloud_t_ns = 0;             // committed_t_ns at the build
+  u32* d_cloud_ids = nullptr;     // [3][cloud_id_cap] present | prefix | where, by creation id
+  size_t cloud_id_cap = 0;
+  u32* d_cloud_scan = nullptr;    // scan scratch for cloud_id_cap ids
+  u32* d_cloud_cnt = nullptr;     // [0] elements [1] cells whose id was outside the bound (must stay 0)
+  u32* h_cloud_cnt = nullptr;     // pinned copy of it
+  hipEvent_t evt_cloud_built[2] = {nullptr, nullptr};
+  hipEvent_t evt_cloud_read[2] = {nullptr, nullptr};   // the tracker stream's newest gather out of that buffer
+  bool cloud_read_pending[2] = {false, false};
 
   // tracker residual / Jacobian evaluation (kernels_track.hip): own stream, own images, synchronous calls
   hipStream_t stream_t = nullptr;

@@ -52,6 +52,25 @@ void launch_track_reference(const float* xyz, u32 n, const TrackRef& r, double* 
   hipLaunchKernelGGL(track_reference_kernel, dim3((n + 255) / 256), dim3(256), 0, s, xyz, n, r, pts);
 }
 
+// The same loop on a cloud that is already on the device (esvo_track_set_reference_from_cloud): position i takes the cloud's
+// point order[i] -- what ref->vPointXYZPtr_[i] is after the swaps of :48-49 -- or point i (order == nullptr); gather and
+// transform in one launch, the expressions of track_reference_kernel.  The host has checked every index against the count.
+__global__ void __launch_bounds__(256) track_reference_gather_kernel(const float* __restrict__ cloud, const u32* __restrict__ order, u32 n,
+                                                                     TrackRef r, double* __restrict__ pts) {
+  const u32 i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const size_t j = order ? order[i] : i;
+  double d[3];
+#pragma unroll
+  for (int k = 0; k < 3; ++k) d[k] = (double)cloud[3 * j + k] - r.T[k * 4 + 3];
+#pragma unroll
+  for (int c = 0; c < 3; ++c) pts[3 * i + c] = (r.T[0 * 4 + c] * d[0] + r.T[1 * 4 + c] * d[1]) + r.T[2 * 4 + c] * d[2];
+}
+void launch_track_reference_gather(const float* cloud_xyz, const u32* order, u32 n, const TrackRef& r, double* pts, hipStream_t s) {
+  if (n == 0) return;
+  hipLaunchKernelGGL(track_reference_gather_kernel, dim3((n + 255) / 256), dim3(256), 0, s, cloud_xyz, order, n, r, pts);
+}
+
 // reprojection (:387-401) + isValidPatch (:366-385) for a 1x1 patch
 __device__ inline bool trk_reproject(const TrackArgs& a, const double p[3], const double* T, double x[2]) {
   double pl[3];

@@ -10,14 +10,14 @@ import subprocess
 
 import numpy as np
 
-from .abi import (DEPTH_POINT_DTYPE, EM_POSE_FN, EVENT_DTYPE, MATCH_DTYPE, CalibStruct, EmSelectionStruct,
+from .abi import (DEPTH_POINT_DTYPE, EM_POSE_FN, ERR_CAPACITY, ERR_INVALID_ARG, ERR_STATE, EVENT_DTYPE, MATCH_DTYPE, CalibStruct, EmSelectionStruct,
                   EmStatsStruct, ParamsStruct, SgmStatsStruct, StatsStruct, TRACK_ITER_DTYPE, TRACK_SOLVE_MAX_ITERATIONS,
                   TrackSolveInfoStruct, TrackSolveParamsStruct)
 
 _CSRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc")
 # ESVO_HIP_LIB: another build of the same library (A/B measurements of kernel variants, tools/ab_build.py); never a fallback
 _LIB_PATH = os.environ.get("ESVO_HIP_LIB") or os.path.join(_CSRC, "libesvo_hip.so")
-_SOURCES = ["api_core.hip", "api_ts.hip", "api_map.hip", "api_comm.hip", "api_bag.hip", "api_track.hip", "scan.hip", "kernels_ts.hip", "kernels_bm.hip", "kernels_lm.hip", "kernels_lm_any.hip", "kernels_fuse.hip", "kernels_shard.hip", "kernels_track.hip", "kernels_viz.hip", "kernels_sgm.hip", "api_em.hip", "kernels_em.hip"]
+_SOURCES = ["api_core.hip", "api_ts.hip", "api_map.hip", "api_comm.hip", "api_bag.hip", "api_track.hip", "scan.hip", "kernels_ts.hip", "kernels_bm.hip", "kernels_lm.hip", "kernels_lm_any.hip", "kernels_fuse.hip", "kernels_shard.hip", "kernels_track.hip", "kernels_viz.hip", "kernels_sgm.hip", "api_em.hip", "kernels_em.hip", "kernels_cloud.hip"]
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared",
                "-Wno-unused-value", "-Wno-unused-result", "-ldl"]
 
@@ -37,6 +37,7 @@ SYMBOLS = [
     "esvo_comm_tick", "esvo_comm_tick_resident", "esvo_comm_get_stats", "esvo_comm_flush", "esvo_comm_newest_map", "esvo_comm_shard_tick", "esvo_comm_gather_map", "esvo_comm_gather_pointcloud_xyz", "esvo_comm_gather_ts",
     "esvo_map_match_em", "esvo_map_tick_em", "esvo_map_em_get_selection", "esvo_map_em_stats", "esvo_em_sizes",
     "esvo_map_tick_sgm", "esvo_map_push_disparity_frame", "esvo_map_sgm_stats", "esvo_sgm_sizes",
+    "esvo_map_cloud_build", "esvo_map_cloud_get", "esvo_map_cloud_device", "esvo_track_set_reference_from_cloud", "esvo_track_stochastic_order",
 ]
 
 ALL_GATHER_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p)
@@ -218,6 +219,11 @@ def load():
     lib.esvo_map_sgm_stats.argtypes = [vp, vp]
     lib.esvo_sgm_sizes.argtypes = [vp]
     lib.esvo_sgm_sizes.restype = None
+    lib.esvo_map_cloud_build.argtypes = [vp, psz]
+    lib.esvo_map_cloud_get.argtypes = [vp, vp, sz, psz]
+    lib.esvo_map_cloud_device.argtypes = [vp, C.POINTER(vp), psz, C.POINTER(C.c_uint64)]
+    lib.esvo_track_set_reference_from_cloud.argtypes = [vp, vp, sz, vp]
+    lib.esvo_track_stochastic_order.argtypes = [sz, sz, vp, vp]
     for s in SYMBOLS:
         if s not in ("esvo_default_params", "esvo_last_error", "esvo_abi_sizes", "esvo_bag_last_error", "esvo_em_sizes", "esvo_sgm_sizes",
                      "esvo_track_sizes"):
@@ -227,6 +233,37 @@ def load():
     lib.esvo_bag_last_error.restype = C.c_char_p
     _lib = lib
     return lib
+
+
+def stochastic_order(n_cloud, n_take, draws):
+    """The order RegProblemLM::setProblem's swaps (RegProblemLM.cpp:45-49) leave, from the cloud's size and the draws alone:
+    for i < min(n_take, n_cloud), positions i and i + draws[i] % (n_cloud - i) of the identity over n_cloud are swapped;
+    returns what ends up at the positions [0, n_take) as uint32.  O(n_take) through a sparse map -- include/esvo_hip.hpp's
+    esvo_hip::stochastic_order (and the library's esvo_track_stochastic_order) in Python."""
+    n_cloud, n_take = int(n_cloud), min(int(n_take), int(n_cloud))
+    draws = np.asarray(draws, np.uint32)
+    assert len(draws) >= n_take, "one draw per taken point"
+    moved, order = {}, np.empty(n_take, np.uint32)
+    for i in range(n_take):
+        j = i + int(draws[i]) % (n_cloud - i)
+        vi, vj = moved.get(i, i), moved.get(j, j)
+        order[i] = vj
+        moved[j] = vi
+        moved.pop(i, None)
+    return order
+
+
+def stochastic_order_c(n_cloud, n_take, draws):
+    """the same through the library's C entry esvo_track_stochastic_order (which calls the C++ inline)"""
+    lib = load()
+    n_cloud, n_take = int(n_cloud), min(int(n_take), int(n_cloud))
+    draws = np.ascontiguousarray(draws, np.uint32)
+    assert len(draws) >= n_take, "one draw per taken point"
+    order = np.empty(n_take, np.uint32)
+    rc = lib.esvo_track_stochastic_order(n_cloud, n_take, draws.ctypes.data if n_take else None, order.ctypes.data if n_take else None)
+    if rc != 0:
+        raise EsvoError(f"esvo_track_stochastic_order failed ({rc}): {lib.esvo_last_error(None).decode(errors='replace')}", code=rc)
+    return order
 
 
 def selftest_division(n=1 << 28, seed=1):
@@ -608,6 +645,27 @@ class Esvo:
         self._ck(self.lib.esvo_map_get_pointcloud_xyz(self.h, out.ctypes.data, out.shape[0], C.byref(n)))
         return out[: n.value].copy()
 
+    def map_cloud_build(self):
+        """esvo_map_cloud_build: the cloud of get_pointcloud() built and kept on the device (a snapshot); returns its point count"""
+        n = C.c_size_t(0)
+        self._ck(self.lib.esvo_map_cloud_build(self.h, C.byref(n)))
+        return int(n.value)
+
+    def map_cloud(self):
+        """the snapshot of the last map_cloud_build() as (n, 3) float32 (12 B per point cross the bus); empty before a build"""
+        n = C.c_size_t(0)
+        self._ck(self.lib.esvo_map_cloud_get(self.h, None, 0, C.byref(n)))
+        out = np.zeros((int(n.value), 3), np.float32)
+        if n.value:
+            self._ck(self.lib.esvo_map_cloud_get(self.h, out.ctypes.data, out.shape[0], C.byref(n)))
+        return out
+
+    def map_cloud_device(self):
+        """(device pointer, point count, stamp of the tick it was built from) of the snapshot: valid until the next build / reset"""
+        ptr, n, t = C.c_void_p(), C.c_size_t(), C.c_uint64()
+        self._ck(self.lib.esvo_map_cloud_device(self.h, C.byref(ptr), C.byref(n), C.byref(t)))
+        return (ptr.value or 0), int(n.value), int(t.value)
+
     def get_debug_images(self, age_max_range=10.0):
         """(inverse depth, standard deviation, age, cost) images of publishMappingResults, BGR8"""
         imgs = [np.empty((self.H, self.W, 3), np.uint8) for _ in range(4)]
@@ -672,6 +730,17 @@ class Esvo:
         xyz = np.ascontiguousarray(xyz_world, np.float32).reshape(-1, 3)
         T = np.ascontiguousarray(T_world_ref, np.float64).reshape(16)
         self._ck(self.lib.esvo_track_set_reference(self.h, xyz.ctypes.data, xyz.shape[0], T.ctypes.data))
+
+    def track_set_reference_from_cloud(self, order, T_world_ref, n=None):
+        """esvo_track_set_reference_from_cloud: position i of the reference = point order[i] of the map_cloud_build() snapshot
+        (stochastic_order); order None: the first n points in list order.  Same bits as track_set_reference(cloud[order], T)"""
+        T = np.ascontiguousarray(T_world_ref, np.float64).reshape(16)
+        if order is None:
+            assert n is not None, "order=None needs n"
+            self._ck(self.lib.esvo_track_set_reference_from_cloud(self.h, None, int(n), T.ctypes.data))
+            return
+        o = np.ascontiguousarray(order, np.uint32).reshape(-1)
+        self._ck(self.lib.esvo_track_set_reference_from_cloud(self.h, o.ctypes.data if len(o) else None, len(o), T.ctypes.data))
 
     def track_residuals(self, T_left_ref, offset, count, huber=True, huber_threshold=50.0):
         T = np.ascontiguousarray(T_left_ref, np.float64).reshape(16)

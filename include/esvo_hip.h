@@ -567,6 +567,26 @@ int esvo_map_get_committed(esvo_handle h, esvo_depth_point_t* out, size_t cap, s
 /* Replaces the loop of publishPointCloud (esvo_Mapping.cpp:925-932): p_world = R p_cam + t
  * as float32 xyz triples, the payload of /esvo_mapping/pointcloud_local. */
 int esvo_map_get_pointcloud_xyz(esvo_handle h, float* out_xyz, size_t cap_points, size_t* n);
+/* The same cloud built and KEPT on the device: replaces publishPointCloud's loop (esvo_Mapping.cpp:925-932) together with the
+ * /esvo_mapping/pointcloud_local hop to the tracking node (esvo_Tracking.cpp:107-108, refDataTransferring :203-234) -- the
+ * tracker takes its reference straight from this buffer (esvo_track_set_reference_from_cloud).
+ * esvo_map_cloud_build completes a pending tick as esvo_map_get_pointcloud_xyz does, then writes the cloud of the current
+ * DepthMap into a buffer the handle owns: the points, order (the reference's list order) and float bits of
+ * esvo_map_get_pointcloud_xyz, with no element download and no host sort; *n (may be NULL) receives the point count, the one
+ * value the host reads.  The buffer is a SNAPSHOT: later ticks leave it alone until the next build; esvo_reset empties it.
+ * Mapper-group call; it may run while the tracker group registers against the previous snapshot (the two are ordered on the
+ * device, neither waits on the host for the other).  ESVO_ERR_STATE on a sharded handle (esvo_comm_gather_pointcloud_xyz is
+ * the band mode's cloud).
+ * esvo_map_cloud_get copies the snapshot out, 12 bytes per point: *n = its point count (0 before the first build and after a
+ * reset); out_xyz == NULL returns the count only; ESVO_ERR_CAPACITY when cap_points is too small.
+ * esvo_map_cloud_device lends the snapshot to a HIP caller: *d_xyz = device pointer to *n float triples (NULL when there is
+ * none), *t_ns (may be NULL) = stamp of the tick the snapshot was built from.  Stream rule: the snapshot is complete when
+ * esvo_map_cloud_build returns, so any stream may read it from then on without an event; the pointer stays valid and its
+ * contents unchanged until the next esvo_map_cloud_build, esvo_reset or esvo_destroy, and the caller must have waited for its
+ * own reads (an event or a stream synchronisation of its own) before it makes one of these calls. */
+int esvo_map_cloud_build(esvo_handle h, size_t* n);
+int esvo_map_cloud_get(esvo_handle h, float* out_xyz, size_t cap_points, size_t* n);
+int esvo_map_cloud_device(esvo_handle h, const float** d_xyz, size_t* n, uint64_t* t_ns);
 /* ---- Debug images and global-cloud helpers ----
  * Replaces Visualization::plot_map / DrawPoint (Visualization.cpp:13-94) as esvo_Mapping::publishMappingResults calls
  * them for the topics Inverse_Depth_Map, Standard_Variance_Map, Age_Map and cost_map (esvo_Mapping.cpp:868-884): BGR8
@@ -751,6 +771,19 @@ int esvo_track_get_images(esvo_handle h, uint8_t* neg, int16_t* du, int16_t* dv)
  * xyz_world: n x 3 float32 in the caller's order, i.e. after the stochastic swaps of :48-49 (rand() stays with
  * the caller). */
 int esvo_track_set_reference(esvo_handle h, const float* xyz_world, size_t n, const double T_world_ref[16]);
+/* The same loop (RegProblemLM.cpp:38-55) on the snapshot of esvo_map_cloud_build, in one launch on the tracker's stream:
+ * position i of the reference takes cloud point order[i] -- what ref->vPointXYZPtr_[i] is after the swaps of :48-49
+ * (esvo_track_stochastic_order) -- then p = R_world_ref^T (p_world - t_world_ref).  Equal bit for bit to
+ * esvo_track_set_reference(h, cloud[order], n, T_world_ref); only the n indices travel.  order == NULL: the first
+ * min(n, cloud) points in list order.  An index may repeat.  Refused with the previous reference left in place:
+ * ESVO_ERR_STATE before any esvo_map_cloud_build or after esvo_reset, ESVO_ERR_INVALID_ARG for an index >= the cloud's
+ * count.  Tracker-group call. */
+int esvo_track_set_reference_from_cloud(esvo_handle h, const uint32_t* order, size_t n, const double T_world_ref[16]);
+/* The stochastic swaps of setProblem (RegProblemLM.cpp:45-49) from the cloud's SIZE alone (host code, no handle): for
+ * i < n_take, positions i and i + draws[i] % (n_cloud - i) of the identity over n_cloud are swapped; order[i] is what ends
+ * up at position i.  draws[i] is the reference's rand() of that step, which stays with the caller.  n_take > n_cloud is
+ * clamped (:39-40); O(n_take) time and memory.  esvo_hip::stochastic_order (esvo_hip.hpp) is the same function inline. */
+int esvo_track_stochastic_order(size_t n_cloud, size_t n_take, const uint32_t* draws, uint32_t* order);
 /* RegProblemLM::operator() (:91-136) on the batch [offset, offset+count) of setStochasticSampling (:71-88):
  * fvec[i] = sqrt(w_i) r_i, r_i = TS_negative(x_i) or 255 when the point does not reproject. */
 int esvo_track_residuals(esvo_handle h, const double T_left_ref[16], size_t offset, size_t count, int ls_norm,

@@ -28,6 +28,7 @@
 #include <memory>
 #include <stdexcept>
 #include <string>
+#include <unordered_map>
 #include <vector>
 
 #include "esvo_hip.h"
@@ -278,6 +279,19 @@ class DepthFusion {
     size_t n = 0;
     ctx_->check(esvo_map_get_pointcloud_xyz(ctx_->handle(), xyz.data(), xyz.size() / 3, &n), "esvo_map_get_pointcloud_xyz");
     xyz.resize(n * 3);
+  }
+  // the same cloud built and KEPT on the device (esvo_map_cloud_build): returns its point count; RegProblemLM::setProblemFromMap
+  // registers against it, getDevicePointCloud copies it out (12 B per point)
+  size_t buildPointCloud() {
+    size_t n = 0;
+    ctx_->check(esvo_map_cloud_build(ctx_->handle(), &n), "esvo_map_cloud_build");
+    return n;
+  }
+  void getDevicePointCloud(std::vector<float>& xyz) {
+    size_t n = 0;
+    ctx_->check(esvo_map_cloud_get(ctx_->handle(), nullptr, 0, &n), "esvo_map_cloud_get");
+    xyz.resize(n * 3);
+    ctx_->check(esvo_map_cloud_get(ctx_->handle(), xyz.data(), n, &n), "esvo_map_cloud_get");
   }
 
  private:
@@ -551,6 +565,26 @@ Registration gauss_newton_register(NormalEq&& normal_eq, const double R0[9], con
   return g;
 }
 
+// The stochastic swaps of RegProblemLM::setProblem (RegProblemLM.cpp:45-49) without the cloud: for i < n_take the reference swaps
+// vPointXYZPtr_[i] with vPointXYZPtr_[i + rand() % (size - i)]; draws[i] is that rand() (it stays with the caller), and
+// order[i] is the index -- in the cloud as it was before the swaps -- of the point that ends up at position i.  Only the
+// positions the swaps touch are remembered (a sparse map over the identity): O(n_take) time and memory whatever n_cloud is.
+// n_take > n_cloud is clamped (:39-40); order has room for min(n_take, n_cloud) indices.  Returns how many it wrote.
+inline size_t stochastic_order(size_t n_cloud, size_t n_take, const uint32_t* draws, uint32_t* order) {
+  if (n_take > n_cloud) n_take = n_cloud;
+  std::unordered_map<size_t, uint32_t> moved;  // position -> what it holds, where that is not the position itself
+  moved.reserve(2 * n_take);
+  auto at = [&](size_t p) { const auto it = moved.find(p); return it == moved.end() ? (uint32_t)p : it->second; };
+  for (size_t i = 0; i < n_take; ++i) {
+    const size_t j = i + (size_t)draws[i] % (n_cloud - i);
+    const uint32_t vi = at(i), vj = at(j);
+    order[i] = vj;      // position i is final: every later swap touches positions > i only
+    moved[j] = vi;
+    moved.erase(i);
+  }
+  return n_take;
+}
+
 // esvo_core::core::RegProblemLM's evaluation side (esvo_core/src/core/RegProblemLM.cpp): the per-point loops of
 // setProblem (:44-56), operator() (:91-136) and df (:178-269) on the device.  The 6-DoF LM driver, the Cayley update and
 // the SVD re-orthonormalisation (getWarpingTransformation / addMotionUpdate, :328-364) stay with the caller, who passes
@@ -570,6 +604,28 @@ class RegProblemLM {
   void setProblem(const float* ref_xyz_world, size_t n_points, const double T_world_ref[16], const uint8_t* cur_TS_left) {
     numPoints_ = std::min(n_points, cfg_.MAX_REGISTRATION_POINTS);
     ctx_->check(esvo_track_set_reference(ctx_->handle(), ref_xyz_world, numPoints_, T_world_ref), "esvo_track_set_reference");
+    ctx_->check(esvo_track_set_current(ctx_->handle(), cur_TS_left, cfg_.kernelSize), "esvo_track_set_current");
+    numBatches_ = std::max(numPoints_ / cfg_.BATCH_SIZE, (size_t)1);
+    setStochasticSampling(0, numPoints_);
+  }
+  // setProblem on the mapper's device-resident cloud (DepthFusion::buildPointCloud, same Context): what the tracking node's
+  // refDataTransferring + setProblem do with /esvo_mapping/pointcloud_local (esvo_Tracking.cpp:203-234, RegProblemLM.cpp:38-55)
+  // without the cloud leaving the device.  draws[i]: the rand() of swap i (:49), n_draws >= min(cloud, MAX_REGISTRATION_POINTS)
+  // of them; draws == nullptr: no swaps, the first points in list order.
+  void setProblemFromMap(const uint32_t* draws, size_t n_draws, const double T_world_ref[16], size_t MAX_REGISTRATION_POINTS,
+                         const uint8_t* cur_TS_left) {
+    const float* d_xyz = nullptr;
+    size_t n_cloud = 0;
+    ctx_->check(esvo_map_cloud_device(ctx_->handle(), &d_xyz, &n_cloud, nullptr), "esvo_map_cloud_device");
+    numPoints_ = std::min(n_cloud, MAX_REGISTRATION_POINTS);
+    if (draws) {
+      if (n_draws < numPoints_) throw Error(ESVO_ERR_INVALID_ARG, "setProblemFromMap: fewer draws than registration points");
+      std::vector<uint32_t> order(numPoints_);
+      stochastic_order(n_cloud, numPoints_, draws, order.data());
+      ctx_->check(esvo_track_set_reference_from_cloud(ctx_->handle(), order.data(), numPoints_, T_world_ref), "esvo_track_set_reference_from_cloud");
+    } else {
+      ctx_->check(esvo_track_set_reference_from_cloud(ctx_->handle(), nullptr, numPoints_, T_world_ref), "esvo_track_set_reference_from_cloud");
+    }
     ctx_->check(esvo_track_set_current(ctx_->handle(), cur_TS_left, cfg_.kernelSize), "esvo_track_set_current");
     numBatches_ = std::max(numPoints_ / cfg_.BATCH_SIZE, (size_t)1);
     setStochasticSampling(0, numPoints_);
