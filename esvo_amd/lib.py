@@ -17,7 +17,7 @@ from .abi import (DEPTH_POINT_DTYPE, EM_POSE_FN, ERR_CAPACITY, ERR_INVALID_ARG, 
 _CSRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc")
 # ESVO_HIP_LIB: another build of the same library (A/B measurements of kernel variants, tools/ab_build.py); never a fallback
 _LIB_PATH = os.environ.get("ESVO_HIP_LIB") or os.path.join(_CSRC, "libesvo_hip.so")
-_SOURCES = ["api_core.hip", "api_ts.hip", "api_map.hip", "api_comm.hip", "api_bag.hip", "api_track.hip", "scan.hip", "kernels_ts.hip", "kernels_bm.hip", "kernels_lm.hip", "kernels_lm_any.hip", "kernels_fuse.hip", "kernels_shard.hip", "kernels_track.hip", "kernels_viz.hip", "kernels_sgm.hip", "api_em.hip", "kernels_em.hip", "kernels_cloud.hip"]
+_SOURCES = ["api_core.hip", "api_ts.hip", "api_map.hip", "api_comm.hip", "api_bag.hip", "api_track.hip", "scan.hip", "kernels_ts.hip", "kernels_bm.hip", "kernels_lm.hip", "kernels_lm_any.hip", "kernels_fuse.hip", "kernels_shard.hip", "kernels_track.hip", "kernels_viz.hip", "kernels_sgm.hip", "api_em.hip", "kernels_em.hip", "kernels_cloud.hip", "api_dev.hip"]
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared",
                "-Wno-unused-value", "-Wno-unused-result", "-ldl"]
 
@@ -277,6 +277,212 @@ def selftest_division(n=1 << 28, seed=1):
     if rc != 0:
         raise EsvoError(f"selftest failed ({rc}): {lib.esvo_last_error(None).decode(errors='replace')}")
     return bad.value
+
+
+# ---- esvo_debug_* (api_dev.hip): the shared device primitives one launch at a time; tests/test_gpu_primitives.py -----------------
+# Not part of the documented ABI.  Every buffer the kernel may write sits between guard words on the device; the buffers start
+# filled with DEBUG_PREFILL_BYTE, so "never written" and "written as zero" differ.  Each call returns its results and, last,
+# the number of disturbed guard words (must be 0).
+DEBUG_PREFILL_BYTE = 0xC7
+DEBUG_PREFILL_U32 = 0xC7C7C7C7
+
+
+def _prefilled(n, dtype):
+    a = np.empty(int(n), dtype)
+    a.view(np.uint8)[...] = DEBUG_PREFILL_BYTE
+    return a
+
+
+def _dbg_fn(name, argtypes):
+    fn = getattr(load(), name)
+    fn.argtypes, fn.restype = argtypes, C.c_int
+    return fn
+
+
+def _dbg_rc(rc, name):
+    if rc < 0:
+        raise EsvoError(f"{name} failed ({rc}): {load().esvo_last_error(None).decode(errors='replace')}", code=rc)
+    return int(rc)
+
+
+def _dbg_array(a, dtype, name, n=None):
+    a = np.asarray(a)
+    if a.dtype != dtype or a.ndim != 1:
+        raise ValueError(f"{name}: a one-dimensional {np.dtype(dtype)} array is expected, not {a.dtype} with {a.ndim} axes")
+    if n is not None and len(a) != n:
+        raise ValueError(f"{name}: {n} elements expected, not {len(a)}")
+    return np.ascontiguousarray(a)
+
+
+def debug_scan_predicates(n):
+    """(scan_is_small(n), scan_compact_is_small(n), scan_tiles(n), scan_scratch_elems(n))"""
+    out = (C.c_size_t * 4)()
+    _dbg_rc(_dbg_fn("esvo_debug_scan_predicates", [C.c_size_t, C.c_void_p])(int(n), out), "esvo_debug_scan_predicates")
+    return bool(out[0]), bool(out[1]), int(out[2]), int(out[3])
+
+
+def debug_scan_u32(x, in_place=False, want_total=True):
+    """launch_exclusive_scan_u32 -> (out, total or None, disturbed guard words); in_place: d_out == d_in"""
+    x = _dbg_array(x, np.uint32, "x")
+    out = _prefilled(len(x), np.uint32)
+    total = _prefilled(1, np.uint32) if want_total else None
+    fn = _dbg_fn("esvo_debug_scan_u32", [C.c_void_p, C.c_size_t, C.c_void_p, C.c_int, C.c_void_p])
+    g = _dbg_rc(fn(x.ctypes.data, len(x), out.ctypes.data, 1 if in_place else 0, _p(total)), "esvo_debug_scan_u32")
+    return out, (int(total[0]) if want_total else None), g
+
+
+def debug_scan_code_bit0(codes, tile_sums=None, want_total=True, zero_words=None):
+    """launch_exclusive_scan_code_bit0, or with tile_sums (scan_tiles(n) words) launch_scan_down_code_bit0 alone
+    -> (out, total or None, zero or None, disturbed guard words); zero_words (>= n): the size of the buffer cleared on the way"""
+    codes = _dbg_array(codes, np.uint8, "codes")
+    n = len(codes)
+    if tile_sums is not None:
+        if debug_scan_predicates(n)[0]:
+            raise ValueError("the down-sweep alone is for n above the single-workgroup bound")
+        tile_sums = _dbg_array(tile_sums, np.uint32, "tile_sums", debug_scan_predicates(n)[2])
+    if zero_words is not None and zero_words < n:
+        raise ValueError(f"zero_words: at least n = {n} words are cleared")
+    out = _prefilled(n, np.uint32)
+    total = _prefilled(1, np.uint32) if want_total else None
+    zero = None if zero_words is None else _prefilled(zero_words, np.uint32)
+    fn = _dbg_fn("esvo_debug_scan_code_bit0", [C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t])
+    g = _dbg_rc(fn(codes.ctypes.data, n, _p(tile_sums), out.ctypes.data, _p(total), _p(zero), 0 if zero is None else len(zero)),
+                "esvo_debug_scan_code_bit0")
+    return out, (int(total[0]) if want_total else None), zero, g
+
+
+def _check_compact_args(flags, slots, dtype):
+    flags = _dbg_array(flags, np.uint32, "flags")
+    slots = _dbg_array(slots, dtype, "slots", len(flags))
+    if not debug_scan_predicates(len(flags))[1]:   # scan_compact_is_small: the library's own bound
+        raise ValueError("the single-workgroup compaction takes 1 .. SCAN_COMPACT_SMALL_MAX flags")
+    if flags.max() > 1:
+        raise ValueError("flags are 0 or 1")
+    return flags, slots
+
+
+def debug_compact_matches(flags, slots, want_out=True, want_slot_of=True):
+    """launch_scan_compact_matches_small -> dict(prefix, total, out, slot_of, guards); out / slot_of None where not asked for"""
+    flags, slots = _check_compact_args(flags, slots, MATCH_DTYPE)
+    n = len(flags)
+    prefix, total = _prefilled(n, np.uint32), _prefilled(1, np.uint32)
+    out = _prefilled(n, MATCH_DTYPE) if want_out else None
+    slot_of = _prefilled(n, np.uint32) if want_slot_of else None
+    fn = _dbg_fn("esvo_debug_compact_matches", [C.c_void_p, C.c_size_t] + [C.c_void_p] * 5)
+    g = _dbg_rc(fn(flags.ctypes.data, n, slots.ctypes.data, prefix.ctypes.data, total.ctypes.data, _p(out), _p(slot_of)),
+                "esvo_debug_compact_matches")
+    return dict(prefix=prefix, total=int(total[0]), out=out, slot_of=slot_of, guards=g)
+
+
+def debug_compact_points(flags, slots, want_out=True, row=None, total_index=0, pinned_row=False):
+    """launch_scan_compact_points_small -> dict(prefix, total, out, row, row_host, guards).  row (uint32 words): the device counter
+    row whose word total_index is the total (returned as it is afterwards); pinned_row: the kernel also writes the finished row
+    to pinned host memory (row_host, prefilled)"""
+    flags, slots = _check_compact_args(flags, slots, DEPTH_POINT_DTYPE)
+    n = len(flags)
+    if row is None and pinned_row:
+        raise ValueError("pinned_row needs the device row it mirrors")
+    if row is not None:
+        row = _dbg_array(row, np.uint32, "row").copy()
+        if not 0 <= total_index < len(row) <= 1024:
+            raise ValueError("total_index must lie inside the row (at most 1024 words)")
+    prefix, total = _prefilled(n, np.uint32), _prefilled(1, np.uint32)
+    out = _prefilled(n, DEPTH_POINT_DTYPE) if want_out else None
+    row_host = _prefilled(len(row), np.uint32) if pinned_row else None
+    fn = _dbg_fn("esvo_debug_compact_points", [C.c_void_p, C.c_size_t] + [C.c_void_p] * 5 + [C.c_uint32, C.c_uint32, C.c_void_p])
+    g = _dbg_rc(fn(flags.ctypes.data, n, slots.ctypes.data, prefix.ctypes.data, None if row is not None else total.ctypes.data, _p(out),
+                   _p(row), 0 if row is None else len(row), int(total_index), _p(row_host)), "esvo_debug_compact_points")
+    return dict(prefix=prefix, total=int(total[0]) if row is None else int(row[total_index]), out=out, row=row, row_host=row_host,
+                guards=g)
+
+
+def debug_upload_words(src, zero_words=None, n_zero=0):
+    """launch_upload_words from a pinned copy of src (uint32) -> (dst, zero or None, disturbed guard words)"""
+    src = _dbg_array(src, np.uint32, "src")
+    if not 0 <= n_zero <= 256 or n_zero > (zero_words or 0):
+        raise ValueError("n_zero: at most 256 words, inside the zero buffer")
+    dst = _prefilled(len(src), np.uint32)
+    zero = None if zero_words is None else _prefilled(zero_words, np.uint32)
+    fn = _dbg_fn("esvo_debug_upload_words", [C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32])
+    g = _dbg_rc(fn(src.ctypes.data if len(src) else None, src.nbytes, dst.ctypes.data if len(src) else None, _p(zero),
+                   0 if zero is None else len(zero), int(n_zero)), "esvo_debug_upload_words")
+    return dst, zero, g
+
+
+def debug_back_prologue(src, a, b, a_flags=None, a_prefix=None):
+    """launch_back_prologue -> (dst, a_dst, b_dst, disturbed guard words).  src: uint32 words (through pinned memory), b: uint64
+    words; a: uint64 words (plain copy), or with a_flags / a_prefix the depth-point slot records that are gathered into a_dst
+    (as many records as slots, prefilled)"""
+    src, b = _dbg_array(src, np.uint32, "src"), _dbg_array(b, np.uint64, "b")
+    gather = a_flags is not None
+    if gather:
+        a_flags = _dbg_array(a_flags, np.uint32, "a_flags")
+        a = _dbg_array(a, DEPTH_POINT_DTYPE, "a", len(a_flags))
+        a_prefix = _dbg_array(a_prefix, np.uint32, "a_prefix", len(a_flags))
+        if len(a_flags) and int(a_prefix[a_flags != 0].max(initial=0)) >= len(a_flags):
+            raise ValueError("a_prefix points outside a_dst")
+        a_dst = _prefilled(len(a), DEPTH_POINT_DTYPE)
+    else:
+        if a_prefix is not None:
+            raise ValueError("a_prefix without a_flags")
+        a = _dbg_array(a, np.uint64, "a")
+        a_dst = _prefilled(len(a), np.uint64)
+    dst, b_dst = _prefilled(len(src), np.uint32), _prefilled(len(b), np.uint64)
+
+    def ptr(x):
+        return x.ctypes.data if x.nbytes else None
+    fn = _dbg_fn("esvo_debug_back_prologue", [C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t,
+                                              C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32])
+    if gather and len(a_flags) == 0:
+        raise ValueError("gather mode needs at least one slot")
+    g = _dbg_rc(fn(ptr(src), src.nbytes, ptr(dst), ptr(a), a.nbytes, ptr(a_dst), a_dst.nbytes, ptr(b), b.nbytes, ptr(b_dst),
+                   _p(a_flags), _p(a_prefix), len(a_flags) if gather else 0), "esvo_debug_back_prologue")
+    return dst, a_dst, b_dst, g
+
+
+def debug_fdiv(a, b):
+    """fdiv.hpp on pairs -> dict(div_by, div_fast, div_refined, fast, ok_a, guards): div_by(a, make_recip(b)); div_fast(a,
+    make_recip(b)) and div_fast(a, {b, recip_refined(b)}) (computed on every pair; meaningful where fast & ok_a);
+    make_recip(b).fast; fdiv_ok(a)"""
+    a = _dbg_array(a, np.float64, "a")
+    b = _dbg_array(b, np.float64, "b", len(a))
+    n = len(a)
+    q_by, q_fast, q_ref = _prefilled(n, np.float64), _prefilled(n, np.float64), _prefilled(n, np.float64)
+    fast, ok_a = _prefilled(n, np.uint32), _prefilled(n, np.uint32)
+    fn = _dbg_fn("esvo_debug_fdiv", [C.c_void_p, C.c_void_p, C.c_size_t] + [C.c_void_p] * 5)
+    g = _dbg_rc(fn(a.ctypes.data, b.ctypes.data, n, q_by.ctypes.data, q_fast.ctypes.data, q_ref.ctypes.data, fast.ctypes.data,
+                   ok_a.ctypes.data), "esvo_debug_fdiv")
+    return dict(div_by=q_by, div_fast=q_fast, div_refined=q_ref, fast=fast, ok_a=ok_a, guards=g)
+
+
+def debug_fdiv_b4(b, a1, a2, a3, a4):
+    """fdiv_ok_b4(b, a1, a2, a3, a4) -> (ok uint32 per tuple, the four div_fast quotients (n, 4), disturbed guard words)"""
+    b = _dbg_array(b, np.float64, "b")
+    n = len(b)
+    a1, a2, a3, a4 = (_dbg_array(x, np.float64, f"a{k + 1}", n) for k, x in enumerate((a1, a2, a3, a4)))
+    ok, q = _prefilled(n, np.uint32), _prefilled(4 * n, np.float64)
+    fn = _dbg_fn("esvo_debug_fdiv_b4", [C.c_void_p] * 5 + [C.c_size_t, C.c_void_p, C.c_void_p])
+    g = _dbg_rc(fn(b.ctypes.data, a1.ctypes.data, a2.ctypes.data, a3.ctypes.data, a4.ctypes.data, n, ok.ctypes.data, q.ctypes.data),
+                "esvo_debug_fdiv_b4")
+    return ok, q.reshape(n, 4), g
+
+
+def debug_recip(b):
+    """(make_recip(b).y, recip_refined(b), disturbed guard words): the refined reciprocals themselves"""
+    b = _dbg_array(b, np.float64, "b")
+    y_make, y_ref = _prefilled(len(b), np.float64), _prefilled(len(b), np.float64)
+    fn = _dbg_fn("esvo_debug_recip", [C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p])
+    g = _dbg_rc(fn(b.ctypes.data, len(b), y_make.ctypes.data, y_ref.ctypes.data), "esvo_debug_recip")
+    return y_make, y_ref, g
+
+
+def debug_sqrt_moderate(x):
+    """sqrt_moderate(x) -> (values, disturbed guard words)"""
+    x = _dbg_array(x, np.float64, "x")
+    out = _prefilled(len(x), np.float64)
+    fn = _dbg_fn("esvo_debug_sqrt_moderate", [C.c_void_p, C.c_size_t, C.c_void_p])
+    g = _dbg_rc(fn(x.ctypes.data, len(x), out.ctypes.data), "esvo_debug_sqrt_moderate")
+    return out, g
 
 
 class BagReader:
