@@ -234,6 +234,22 @@ class SgmStatsStruct(C.Structure):
     ]
 
 
+# ---- the global point cloud (esvo_map_gpc_* of include/esvo_hip.h)
+class GpcParamsStruct(C.Structure):
+    _fields_ = [
+        ("visualize_range", C.c_double), ("interval_s", C.c_double), ("num_added_per_refresh", C.c_uint64),
+        ("capacity_points", C.c_uint64), ("leaf", C.c_float), ("reserved", C.c_uint32),
+    ]
+
+
+class GpcStatsStruct(C.Structure):
+    _fields_ = [
+        ("updates", C.c_uint64), ("refreshes", C.c_uint64), ("total_points", C.c_uint64),
+        ("last_near", C.c_uint32), ("last_voxels", C.c_uint32), ("last_added", C.c_uint32), ("last_refreshed", C.c_uint32),
+        ("t_last_pub", C.c_double), ("ms_last", C.c_float), ("pad", C.c_uint32),
+    ]
+
+
 # ---- the tracker's registration loop (esvo_track_solve of include/esvo_hip.h)
 TRACK_SOLVE_MAX_ITERATIONS = 64
 

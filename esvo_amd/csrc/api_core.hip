@@ -371,6 +371,7 @@ int esvo_destroy(esvo_handle h) {
   if (h->stream_b) hipStreamSynchronize(h->stream_b);
   comm_release(h);
   em_release(h);
+  gpc_release(h);
   void* ptrs[] = {h->d_lut, h->d_mask, h->d_fixmap[0], h->d_fixmap[1], h->d_sae[0], h->d_sae[1], h->d_raw, h->d_raw1, h->d_fwd_lut[0], h->d_fwd_lut[1], h->d_fwd_off[0], h->d_fwd_off[1],
                   h->d_fwd_src[0], h->d_fwd_src[1], h->d_fwd_val, h->d_ts[0],
                   h->d_ts[1], h->d_ring[0], h->d_ring[1], h->d_obs2[0][0], h->d_obs2[0][1], h->d_obs2[1][0], h->d_obs2[1][1], h->d_obs_tmp,
@@ -481,6 +482,7 @@ int esvo_reset(esvo_handle h) {
   h->cloud_n = 0;
   h->cloud_t_ns = 0;
   h->cloud_read_pending[0] = h->cloud_read_pending[1] = false;
+  gpc_reset(h);
   h->obs_set = false;
   h->n_pose = 0;
   HIPCHK(hipStreamSynchronize(h->stream));
@@ -563,6 +565,12 @@ extern "C" void esvo_abi_sizes(size_t out[8]) {
   out[0] = sizeof(esvo_event_t); out[1] = sizeof(esvo_calib_t); out[2] = sizeof(esvo_params_t);
   out[3] = sizeof(esvo_match_t); out[4] = sizeof(esvo_depth_point_t); out[5] = sizeof(esvo_stats_t);
   out[6] = 0; out[7] = ESVO_HIP_ABI_VERSION;
+}
+
+// sizeof() of the global cloud's PODs and its default capacity (api_gpc.hip)
+extern "C" void esvo_gpc_sizes(size_t out[4]) {
+  out[0] = sizeof(esvo_gpc_params_t); out[1] = sizeof(esvo_gpc_stats_t);
+  out[2] = 5000000; out[3] = 0;
 }
 
 // ---- device self-test: div_by(a, make_recip(b)) == a / b and sqrt_moderate(x) == sqrt(x), bit for bit ----------

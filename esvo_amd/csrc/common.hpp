@@ -447,4 +447,25 @@ void launch_map_compact(const MapCell* map, u32* flags, u32* prefix, u32* d_tota
 void launch_map_cloud(const MapCell* map, u32 id_n, u32* present, u32* prefix, u32* where, u32* counts, u32* scan_tmp, const double* T_world_frame,
                       float* xyz, u32 cap_points, const DevParams& p, hipStream_t s);
 
+// ... and its near part (pc_near_): the elements with sqrt((x x + y y) + z z) < range on p_cam
+void launch_map_cloud_near(const MapCell* map, u32 id_n, double range, u32* present, u32* prefix, u32* where, u32* counts, u32* scan_tmp,
+                           const double* T_world_frame, float* xyz, u32 cap_points, const DevParams& p, hipStream_t s);
+// kernels_voxel.hip: pcl::VoxelGrid with a cubic leaf on a device cloud.  The grid block is what the host reads between the
+// stages: after launch_voxel_bounds n_finite / too_large / key_bits, after launch_voxel_centroids n_voxels.
+struct VoxelGrid {
+  u32 mn[3], mx[3];        // per-axis bounds of the finite rows, as order-preserving integers
+  u32 n_finite;            // rows whose three coordinates are finite
+  u32 too_large;           // the grid has more than 2^31 - 1 cells
+  long long minb[3], div[3];
+  u32 cells, key_bits;     // div.x div.y div.z; bits of that number (the key of the rows that are not finite)
+  u32 n_voxels;            // occupied voxels
+  float inv;               // 1 / leaf
+};
+size_t voxel_hist_words(size_t n);  // words of the radix sort's histogram for n rows
+void launch_voxel_bounds(const float* xyz, u32 n, float leaf, VoxelGrid* grid, hipStream_t s);
+const u64* launch_voxel_sort(const float* xyz, u32 n, const VoxelGrid* grid, u32 key_bits, u64* const pairs[2], u32* hist, u32* scan_tmp,
+                             hipStream_t s);
+void launch_voxel_centroids(const float* xyz, const u64* sorted, u32 n_finite, u32* heads, u32* rank, VoxelGrid* grid, u32* scan_tmp,
+                            float* centroids, u32 cap_points, hipStream_t s);
+
 }  // namespace esvo

@@ -135,6 +135,7 @@ struct esvo_context {
   u32 back_frames[2] = {0, 0};
   double baseline = 0;
   struct EmState* em = nullptr;  // event-to-event matching (api_em.hip): buffers, last selection and counts; created on first use
+  struct GpcState* gpc = nullptr;  // the global point cloud (api_gpc.hip): near-cloud and voxel-filter scratch, pc_global_, its stats
 
   // ---- threading contract (include/esvo_hip.h, "Threads"): three groups of calls may run concurrently on one handle --
   // INGEST (esvo_ts_push_events / _event_array / _bag: the ROS spinner's eventsCallback), TRACKER (esvo_track_*) and
@@ -473,6 +474,10 @@ int ts_render_pair(esvo_context* h, uint64_t t_ns, uint8_t* const obs_out[2]);
 // api_map.hip
 int flush_pending_tick(esvo_context* h);  // completes a lazily finished tick (see esvo_context::TickState)
 void em_release(esvo_context* h);  // frees the event-matching state of api_em.hip (esvo_destroy)
+// api_gpc.hip
+void gpc_release(esvo_context* h);  // frees the global-cloud state (esvo_destroy)
+void gpc_reset(esvo_context* h);    // empties the global cloud, keeps t_last_pub (esvo_reset)
+// api_map.hip
 u64 lower_bound_sec(const esvo_context* h, int cam, double t);
 u64 ros_time_from_sec(double t);
 int finalize_tick_stats(esvo_context* h);

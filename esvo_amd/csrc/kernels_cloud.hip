@@ -56,6 +56,24 @@ __global__ void __launch_bounds__(256) cloud_xyz_kernel(const MapCell* __restric
         (float)__dadd_rn(__dadd_rn(__dadd_rn(__dmul_rn(P.T[r * 4 + 0], a), __dmul_rn(P.T[r * 4 + 1], b)), __dmul_rn(P.T[r * 4 + 2], d)), P.T[r * 4 + 3]);
 }
 
+// pc_near_ (esvo_Mapping.cpp:925-932: `if (p_cam.norm() < visualize_range)`): the same mark with the predicate of
+// esvo_map_get_pointcloud_near_xyz in it -- sqrt((x x + y y) + z z) < range in f64, in that order -- so that the scan and the
+// gather leave the near elements in list order
+__global__ void __launch_bounds__(256) cloud_mark_near_kernel(const MapCell* __restrict__ map, int ncell, int W, int band0, int band1, u32 id_n,
+                                                              double range, u32* __restrict__ present, u32* __restrict__ where,
+                                                              u32* __restrict__ n_out_of_range) {
+  const int cell = blockIdx.x * blockDim.x + threadIdx.x;
+  if (cell >= ncell) return;
+  const int row = cell / W;
+  if (row < band0 || row >= band1 || !(map_flags(map, ncell)[cell] & CELL_ALIVE)) return;
+  const u32 id = map[cell].seq;
+  if (id >= id_n) { atomicAdd(n_out_of_range, 1u); return; }
+  const double x = map[cell].p_cam[0], y = map[cell].p_cam[1], z = map[cell].p_cam[2];
+  if (!(__dsqrt_rn(__dadd_rn(__dadd_rn(__dmul_rn(x, x), __dmul_rn(y, y)), __dmul_rn(z, z))) < range)) return;
+  present[id] = 1u;
+  where[id] = (u32)cell;
+}
+
 // ids [0, id_n): present | prefix | where are id_n words each; counts: [0] elements (the scan's total) [1] cells with an id
 // outside the range (cleared here); scan_tmp: scan_scratch_elems(id_n) words; xyz: cap_points x 3 floats
 void launch_map_cloud(const MapCell* map, u32 id_n, u32* present, u32* prefix, u32* where, u32* counts, u32* scan_tmp, const double* T_world_frame,
@@ -66,6 +84,21 @@ void launch_map_cloud(const MapCell* map, u32 id_n, u32* present, u32* prefix, u
   hipMemsetAsync(present, 0, sizeof(u32) * (size_t)id_n, s);
   hipLaunchKernelGGL(cloud_mark_kernel, dim3((ncell + 255) / 256), dim3(256), 0, s, map, ncell, p.W, p.band_y0, p.band_y1, id_n, present, where,
                      counts + 1);
+  launch_exclusive_scan_u32(present, prefix, counts, scan_tmp, (size_t)id_n, s);
+  CloudPose P;
+  for (int i = 0; i < 12; ++i) P.T[i] = T_world_frame[i];
+  hipLaunchKernelGGL(cloud_xyz_kernel, dim3((id_n + 255) / 256), dim3(256), 0, s, map, present, prefix, where, id_n, cap_points, P, xyz);
+}
+
+// the near cloud: launch_map_cloud with cloud_mark_near_kernel as its first pass (same scratch, same counts)
+void launch_map_cloud_near(const MapCell* map, u32 id_n, double range, u32* present, u32* prefix, u32* where, u32* counts, u32* scan_tmp,
+                           const double* T_world_frame, float* xyz, u32 cap_points, const DevParams& p, hipStream_t s) {
+  const int ncell = p.W * p.H;
+  hipMemsetAsync(counts, 0, sizeof(u32) * 2, s);
+  if (id_n == 0) return;
+  hipMemsetAsync(present, 0, sizeof(u32) * (size_t)id_n, s);
+  hipLaunchKernelGGL(cloud_mark_near_kernel, dim3((ncell + 255) / 256), dim3(256), 0, s, map, ncell, p.W, p.band_y0, p.band_y1, id_n, range, present,
+                     where, counts + 1);
   launch_exclusive_scan_u32(present, prefix, counts, scan_tmp, (size_t)id_n, s);
   CloudPose P;
   for (int i = 0; i < 12; ++i) P.T[i] = T_world_frame[i];

@@ -11,13 +11,13 @@ import subprocess
 import numpy as np
 
 from .abi import (DEPTH_POINT_DTYPE, EM_POSE_FN, ERR_CAPACITY, ERR_INVALID_ARG, ERR_STATE, EVENT_DTYPE, MATCH_DTYPE, CalibStruct, EmSelectionStruct,
-                  EmStatsStruct, ParamsStruct, SgmStatsStruct, StatsStruct, TRACK_ITER_DTYPE, TRACK_SOLVE_MAX_ITERATIONS,
+                  EmStatsStruct, GpcParamsStruct, GpcStatsStruct, ParamsStruct, SgmStatsStruct, StatsStruct, TRACK_ITER_DTYPE, TRACK_SOLVE_MAX_ITERATIONS,
                   TrackSolveInfoStruct, TrackSolveParamsStruct)
 
 _CSRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc")
 # ESVO_HIP_LIB: another build of the same library (A/B measurements of kernel variants, tools/ab_build.py); never a fallback
 _LIB_PATH = os.environ.get("ESVO_HIP_LIB") or os.path.join(_CSRC, "libesvo_hip.so")
-_SOURCES = ["api_core.hip", "api_ts.hip", "api_map.hip", "api_comm.hip", "api_bag.hip", "api_track.hip", "scan.hip", "kernels_ts.hip", "kernels_bm.hip", "kernels_lm.hip", "kernels_lm_any.hip", "kernels_fuse.hip", "kernels_shard.hip", "kernels_track.hip", "kernels_viz.hip", "kernels_sgm.hip", "api_em.hip", "kernels_em.hip", "kernels_cloud.hip", "api_dev.hip"]
+_SOURCES = ["api_core.hip", "api_ts.hip", "api_map.hip", "api_comm.hip", "api_bag.hip", "api_track.hip", "scan.hip", "kernels_ts.hip", "kernels_bm.hip", "kernels_lm.hip", "kernels_lm_any.hip", "kernels_fuse.hip", "kernels_shard.hip", "kernels_track.hip", "kernels_viz.hip", "kernels_sgm.hip", "api_em.hip", "kernels_em.hip", "kernels_cloud.hip", "api_dev.hip", "api_gpc.hip", "kernels_voxel.hip"]
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared",
                "-Wno-unused-value", "-Wno-unused-result", "-ldl"]
 
@@ -38,6 +38,8 @@ SYMBOLS = [
     "esvo_map_match_em", "esvo_map_tick_em", "esvo_map_em_get_selection", "esvo_map_em_stats", "esvo_em_sizes",
     "esvo_map_tick_sgm", "esvo_map_push_disparity_frame", "esvo_map_sgm_stats", "esvo_sgm_sizes",
     "esvo_map_cloud_build", "esvo_map_cloud_get", "esvo_map_cloud_device", "esvo_track_set_reference_from_cloud", "esvo_track_stochastic_order",
+    "esvo_map_cloud_near", "esvo_map_voxel_filter", "esvo_map_gpc_configure", "esvo_map_gpc_update", "esvo_map_gpc_get", "esvo_map_gpc_device",
+    "esvo_map_gpc_stats", "esvo_gpc_sizes",
 ]
 
 ALL_GATHER_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p)
@@ -224,9 +226,18 @@ def load():
     lib.esvo_map_cloud_device.argtypes = [vp, C.POINTER(vp), psz, C.POINTER(C.c_uint64)]
     lib.esvo_track_set_reference_from_cloud.argtypes = [vp, vp, sz, vp]
     lib.esvo_track_stochastic_order.argtypes = [sz, sz, vp, vp]
+    lib.esvo_map_cloud_near.argtypes = [vp, C.c_double, vp, sz, psz]
+    lib.esvo_map_voxel_filter.argtypes = [vp, vp, sz, C.c_float, vp, sz, psz]
+    lib.esvo_map_gpc_configure.argtypes = [vp, vp]
+    lib.esvo_map_gpc_update.argtypes = [vp, u64, C.POINTER(C.c_int)]
+    lib.esvo_map_gpc_get.argtypes = [vp, vp, sz, psz]
+    lib.esvo_map_gpc_device.argtypes = [vp, C.POINTER(vp), psz]
+    lib.esvo_map_gpc_stats.argtypes = [vp, vp]
+    lib.esvo_gpc_sizes.argtypes = [vp]
+    lib.esvo_gpc_sizes.restype = None
     for s in SYMBOLS:
         if s not in ("esvo_default_params", "esvo_last_error", "esvo_abi_sizes", "esvo_bag_last_error", "esvo_em_sizes", "esvo_sgm_sizes",
-                     "esvo_track_sizes"):
+                     "esvo_track_sizes", "esvo_gpc_sizes"):
             getattr(lib, s).restype = C.c_int
     lib.esvo_abi_sizes.argtypes = [vp]
     lib.esvo_abi_sizes.restype = None
@@ -583,6 +594,13 @@ def sgm_sizes():
     return list(out)
 
 
+def gpc_sizes():
+    """sizeof(esvo_gpc_params_t), sizeof(esvo_gpc_stats_t), the default capacity_points, 0 (esvo_gpc_sizes)"""
+    out = (C.c_size_t * 4)()
+    load().esvo_gpc_sizes(out)
+    return list(out)
+
+
 def track_sizes():
     """sizeof() of esvo_track_solve_params_t, esvo_track_iter_t, esvo_track_solve_info_t, and the iteration limit (esvo_track_sizes)"""
     out = (C.c_size_t * 4)()
@@ -883,6 +901,57 @@ class Esvo:
         out = np.zeros((self.W * self.H, 3), np.float32)
         self._ck(self.lib.esvo_map_get_pointcloud_near_xyz(self.h, float(visualize_range), out.ctypes.data, out.shape[0], C.byref(n)))
         return out[: n.value].copy()
+
+    def map_cloud_near(self, visualize_range):
+        """esvo_map_cloud_near: get_pointcloud_near() built on the device -- same points, order and bits; only the points come back"""
+        n = C.c_size_t(0)
+        out = np.zeros((self.W * self.H, 3), np.float32)
+        self._ck(self.lib.esvo_map_cloud_near(self.h, float(visualize_range), out.ctypes.data, out.shape[0], C.byref(n)))
+        return out[: n.value].copy()
+
+    def map_voxel_filter(self, xyz, leaf, cap_points=None, out=None):
+        """esvo_map_voxel_filter: lib.voxel_filter() with all arithmetic on the device, the same bytes.  cap_points / out: the
+        capacity handed to the C call and the array it writes (tests); default: room for one centroid per row"""
+        xyz = np.ascontiguousarray(xyz, np.float32).reshape(-1, 3)
+        if out is None:
+            out = np.empty((max(len(xyz), 1) if cap_points is None else max(int(cap_points), 1), 3), np.float32)
+        n = C.c_size_t()
+        self._ck(self.lib.esvo_map_voxel_filter(self.h, xyz.ctypes.data if len(xyz) else None, xyz.shape[0], float(leaf), out.ctypes.data,
+                                                out.shape[0] if cap_points is None else int(cap_points), C.byref(n)))
+        return out[: n.value].copy()
+
+    def gpc_configure(self, visualize_range=2.5, interval_s=3.0, num_added_per_refresh=1000, capacity_points=0, leaf=0.3):
+        """esvo_map_gpc_configure: allocates the global cloud (capacity_points 0: 5 000 000), empties it, t_last_pub = 0"""
+        p = GpcParamsStruct(visualize_range=float(visualize_range), interval_s=float(interval_s),
+                            num_added_per_refresh=int(num_added_per_refresh), capacity_points=int(capacity_points), leaf=float(leaf),
+                            reserved=0)
+        self._ck(self.lib.esvo_map_gpc_configure(self.h, C.byref(p)))
+
+    def gpc_update(self, t_ns):
+        """esvo_map_gpc_update: publishPointCloud's global-cloud branch on the current map; True when the interval let it through"""
+        r = C.c_int(0)
+        self._ck(self.lib.esvo_map_gpc_update(self.h, int(t_ns), C.byref(r)))
+        return bool(r.value)
+
+    def gpc_cloud(self):
+        """the global cloud as (n, 3) float32; empty before gpc_configure"""
+        n = C.c_size_t(0)
+        self._ck(self.lib.esvo_map_gpc_get(self.h, None, 0, C.byref(n)))
+        out = np.zeros((int(n.value), 3), np.float32)
+        if n.value:
+            self._ck(self.lib.esvo_map_gpc_get(self.h, out.ctypes.data, out.shape[0], C.byref(n)))
+        return out
+
+    def gpc_device(self):
+        """(device pointer, point count) of the global cloud: valid until the next refreshing gpc_update / gpc_configure / reset"""
+        ptr, n = C.c_void_p(), C.c_size_t()
+        self._ck(self.lib.esvo_map_gpc_device(self.h, C.byref(ptr), C.byref(n)))
+        return (ptr.value or 0), int(n.value)
+
+    def gpc_stats(self):
+        st = GpcStatsStruct()
+        self._ck(self.lib.esvo_map_gpc_stats(self.h, C.byref(st)))
+        return st
 
     def save_depth_map(self, save_dir, t_ns):
         """esvo_MVStereo::saveDepthMap: writes <save_dir><t_ns>.txt ("x y depth" per valid element); returns the line count"""

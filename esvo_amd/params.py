@@ -94,6 +94,18 @@ PRESETS = {
         BM_step=1, BM_ZNCC_Threshold=0.1, node="mapping"),
 }
 
+# The global point cloud of the mapper node (publishPointCloud, esvo_Mapping.cpp:955-977): the four keys of every shipped
+# cfg/mapping/*.yaml, and the code defaults of esvo_Mapping.cpp:83-86.  Kept apart from PRESETS: esvo_params_t has no such
+# fields, they parameterise esvo_map_gpc_configure (Esvo.gpc_configure).
+GPC_PRESETS = {
+    "code_defaults": dict(bVisualizeGlobalPC=False, visualizeGPC_interval=3, NumGPC_added_per_refresh=1000, visualize_range=2.5),
+    "mapping_upenn": dict(bVisualizeGlobalPC=True, visualizeGPC_interval=1, NumGPC_added_per_refresh=3000, visualize_range=5.0),
+    "mapping_rpg": dict(bVisualizeGlobalPC=True, visualizeGPC_interval=3, NumGPC_added_per_refresh=1000, visualize_range=5.0),
+    "mapping_hkust": dict(bVisualizeGlobalPC=True, visualizeGPC_interval=1, NumGPC_added_per_refresh=1500, visualize_range=2.5),
+    "mapping_dsec": dict(bVisualizeGlobalPC=True, visualizeGPC_interval=0.5, NumGPC_added_per_refresh=10000, visualize_range=30),
+}
+GPC_LEAF = 0.3  # sor.setLeafSize(0.3, 0.3, 0.3), hard-coded at esvo_Mapping.cpp:964
+
 
 def disparity_range(cfg, focal, baseline):
     """esvo_Mapping.cpp:110-116."""

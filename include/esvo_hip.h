@@ -599,6 +599,64 @@ int esvo_map_get_pointcloud_near_xyz(esvo_handle h, double visualize_range, floa
  * One centroid per occupied voxel, ascending voxel index; the node appends the last NumGPC_added_per_refresh - 1 of them
  * to its global cloud (:966-969). */
 int esvo_voxel_filter_xyz(const float* xyz, size_t n, float leaf, float* out_xyz, size_t cap_points, size_t* n_out);
+/* ---- The global point cloud (pc_global_), accumulated on the device ----
+ * Replaces the global-cloud branch of publishPointCloud (esvo_Mapping.cpp:955-977): once per visualizeGPC_interval the near
+ * part of the current map's cloud goes through pcl::VoxelGrid with a cubic leaf and the tail of the filtered cloud is appended
+ * to pc_global_.  Near cloud, filter and append run on the device; the host reads counts and an error flag.  The two halves
+ * are also calls of their own, equal bit for bit to the host helpers above (which stay the yardsticks).
+ * All handle calls here are mapper-group calls; those that read the map complete a pending tick first, as
+ * esvo_map_cloud_build does.  They use buffers of their own: neither the esvo_map_cloud_build snapshot nor anything a tick
+ * reads is touched.  ESVO_ERR_STATE on a band-sharded or tick-interleaved handle. */
+typedef struct esvo_gpc_params_t {
+  double   visualize_range;        /* visualize_range (2.5) */
+  double   interval_s;             /* visualizeGPC_interval (3) */
+  uint64_t num_added_per_refresh;  /* NumGPC_added_per_refresh (1000); >= 1 */
+  uint64_t capacity_points;        /* device capacity of the global cloud; 0 -> 5 000 000 (the node's reserve, :151) */
+  float    leaf;                   /* 0.3f: the node hard-codes it (:964) */
+  uint32_t reserved;
+} esvo_gpc_params_t;
+
+typedef struct esvo_gpc_stats_t {  /* last update + totals since configure */
+  uint64_t updates, refreshes;     /* calls; calls the interval let through */
+  uint64_t total_points;           /* size of the global cloud */
+  uint32_t last_near, last_voxels, last_added, last_refreshed;
+  double   t_last_pub;             /* t_last_pub_pc_ */
+  float    ms_last;                /* device time of the last refresh (HIP events around it) */
+  uint32_t pad;
+} esvo_gpc_stats_t;
+
+/* pc_near_ (:925-932) built on the device: the alive elements in list order with sqrt((x*x + y*y) + z*z) < visualize_range on
+ * p_cam (f64, in that order), transformed by the observation's pose -- the points, order and float bits of
+ * esvo_map_get_pointcloud_near_xyz; only the points cross the bus.  out_xyz == NULL returns the count only;
+ * ESVO_ERR_CAPACITY when cap_points is too small. */
+int esvo_map_cloud_near(esvo_handle h, double visualize_range, float* out_xyz, size_t cap_points, size_t* n);
+/* The device twin of esvo_voxel_filter_xyz: host arrays in and out, all arithmetic on the device (bounds reduction, keys,
+ * a stable radix sort of (key, input index), run heads, one sequential float sum per voxel in input order), the same bytes.
+ * Rows with a coordinate that is not finite are dropped.  leaf <= 0: ESVO_ERR_INVALID_ARG.  A grid of more than 2^31 - 1
+ * cells: ESVO_ERR_CAPACITY, nothing written.  out_xyz == NULL returns the count only; cap_points too small:
+ * ESVO_ERR_CAPACITY.  The handle lends its device and scratch buffers (grown on demand); its map is not read. */
+int esvo_map_voxel_filter(esvo_handle h, const float* xyz, size_t n, float leaf, float* out_xyz, size_t cap_points, size_t* n_out);
+/* Allocates the device buffers of the global cloud (the only call of the five below that allocates), empties the cloud and
+ * sets t_last_pub = 0.0 (:152).  ESVO_ERR_INVALID_ARG: num_added_per_refresh == 0 (the reference's `threshold - 1` is a size_t
+ * and would wrap), leaf <= 0, a range or interval that is NaN. */
+int esvo_map_gpc_configure(esvo_handle h, const esvo_gpc_params_t* prm);
+/* The branch :956-977 on the current map.  now = toSec(t_ns).  If !(now - t_last_pub > interval_s): *refreshed = 0, nothing
+ * else happens (the call is counted in stats.updates).  Otherwise: near cloud -> voxel filter with `leaf` -> L centroids ->
+ * the last min(L, num_added_per_refresh) - 1 of them are appended to the global cloud; t_last_pub = now; *refreshed = 1.
+ * Where the reference is undefined: L == 0 appends nothing and still counts as a refresh (the reference's size_t subtraction
+ * wraps there).  An append beyond capacity_points fails with ESVO_ERR_CAPACITY and leaves the cloud, t_last_pub and the stats
+ * as they were; so does a grid of more than 2^31 - 1 cells.  ESVO_ERR_STATE before esvo_map_gpc_configure.
+ * The centroids never visit the host.  Synchronous: the cloud is complete when the call returns. */
+int esvo_map_gpc_update(esvo_handle h, uint64_t t_ns, int* refreshed);
+/* The global cloud: a copy (out_xyz == NULL: the count only), or the device buffer itself -- valid and unchanged until the
+ * next esvo_map_gpc_update that refreshes, esvo_map_gpc_configure, esvo_reset or esvo_destroy.  Empty before configure.
+ * esvo_reset empties the cloud and keeps t_last_pub, as esvo_Mapping::reset does (:779-780 clear the clouds, nothing resets
+ * t_last_pub_pc_). */
+int esvo_map_gpc_get(esvo_handle h, float* out_xyz, size_t cap_points, size_t* n);
+int esvo_map_gpc_device(esvo_handle h, const float** d_xyz, size_t* n);
+int esvo_map_gpc_stats(esvo_handle h, esvo_gpc_stats_t* out);
+/* sizeof(esvo_gpc_params_t), sizeof(esvo_gpc_stats_t), the default capacity_points (5 000 000), 0. */
+void esvo_gpc_sizes(size_t out[4]);
 /* Replaces esvo_MVStereo::saveDepthMap (esvo_MVStereo.cpp:982-1000; the call sites at :302, :373, :521 are compiled out upstream
  * with `if (false)`: "to save the depth result, set it to true"): writes <save_dir><t_ns>.txt, one line "x y depth" per valid
  * element of the DepthMap in list order, formatted as Eigen's operator<< and the ofstream format it.  save_dir is used as a

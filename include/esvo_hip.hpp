@@ -298,6 +298,55 @@ class DepthFusion {
   ContextPtr ctx_;
 };
 
+// pc_global_ of the mapper node (publishPointCloud's global-cloud branch, esvo_Mapping.cpp:955-977), accumulated on the device:
+// construct once (the node's `if (bVisualizeGlobalPC_) reserve`, :148-153), call update(t) where the node enters the branch,
+// get() for the message.  nearCloud is pc_near_ (:925-932) by itself.
+class GlobalPointCloud {
+ public:
+  GlobalPointCloud(ContextPtr ctx, double visualize_range = 2.5, double visualizeGPC_interval = 3, size_t numAddedPC_threshold = 1000,
+                   size_t capacity_points = 0, float leaf = 0.3f)
+      : ctx_(std::move(ctx)) {
+    esvo_gpc_params_t p{};
+    p.visualize_range = visualize_range;
+    p.interval_s = visualizeGPC_interval;
+    p.num_added_per_refresh = numAddedPC_threshold;
+    p.capacity_points = capacity_points;
+    p.leaf = leaf;
+    ctx_->check(esvo_map_gpc_configure(ctx_->handle(), &p), "esvo_map_gpc_configure");
+  }
+  // true when the interval let the refresh through (t_last_pub_pc_ = t.toSec() then)
+  bool update(uint64_t t_ns) {
+    int refreshed = 0;
+    ctx_->check(esvo_map_gpc_update(ctx_->handle(), t_ns, &refreshed), "esvo_map_gpc_update");
+    return refreshed != 0;
+  }
+  void get(std::vector<float>& xyz) {
+    size_t n = 0;
+    ctx_->check(esvo_map_gpc_get(ctx_->handle(), nullptr, 0, &n), "esvo_map_gpc_get");
+    xyz.resize(n * 3);
+    ctx_->check(esvo_map_gpc_get(ctx_->handle(), xyz.data(), n, &n), "esvo_map_gpc_get");
+  }
+  size_t size() {
+    size_t n = 0;
+    ctx_->check(esvo_map_gpc_get(ctx_->handle(), nullptr, 0, &n), "esvo_map_gpc_get");
+    return n;
+  }
+  esvo_gpc_stats_t stats() {
+    esvo_gpc_stats_t st{};
+    ctx_->check(esvo_map_gpc_stats(ctx_->handle(), &st), "esvo_map_gpc_stats");
+    return st;
+  }
+  void nearCloud(double visualize_range, std::vector<float>& xyz) {
+    xyz.resize((size_t)ctx_->width() * ctx_->height() * 3);
+    size_t n = 0;
+    ctx_->check(esvo_map_cloud_near(ctx_->handle(), visualize_range, xyz.data(), xyz.size() / 3, &n), "esvo_map_cloud_near");
+    xyz.resize(n * 3);
+  }
+
+ private:
+  ContextPtr ctx_;
+};
+
 // esvo_Mapping::createDenoisingMask + extractDenoisedEvents (esvo_Mapping.cpp:1046-1072) for the stage-wise
 // path (esvo_map_tick applies them itself when params.denoising is set): binary map of the selected events
 // at their RAW pixels -> 3x3 median (BORDER_REPLICATE) -> keep the events whose pixel is 255, in order.
