@@ -126,11 +126,15 @@ class _Band:
         return self.dev.comm_gather_map()
 
 
-def _loop(rig, st, p, ops, t0, T0, xyz0, n_ticks, reref, verbose=False, device_register=False, device_reference=False):
+def _loop(rig, st, p, ops, t0, T0, xyz0, n_ticks, reref, verbose=False, device_register=False, device_reference=False,
+          reproj_map=False):
     """tracker -> mapper for n_ticks ticks after the bootstrap at t0 (pose T0, reference cloud xyz0); `ops`: _OneGpu / _Band.
     device_reference (one plain handle): a re-reference builds the map's cloud on the device (map_cloud_build) and the tracker
     gathers its 2000 points out of it (track_set_reference_from_cloud) -- the same rng.permutation(n)[:2000] indices as the
-    host route takes out of the downloaded cloud, so both routes register against the same points, bit for bit."""
+    host route takes out of the downloaded cloud, so both routes register against the same points, bit for bit.
+    reproj_map: after each registration the tracker's Reproj_Map_Left is drawn on the device for the registered motion
+    (track_reprojection_map, the image stays there); out["reproj_inside"] collects its n_inside per tick.  Outside the timed
+    spans, and nothing else changes."""
     assert not device_reference or (xyz0 is None and isinstance(ops, _OneGpu)), "the device-resident cloud is a one-GPU handle's"
     dev = ops.dev
     T_est = {t0: T0}
@@ -163,6 +167,9 @@ def _loop(rig, st, p, ops, t0, T0, xyz0, n_ticks, reref, verbose=False, device_r
         Tw[:3, 3] = T_est[t_ref][:3, :3] @ t_ + T_est[t_ref][:3, 3]
         T_est[t] = Tw
         c1 = time.perf_counter()
+        if reproj_map:
+            _, n_in = dev.track_reprojection_map(R_, t_, 2000, p.invdepth_min, p.invdepth_max, download=False)
+            out.setdefault("reproj_inside", []).append(n_in)
         gt = st.pose(t)
         d_est = Tw[:3, 3] - T_est[t0][:3, 3]
         d_gt = gt[:3, 3] - st.pose(t0)[:3, 3]
@@ -211,7 +218,8 @@ def _scene(seed, speed):
     return rig, st, p, st.t0_ns + int(0.08e9)
 
 
-def run(n_ticks=15, reref=10**9, speed=1.0, seed=20250419, verbose=False, device_register=False, device_reference=False):
+def run(n_ticks=15, reref=10**9, speed=1.0, seed=20250419, verbose=False, device_register=False, device_reference=False,
+        reproj_map=False):
     rig, st, p, t0 = _scene(seed, speed)
     dev = lib.Esvo(p, rig)
     dev.ts_push_events(0, st.ev_left)
@@ -221,7 +229,7 @@ def run(n_ticks=15, reref=10**9, speed=1.0, seed=20250419, verbose=False, device
     T0 = st.pose(t0)                      # bootstrap pose given, as the reference's identity at start-up
     dev.set_observation(t0, None, None, T0)
     n_sgm, _ = dev.init_sgm(None, None, min_points=100)
-    out = _loop(rig, st, p, _OneGpu(dev), t0, T0, None, n_ticks, reref, verbose, device_register, device_reference)
+    out = _loop(rig, st, p, _OneGpu(dev), t0, T0, None, n_ticks, reref, verbose, device_register, device_reference, reproj_map)
     out["sgm_points"] = n_sgm
     dev.close()
     return out

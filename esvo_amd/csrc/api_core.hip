@@ -81,6 +81,18 @@ void release_routing(esvo_context* h) {
   h->h_route_gidx = nullptr;
 }
 
+// the reference's colour tables are jet on i / 255 (Visualization.cpp:128-226): 255 * channel =
+// clamp(min(4 i + a, -4 i + b), 0, 255), stored in an 8-bit image by rounding half to even
+void jet256_bgr(uint8_t jet[768]) {
+  const double ab[3][2] = {{127.5, 637.5}, {-127.5, 892.5}, {-382.5, 1147.5}};  // B, G, R
+  for (int i = 0; i < 256; ++i)
+    for (int c = 0; c < 3; ++c) {
+      double v = std::min(4.0 * i + ab[c][0], -4.0 * i + ab[c][1]);
+      v = v < 0 ? 0 : (v > 255 ? 255 : v);
+      jet[3 * i + c] = (uint8_t)std::nearbyint(v);
+    }
+}
+
 }  // namespace esvo_host
 
 // =================================================================================================
@@ -416,7 +428,7 @@ int esvo_destroy(esvo_handle h) {
   if (h->stream_t) { hipStreamSynchronize(h->stream_t); hipStreamDestroy(h->stream_t); }
   if (h->stream_i) { hipStreamSynchronize(h->stream_i); hipStreamDestroy(h->stream_i); }
   for (void* q : {(void*)h->d_trk_blur, (void*)h->d_trk_neg, (void*)h->d_trk_du, (void*)h->d_trk_dv, (void*)h->d_trk_xyz, (void*)h->d_trk_pts,
-                  (void*)h->d_trk_out})
+                  (void*)h->d_trk_out, (void*)h->d_trk_viz_bgr, (void*)h->d_trk_viz_owner, (void*)h->d_trk_viz_jet, (void*)h->d_trk_viz_cnt})
     if (q) hipFree(q);
   delete h;
   return ESVO_OK;

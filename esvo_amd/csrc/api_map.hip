@@ -2054,16 +2054,8 @@ int esvo_map_get_debug_images(esvo_handle h, double age_max_range, uint8_t* inv_
     HIPCHK(hipMalloc(reinterpret_cast<void**>(&h->d_viz_bgr), npx * 3));
     HIPCHK(hipMalloc(reinterpret_cast<void**>(&h->d_viz_owner), npx * sizeof(u32)));
     HIPCHK(hipMalloc(reinterpret_cast<void**>(&h->d_viz_jet), 768));
-    // the reference's colour tables are jet on i / 255 (Visualization.cpp:128-226): 255 * channel =
-    // clamp(min(4 i + a, -4 i + b), 0, 255), stored in an 8-bit image by rounding half to even
     uint8_t jet[768];
-    const double ab[3][2] = {{127.5, 637.5}, {-127.5, 892.5}, {-382.5, 1147.5}};  // B, G, R
-    for (int i = 0; i < 256; ++i)
-      for (int c = 0; c < 3; ++c) {
-        double v = std::min(4.0 * i + ab[c][0], -4.0 * i + ab[c][1]);
-        v = v < 0 ? 0 : (v > 255 ? 255 : v);
-        jet[3 * i + c] = (uint8_t)std::nearbyint(v);
-      }
+    jet256_bgr(jet);
     HIPCHK(hipMemcpy(h->d_viz_jet, jet, 768, hipMemcpyHostToDevice));
   }
   const esvo_params_t& p = h->prm;

@@ -365,6 +365,60 @@ int esvo_track_solve(esvo_handle h, const esvo_track_solve_params_t* prm, double
   return ESVO_OK;
 }
 
+// The visualisation block of RegProblemSolverLM (RegProblemSolverLM.cpp:180-209) on the tracker's own stream and buffers
+// (kernels_track_viz.hip states the image); nothing of the mapper group is touched, so esvo_map_get_debug_images may run beside it.
+int esvo_track_reprojection_map(esvo_handle h, const double R[9], const double t[3], size_t n_points, double inv_depth_min,
+                                double inv_depth_max, uint8_t* bgr_out, size_t* n_inside) {
+  if (!h || !R || !t || !std::isfinite(inv_depth_min) || !std::isfinite(inv_depth_max) || inv_depth_max == inv_depth_min)
+    return ESVO_ERR_INVALID_ARG;
+  std::lock_guard<std::mutex> _trk_lock(h->mu_track);
+  if (!h->trk_cur) FAIL(ESVO_ERR_STATE, "esvo_track_set_current has not been called");
+  HIPCHK(hipSetDevice(h->device));
+  const size_t npx = (size_t)h->W * h->H;
+  if (!h->d_trk_viz_cnt) {
+    if (!h->d_trk_viz_bgr) HIPCHK(hipMalloc(reinterpret_cast<void**>(&h->d_trk_viz_bgr), (npx + 3) / 4 * 12));
+    if (!h->d_trk_viz_owner) HIPCHK(hipMalloc(reinterpret_cast<void**>(&h->d_trk_viz_owner), (npx + 3) / 4 * 4 * sizeof(u32)));
+    if (!h->d_trk_viz_jet) HIPCHK(hipMalloc(reinterpret_cast<void**>(&h->d_trk_viz_jet), 768));
+    uint8_t jet[768];
+    jet256_bgr(jet);
+    HIPCHK(hipMemsetAsync(h->d_trk_viz_owner, 0, (npx + 3) / 4 * 4 * sizeof(u32), h->stream_t));  // the only clear: every call leaves it 0
+    HIPCHK(hipMemcpyAsync(h->d_trk_viz_jet, jet, 768, hipMemcpyHostToDevice, h->stream_t));
+    HIPCHK(hipStreamSynchronize(h->stream_t));  // (jet lives on this frame)
+    HIPCHK(hipMalloc(reinterpret_cast<void**>(&h->d_trk_viz_cnt), sizeof(u32)));  // last: marks the set complete
+  }
+  TrackArgs a;
+  fill_track_args(h, a);
+  TrackPose pose;  // T_left_ref = [R^T | -R^T t] exactly as esvo_track_jacobian builds it (:191-192)
+  std::memset(&pose, 0, sizeof(pose));
+  for (int r = 0; r < 3; ++r) {
+    for (int c = 0; c < 3; ++c) pose.T[r * 4 + c] = R[c * 3 + r];
+    pose.T[r * 4 + 3] = (-R[0 * 3 + r] * t[0] + -R[1 * 3 + r] * t[1]) + -R[2 * 3 + r] * t[2];
+  }
+  pose.T[15] = 1.0;
+  const u32 n = (u32)std::min<size_t>(std::min<size_t>(n_points, h->trk_n), 0xffffffffull);  // numVisualization, :194
+  launch_track_reprojection_map(a, pose, n, inv_depth_min, inv_depth_max, h->d_trk_viz_jet, h->d_trk_viz_owner, h->d_trk_viz_bgr,
+                                h->d_trk_viz_cnt, h->stream_t);
+  HIPCHK(hipGetLastError());
+  h->trk_viz_valid = true;
+  u32 cnt = 0;
+  if (bgr_out) HIPCHK(hipMemcpyAsync(bgr_out, h->d_trk_viz_bgr, npx * 3, hipMemcpyDeviceToHost, h->stream_t));
+  if (n_inside) HIPCHK(hipMemcpyAsync(&cnt, h->d_trk_viz_cnt, sizeof(u32), hipMemcpyDeviceToHost, h->stream_t));
+  if (bgr_out || n_inside) {
+    HIPCHK(hipStreamSynchronize(h->stream_t));
+    h->trk_xyz_inflight = false;
+  }
+  if (n_inside) *n_inside = cnt;
+  return ESVO_OK;
+}
+
+int esvo_track_reprojection_map_device(esvo_handle h, const uint8_t** d_bgr) {
+  if (!h || !d_bgr) return ESVO_ERR_INVALID_ARG;
+  std::lock_guard<std::mutex> _trk_lock(h->mu_track);
+  if (!h->trk_viz_valid) FAIL(ESVO_ERR_STATE, "esvo_track_reprojection_map has not been called");
+  *d_bgr = h->d_trk_viz_bgr;
+  return ESVO_OK;
+}
+
 void esvo_track_sizes(size_t out[4]) {
   out[0] = sizeof(esvo_track_solve_params_t);
   out[1] = sizeof(esvo_track_iter_t);

@@ -316,6 +316,10 @@ struct TrackSolveOut {   // the pinned block the kernel writes once: results, in
   esvo_track_iter_t trace[TRK_SOLVE_MAX_ITERATIONS];
 };
 void launch_track_solve(const TrackArgs& a, const TrackSolveArgs& s, TrackSolveOut* out, hipStream_t st);
+// kernels_track_viz.hip: the reprojection map of RegProblemSolverLM (the first n reference points painted over the grey neg image);
+// owner holds W * H zeros on entry and on exit, *n_inside is zeroed and counted
+void launch_track_reprojection_map(const TrackArgs& a, const TrackPose& pose, u32 n, double min_range, double max_range,
+                                   const uint8_t* jet, u32* owner, uint8_t* bgr, u32* n_inside, hipStream_t s);
 
 // kernels_shard.hip: ordering of a tick's frame from the ranks' (matched, kept) bits
 void launch_shard_codes(const u32* own_w, const u32* keep, const u32* n_local, u32 max_local, u32 N, uint8_t* block, hipStream_t s);

@@ -421,6 +421,13 @@ struct esvo_context {
   size_t trk_cap = 0, trk_n = 0;
   bool trk_cur = false;
   hipEvent_t evt_trk_read = nullptr;  // the tracker stream has read the resident left Time Surface (mu_ts)
+  // the reprojection map (kernels_track_viz.hip): the tracker group's own image, owner words, jet table and counter, allocated
+  // on first use under mu_track -- the d_viz_* buffers below are the mapper group's
+  uint8_t* d_trk_viz_bgr = nullptr;
+  u32* d_trk_viz_owner = nullptr;   // all 0 between calls (the paint pass clears what the mark pass set)
+  uint8_t* d_trk_viz_jet = nullptr;
+  u32* d_trk_viz_cnt = nullptr;
+  bool trk_viz_valid = false;       // d_trk_viz_bgr holds the image of a call
   bool trk_read_pending = false;
 
   // pinned staging slots for frame pose tables that arrive from the host (push_frame variants): a slot is reused only
@@ -465,6 +472,7 @@ extern thread_local std::string g_create_error;
 void fill_dev_params(esvo_context* h);
 void set_compute_band(esvo_context* h);
 void release_routing(esvo_context* h);
+void jet256_bgr(uint8_t jet[768]);  // DrawPoint's 256 BGR triples: the mapper's debug images and the tracker's reprojection map
 // api_ts.hip
 void collect_ts_timing(esvo_context* h, int only = -1);
 void ingest_fence(esvo_context* h, int cam);  // caller holds mu_ring

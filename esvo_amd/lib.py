@@ -17,7 +17,7 @@ from .abi import (DEPTH_POINT_DTYPE, EM_POSE_FN, ERR_CAPACITY, ERR_INVALID_ARG, 
 _CSRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc")
 # ESVO_HIP_LIB: another build of the same library (A/B measurements of kernel variants, tools/ab_build.py); never a fallback
 _LIB_PATH = os.environ.get("ESVO_HIP_LIB") or os.path.join(_CSRC, "libesvo_hip.so")
-_SOURCES = ["api_core.hip", "api_ts.hip", "api_map.hip", "api_comm.hip", "api_bag.hip", "api_track.hip", "scan.hip", "kernels_ts.hip", "kernels_bm.hip", "kernels_lm.hip", "kernels_lm_any.hip", "kernels_fuse.hip", "kernels_shard.hip", "kernels_track.hip", "kernels_viz.hip", "kernels_sgm.hip", "api_em.hip", "kernels_em.hip", "kernels_cloud.hip", "api_dev.hip", "api_gpc.hip", "kernels_voxel.hip"]
+_SOURCES = ["api_core.hip", "api_ts.hip", "api_map.hip", "api_comm.hip", "api_bag.hip", "api_track.hip", "scan.hip", "kernels_ts.hip", "kernels_bm.hip", "kernels_lm.hip", "kernels_lm_any.hip", "kernels_fuse.hip", "kernels_shard.hip", "kernels_track.hip", "kernels_track_viz.hip", "kernels_viz.hip", "kernels_sgm.hip", "api_em.hip", "kernels_em.hip", "kernels_cloud.hip", "api_dev.hip", "api_gpc.hip", "kernels_voxel.hip"]
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared",
                "-Wno-unused-value", "-Wno-unused-result", "-ldl"]
 
@@ -40,6 +40,7 @@ SYMBOLS = [
     "esvo_map_cloud_build", "esvo_map_cloud_get", "esvo_map_cloud_device", "esvo_track_set_reference_from_cloud", "esvo_track_stochastic_order",
     "esvo_map_cloud_near", "esvo_map_voxel_filter", "esvo_map_gpc_configure", "esvo_map_gpc_update", "esvo_map_gpc_get", "esvo_map_gpc_device",
     "esvo_map_gpc_stats", "esvo_gpc_sizes",
+    "esvo_track_reprojection_map", "esvo_track_reprojection_map_device",
 ]
 
 ALL_GATHER_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p)
@@ -235,6 +236,8 @@ def load():
     lib.esvo_map_gpc_stats.argtypes = [vp, vp]
     lib.esvo_gpc_sizes.argtypes = [vp]
     lib.esvo_gpc_sizes.restype = None
+    lib.esvo_track_reprojection_map.argtypes = [vp, vp, vp, sz, C.c_double, C.c_double, vp, psz]
+    lib.esvo_track_reprojection_map_device.argtypes = [vp, C.POINTER(vp)]
     for s in SYMBOLS:
         if s not in ("esvo_default_params", "esvo_last_error", "esvo_abi_sizes", "esvo_bag_last_error", "esvo_em_sizes", "esvo_sgm_sizes",
                      "esvo_track_sizes", "esvo_gpc_sizes"):
@@ -1080,6 +1083,27 @@ class Esvo:
         self._ck(self.lib.esvo_track_solve(self.h, C.addressof(prm), R.ctypes.data, t.ctypes.data, C.addressof(info), trace.ctypes.data,
                                            len(trace)))
         return R.reshape(3, 3), t, info, trace[:info.iterations].copy()
+
+    def track_reprojection_map(self, R, t, n_points=2000, inv_depth_min=None, inv_depth_max=None, download=True):
+        """esvo_track_reprojection_map: RegProblemSolverLM's Reproj_Map_Left for the motion (R, t) -- the grey TS_negative_left_
+        with the first n_points reference points painted in the jet colour of 1/z between inv_depth_min and inv_depth_max
+        (the tracker's invDepth_min_range / invDepth_max_range; no default: they are the node's parameters).
+        -> ((H, W, 3) uint8 BGR, n_inside); download=False leaves the image on the device (track_reprojection_map_device) and
+        returns (None, n_inside)"""
+        assert inv_depth_min is not None and inv_depth_max is not None, "inv_depth_min / inv_depth_max are the tracker's ranges"
+        R = np.ascontiguousarray(R, np.float64).reshape(9)
+        t = np.ascontiguousarray(t, np.float64).reshape(3)
+        img = np.empty((self.H, self.W, 3), np.uint8) if download else None
+        n = C.c_size_t()
+        self._ck(self.lib.esvo_track_reprojection_map(self.h, R.ctypes.data, t.ctypes.data, int(n_points), float(inv_depth_min),
+                                                      float(inv_depth_max), None if img is None else img.ctypes.data, C.byref(n)))
+        return img, int(n.value)
+
+    def track_reprojection_map_device(self):
+        """device pointer of the last track_reprojection_map()'s H x W x 3 image: valid until the next such call / destroy"""
+        ptr = C.c_void_p()
+        self._ck(self.lib.esvo_track_reprojection_map_device(self.h, C.byref(ptr)))
+        return ptr.value or 0
 
     # ---- multi-GPU exchange behind the C-ABI (api_comm.hip): RCCL, or the two collectives as callbacks ----
     def comm_init(self, unique_id, rank, world):

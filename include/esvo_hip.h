@@ -919,6 +919,23 @@ int esvo_track_solve(esvo_handle h, const esvo_track_solve_params_t* prm, double
                      esvo_track_solve_info_t* info, esvo_track_iter_t* trace, size_t trace_cap);
 /* sizeof of esvo_track_solve_params_t, esvo_track_iter_t, esvo_track_solve_info_t, and ESVO_TRACK_SOLVE_MAX_ITERATIONS */
 void esvo_track_sizes(size_t out[4]);
+/* RegProblemSolverLM's reprojection map (RegProblemSolverLM.cpp:180-209; :106-135 per iteration of solve_numerical):
+ * TS_negative_left_ of the last esvo_track_set_current in grey, the first min(n_points, reference size) points of the
+ * reference (ResItems_ order) reprojected with [R^T | -R^T t] and painted as DrawPoint paints them (radius-1 filled circle,
+ * jet colour of 1/z between inv_depth_min and inv_depth_max = invDepth_min_range / invDepth_max_range; later points over
+ * earlier ones).  bgr_out: H x W x 3 bytes, or NULL to leave the image on the device.  n_inside (may be NULL): points whose
+ * centre pixel is inside the image.  Tracker-group call.
+ * None of the residual's tests applies (no bounds, no mask): the centre is ((int)x, (int)y) of the projection, truncated toward
+ * zero, and each of the plus' five pixels is painted iff it lies inside the image.  1/z is the point's inverse depth in the
+ * reference frame; the colour index floor((1/z - min) / (max - min) * 255) is clamped to 0..255 before it becomes an int.
+ * Where the reference is undefined the point is skipped: a coordinate that is not finite or of magnitude >= 2^30, a NaN
+ * index.  cv::circle's raster is restated, not pinned to OpenCV.  A reference of 0 points or n_points == 0 gives the grey
+ * image and n_inside = 0.  ESVO_ERR_STATE before esvo_track_set_current; ESVO_ERR_INVALID_ARG: R or t NULL, a range that
+ * is not finite, inv_depth_max == inv_depth_min.  Waits for the tracker's stream once, when bgr_out or n_inside is given. */
+int esvo_track_reprojection_map(esvo_handle h, const double R[9], const double t[3], size_t n_points,
+                                double inv_depth_min, double inv_depth_max, uint8_t* bgr_out, size_t* n_inside);
+/* the image of the last such call on the device (valid until the next one or esvo_destroy); ESVO_ERR_STATE before any */
+int esvo_track_reprojection_map_device(esvo_handle h, const uint8_t** d_bgr);
 
 #ifdef __cplusplus
 }

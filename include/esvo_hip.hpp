@@ -736,6 +736,16 @@ class RegProblemLM {
     };
     return gauss_newton_register(ne, R0, t0, MAX_ITERATION, damping, !batches);
   }
+  // the visualisation block of RegProblemSolverLM (RegProblemSolverLM.cpp:180-209): the bytes of Reproj_Map_Left (bgr8, H x W x 3)
+  // for the registered motion (R, t); invDepth_*_range are the tracker's 1 / z_max_ and 1 / z_min_.  Returns the number of
+  // points whose centre pixel is inside the image.
+  size_t reprojectionMap(const double R[9], const double t[3], double invDepth_min_range, double invDepth_max_range, uint8_t* bgr,
+                         size_t numVisualization = 2000) const {
+    size_t n_inside = 0;
+    ctx_->check(esvo_track_reprojection_map(ctx_->handle(), R, t, numVisualization, invDepth_min_range, invDepth_max_range, bgr, &n_inside),
+                "esvo_track_reprojection_map");
+    return n_inside;
+  }
   size_t numBatches_ = 1, numPoints_ = 0;
 
  private:
