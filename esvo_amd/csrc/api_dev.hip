@@ -242,6 +242,49 @@ int esvo_debug_compact_points(const uint32_t* flags, size_t n, const esvo_depth_
   DEV_RETURN();
 }
 
+// launch_lm_pixel_order (kernels_lm.hip): the processing order of a narrow LM launch bounded by max_matches whose compacted list
+// holds the n records of `matches` (the count goes to the device, as in a tick); slot s holds match stride_item(s, n, num_threads).
+// left / right: the width x height observation images (read by the SSD variant only).  order: in/out, max_matches words.
+// *variant (nullable) receives lm_order_variant(): 0 the key is the pixel alone, 1 the patch-SSD octave lies above it.
+int esvo_debug_lm_order(const esvo_match_t* matches, size_t n, size_t max_matches, int width, int height, int num_threads, int updown,
+                        const uint8_t* left, const uint8_t* right, uint32_t* order, int* variant) {
+  if (variant) *variant = esvo::lm_order_variant();
+  if (!max_matches || n > max_matches || max_matches > 4000000u || (n && !matches) || !order || !left || !right) return ESVO_ERR_INVALID_ARG;
+  if (width < 1 || height < 1 || (size_t)width * height > 4000000u || num_threads < 1) return ESVO_ERR_INVALID_ARG;
+  DEV_BEGIN();
+  GBuf d_m, d_n, d_l, d_r, d_rows[2], d_hist, d_tmp, d_order;
+  const u32 n32 = (u32)n, cap = (u32)max_matches;
+  const size_t npx = (size_t)width * height, img_bytes = (npx + 3) / 4 * 4;
+  std::vector<uint8_t> img(img_bytes, 0);
+  HIPCHK(d_m.make(std::max<size_t>(n, 1) * sizeof(esvo_match_t), nullptr));
+  if (n) HIPCHK(hipMemcpy(d_m.ptr<void>(), matches, n * sizeof(esvo_match_t), hipMemcpyHostToDevice));
+  HIPCHK(d_n.make(4, &n32));
+  std::memcpy(img.data(), left, npx);
+  HIPCHK(d_l.make(img_bytes, img.data()));
+  std::memcpy(img.data(), right, npx);
+  HIPCHK(d_r.make(img_bytes, img.data()));
+  for (int k = 0; k < 2; ++k) HIPCHK(d_rows[k].make(max_matches * 8, nullptr));
+  HIPCHK(d_hist.make(esvo::voxel_hist_words(max_matches) * 4, nullptr));
+  HIPCHK(d_tmp.make(esvo::scan_scratch_elems(esvo::voxel_hist_words(max_matches)) * 4, nullptr));
+  HIPCHK(d_order.make(max_matches * 4, order));
+  esvo::DevParams dp;
+  std::memset(&dp, 0, sizeof(dp));
+  dp.W = width; dp.H = height; dp.num_threads = num_threads; dp.updown = updown;
+  esvo::u64* const rows[2] = {d_rows[0].ptr<esvo::u64>(), d_rows[1].ptr<esvo::u64>()};
+  esvo::launch_lm_pixel_order(d_m.ptr<esvo_match_t>(), d_n.ptr<u32>(), cap, 0, d_l.ptr<uint8_t>(), d_r.ptr<uint8_t>(), dp, rows,
+                              d_hist.ptr<u32>(), d_tmp.ptr<u32>(), d_order.ptr<u32>(), st.s);
+  DEV_RUN_DONE();
+  HIPCHK(d_m.finish(nullptr, &bad));
+  HIPCHK(d_n.finish(nullptr, &bad));
+  HIPCHK(d_l.finish(nullptr, &bad));
+  HIPCHK(d_r.finish(nullptr, &bad));
+  for (int k = 0; k < 2; ++k) HIPCHK(d_rows[k].finish(nullptr, &bad));
+  HIPCHK(d_hist.finish(nullptr, &bad));
+  HIPCHK(d_tmp.finish(nullptr, &bad));
+  HIPCHK(d_order.finish(order, &bad));
+  DEV_RETURN();
+}
+
 // launch_upload_words: src (bytes, a multiple of 4) goes through a pinned buffer; dst: in/out, bytes; zero: nullable, in/out,
 // zero_words words of which the launch clears the first n_zero (<= 256)
 int esvo_debug_upload_words(const void* src, size_t bytes, void* dst, uint32_t* zero, uint32_t zero_words, uint32_t n_zero) {

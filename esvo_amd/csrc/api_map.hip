@@ -111,6 +111,17 @@ static int lm_pair_policy(esvo_context* h, u32 n_events) {
   else if (recent_min(h->lm_pair_current ^ 1) < 0.95f * recent_min(h->lm_pair_current)) h->lm_pair_current ^= 1;
   return (k % 64u == 63u) ? h->lm_pair_current ^ 1 : h->lm_pair_current;  // (a periodic sample of the other one keeps its estimate fresh)
 }
+// The processing order of the LM launch that follows (kernels_lm.hip): on the front queue, behind the match compaction of the
+// tick -- the count stays on the device.  Launches that do not read an order (wide, pair, dense, band, split) get none.
+static void run_lm_order(esvo_context* h, u32 max_matches) {
+  h->lm_order_next = nullptr;
+  const bool split = h->d_lm_fvec0 != nullptr && max_matches >= esvo::LM_SPLIT_MIN_EVENTS;
+  if (!h->lm_order_on || !h->d_lm_pix_order2[0] || !lm_launch_is_ordered(max_matches, false, false, split, h->dp)) return;
+  u32* order = h->d_lm_pix_order2[h->fpar];
+  launch_lm_pixel_order(h->d_matches, h->d_counters + 0, max_matches, 0, h->d_obs[0], h->d_obs[1], h->dp, h->d_lm_sort_rows, h->d_lm_sort_hist,
+                        h->d_scan_tmp, order, h->stream);
+  h->lm_order_next = order;
+}
 int run_lm(esvo_context* h, u32 max_matches, int cull, bool dense, hipStream_t st = nullptr, int pair = -1) {
   if (!st) st = h->stream;
   if (h->gather_guard[h->fpar]) {  // a back stage's first launch reads this parity's solver slots (latency mode, tick_phase2): not
@@ -121,6 +132,8 @@ int run_lm(esvo_context* h, u32 max_matches, int cull, bool dense, hipStream_t s
   LmArgs a;
   a.matches = h->d_matches; a.n_matches = h->d_counters + (dense ? 8 : 0); a.max_matches = max_matches;
   a.match_index = nullptr;
+  a.order = dense ? nullptr : h->lm_order_next;
+  h->lm_order_next = nullptr;
   if (h->match_by_index && !dense) { a.matches = h->d_match_slots; a.match_index = h->d_own_w; }
   a.tsL = h->d_obs[0]; a.tsR = h->d_obs[1];
   a.pose_T = h->d_pose_T; std::memcpy(a.T_world_obs, h->T_world_obs, sizeof(double) * 16);
@@ -158,6 +171,7 @@ int run_order_points(esvo_context* h, u32 max_matches, DevPoint* dst, hipStream_
 }
 int run_refine(esvo_context* h, u32 max_matches, int cull, DevPoint* dst) {
   HIPCHK(hipMemsetAsync(h->d_counters + 2, 0, sizeof(u32), h->stream));  // n_solved (a tick zeroes all counters at once)
+  run_lm_order(h, max_matches);
   int rc = run_lm(h, max_matches, cull, false);
   if (rc) return rc;
   return run_order_points(h, max_matches, dst);
@@ -896,6 +910,7 @@ int tick_phase0(esvo_context* h, uint64_t t_ns, const uint64_t* pose_t_ns, const
     h->match_by_index = tk.lat && scan_compact_is_small(n) && lm_launch_is_wide(n, h->dp);
     rc = run_order_matches(h, n, false);
     if (rc) { h->match_by_index = false; return rc; }
+    run_lm_order(h, n);
     hipStream_t sl = h->stream;
     if (h->split_now && !tk.lat) {  // the LM stage on its own stream, behind this tick's matches
       HIPCHK(hipEventRecord(h->evt[EV_A1 + h->fpar * EV_FRONT_STRIDE], h->stream));

@@ -361,6 +361,9 @@ struct LmArgs {
   // j-th match of the compacted list -- the list itself (48 B per record through one workgroup) is never written.  nullptr: `matches`
   // is the compacted list.
   const u32* match_index;
+  // narrow layout, single launch only (kernels_lm.hip "the processing order"): order[pos] is the solver slot that grid position
+  // pos works on -- a permutation of [0, *n_matches), the identity behind it (launch_lm_pixel_order).  nullptr: slot = position.
+  const u32* order = nullptr;
   // In-run shader-clock probe (nullable): lane 0 of every 65th workgroup reads s_memtime (shader cycles) and s_memrealtime
   // (the constant reference clock) when it starts and when it ends and adds the two differences to clk[2 xcc], clk[2 xcc + 1]
   // (xcc = the XCD the wave ran on), one sample to clk[16]; the start values wait in clk[CLK_SCRATCH + 2 * (block / 65) ...].
@@ -376,8 +379,20 @@ constexpr u32 CLK_XCDS = 8, CLK_SAMPLES = 16, CLK_SCRATCH = 32, CLK_STRIDE = 65;
 inline size_t clk_words(u32 max_ev) { return CLK_SCRATCH + 2 * ((size_t)max_ev / 64 + 2); }
 constexpr u32 LM_PAIR_MAX_EVENTS = 10000u;       // launches bounded by more events never use the pair layout (2 waves per match)
 constexpr u32 LM_TWO_QUEUES_MAX_EVENTS = 40000u;  // = LM_WIDE_MAX (kernels_lm.hip): launches that use the wide layout
-constexpr u32 LM_SPLIT_MIN_EVENTS = 400000u;  // launches bounded by at least this many events use the split launch (kernels_lm.hip, LmSplit)
+#ifndef LM_SPLIT_MIN
+#define LM_SPLIT_MIN 400000u
+#endif
+constexpr u32 LM_SPLIT_MIN_EVENTS = LM_SPLIT_MIN;  // launches bounded by at least this many events use the split launch (kernels_lm.hip, LmSplit)
 void launch_lm_refine(const LmArgs& a, const DevParams& p, u32* n_solved, hipStream_t s);
+// The processing order of a narrow launch (kernels_lm.hip): the solver slots sorted by their match's pixel, tile-major, stable.
+// rows[0] / rows[1]: max_matches words of 64 bits; hist: voxel_hist_words(max_matches); scan_tmp: scan_scratch_elems of that;
+// order: max_matches words.  dense: slot s holds match s (else match stride_item(s, *n_matches, num_threads)).
+// whether launch_lm_refine reads LmArgs::order for a launch bounded by max_matches (split: the launch is a split launch)
+bool lm_launch_is_ordered(u32 max_matches, bool dense, bool band, bool split, const DevParams& p);
+int lm_order_variant();                                          // 0: the pixel alone; 1: the patch-SSD octave above it
+u32 lm_order_key(u32 x, u32 y, u32 ssd, int W, int H);           // the sort key (host and tests: the kernel computes the same)
+void launch_lm_pixel_order(const esvo_match_t* matches, const u32* n_matches, u32 max_matches, int dense, const uint8_t* tsL,
+                           const uint8_t* tsR, const DevParams& p, u64* const rows[2], u32* hist, u32* scan_tmp, u32* order, hipStream_t s);
 void launch_compact_points(const DevPoint* slots, const u32* flags, const u32* prefix, const u32* n_in,
                            u32 max_n, DevPoint* out, hipStream_t s);
 
@@ -467,6 +482,9 @@ struct VoxelGrid {
 };
 size_t voxel_hist_words(size_t n);  // words of the radix sort's histogram for n rows
 void launch_voxel_bounds(const float* xyz, u32 n, float leaf, VoxelGrid* grid, hipStream_t s);
+// the sort by itself (rows key << 32 | index, the count optionally on the device; kernels_voxel.hip)
+const u64* launch_radix_sort_pairs(u64* const pairs[2], u32 n, const u32* n_dev, u32 key_bits, u32* hist, u32* scan_tmp, u32* out_index,
+                                   hipStream_t s);
 const u64* launch_voxel_sort(const float* xyz, u32 n, const VoxelGrid* grid, u32 key_bits, u64* const pairs[2], u32* hist, u32* scan_tmp,
                              hipStream_t s);
 void launch_voxel_centroids(const float* xyz, const u64* sorted, u32 n_finite, u32* heads, u32* rank, VoxelGrid* grid, u32* scan_tmp,

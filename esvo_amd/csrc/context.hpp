@@ -224,6 +224,14 @@ struct esvo_context {
   u32* d_lm_meta = nullptr;
   u32* d_lm_order = nullptr;
   u32* d_lm_hist = nullptr;
+  // the processing order of the narrow LM launch (kernels_lm.hip): built on the front queue behind the match compaction, read by
+  // the LM launch on its own queue while the next tick's front stage runs -- so the order exists per front parity (as d_matches2
+  // does); the sort's rows and histogram are the front queue's alone.  Allocated when the handle can see narrow launches.
+  u32* d_lm_pix_order2[2] = {nullptr, nullptr};
+  u64* d_lm_sort_rows[2] = {nullptr, nullptr};
+  u32* d_lm_sort_hist = nullptr;
+  bool lm_order_on = true;        // ESVO_LM_ORDER=0 (test / A/B only): the launch takes its slots in grid order
+  const u32* lm_order_next = nullptr;  // the order run_lm_order built for the run_lm that follows it (nullptr: none)
   u64* d_clk = nullptr;           // in-run shader-clock probe of the LM kernel (LmArgs::clk, common.hpp); read by esvo_get_stats
   bool clk_probe = true;          // ESVO_CLK_PROBE=0 (A/B only) launches the LM kernel without it
   DevPoint* d_pt_slots = nullptr;   // LM output by slot + keep flags + their scan: alias one of two sets (front parity)

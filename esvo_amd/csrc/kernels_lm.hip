@@ -481,6 +481,10 @@ __device__ bool lm_eval(const DevParams& p, const LmProblem& pr, LmCache<WIDE>& 
 // first (the tail of the launch is filled with cheap ones).  Every match is solved by the same instructions on the same
 // operands as in the single launch -- only its position in the grid changes -- and results are written by slot, so the
 // output is bit-identical.  F(x0) travels through a scratch buffer (LmArgs::split_*: 7 x 16 doubles per match).
+// Used for launches bounded by >= LM_SPLIT_MIN_EVENTS events only (the 1280x720 stress stream).  Every other narrow launch is
+// ONE launch that takes its slots from "the processing order" further down (LmArgs::order): the same idea -- waves of matches
+// that cost alike, the expensive ones first -- from what is known BEFORE the launch (the match's pixel and patch SSD), with no
+// first stage, no scratch and no second launch.  The two never combine: a split launch reads sp.order, not LmArgs::order.
 struct LmSplit {
   double* fvec0;   // [max_matches][7][16]
   double* fnorm0;  // [max_matches]
@@ -544,6 +548,12 @@ __global__ void __launch_bounds__(PAIR ? 128 : LM_BLOCK, WIDE ? LM_WIDE_WAVES : 
     // the sort's counters, for the next launch (its kernels are done): 2 x STRIPES x BINS words, 64 per block
     if (blockIdx.x < 2 * LM_SPLIT_STRIPES * LM_SPLIT_BINS / LM_BLOCK) sp.hist[blockIdx.x * LM_BLOCK + threadIdx.x] = 0u;
     s = active ? sp.order[pos] : 0xffffffffu;
+  }
+  if constexpr (!WIDE && !BAND && STAGE == 0) {  // the processing order: which slot this position works on (a permutation of [0, M))
+    if (a.order && active) {
+      const u32 o = a.order[pos];
+      s = o < M ? o : pos;
+    }
   }
   // The grid is sized for the worst case (every event matched): waves without any match leave at once (~39 000 of 49 000 on the
   // headline workload; they are the LAST in dispatch order, execute ~12 instructions each -- 0.1 % of the launch -- and delay no
@@ -896,10 +906,83 @@ __global__ void __launch_bounds__(256) lm_order_kernel(const u32* __restrict__ n
   sp.order[base[st][key] + atomicAdd(&fill[st * LM_SPLIT_BINS + key], 1u)] = s;
 }
 
+// ---- the processing order (narrow layout, single launch) --------------------------------------------------------------------
+// Four matches share a wave in lockstep and the wave runs the longest of the four, evaluation by evaluation.  In slot order the
+// four are four consecutive solver slots -- matches far apart in the image.  Matches on one pixel (a third of a tick's matches
+// share theirs with another one: same start point, same patch, another pose) and on neighbouring pixels of one edge behave
+// alike, so the launch works through the slots in PIXEL order, tile-major: grid position pos solves slot order[pos].  The pixel
+// is known before the launch: one key kernel and the stable radix sort of kernels_voxel.hip on the front queue, no first
+// evaluation, no second launch.  Every match is solved by the same instructions on the same operands and written to its own
+// slot with its own seq, so the output is the same bits.
+// LM_ORDER_SSD_OCTAVE 1 puts five bits above the pixel: the octave of the integer-patch SSD of the match, sum (l - r)^2 over the
+// 15 x 7 patches at the matched disparity, largest first (the expensive waves start first).
+#ifndef LM_ORDER_SSD_OCTAVE
+#define LM_ORDER_SSD_OCTAVE 1  // measured against 0 (the pixel alone) on the headline workload: profiles/r08_lm_order_ab.txt
+#endif
+#define LM_ORDER_TILE_LOG2 3  // 8 x 8 pixel tiles, raster inside
+__host__ __device__ inline u32 lm_order_tiles_x(int W) { return ((u32)W + (1u << LM_ORDER_TILE_LOG2) - 1u) >> LM_ORDER_TILE_LOG2; }
+__host__ __device__ inline u32 lm_order_pixel_key(u32 x, u32 y, int W) {
+  constexpr u32 L = LM_ORDER_TILE_LOG2, m = (1u << L) - 1u;
+  return ((((y >> L) * lm_order_tiles_x(W) + (x >> L)) << (2 * L)) | ((y & m) << L)) | (x & m);
+}
+__host__ __device__ inline u32 lm_order_bits(u32 v) {  // bits of v (0 for 0)
+  u32 b = 0;
+  while (v) { ++b; v >>= 1; }
+  return b;
+}
+__host__ __device__ inline u32 lm_order_pixel_bits(int W, int H) { return lm_order_bits(lm_order_pixel_key((u32)W - 1u, (u32)H - 1u, W)); }
+__host__ __device__ inline u32 lm_order_key_of(u32 x, u32 y, u32 ssd, int W, int H) {
+  const u32 k = lm_order_pixel_key(x, y, W);
+  return LM_ORDER_SSD_OCTAVE ? (((31u - lm_order_bits(ssd)) << lm_order_pixel_bits(W, H)) | k) : k;
+}
+int lm_order_variant() { return LM_ORDER_SSD_OCTAVE; }
+u32 lm_order_key(u32 x, u32 y, u32 ssd, int W, int H) { return lm_order_key_of(x, y, ssd, W, H); }
+
+__global__ void __launch_bounds__(256) lm_pixel_key_kernel(const esvo_match_t* __restrict__ matches, const u32* __restrict__ n_matches,
+                                                           u32 max_matches, int dense, const uint8_t* __restrict__ tsL,
+                                                           const uint8_t* __restrict__ tsR, int W, int H, u32 T, int updown,
+                                                           u64* __restrict__ rows, u32* __restrict__ order) {
+  const u32 s = blockIdx.x * blockDim.x + threadIdx.x;
+  if (s >= max_matches) return;
+  u32 M = *n_matches;
+  if (M > max_matches) M = max_matches;
+  if (s >= M) { order[s] = s; return; }  // behind the matches: the identity (the sort leaves these positions alone)
+  const u32 j = dense ? s : stride_item(s, M, T);
+  const double fx = floor(matches[j].x_left[0]), fy = floor(matches[j].x_left[1]);
+  const int x = fx >= 0. ? (fx < (double)W ? (int)fx : W - 1) : 0;  // (a match lies inside the image; anything else, NaN included, is clamped)
+  const int y = fy >= 0. ? (fy < (double)H ? (int)fy : H - 1) : 0;
+  u32 ssd = 0;
+  if (LM_ORDER_SSD_OCTAVE) {
+    const double fd = matches[j].disp;
+    const int d = fd >= 0. ? (fd < 65536. ? (int)fd : 65535) : 0;
+    for (int dy = -(LM_ROWS / 2); dy <= LM_ROWS / 2; ++dy)
+      for (int dx = -(LM_COLS / 2); dx <= LM_COLS / 2; ++dx) {
+        const int ly = min(max(y + dy, 0), H - 1), lx = min(max(x + dx, 0), W - 1);  // (border pixels repeat)
+        const int ry = min(max(ly - (updown ? d : 0), 0), H - 1), rx = min(max(lx - (updown ? 0 : d), 0), W - 1);
+        const int e = (int)tsL[(size_t)ly * W + lx] - (int)tsR[(size_t)ry * W + rx];
+        ssd += (u32)(e * e);
+      }
+  }
+  rows[s] = ((u64)lm_order_key_of((u32)x, (u32)y, ssd, W, H) << 32) | s;
+}
+void launch_lm_pixel_order(const esvo_match_t* matches, const u32* n_matches, u32 max_matches, int dense, const uint8_t* tsL,
+                           const uint8_t* tsR, const DevParams& p, u64* const rows[2], u32* hist, u32* scan_tmp, u32* order, hipStream_t s) {
+  if (max_matches == 0) return;
+  hipLaunchKernelGGL(lm_pixel_key_kernel, dim3((max_matches + 255u) / 256u), dim3(256), 0, s, matches, n_matches, max_matches, dense, tsL,
+                     tsR, p.W, p.H, (u32)p.num_threads, p.updown, rows[0], order);
+  const u32 key_bits = lm_order_pixel_bits(p.W, p.H) + (LM_ORDER_SSD_OCTAVE ? 5u : 0u);
+  launch_radix_sort_pairs(rows, max_matches, n_matches, key_bits, hist, scan_tmp, order, s);
+}
+
 void launch_lm_refine_any(const LmArgs& a, const DevParams& p, u32* n_solved, hipStream_t s);  // kernels_lm_any.hip
 // whether a launch bounded by max_matches takes the one-wave-per-match layout -- the one that reads LmArgs::match_index
 bool lm_launch_is_wide(u32 max_matches, const DevParams& p) {
   return max_matches > 0 && p.wx == LM_COLS && p.wy == LM_ROWS && p.ls_norm != ESVO_LSNORM_L2 && max_matches <= LM_WIDE_MAX && LM_BLOCK == 64;
+}
+// whether the launch reads LmArgs::order: the single narrow launch of a one-GPU handle (the wide and pair layouts hold one match
+// per wave -- no lockstep to lose --, a dense or band launch is a rank's share, the general kernel has layouts of its own)
+bool lm_launch_is_ordered(u32 max_matches, bool dense, bool band, bool split, const DevParams& p) {
+  return max_matches > LM_WIDE_MAX && p.wx == LM_COLS && p.wy == LM_ROWS && !dense && !band && !split;
 }
 void launch_lm_refine(const LmArgs& a, const DevParams& p, u32* n_solved, hipStream_t s) {
   if (a.max_matches == 0) return;

@@ -7,7 +7,8 @@
 //             CELL COUNT for a row that is not finite: one more than the largest key, so those rows sort behind all others
 //   sort      LSD radix sort of the pairs by key, 8 bits per pass, as many passes as the cell count has bits.  Every pass is
 //             STABLE -- tile histogram, one exclusive scan over [digit][tile] (scan.hip), scatter by rank within the tile --
-//             and the pairs start in input order, so the rows of a voxel end up in input order
+//             and the pairs start in input order, so the rows of a voxel end up in input order.  The sort by itself is
+//             launch_radix_sort_pairs, which the LM launch's processing order uses as well (kernels_lm.hip)
 //   heads     flag per sorted position: first row of its voxel; their exclusive scan numbers the voxels in ascending key
 //   centroids one thread per voxel walks its run: a sequential float sum per axis from 0 in input order, then / (float)count
 //
@@ -98,8 +99,11 @@ __global__ void __launch_bounds__(256) voxel_keys_kernel(const float* __restrict
 __device__ inline u32 vox_digit(u64 pair, u32 shift) { return (u32)(pair >> (32u + shift)) & 255u; }
 
 // hist[digit * n_tiles + tile] = rows of the tile with that digit
-__global__ void __launch_bounds__(VOX_B) voxel_hist_kernel(const u64* __restrict__ pairs, u32 n, u32 shift, u32* __restrict__ hist) {
+// (n_dev, nullable: the row count lives on the device and n bounds it -- the grid, and with it the layout of hist, follow the bound)
+__global__ void __launch_bounds__(VOX_B) voxel_hist_kernel(const u64* __restrict__ pairs, u32 n, const u32* __restrict__ n_dev, u32 shift,
+                                                           u32* __restrict__ hist) {
   __shared__ u32 cnt[256];
+  if (n_dev) n = min(n, *n_dev);
   cnt[threadIdx.x] = 0u;
   __syncthreads();
   const size_t base = (size_t)blockIdx.x * VOX_TILE;
@@ -114,9 +118,12 @@ __global__ void __launch_bounds__(VOX_B) voxel_hist_kernel(const u64* __restrict
 // offs: the exclusive scan of hist -- where the tile's first row with that digit goes.  A row's place is that plus the rows
 // of the tile in front of it with the same digit: those of earlier rounds (base), of earlier waves of its round (wcnt) and of
 // lower lanes of its wave (the match mask), which keeps equal digits in their order.
-__global__ void __launch_bounds__(VOX_B) voxel_scatter_kernel(const u64* __restrict__ in, u64* __restrict__ out, u32 n, u32 shift,
-                                                              const u32* __restrict__ offs) {
+// out_index (non-null in the last pass of a sort whose caller wants the permutation alone): the row's index goes there, not the pair
+__global__ void __launch_bounds__(VOX_B) voxel_scatter_kernel(const u64* __restrict__ in, u64* __restrict__ out, u32 n,
+                                                              const u32* __restrict__ n_dev, u32 shift, const u32* __restrict__ offs,
+                                                              u32* __restrict__ out_index) {
   constexpr int NW = VOX_B / ESVO_WAVE;
+  if (n_dev) n = min(n, *n_dev);
   __shared__ u32 base[256];
   __shared__ u32 wcnt[NW][256];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -142,7 +149,10 @@ __global__ void __launch_bounds__(VOX_B) voxel_scatter_kernel(const u64* __restr
     if (valid) {
       u32 pos = base[d] + rank;
       for (int w = 0; w < wave; ++w) pos += wcnt[w][d];
-      if (pos < n) out[pos] = pair;  // (a permutation of [0, n): always)
+      if (pos < n) {  // (a permutation of [0, n): always)
+        if (out_index) out_index[pos] = (u32)pair;
+        else out[pos] = pair;
+      }
     }
     __syncthreads();
     u32 add = 0u;
@@ -192,20 +202,31 @@ void launch_voxel_bounds(const float* xyz, u32 n, float leaf, VoxelGrid* grid, h
   hipLaunchKernelGGL(voxel_grid_kernel, dim3(1), dim3(1), 0, s, leaf, grid);
 }
 
-// pairs[0] / pairs[1]: n words of 64 bits each; hist: voxel_hist_words(n); scan_tmp: scan_scratch_elems of that.
-// Returns the buffer that holds the sorted pairs.
-const u64* launch_voxel_sort(const float* xyz, u32 n, const VoxelGrid* grid, u32 key_bits, u64* const pairs[2], u32* hist, u32* scan_tmp,
-                             hipStream_t s) {
-  hipLaunchKernelGGL(voxel_keys_kernel, dim3((n + 255u) / 256u), dim3(256), 0, s, xyz, n, grid, pairs[0]);
+// The sort by itself: stable LSD radix sort of the rows (key << 32 | index) in pairs[0] by the low key_bits bits of their keys,
+// 8 bits per pass.  n bounds the row count and sizes the launches; n_dev (nullable) is the count itself where it lives on the
+// device -- rows behind it are neither read nor written.  pairs[0] / pairs[1]: n words of 64 bits each; hist:
+// voxel_hist_words(n); scan_tmp: scan_scratch_elems of that.  Returns the buffer that holds the sorted pairs -- or, with
+// out_index (n words) and at least one pass, nullptr: the last pass then writes the sorted rows' indices there and nothing else.
+const u64* launch_radix_sort_pairs(u64* const pairs[2], u32 n, const u32* n_dev, u32 key_bits, u32* hist, u32* scan_tmp, u32* out_index,
+                                   hipStream_t s) {
   const u32 tiles = voxel_tiles(n);
   int cur = 0;
-  for (u32 shift = 0; shift < key_bits; shift += 8u) {
-    hipLaunchKernelGGL(voxel_hist_kernel, dim3(tiles), dim3(VOX_B), 0, s, pairs[cur], n, shift, hist);
+  for (u32 shift = 0; n && shift < key_bits; shift += 8u) {
+    u32* const index = shift + 8u >= key_bits ? out_index : nullptr;
+    hipLaunchKernelGGL(voxel_hist_kernel, dim3(tiles), dim3(VOX_B), 0, s, pairs[cur], n, n_dev, shift, hist);
     launch_exclusive_scan_u32(hist, hist, nullptr, scan_tmp, 256 * (size_t)tiles, s);
-    hipLaunchKernelGGL(voxel_scatter_kernel, dim3(tiles), dim3(VOX_B), 0, s, pairs[cur], pairs[cur ^ 1], n, shift, hist);
+    hipLaunchKernelGGL(voxel_scatter_kernel, dim3(tiles), dim3(VOX_B), 0, s, pairs[cur], pairs[cur ^ 1], n, n_dev, shift, hist, index);
+    if (index) return nullptr;
     cur ^= 1;
   }
   return pairs[cur];
+}
+
+// Returns the buffer that holds the sorted pairs (buffers: launch_radix_sort_pairs).
+const u64* launch_voxel_sort(const float* xyz, u32 n, const VoxelGrid* grid, u32 key_bits, u64* const pairs[2], u32* hist, u32* scan_tmp,
+                             hipStream_t s) {
+  hipLaunchKernelGGL(voxel_keys_kernel, dim3((n + 255u) / 256u), dim3(256), 0, s, xyz, n, grid, pairs[0]);
+  return launch_radix_sort_pairs(pairs, n, nullptr, key_bits, hist, scan_tmp, nullptr, s);
 }
 
 // heads | rank: n_finite words each; the voxel count lands in grid->n_voxels; centroids: cap_points x 3 floats

@@ -388,6 +388,22 @@ def debug_compact_matches(flags, slots, want_out=True, want_slot_of=True):
     return dict(prefix=prefix, total=int(total[0]), out=out, slot_of=slot_of, guards=g)
 
 
+def debug_lm_order(matches, max_matches, width, height, left, right, num_threads=1, updown=False):
+    """launch_lm_pixel_order on a compacted list of match records and a launch bound -> dict(order, variant, guards): the
+    processing order of the narrow LM launch (max_matches words, prefilled), which sort key the library was built with
+    (0: the pixel; 1: the patch-SSD octave above it) and the disturbed guard words"""
+    matches = _dbg_array(matches, MATCH_DTYPE, "matches")
+    left = _dbg_array(np.asarray(left).reshape(-1), np.uint8, "left", width * height)
+    right = _dbg_array(np.asarray(right).reshape(-1), np.uint8, "right", width * height)
+    order = _prefilled(max_matches, np.uint32)
+    variant = C.c_int(-1)
+    fn = _dbg_fn("esvo_debug_lm_order", [C.c_void_p, C.c_size_t, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                                         C.c_void_p, C.c_void_p])
+    g = _dbg_rc(fn(matches.ctypes.data if len(matches) else None, len(matches), int(max_matches), int(width), int(height), int(num_threads),
+                   1 if updown else 0, left.ctypes.data, right.ctypes.data, order.ctypes.data, C.addressof(variant)), "esvo_debug_lm_order")
+    return dict(order=order, variant=int(variant.value), guards=g)
+
+
 def debug_compact_points(flags, slots, want_out=True, row=None, total_index=0, pinned_row=False):
     """launch_scan_compact_points_small -> dict(prefix, total, out, row, row_host, guards).  row (uint32 words): the device counter
     row whose word total_index is the total (returned as it is afterwards); pinned_row: the kernel also writes the finished row
