@@ -420,18 +420,11 @@ int round_collect(esvo_context* h) {
     rc = commit_frame(h, off, n, tk.m ? tk.poses.data() : ident, tk.m);
     if (rc) return rc;
     if (owner == c->rank) {  // MappingAtTime's fusion for the own tick (esvo_Mapping.cpp:370-395)
-      const int par = h->par;
-      h->par ^= 1;
-      HIPCHK(hipEventSynchronize(h->evt[EV_RG1 + par * EV_BACK_STRIDE]));
-      collect_back(h, par);
-      rc = run_fuse(h, par, R.own_T);
+      rc = fuse_window_now(h, R.own_T);
       if (rc) return rc;
       h->committed_t_ns = tk.t_ns;
       h->stats.ticks++;
-      h->stats.last_window_frames = (u32)h->n_window_frames;
-      u32 np = 0;
-      for (auto& f : h->frames) np += f.count;
-      h->stats.last_window_points = np;
+      window_stats(h);
       h->stats_pending = true;
       c->last_own = (long long)(R.k0 + j);
     }
@@ -497,22 +490,20 @@ int own_front(esvo_context* h, uint64_t t_ns, const double T_world_cam[16], cons
   }
   // the LM launch on its own queue (as in the lazy single-GPU tick): the front stages of the next rounds, enqueued while this
   // launch runs, overlap it
-  h->split_now = !h->prm.denoising;
-  rc = tick_phase0(h, t_ns, pose_t_ns, pose_T, m);
-  const bool split = h->split_now;
-  h->split_now = false;
+  const bool split = !h->prm.denoising;
+  rc = tick_phase0(h, t_ns, pose_t_ns, pose_T, m, FrontOpts{split, false, false});
   if (rc) return rc;
   const esvo_context::TickState& tk = h->tk[h->fpar];
   // frame compaction, header and counters: on the idle second LM queue when there is one (the next LM launch then follows this
   // one directly on its queue), behind the LM kernel
   hipStream_t sl = tk.n ? tk.lm_stream : h->stream;
   hipStream_t sn = sl;
-  if (tk.n && split && !h->lm_two_now && (sl == h->stream_l || sl == h->stream_l1)) {
+  if (tk.n && split && !tk.lm_two && (sl == h->stream_l || sl == h->stream_l1)) {
     sn = sl == h->stream_l ? h->stream_l1 : h->stream_l;
     HIPCHK(hipStreamWaitEvent(sn, h->evt[EV_LM1 + h->fpar * EV_FRONT_STRIDE], 0));
   }
   if (tk.n) { rc = run_order_points(h, tk.n, reinterpret_cast<DevPoint*>(o.d_block + 2), sn); if (rc) return rc; }
-  hipLaunchKernelGGL(esvo::comm_block_header_kernel, dim3(1), dim3(1), 0, sn, h->d_counters + 1, o.d_block);
+  hipLaunchKernelGGL(esvo::comm_block_header_kernel, dim3(1), dim3(1), 0, sn, h->d_counters + CNT_POINTS, o.d_block);
   HIPCHK(hipMemcpyAsync(o.h_cnt, h->d_counters, sizeof(u32) * CNT_ROW, hipMemcpyDeviceToHost, sn));
   HIPCHK(hipEventRecord(h->evt[EV_CNT + h->fpar * EV_FRONT_STRIDE], sn));
   HIPCHK(hipGetLastError());
@@ -779,10 +770,10 @@ int gather_map_device(esvo_context* h, size_t* n_total) {
   if (!c->ev_map) HIPCHK(hipEventCreateWithFlags(&c->ev_map, hipEventDisableTiming));
   if (!c->d_merged_n) HIPCHK(hipMalloc(reinterpret_cast<void**>(&c->d_merged_n), sizeof(u32) * 2));
   // the band's alive cells, in cell order (esvo_depth_point_t with the global creation id in seq), on the back stream
-  launch_map_compact(h->d_map_cur, h->d_exp_flags, h->d_exp_prefix, h->d_cnt_b + 5, h->d_scan_tmp_b, h->d_export, nullptr, h->dp, h->stream_b);
+  launch_map_compact(h->d_map_cur, h->d_exp_flags, h->d_exp_prefix, h->d_cnt_b + CNTB_MAP, h->d_scan_tmp_b, h->d_export, nullptr, h->dp, h->stream_b);
   u64* d_hs = c->d_map_heads;
   u64* d_hr = c->d_map_heads + 2;
-  hipLaunchKernelGGL(esvo::band_counts_kernel, dim3(1), dim3(64), 0, h->stream_b, h->d_cnt_b + 5, d_hs);
+  hipLaunchKernelGGL(esvo::band_counts_kernel, dim3(1), dim3(64), 0, h->stream_b, h->d_cnt_b + CNTB_MAP, d_hs);
   HIPCHK(hipEventRecord(c->ev_map, h->stream_b));
   HIPCHK(hipStreamWaitEvent(h->stream, c->ev_map, 0));
   rc = comm_all_gather(h, d_hs, d_hr, 16);

@@ -306,10 +306,10 @@ int esvo_create(const esvo_params_t* params, const esvo_calib_t* left, const esv
   CK(hipHostMalloc(reinterpret_cast<void**>(&h->h_pin), sizeof(double) * 2 * ((size_t)h->max_poses * 17 + 16)));
   CK(dalloc(&h->d_scan_tmp, scan_scratch_elems(std::max(E, npx)) + 8));
   CK(dalloc(&h->d_scan_tmp_b, scan_scratch_elems(std::max(E, npx)) + 8));
-  CK(dalloc(&h->d_cnt_b, 8));
-  CK(hipMemset(h->d_cnt_b, 0, sizeof(u32) * 8));
-  CK(hipHostMalloc(reinterpret_cast<void**>(&h->h_cnt_b), sizeof(u32) * 8 * 4));  // rows 0, 1: tick parities; 2: exports; 3: [par] halo violations
-  std::memset(h->h_cnt_b, 0, sizeof(u32) * 8 * 4);
+  CK(dalloc(&h->d_cnt_b, CNTB_ROW));
+  CK(hipMemset(h->d_cnt_b, 0, sizeof(u32) * CNTB_ROW));
+  CK(hipHostMalloc(reinterpret_cast<void**>(&h->h_cnt_b), sizeof(u32) * CNTB_ROW * CNTB_ROWS));  // (common.hpp: CNTB_ROW_*)
+  std::memset(h->h_cnt_b, 0, sizeof(u32) * CNTB_ROW * CNTB_ROWS);
   CK(dalloc(&h->d_halo_viol, 2));
   CK(hipMemset(h->d_halo_viol, 0, sizeof(u32) * 2));
   // fusion window
@@ -322,7 +322,7 @@ int esvo_create(const esvo_params_t* params, const esvo_calib_t* left, const esv
     h->max_frames = std::max(h->max_frames, (u32)(1.5 * params->max_fusion_points) + 4u);
   // pose-table slots of the window's non-empty frames: max_frames + 1 in the worst case (CONST_POINTS with one point per
   // frame: 1 GB of tables at 20 000 points x 256 poses), a handful in practice -- allocated for 1024 frames and doubled on
-  // demand (alloc_pose_slot, api_map.hip).  ESVO_POSE_SLOTS0 (tests): a smaller first allocation.
+  // demand (alloc_pose_slot, api_window.hip).  ESVO_POSE_SLOTS0 (tests): a smaller first allocation.
   h->slot_used.assign(h->max_frames + 1, 0);
   h->n_pose_slots = std::min<u32>(h->max_frames + 1, 1024u);
   if (const char* e0 = esvo_dev_switch("ESVO_POSE_SLOTS0")) h->n_pose_slots = std::min<u32>(h->max_frames + 1, (u32)std::max(1, std::atoi(e0)));
@@ -476,7 +476,7 @@ int esvo_reset(esvo_handle h) {
   h->dn_pending = false;
   h->resync = esvo_context::Resync();
   HIPCHK(hipMemsetAsync(h->d_halo_viol, 0, sizeof(u32) * 2, h->stream));
-  std::memset(h->h_cnt_b + 8 * 3, 0, sizeof(u32) * 8);
+  std::memset(h->h_cnt_b + CNTB_ROW * CNTB_ROW_HALO, 0, sizeof(u32) * CNTB_ROW);
   h->sh_first = 0;
   h->sh_first_prev = 0;
   h->trk_read_pending = false;

@@ -37,12 +37,32 @@ struct CamConst {
 };
 
 // Parameters the kernels read (a by-value kernel argument: lives in SGPRs / kernarg segment).
-// One row of per-tick device counters (esvo_context::d_counters): [0] n_matches [1] n_points [2] n_solved [3] n_fusion
-// [4] n_records [5] n_map [6] touched cells [7] regulariser elements [8] own matches (sharded); from CNT_BM_FAIL on, three
-// blocks of CNT_STRIPES partial sums: block matching failures by reason (info-noise ratio, coarse search, fine search).
+// One row of per-tick device counters of the front stage (esvo_context::d_counters, one row per front parity); from CNT_BM_FAIL
+// on, three blocks of CNT_STRIPES partial sums: block matching failures by reason (info-noise ratio, coarse search, fine search).
+// Kernels take pointers to the words; the host names them:
+enum : int {
+  CNT_MATCHES = 0,        // matches of the tick (sharded: of all ranks, after exchange 1)
+  CNT_POINTS = 1,         // points of its frame
+  CNT_SOLVED = 2,         // refinements that ran (sharded: this rank's share)
+  CNT_DENOISE_KEPT = 5,   // Denoising: events kept by the mask (read back before block matching sizes its launch)
+  CNT_OWN_MATCHES = 8,    // sharded: length of the rank's dense local match list
+  CNT_MAX_KEPT = 9,       // sharded: largest kept count among the ranks (block length of exchange 2)
+  CNT_SCRATCH = 10,       // four words, per mode: [0] this rank's halo violations in a routed tick (LM kernel, carried by exchange 2);
+                          // esvo_MVStereo mode 4: [0..3] on-image / matched-column / disparity-ok / zero-disparity events (SGM statistics)
+};
 constexpr int CNT_STRIPES = 16;
 constexpr int CNT_BM_FAIL = 16;
 constexpr int CNT_ROW = CNT_BM_FAIL + 3 * CNT_STRIPES;  // 64 words
+// The back stage's device counters (esvo_context::d_cnt_b, one row) ...
+enum : int { CNTB_OVER_CURSOR = 2,  // overflow cursor of the fusion front
+             CNTB_FUSIONS = 3, CNTB_RECORDS = 4, CNTB_MAP = 5, CNTB_TOUCHED = 6,  // fusions, records, exported map cells, touched cells
+             CNTB_REG_ELEMS = 7,    // regulariser elements (alive cells of the band)
+             CNTB_ROW = 8 };
+// ... and the rows of their pinned host copy (h_cnt_b): a back stage's row by tick parity, the exports' row, and one whose words
+// [par] hold the routed mode's halo violations (the running total over all ranks) as read behind that parity's back stage
+enum : int { CNTB_ROW_PAR0 = 0, CNTB_ROW_PAR1 = 1, CNTB_ROW_EXPORT = 2, CNTB_ROW_HALO = 3, CNTB_ROWS = 4 };
+// esvo_context::d_fuse_ctr (kernels_fuse.hip): [0..1023] class_count, [1024..2048] class_total, then the two cursors
+enum : int { FUSE_CTR_CLASS_TOTAL = 1024, FUSE_CTR_REC_CURSOR = 2080, FUSE_CTR_OVER_COUNT = 2081 };
 
 struct DevParams {
   int W, H;
@@ -236,7 +256,7 @@ void launch_gaussian5_pair(const uint8_t* in0, const uint8_t* in1, uint8_t* out0
 void launch_denoise_flags(const esvo_event_t* ring, u64 first, u64 cap, u32 n, uint8_t* evmap, u32* flags, int W, int H,
                           hipStream_t s);
 void launch_denoise_select(const u32* flags, const u32* prefix, u32 n, u32* sel, hipStream_t s);
-// routed band mode (api_map.hip, routed_denoise_begin / _resume): the rank's bits of the kept flags, one per walk position
+// routed band mode (api_shard.hip, routed_denoise_begin / _resume): the rank's bits of the kept flags, one per walk position
 void launch_denoise_bits_routed(const esvo_event_t* ring, u64 first, u64 cap, u32 n_loc, const u32* gidx, u32 g_first, u32 n, uint8_t* evmap,
                                 int W, int H, int band_y0, int band_y1, u32* bits, hipStream_t s);
 void launch_denoise_bits_unpack(const u32* blocks, u32 block_words, u32 N, u32 n, u32* flags, hipStream_t s);

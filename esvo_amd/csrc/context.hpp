@@ -5,7 +5,11 @@
 // streams, the call sequence of the reference seam it replaces (cited in include/esvo_hip.h); nothing computes on the
 // CPU except bookkeeping (time-stamp binary searches, window policy, output ordering).
 //   api_core.hip   lifecycle, parameters, self-tests           api_ts.hip     event ingest, Time-Surface render
-//   api_map.hip    mapper: stage-wise calls, ticks, sharding   api_track.hip  tracker residual / Jacobian evaluation
+//   api_map.hip    mapper: stage launches, the tick pipeline   api_window.hip fusion window, back stage, map export
+//   api_modes.hip  synchronous MVStereo modes 1 and 4, SGM     api_shard.hip  band mode: routed front, phases, configuration
+//   api_out.hip    DepthMap / cloud / image outputs, stats     api_comm.hip   tick-interleaved multi-GPU exchange
+//   api_em.hip     event-to-event matching (modes 0 and 2)     api_gpc.hip    the global point cloud
+//   api_track.hip  tracker residual / Jacobian evaluation      api_bag.hip, api_dev.hip  bag reader, development hooks
 #pragma once
 #include <algorithm>
 #include <array>
@@ -60,7 +64,6 @@ struct esvo_context {
   // long dependent chains -- drains.  Used for launches in the latency-bound (wide) layout; everything the stage writes
   // (d_pt_slots / d_pt_flags / d_pt_prefix / the scan scratch, besides the buffers listed above) exists once per parity.
   hipStream_t stream_l1 = nullptr;
-  bool lm_two_now = false;     // this tick's LM launch alternates between the two queues
   // Whether the second queue pays depends on what else the tick holds: where the LM launch is much longer than the fusion
   // stage (346x260, no regulariser: 0.37 ms against 0.12) two launches in flight raise the rate by 18 %; where the two are
   // of similar length (DSEC's reference-faithful tick: 0.25 against 0.30 ms) the fusion stage is the bottleneck either way
@@ -80,14 +83,11 @@ struct esvo_context {
   std::vector<std::array<float, 4>> tl_back;
   // the pipeline's way back from its slow operating point (api_map.hip, pipeline_resync)
   struct Resync { double last_ms = 0; float period_ema = 0, period_before = 0; u32 streak = 0, cooldown = 0, check_in = 0; bool lm_wait_back = false; } resync;
-  bool split_now = false;         // set by esvo_map_tick around its front stage: only the lazy tick path splits
   // Latency mode (round 6, api_map.hip): a tick that arrives while nothing of the previous one is pending -- the caller reads every
   // tick's result before it hands in the next, as the ROS node does -- has nothing to overlap with.  Its LM launch stays in the
   // front queue (no cross-queue hand-off: ~25 us) and the host polls for its counters and its end instead of sleeping on the
   // completion interrupt (~10-20 us per wake-up), for ticks of at most lat_max_events events.  ESVO_LOWLAT=0 (A/B) switches it off.
   bool lat_mode = true;
-  bool lat_now = false;           // set by esvo_map_tick around its front stage
-  bool pipe_now = false;          // ... when the previous tick is still pending (the two overlap)
   bool lat_last = false;          // the newest tick was enqueued in latency mode (what synchronising calls look at)
   u32 lat_max_events = 40000u;
   // Stage timings are SAMPLED on that path.  Every hipEventRecord between two dependent kernels costs the queue ~5 us (a marker
@@ -106,10 +106,7 @@ struct esvo_context {
   u32 pipe_seq = 0;
   u32 pipe_timed_every = 4;       // ESVO_PIPE_TIMED_EVERY (A/B; 1 = every tick)
   u32 lat_timed_every = 31;       // ESVO_LOWLAT_TIMED_EVERY (A/B; 1 = every tick)
-  u32* cnt_row_host = nullptr;    // latency mode: where the tick's point compaction leaves the counter row (null: a copy follows)
-  bool cnt_row_sent = false;
   int reg_sparse_forced = -1;     // ESVO_REG_SPARSE (A/B): the regulariser's sparse-map layout never (0) / always (1); -1: by the element count
-  bool match_by_index = false;    // latency mode: this tick's match list is d_own_w (indices into d_match_slots), not d_matches
   bool gather_guard[2] = {false, false};  // the solver-slot buffers of that parity are read by a back stage's first launch (EV_STG releases them)
   bool stage_events_on = true;    // false while a tick whose stage timings are not sampled is being enqueued (api_map.hip)
   bool back_timed[2] = {true, true};  // the back stage of that parity recorded its stage events
@@ -231,7 +228,6 @@ struct esvo_context {
   u64* d_lm_sort_rows[2] = {nullptr, nullptr};
   u32* d_lm_sort_hist = nullptr;
   bool lm_order_on = true;        // ESVO_LM_ORDER=0 (test / A/B only): the launch takes its slots in grid order
-  const u32* lm_order_next = nullptr;  // the order run_lm_order built for the run_lm that follows it (nullptr: none)
   u64* d_clk = nullptr;           // in-run shader-clock probe of the LM kernel (LmArgs::clk, common.hpp); read by esvo_get_stats
   bool clk_probe = true;          // ESVO_CLK_PROBE=0 (A/B only) launches the LM kernel without it
   DevPoint* d_pt_slots = nullptr;   // LM output by slot + keep flags + their scan: alias one of two sets (front parity)
@@ -242,12 +238,11 @@ struct esvo_context {
   u32* d_pt_prefix2[2] = {nullptr, nullptr};
   DevPoint* d_pts_tmp = nullptr;  // stage-wise refine output
   DevPoint* d_stage[2] = {nullptr, nullptr};  // a lazily completed tick's frame (by parity) until its count is known
-  u32* d_counters = nullptr;      // [0] n_matches [1] n_points [2] n_solved [3] n_fusion [4] n_records [5] n_map
-                                  // [6] touched cells [7] regulariser elements [8] own matches (sharded)
+  u32* d_counters = nullptr;      // the front stage's counter row of the current parity (common.hpp: CNT_*)
   u32* h_counters = nullptr;      // pinned
   u32* d_scan_tmp = nullptr;
-  u32* d_cnt_b = nullptr;         // back stage: [2] overflow cursor of the fusion front [3] n_fusion [4] n_records [5] n_map [6] touched cells [7] regulariser elements
-  u32* h_cnt_b = nullptr;         // pinned, one row of 8 per parity + one for exports
+  u32* d_cnt_b = nullptr;         // the back stage's counter row (common.hpp: CNTB_*)
+  u32* h_cnt_b = nullptr;         // pinned, CNTB_ROWS rows of it (CNTB_ROW_*)
   u32* d_scan_tmp_b = nullptr;
 
   // fusion window
@@ -273,7 +268,7 @@ struct esvo_context {
   u32* d_cell_count = nullptr;
   u32* d_cell_offset = nullptr;
   u32* d_cell_list = nullptr;
-  u32* d_fuse_ctr = nullptr;      // [0..1023] class_count [1024..2048] class_total [2080] rec_cursor [2081] over_count
+  u32* d_fuse_ctr = nullptr;      // class_count | class_total | rec_cursor | over_count (common.hpp: FUSE_CTR_*)
   u32 fuse_tile_rec = 4096;       // entries of a tile's own region of d_rec_ids (ESVO_FUSE_TILE_REC: tests)
   u32 fuse_slice_cap = 0;         // entries of one (class, slice) segment of d_cell_list
   u32 fuse_tile_cap = 1024;       // ESVO_FUSE_TILE_CAP (tests): entries per tile list
@@ -356,6 +351,8 @@ struct esvo_context {
     int lm_pair = -1;                 // LM layout of the tick: 1 pair, 0 wide, -1 not a candidate (policy feedback)
     bool lat = false;                 // enqueued in latency mode: LM in the front queue, polled waits
     bool timed = true;                // its stage-timing events were recorded
+    bool lm_two = false;              // its LM launch alternates between the two LM queues
+    bool host_row_sent = false;        // latency mode: its point compaction left the counter row in the pinned host row (no copy follows)
     bool gather = false;              // latency mode: its frame is still in the solver slots (flags + prefix): the back stage's first launch compacts it
     bool timed_lm = true;             // ... at least the two around the LM launch (the layout policy's feedback)
   } tk[2];
@@ -487,31 +484,54 @@ void ingest_fence(esvo_context* h, int cam);  // caller holds mu_ring
 int ts_scatter_ahead(esvo_context* h, uint64_t t_ns);
 void resident_write_begin(esvo_context* h, int cam);
 int ts_render_pair(esvo_context* h, uint64_t t_ns, uint8_t* const obs_out[2]);
-// api_map.hip
-int flush_pending_tick(esvo_context* h);  // completes a lazily finished tick (see esvo_context::TickState)
-void em_release(esvo_context* h);  // frees the event-matching state of api_em.hip (esvo_destroy)
+// api_em.hip
+void em_release(esvo_context* h);  // frees the event-matching state (esvo_destroy)
 // api_gpc.hip
 void gpc_release(esvo_context* h);  // frees the global-cloud state (esvo_destroy)
 void gpc_reset(esvo_context* h);    // empties the global cloud, keeps t_last_pub (esvo_reset)
 // api_map.hip
+struct FrontOpts { bool split = false, lat = false, pipe = false; };  // a front stage's scheduling, decided by the call that enqueues it:
+// split: LM on its own queue (the lazy tick path); lat: nothing is pending before the tick (latency mode); pipe: it overlaps the previous tick
 u64 lower_bound_sec(const esvo_context* h, int cam, double t);
 u64 ros_time_from_sec(double t);
-int finalize_tick_stats(esvo_context* h);
+int upload_poses(esvo_context* h, const uint64_t* pose_t_ns, const double* pose_T, size_t m, u32* d_zero_row = nullptr);
+int select_events(esvo_context* h, uint64_t t_ns, u64* first_out, u32* n_out);
+int denoise_select(esvo_context* h, u32 n, u32* n_kept);
+void switch_front_parity(esvo_context* h);
 int run_bm(esvo_context* h, const esvo_event_t* d_ev, u64 first, u64 cap, int reverse, u32 n, const u32* sel = nullptr);
-int run_order_points(esvo_context* h, u32 max_matches, DevPoint* dst, hipStream_t st = nullptr);
-int back_after_front(esvo_context* h);
-void collect_back(esvo_context* h, int par);
-int window_reserve(esvo_context* h, u32 n, u32* off_out);
-int commit_frame(esvo_context* h, u32 off, u32 count, const double* pose_T_host, u32 m, int pose_buf = 0, bool apply_policy = true);
-int run_fuse(esvo_context* h, int par, const double* T_world_obs, bool naive = false);
-int export_map(esvo_context* h, std::vector<esvo_depth_point_t>& out, std::vector<u32>* cells);
-int tick_phase0(esvo_context* h, uint64_t t_ns, const uint64_t* pose_t_ns, const double* pose_T, size_t m);
+int run_order_matches(esvo_context* h, u32 n, bool local, bool by_index = false);
+int run_lm(esvo_context* h, u32 max_matches, int cull, bool dense, hipStream_t st = nullptr, int pair = -1, const u32* order = nullptr, bool by_index = false);
+int run_order_points(esvo_context* h, u32 max_matches, DevPoint* dst, hipStream_t st = nullptr, u32* host_row = nullptr);
+void collect_bm_failures(esvo_context* h, const u32* row, bool accumulate);
+int read_counters(esvo_context* h);
+int tick_phase0(esvo_context* h, uint64_t t_ns, const uint64_t* pose_t_ns, const double* pose_T, size_t m, FrontOpts opt = FrontOpts());
 int tick_phase1_enqueue(esvo_context* h);
 int tick_phase1_collect(esvo_context* h, int fp);
 int collect_front_stats(esvo_context* h, esvo_context::TickState& tk, const u32* cnt, const hipEvent_t* ev);
 int tick_phase2(esvo_context* h, int fp);
+int flush_pending_tick(esvo_context* h);  // completes a lazily finished tick (see esvo_context::TickState)
+int finalize_tick_stats(esvo_context* h);
 void begin_observation(esvo_context* h);
 void revert_observation(esvo_context* h);
+// api_window.hip
+int back_after_front(esvo_context* h);
+void collect_back(esvo_context* h, int par);
+int window_reserve(esvo_context* h, u32 n, u32* off_out);
+int window_probe_after_pops(esvo_context* h, size_t keep_below, u32 n);
+int commit_frame(esvo_context* h, u32 off, u32 count, const double* pose_T_host, u32 m, int pose_buf = 0, bool apply_policy = true);
+int flush_deferred_copies(esvo_context* h);
+int run_fuse(esvo_context* h, int par, const double* T_world_obs, bool naive = false);
+int fuse_window_now(esvo_context* h, const double* T_world_obs, bool naive = false, int* par_out = nullptr);
+int commit_naive_frame(esvo_context* h, const DevPoint* d_src, u32 count, const double* pose_T_host, u32 m, int pose_buf);
+void window_stats(esvo_context* h);
+int drain_lm_and_back(esvo_context* h);
+int export_map(esvo_context* h, std::vector<esvo_depth_point_t>& out, std::vector<u32>* cells);
+// api_shard.hip
+int select_events_routed(esvo_context* h, uint64_t t_ns, u32* n_out, u32* g_first_out, u64* loc_first_out, u32* n_loc_out, u32* n_own_out);
+int routed_denoise_resume(esvo_context* h);
+int shard_front(esvo_context* h, esvo_context::TickState& tk, u32 n, const u32* sel);
+int shard_order_points(esvo_context* h, esvo_context::TickState& tk);
+int shard_scatter_frame(esvo_context* h, esvo_context::TickState& tk);
 // api_comm.hip
 void comm_release(esvo_context* h);
 void comm_reset(esvo_context* h);
@@ -533,32 +553,22 @@ using namespace esvo_host;
 // call.  The blocking calls sleep on the completion interrupt (10-20 us from the signal to the woken thread); a tick the caller
 // waits for pays that twice (counters, end of tick).  "Not ready" is an error code the runtime remembers: it is cleared here, or
 // the next hipGetLastError() behind a launch would report it.
-inline hipError_t esvo_wait_event(hipEvent_t e, bool poll, double budget_us = 3000.0) {
+template <class T>
+inline hipError_t esvo_wait(hipError_t (*query)(T), hipError_t (*block)(T), T x, bool poll, double budget_us) {
   if (poll) {
     const auto t0 = std::chrono::steady_clock::now();
     for (;;) {
-      const hipError_t q = hipEventQuery(e);
+      const hipError_t q = query(x);
       if (q == hipSuccess) return q;
       (void)hipGetLastError();
       if (q != hipErrorNotReady) return q;
       if (std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count() > budget_us) break;
     }
   }
-  return hipEventSynchronize(e);
+  return block(x);
 }
-inline hipError_t esvo_wait_stream(hipStream_t s, bool poll, double budget_us = 3000.0) {
-  if (poll) {
-    const auto t0 = std::chrono::steady_clock::now();
-    for (;;) {
-      const hipError_t q = hipStreamQuery(s);
-      if (q == hipSuccess) return q;
-      (void)hipGetLastError();
-      if (q != hipErrorNotReady) return q;
-      if (std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count() > budget_us) break;
-    }
-  }
-  return hipStreamSynchronize(s);
-}
+inline hipError_t esvo_wait_event(hipEvent_t e, bool poll, double budget_us = 3000.0) { return esvo_wait(hipEventQuery, hipEventSynchronize, e, poll, budget_us); }
+inline hipError_t esvo_wait_stream(hipStream_t s, bool poll, double budget_us = 3000.0) { return esvo_wait(hipStreamQuery, hipStreamSynchronize, s, poll, budget_us); }
 
 struct StageEventsScope {  // stage-timing events off (or on) for the calls of one scope, back on at its end whatever the exit
   esvo_context* h;

@@ -1,5 +1,5 @@
 // kernels_cloud.hip — publishPointCloud's cloud (esvo_Mapping.cpp:925-932) of the current DepthMap, built and kept on the
-// device (esvo_map_cloud_build, api_map.hip): the points, order and float bits of esvo_map_get_pointcloud_xyz without the
+// device (esvo_map_cloud_build, api_out.hip): the points, order and float bits of esvo_map_get_pointcloud_xyz without the
 // element download and the host sort of export_map.
 //
 // The reference iterates its element list, which is in creation order; an element carries the id of the record that created

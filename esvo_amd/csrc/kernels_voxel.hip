@@ -1,5 +1,5 @@
 // kernels_voxel.hip — pcl::VoxelGrid<PointXYZ> with a cubic leaf (esvo_Mapping.cpp:960-964) on the device: the points, order
-// and float bits of esvo_voxel_filter_xyz (api_map.hip), which stays the host yardstick.
+// and float bits of esvo_voxel_filter_xyz (api_out.hip), which stays the host yardstick.
 //
 //   bounds    per-axis min / max over the rows whose three coordinates are finite, and their count (ordered-integer atomics)
 //   grid      one thread: inv = 1 / leaf, minb = floor(min inv), div = floor(max inv) - minb + 1, the cell count and its bit width

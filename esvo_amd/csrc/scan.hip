@@ -264,7 +264,7 @@ void launch_exclusive_scan_u32(const u32* d_in, u32* d_out, u32* d_total, u32* d
                                hipStream_t s) {
   exclusive_scan(ScanInU32{d_in}, d_out, d_total, d_block_sums, n, nullptr, s);
 }
-// The band mode's frame order (api_map.hip, tick_phase1_enqueue) has the tile sums of its first scan produced by the kernel in
+// The band mode's frame order (api_shard.hip, shard_order_points) has the tile sums of its first scan produced by the kernel in
 // front of it (SCAN_TILE slots per sum), so that scan is its down-sweep alone -- for n above the single-workgroup bound only.
 static_assert(SCAN_TILE == (int)SCAN_TILE_SLOTS, "common.hpp's SCAN_TILE_SLOTS is this file's tile");
 bool scan_is_small(size_t n) { return n <= SCAN_SMALL_MAX; }

@@ -17,7 +17,7 @@ from .abi import (DEPTH_POINT_DTYPE, EM_POSE_FN, ERR_CAPACITY, ERR_INVALID_ARG, 
 _CSRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc")
 # ESVO_HIP_LIB: another build of the same library (A/B measurements of kernel variants, tools/ab_build.py); never a fallback
 _LIB_PATH = os.environ.get("ESVO_HIP_LIB") or os.path.join(_CSRC, "libesvo_hip.so")
-_SOURCES = ["api_core.hip", "api_ts.hip", "api_map.hip", "api_comm.hip", "api_bag.hip", "api_track.hip", "scan.hip", "kernels_ts.hip", "kernels_bm.hip", "kernels_lm.hip", "kernels_lm_any.hip", "kernels_fuse.hip", "kernels_shard.hip", "kernels_track.hip", "kernels_track_viz.hip", "kernels_viz.hip", "kernels_sgm.hip", "api_em.hip", "kernels_em.hip", "kernels_cloud.hip", "api_dev.hip", "api_gpc.hip", "kernels_voxel.hip"]
+_SOURCES = ["api_core.hip", "api_ts.hip", "api_map.hip", "api_window.hip", "api_modes.hip", "api_shard.hip", "api_out.hip", "api_comm.hip", "api_bag.hip", "api_track.hip", "scan.hip", "kernels_ts.hip", "kernels_bm.hip", "kernels_lm.hip", "kernels_lm_any.hip", "kernels_fuse.hip", "kernels_shard.hip", "kernels_track.hip", "kernels_track_viz.hip", "kernels_viz.hip", "kernels_sgm.hip", "api_em.hip", "kernels_em.hip", "kernels_cloud.hip", "api_dev.hip", "api_gpc.hip", "kernels_voxel.hip"]
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared",
                "-Wno-unused-value", "-Wno-unused-result", "-ldl"]
 
@@ -92,7 +92,7 @@ def build(force=False, verbose=False, perturbed=False):
     jobs = [(os.path.join(_CSRC, s), os.path.join(objdir, s[:-4] + ".o"), []) for s in _SOURCES]
     if perturbed:
         jobs.append((os.path.join(_CSRC, "kernels_lm.hip"), os.path.join(objdir, "kernels_lm_perturbed.o"), ["-DESVO_PERTURB_ONE_ULP"]))
-    with ThreadPoolExecutor(max_workers=min(len(jobs), os.cpu_count() or 4)) as ex:
+    with ThreadPoolExecutor(max_workers=min(len(jobs), 16, os.cpu_count() or 4)) as ex:
         rebuilt = list(ex.map(compile_one, jobs))
     objs = [j[1] for j in jobs[:len(_SOURCES)]]
 

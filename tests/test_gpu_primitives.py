@@ -309,7 +309,7 @@ def test_back_prologue_gather_equals_the_compaction(n):
     assert np.array_equal(_bytes(a_dst[:ref_total]), _bytes(comp["out"][:ref_total]))
     assert np.array_equal(_bytes(a_dst[:ref_total]), _bytes(_expected_points(slots, flags)))
     assert (_bytes(a_dst[ref_total:]) == lib.DEBUG_PREFILL_BYTE).all()
-    # the tick's other call (api_map.hip): the gather alone, nothing else to copy
+    # the tick's other call (api_window.hip, flush_deferred_copies): the gather alone, nothing else to copy
     _, a_only, _, g = lib.debug_back_prologue(np.zeros(0, np.uint32), slots, np.zeros(0, np.uint64), a_flags=flags, a_prefix=comp["prefix"])
     assert g == 0 and np.array_equal(_bytes(a_only), _bytes(a_dst))
 
