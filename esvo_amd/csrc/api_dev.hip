@@ -9,6 +9,8 @@
 // passes -- between two guard regions of GUARD_WORDS words holding a fixed pattern.  Written buffers are in/out: the caller's bytes
 // are what the kernel finds there, so the caller chooses the prefill and can tell "not written" from "written as zero".
 // Return value: a negative esvo_status_t, or the number of guard words that no longer hold the pattern (0 when all is well).
+// The exception is esvo_debug_fuse_cell_counts at the end: it takes a handle, launches nothing and copies one buffer of the last
+// fusion out (tests/test_gpu_fuse_cases.py).
 #include <vector>
 
 #include "context.hpp"
@@ -420,6 +422,22 @@ int esvo_debug_sqrt_moderate(const double* x, size_t n, double* out) {
   DEV_RUN_DONE();
   HIPCHK(d_out.finish(out, &bad));
   DEV_RETURN();
+}
+
+// The one entry here that takes a handle, and the one that launches nothing: the per-cell record counts tile_lists_kernel wrote
+// at the handle's last fusion (d_cell_count, width x height words, row-major; cells outside the handle's band keep what an
+// earlier fusion left there).  A pending tick is completed and the back stream drained first, as any read of the map does.
+int esvo_debug_fuse_cell_counts(esvo_handle h, uint32_t* out, size_t n) {
+  if (!h || !out) return ESVO_ERR_INVALID_ARG;
+  API_LOCK(h);
+  if (n != (size_t)h->W * (size_t)h->H) FAIL(ESVO_ERR_INVALID_ARG, "esvo_debug_fuse_cell_counts: width x height words are expected");
+  HIPCHK(hipSetDevice(h->device));
+  int rc = flush_pending_tick(h);
+  if (rc) return rc;
+  rc = drain_lm_and_back(h);
+  if (rc) return rc;
+  HIPCHK(hipMemcpy(out, h->d_cell_count, sizeof(u32) * n, hipMemcpyDeviceToHost));
+  return ESVO_OK;
 }
 
 }  // extern "C"

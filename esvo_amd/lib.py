@@ -875,6 +875,14 @@ class Esvo:
         self._ck(self.lib.esvo_map_get_depth_points(self.h, out.ctypes.data, out.shape[0], C.byref(n)))
         return out[: n.value].copy()
 
+    def debug_fuse_cell_counts(self):
+        """esvo_debug_fuse_cell_counts (api_dev.hip, not part of the ABI): the (H, W) record counts the tile kernel of the last
+        fusion wrote per cell; a copy, nothing is launched.  Cells outside the handle's band hold stale values."""
+        out = np.zeros((self.H, self.W), np.uint32)
+        fn = _dbg_fn("esvo_debug_fuse_cell_counts", [C.c_void_p, C.c_void_p, C.c_size_t])
+        self._ck(fn(self.h, out.ctypes.data, out.size))
+        return out
+
     def get_committed_map(self):
         """(DepthMap of the newest committed tick, its stamp) without completing a pending tick"""
         out = np.zeros(self.W * self.H, DEPTH_POINT_DTYPE)

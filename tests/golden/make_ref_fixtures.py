@@ -649,8 +649,47 @@ def make_node_big():
     print("ref_node_big.npz", os.path.getsize(path) // 1024, "KiB")
 
 
+def run_fuse_case(c):
+    """the reference's DepthFusion / SmartGrid::clean / DepthRegularization on one crafted case (tests/fuse_cases.py): per tick
+    (fusions, map, true cells, dangling cells so far)"""
+    import fuse_cases as FC
+    p, rig = FC.case_params(c)
+    m = R.RefMapper(p, rig)
+    blank = np.zeros((rig.height, rig.width), np.uint8)
+    out = []
+    for k, f in enumerate(c["frames"]):
+        m.set_observation(1_000_000_000 + 10_000_000 * k, blank, blank, np.eye(4))
+        m.push_frame(f, np.eye(4).reshape(1, 16))
+        nf = m.fuse()
+        out.append((nf, m.get_map(), m.get_map_cells(), m.counters()["dangling_cells"]))
+    return out
+
+
+def make_fuse_cases():
+    """tests/fuse_cases.py: crafted frames at the switch points of the fusion front, of clean and of the regulariser, pushed into
+    the reference's own classes.  Recorded results only: per case and tick a digest of the input frame, the fusion count, the map's
+    length, its digest without and with the elements' true cells, and the dangling grid cells met so far."""
+    import fuse_cases as FC
+    out = {}
+    for name in FC.NAMES:
+        c = FC.case(name)
+        l2 = FC.is_l2(c)
+        res = run_fuse_case(c)
+        # one row per tick: (fusions, map length, dangling cells) and the three digests side by side
+        out[f"{name}_counts"] = np.array([(nf, len(mp), dangling) for nf, mp, _, dangling in res], np.int64)
+        out[f"{name}_sha"] = np.stack([np.concatenate([FC.frame_digest(f), FC.map_digest(mp, l2=l2), FC.map_digest(mp, cells, l2=l2)])
+                                       for f, (_, mp, cells, _) in zip(c["frames"], res)])
+        print("fuse case", name, [(nf, len(mp), d) for nf, mp, _, d in res])
+    path = os.path.join(HERE, "ref_fuse_cases.npz")
+    np.savez_compressed(path, **out)
+    print("ref_fuse_cases.npz", os.path.getsize(path) // 1024, "KiB")
+
+
 if __name__ == "__main__":
     assert R.available(), "needs /root/reference (build container only)"
+    if "--fuse-cases" in sys.argv:   # only the crafted back-stage cases: ref_fuse_cases.npz
+        make_fuse_cases()
+        sys.exit(0)
     if "--big" in sys.argv:   # only the shipped-size fixtures (round 4): ref_upenn1k.npz, ref_dsec10k.npz, ref_node_big.npz
         for n in S.BIG:
             make(n)
@@ -675,3 +714,4 @@ if __name__ == "__main__":
     make_bm_step()
     make_l2()
     make_node()
+    make_fuse_cases()
