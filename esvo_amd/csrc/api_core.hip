@@ -275,6 +275,9 @@ int esvo_create(const esvo_params_t* params, const esvo_calib_t* left, const esv
     CK(dalloc(&h->d_lm_sort_hist, voxel_hist_words(E)));
     if (const char* eo = esvo_dev_switch("ESVO_LM_ORDER")) h->lm_order_on = std::atoi(eo) != 0;
   }
+  if (const char* ed = esvo_dev_switch("ESVO_BM_DEDUPE")) h->bm_dedupe_on = std::atoi(ed) != 0;
+  if (const char* em = esvo_dev_switch("ESVO_BM_DEDUPE_MIN")) h->bm_dedupe_min = (u32)std::max(1L, std::atol(em));
+  if (h->bm_dedupe_on && E >= h->bm_dedupe_min) CK(dalloc(&h->d_bm_dedupe, npx + 4 + 2 * E));  // context.hpp: table | count | list | outcomes
   // (two blocks, one per front parity: two LM launches in flight -- the two LM queues -- must not share the probe's scratch, where
   //  a wave leaves its start stamps: a launch that read the other one's stamp added a wrapped difference to the sums)
   CK(dalloc(&h->d_clk, 2 * clk_words(h->max_ev)));
@@ -400,7 +403,7 @@ int esvo_destroy(esvo_handle h) {
                   h->d_win, h->d_frame_pose_T, h->d_fr_table, h->d_prop, h->d_tile_pts, h->d_tile_count, h->d_over_pts,
                   h->d_cell_count, h->d_cell_offset, h->d_cell_list, h->d_fuse_ctr, h->d_rec_ids, h->d_map, h->d_map2, h->d_owner_max, h->d_owner_min, h->d_exp_flags,
                   h->d_exp_prefix, h->d_export, h->d_export_cell, h->d_reg_ab, h->d_reg_cd, h->d_tsq[0], h->d_tsq[1], h->d_tsq_tcount, h->d_tsq_tlist, h->d_tsq_over, h->d_tsq_over_count, h->d_own_w, h->d_lkeep, h->d_codes, h->d_codes_send, h->d_codes_all, h->d_pts_send, h->d_pts_all, h->d_rank_kept,
-                  h->d_sel, h->d_evmap, h->d_lm_fvec0, h->d_lm_fnorm0, h->d_lm_meta, h->d_lm_order, h->d_lm_hist, h->d_lm_pix_order2[0], h->d_lm_pix_order2[1], h->d_lm_sort_rows[0], h->d_lm_sort_rows[1], h->d_lm_sort_hist, h->d_clk, h->d_ring_gidx, h->d_halo_viol, h->d_dn_flags, h->d_merge_a, h->d_merge_b, h->d_merge_plan, h->d_tsq_dup};
+                  h->d_sel, h->d_evmap, h->d_lm_fvec0, h->d_lm_fnorm0, h->d_lm_meta, h->d_lm_order, h->d_lm_hist, h->d_lm_pix_order2[0], h->d_lm_pix_order2[1], h->d_lm_sort_rows[0], h->d_lm_sort_rows[1], h->d_lm_sort_hist, h->d_bm_dedupe, h->d_clk, h->d_ring_gidx, h->d_halo_viol, h->d_dn_flags, h->d_merge_a, h->d_merge_b, h->d_merge_plan, h->d_tsq_dup};
   for (void* p : ptrs) if (p) hipFree(p);
   if (h->h_counters) hipHostFree(h->h_counters);
   if (h->h_cnt_b) hipHostFree(h->h_cnt_b);

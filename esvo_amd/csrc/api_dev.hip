@@ -9,8 +9,9 @@
 // passes -- between two guard regions of GUARD_WORDS words holding a fixed pattern.  Written buffers are in/out: the caller's bytes
 // are what the kernel finds there, so the caller chooses the prefill and can tell "not written" from "written as zero".
 // Return value: a negative esvo_status_t, or the number of guard words that no longer hold the pattern (0 when all is well).
-// The exception is esvo_debug_fuse_cell_counts at the end: it takes a handle, launches nothing and copies one buffer of the last
-// fusion out (tests/test_gpu_fuse_cases.py).
+// The exceptions are at the end, take a handle, launch nothing and copy something out: esvo_debug_fuse_cell_counts one buffer of the
+// last fusion (tests/test_gpu_fuse_cases.py), esvo_debug_bm_owner_count the owner count of the last shared block-matching launch
+// (tests/test_gpu_bm_dedupe.py).
 #include <vector>
 
 #include "context.hpp"
@@ -437,6 +438,22 @@ int esvo_debug_fuse_cell_counts(esvo_handle h, uint32_t* out, size_t n) {
   rc = drain_lm_and_back(h);
   if (rc) return rc;
   HIPCHK(hipMemcpy(out, h->d_cell_count, sizeof(u32) * n, hipMemcpyDeviceToHost));
+  return ESVO_OK;
+}
+
+// Block matching once per distinct raw pixel (context.hpp, d_bm_dedupe): how many searches the newest shared launch ran -- the
+// owner count, read where it lies on the device; *shared = 0 when the handle has never taken the path (then *n_owners = 0).
+int esvo_debug_bm_owner_count(esvo_handle h, uint32_t* n_owners, int* shared) {
+  if (!h || !n_owners || !shared) return ESVO_ERR_INVALID_ARG;
+  API_LOCK(h);
+  HIPCHK(hipSetDevice(h->device));
+  int rc = flush_pending_tick(h);
+  if (rc) return rc;
+  *n_owners = 0;
+  *shared = h->d_bm_dedupe ? 1 : 0;
+  if (!h->d_bm_dedupe) return ESVO_OK;
+  HIPCHK(hipStreamSynchronize(h->stream));
+  HIPCHK(hipMemcpy(n_owners, h->d_bm_dedupe + (size_t)h->W * h->H, sizeof(u32), hipMemcpyDeviceToHost));
   return ESVO_OK;
 }
 

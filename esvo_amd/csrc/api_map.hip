@@ -57,7 +57,15 @@ int run_bm(esvo_context* h, const esvo_event_t* d_ev, u64 first, u64 cap, int re
   a.out_slots = h->d_match_slots; a.out_flags = h->d_match_flags;
   a.fail_counters = h->d_counters;
   if (h->stage_events_on) hipEventRecord(h->evt[EV_BM0 + h->fpar * EV_FRONT_STRIDE], h->stream);
-  launch_bm_match(a, h->dp, h->stream);
+  // a throughput slice: one search per distinct raw pixel (kernels_bm.hip; the lone-tick latency path gains no launch)
+  if (h->d_bm_dedupe && n >= h->bm_dedupe_min && n <= h->max_ev && !h->sharded && bm_dedupe_applies(a, h->dp)) {
+    u32* owner = h->d_bm_dedupe;
+    u32* n_uniq = owner + (size_t)h->W * h->H;
+    u32* uniq_w = n_uniq + 4;
+    launch_bm_match_dedupe(a, h->dp, owner, uniq_w, n_uniq, uniq_w + h->max_ev, h->stream);
+  } else {
+    launch_bm_match(a, h->dp, h->stream);
+  }
   if (h->stage_events_on) hipEventRecord(h->evt[EV_BM1 + h->fpar * EV_FRONT_STRIDE], h->stream);
   HIPCHK(hipGetLastError());
   return ESVO_OK;

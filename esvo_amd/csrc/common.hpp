@@ -289,8 +289,23 @@ struct BmArgs {
   const u32* keep_flags = nullptr;
   const u32* keep_prefix = nullptr;
   u32 n_raw = 0;
+  // one search per distinct raw pixel (launch_bm_match_dedupe): grid position pos < *n_uniq works on slot uniq_w[pos], the lowest
+  // slot of its pixel, and leaves in search_rec[slot] what the events that share the pixel need of it: bit 0 the search
+  // succeeded (its record is then in out_slots[slot] whether or not the owner has a pose), bits 1.. the failure reason 0..3
+  const u32* uniq_w = nullptr;
+  const u32* n_uniq = nullptr;
+  u32* search_rec = nullptr;
 };
 void launch_bm_match(const BmArgs& a, const DevParams& p, hipStream_t s);
+// Everything block matching computes but event_idx and pose_idx follows from the event's raw pixel, and a throughput slice hits a
+// third of its pixels more than once: the search runs once per distinct raw pixel of the selection, every other event at the pixel
+// copies the result (own event_idx, own pose look-up, the owner's failure reason counted once more).  out_slots, out_flags and the
+// failure counters end as launch_bm_match leaves them.  Thread-stride slots of an unsharded handle and the 15 x 7 kernel only.
+//   scratch: owner [W * H] (lowest slot per pixel), uniq_w [n], n_uniq [1], search_rec [n]
+constexpr u32 BM_DEDUPE_MIN_EVENTS = 40001u;  // launches bounded by at least this many events (above LM_WIDE_MAX: the throughput
+                                              // layout's boundary; a reference-faithful tick of 10 000 events shares 1.7 % of its pixels)
+bool bm_dedupe_applies(const BmArgs& a, const DevParams& p);
+void launch_bm_match_dedupe(BmArgs a, const DevParams& p, u32* owner, u32* uniq_w, u32* n_uniq, u32* search_rec, hipStream_t s);
 void launch_compact_matches(const esvo_match_t* slots, const u32* flags, const u32* prefix, u32 n,
                             esvo_match_t* out, u32* slot_of, hipStream_t s);
 void launch_matches_to_points(const esvo_match_t* m, const u32* n_ptr, u32 max_n, esvo_depth_point_t* out, const DevParams& p,

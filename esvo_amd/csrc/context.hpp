@@ -228,6 +228,13 @@ struct esvo_context {
   u64* d_lm_sort_rows[2] = {nullptr, nullptr};
   u32* d_lm_sort_hist = nullptr;
   bool lm_order_on = true;        // ESVO_LM_ORDER=0 (test / A/B only): the launch takes its slots in grid order
+  // block matching once per distinct raw pixel (kernels_bm.hip, launch_bm_match_dedupe): one allocation -- the owner table
+  // [W * H], the owner count (4 words, the first is used), the owner list [max_ev], the search outcomes [max_ev] -- on the front
+  // queue alone, the next tick's block matching is behind its readers.  Allocated when the handle can see launches of
+  // bm_dedupe_min events; run_bm takes the path for those.
+  u32* d_bm_dedupe = nullptr;
+  bool bm_dedupe_on = true;       // ESVO_BM_DEDUPE=0 (test / A/B only): one search per event
+  u32 bm_dedupe_min = esvo::BM_DEDUPE_MIN_EVENTS;  // ESVO_BM_DEDUPE_MIN=<n> (tests): the smallest launch bound that shares
   u64* d_clk = nullptr;           // in-run shader-clock probe of the LM kernel (LmArgs::clk, common.hpp); read by esvo_get_stats
   bool clk_probe = true;          // ESVO_CLK_PROBE=0 (A/B only) launches the LM kernel without it
   DevPoint* d_pt_slots = nullptr;   // LM output by slot + keep flags + their scan: alias one of two sets (front parity)

@@ -147,6 +147,17 @@ __device__ inline void grp_argmin(double& best, int& bestd) {  // ties -> larger
   }
 }
 
+// StampTransformationMap_lower_bound (utils.h:66-71) of the event's time stamp over the tick's pose stamps
+__device__ inline u32 pose_lower_bound(const BmArgs& a, const uint4& e) {
+  const double te = time_to_sec(e.y, e.z);
+  u32 lo = 0, hi = a.n_pose;
+  while (lo < hi) {
+    const u32 mid = (lo + hi) >> 1;
+    if (a.pose_sec[mid] < te) lo = mid + 1; else hi = mid;
+  }
+  return lo;
+}
+
 template <int G, bool COARSE, bool UPDOWN>
 __global__ void __launch_bounds__(BM_BLOCK) bm_match_kernel(BmArgs a, DevParams p, int RD, int lds_per_event) {
   constexpr int EPB = BM_BLOCK / G;  // events per block
@@ -154,8 +165,13 @@ __global__ void __launch_bounds__(BM_BLOCK) bm_match_kernel(BmArgs a, DevParams 
   // slot in thread-stride order; multi-GPU: slots are dealt round-robin and a rank's launch covers its own ones densely --
   // or (routed band mode, bm_item) position w of the walk over the rank's own ring, results indexed by that position
   const u32 pos = blockIdx.x * EPB + grp;
-  const u32 w = a.gidx ? pos : pos * (u32)p.ev_nshards + (u32)p.ev_shard;
   const u32 n_out = a.gidx ? a.n_loc : a.n;
+  u32 w = a.gidx ? pos : pos * (u32)p.ev_nshards + (u32)p.ev_shard;
+  if (a.uniq_w) {  // one search per distinct pixel: the owner slots, in any order; the grid is sized for n, the list is shorter
+    const u32 nu = *a.n_uniq;
+    if (blockIdx.x * EPB >= nu) return;  // (the whole workgroup)
+    w = pos < nu ? a.uniq_w[pos] : n_out;
+  }
   u32* ldsL = reinterpret_cast<u32*>(bm_smem + grp * lds_per_event);  // [7][4] dwords
   u32* ldsR = ldsL + 28;                                              // [7][RD] dwords / UPDOWN: [Nd + 6][4] dwords
   const int nd = p.dmax - p.dmin + 1;
@@ -354,20 +370,17 @@ __global__ void __launch_bounds__(BM_BLOCK) bm_match_kernel(BmArgs a, DevParams 
     // :222 (the fine search re-evaluates the same candidate); a failure here is the COARSE search's in the reference's count
     if (!(bestd >= 0 && best < p.zncc_thr)) { ok = false; reason = 2; }
   }
+  const bool found = ok;  // everything up to here follows from the raw pixel alone; what follows, from the event's time stamp
   u32 pose_idx = 0;
   if (ok) {  // StampTransformationMap_lower_bound, utils.h:66-71
-    const double te = time_to_sec(e.y, e.z);
-    u32 lo = 0, hi = a.n_pose;
-    while (lo < hi) {
-      const u32 mid = (lo + hi) >> 1;
-      if (a.pose_sec[mid] < te) lo = mid + 1; else hi = mid;
-    }
-    pose_idx = lo;
-    ok = lo < a.n_pose;  // EventBM.cpp:155-156
+    pose_idx = pose_lower_bound(a, e);
+    ok = pose_idx < a.n_pose;  // EventBM.cpp:155-156
   }
   if (w < n_out && l == 0) {
     a.out_flags[w] = ok ? 1u : 0u;
-    if (ok) {
+    // (an owner beyond the last pose stamp still hands its record to the events of its pixel that have a pose)
+    if (a.uniq_w) a.search_rec[w] = (found ? 1u : 0u) | ((u32)reason << 1);
+    if (ok || (a.uniq_w && found)) {
       esvo_match_t m;
       const double disparity = (double)bestd;         // x1(0) - bestMatch(0) / x1(1) - bestMatch(1), :146-151
       const double depth = p.baseline_f / disparity;  // :152
@@ -626,6 +639,103 @@ void launch_bm_match(const BmArgs& a, const DevParams& p, hipStream_t s) {
     if (coarse) launch_bm_mode<true, false>(bestG, a, p, RD, s);
     else launch_bm_mode<false, false>(bestG, a, p, RD, s);
   }
+}
+
+// ---- one search per distinct raw pixel (common.hpp: launch_bm_match_dedupe) ----
+// Claim: the lowest slot of every raw pixel owns it (a minimum: the same owner whatever the order the waves run in).  An event
+// outside the image owns itself: it fails at once, as it does without the sharing.
+__global__ void __launch_bounds__(256) bm_claim_kernel(BmArgs a, DevParams p, u32* __restrict__ owner, u32* __restrict__ n_uniq) {
+  const u32 w = blockIdx.x * blockDim.x + threadIdx.x;
+  if (w == 0) *n_uniq = 0u;  // (the list kernel behind this launch counts into it)
+  if (w >= a.n) return;
+  u32 k = 0;
+  uint4 e;
+  bool ok = true;
+  bm_item(a, p, w, k, e, ok);
+  const int ex = e.x & 0xffffu, ey = e.x >> 16;
+  if (ex < p.W && ey < p.H) atomicMin(owner + ey * p.W + ex, w);
+}
+// Owner list: the slots that own their pixel, in any order (results are written by slot) -- positions from one atomic per workgroup
+__global__ void __launch_bounds__(256) bm_owner_list_kernel(BmArgs a, DevParams p, const u32* __restrict__ owner, u32* __restrict__ uniq_w,
+                                                            u32* __restrict__ n_uniq) {
+  __shared__ u32 wave_cnt[4];
+  __shared__ u32 base;
+  const u32 w = blockIdx.x * blockDim.x + threadIdx.x;
+  bool own = false;
+  if (w < a.n) {
+    u32 k = 0;
+    uint4 e;
+    bool ok = true;
+    bm_item(a, p, w, k, e, ok);
+    const int ex = e.x & 0xffffu, ey = e.x >> 16;
+    own = !(ex < p.W && ey < p.H) || owner[ey * p.W + ex] == w;
+  }
+  const u64 bal = __ballot(own);
+  const u32 lane = threadIdx.x & 63u, wv = threadIdx.x >> 6;
+  if (lane == 0) wave_cnt[wv] = (u32)__popcll(bal);
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    const u32 total = wave_cnt[0] + wave_cnt[1] + wave_cnt[2] + wave_cnt[3];
+    base = total ? atomicAdd(n_uniq, total) : 0u;
+  }
+  __syncthreads();
+  if (!own) return;
+  u32 off = base + (u32)__popcll(bal & ((1ull << lane) - 1ull));
+  for (u32 i = 0; i < wv; ++i) off += wave_cnt[i];
+  uniq_w[off] = w;  // off < n: every slot is listed at most once
+}
+// Fan-out: a slot that does not own its pixel takes its owner's search outcome -- the record with its own event_idx and its own
+// pose look-up (the owner's flag folds the owner's pose test in, search_rec does not), or the owner's failure reason, counted
+// once more at the striped addresses bm_match_kernel uses.  Owners and the others write disjoint slots.
+__global__ void __launch_bounds__(256) bm_fanout_kernel(BmArgs a, DevParams p, const u32* __restrict__ owner) {
+  const u32 w = blockIdx.x * blockDim.x + threadIdx.x;
+  int reason = 0;
+  if (w < a.n) {
+    u32 k = 0;
+    uint4 e;
+    bool ok = true;
+    bm_item(a, p, w, k, e, ok);
+    const int ex = e.x & 0xffffu, ey = e.x >> 16;
+    const u32 o = (ex < p.W && ey < p.H) ? owner[ey * p.W + ex] : w;
+    if (o != w) {
+      const u32 rec = a.search_rec[o];
+      reason = (int)(rec >> 1);
+      ok = (rec & 1u) != 0u;
+      u32 pose_idx = 0;
+      if (ok) {
+        pose_idx = pose_lower_bound(a, e);
+        ok = pose_idx < a.n_pose;  // EventBM.cpp:155-156
+      }
+      a.out_flags[w] = ok ? 1u : 0u;
+      if (ok) {
+        esvo_match_t m = a.out_slots[o];
+        m.event_idx = k;
+        m.pose_idx = pose_idx;
+        a.out_slots[w] = m;
+      }
+    }
+  }
+  if (a.fail_counters) {
+#pragma unroll
+    for (int r = 1; r <= 3; ++r) {
+      const int n = __popcll(__ballot(reason == r));
+      if (n && (threadIdx.x & 63) == 0)
+        atomicAdd(a.fail_counters + CNT_BM_FAIL + (r - 1) * CNT_STRIPES + (blockIdx.x % CNT_STRIPES), (u32)n);
+    }
+  }
+}
+bool bm_dedupe_applies(const BmArgs& a, const DevParams& p) {
+  return a.n > 0 && !a.gidx && !a.keep_flags && p.ev_nshards == 1 && p.wx == 15 && p.wy == 7;
+}
+void launch_bm_match_dedupe(BmArgs a, const DevParams& p, u32* owner, u32* uniq_w, u32* n_uniq, u32* search_rec, hipStream_t s) {
+  if (a.n == 0) return;
+  const dim3 grid((a.n + 255) / 256), block(256);
+  hipMemsetAsync(owner, 0xff, sizeof(u32) * (size_t)p.W * (size_t)p.H, s);  // no owner: above every slot
+  hipLaunchKernelGGL(bm_claim_kernel, grid, block, 0, s, a, p, owner, n_uniq);
+  hipLaunchKernelGGL(bm_owner_list_kernel, grid, block, 0, s, a, p, owner, uniq_w, n_uniq);
+  a.uniq_w = uniq_w; a.n_uniq = n_uniq; a.search_rec = search_rec;
+  launch_bm_match(a, p, s);
+  hipLaunchKernelGGL(bm_fanout_kernel, grid, block, 0, s, a, p, owner);
 }
 
 // stable compaction: slot w -> position prefix[w]; slot_of (optional) remembers w

@@ -883,6 +883,14 @@ class Esvo:
         self._ck(fn(self.h, out.ctypes.data, out.size))
         return out
 
+    def debug_bm_owner_count(self):
+        """esvo_debug_bm_owner_count (api_dev.hip, not part of the ABI): the searches of the newest block-matching launch that ran
+        once per distinct raw pixel (its owner count), or None for a handle that has no such path."""
+        n, shared = C.c_uint32(0), C.c_int(0)
+        fn = _dbg_fn("esvo_debug_bm_owner_count", [C.c_void_p, C.c_void_p, C.c_void_p])
+        self._ck(fn(self.h, C.byref(n), C.byref(shared)))
+        return int(n.value) if shared.value else None
+
     def get_committed_map(self):
         """(DepthMap of the newest committed tick, its stamp) without completing a pending tick"""
         out = np.zeros(self.W * self.H, DEPTH_POINT_DTYPE)
