@@ -150,9 +150,9 @@ struct CommRound {
 // of the own tick two rounds later (same front parity) is enqueued BEFORE that happens: the block the frame is compacted
 // into (and re-gathered from, should the blocks have to grow), the pinned counter row, the front-stage events, the tick state.
 struct OwnTick {
-  u64* d_block = nullptr;              // [2 + max_ev * 13] header + frame
-  u32* h_cnt = nullptr;                // pinned, CNT_ROW
-  hipEvent_t ev[EV_FRONT_STRIDE];      // installed into h->evt[EV_T0 + fp * EV_FRONT_STRIDE ...] while the tick's front stage is enqueued
+  DevBuf<u64> d_block;                 // [2 + max_ev * 13] header + frame
+  PinBuf<u32> h_cnt;                   // pinned, CNT_ROW
+  hipEvent_t ev[EV_FRONT_STRIDE];      // raw handles, lent: installed into h->evt[EV_T0 + fp * EV_FRONT_STRIDE ...] while the tick's front stage is enqueued
   esvo_context::TickState tk;
   int fp = 0;
   bool live = false;                   // enqueued; EV_CNT of this slot marks "frame, header and counters ready"
@@ -175,32 +175,28 @@ struct esvo_comm {
   u64 own_seq = 0;                 // own ticks so far
   int last_slot_of_fp[2] = {-1, -1};
   hipEvent_t orig_ev[2][EV_FRONT_STRIDE];  // the handle's own front-stage events, put back by esvo_comm_destroy
-  u64* d_empty = nullptr;          // the block of a round without an own tick (a flushed partial round): zeros
-  u64* d_recv[2] = {nullptr, nullptr};
-  u64* d_heads = nullptr;          // [2][world] point counts of the gathered blocks
-  u64* d_map_heads = nullptr;      // esvo_comm_newest_map: [2] send + [2 * world] gathered (size, tick index + 1) -- a buffer of
+  DevBuf<u64> d_empty;             // the block of a round without an own tick (a flushed partial round): zeros
+  DevBuf<u64> d_recv[2];
+  DevBuf<u64> d_heads;             // [2][world] point counts of the gathered blocks
+  DevBuf<u64> d_map_heads;         // esvo_comm_newest_map: [2] send + [2 * world] gathered (size, tick index + 1) -- a buffer of
                                    // its own: the back stream may still copy frames out of d_recv[] while the maps are exchanged
-  u64* h_heads = nullptr;          // pinned, [2][world]
-  hipEvent_t gathered[2];          // the gather into d_recv[i] and the copy of its counts have completed
-  hipEvent_t pushed[2];            // the back stream has copied every frame out of d_recv[i]
-  bool events_ok = false;
+  PinBuf<u64> h_heads;             // pinned, [2][world]
+  DevEvent gathered[2];            // the gather into d_recv[i] and the copy of its counts have completed
+  DevEvent pushed[2];              // the back stream has copied every frame out of d_recv[i]
+  bool events_ok = false;          // the OwnTick events exist and the handle's own are kept in orig_ev
   u64 rounds = 0;                  // rounds whose gather has been enqueued
   esvo_comm_stats_t st = {};
   // band mode: all-gather of the band maps, merged on the device; of the Time-Surface bands
-  esvo_depth_point_t* d_band_recv = nullptr;  // [world][band_block_pts]
-  size_t band_block_pts = 0;
-  esvo_depth_point_t* d_merged = nullptr;     // [merged_cap] the unsharded element list
-  size_t merged_cap = 0;
-  u32* d_id_present = nullptr;                // [id_cap] x 3: present, prefix, where
-  u32* d_id_scan_tmp = nullptr;
+  DevBuf<esvo_depth_point_t> d_band_recv;     // [world][cap() / world]
+  DevBuf<esvo_depth_point_t> d_merged;        // the unsharded element list
+  DevBuf<u32> d_id_present;                   // [id_cap] x 3: present, prefix, where
+  DevBuf<u32> d_id_scan_tmp;
   size_t id_cap = 0;
-  u32* d_merged_n = nullptr;
-  float* d_xyz = nullptr;
-  size_t xyz_cap = 0;
-  uint8_t* d_ts_send = nullptr;
-  uint8_t* d_ts_recv = nullptr;
-  size_t ts_block = 0;
-  hipEvent_t ev_map = nullptr;                // the band's export is on the back stream, the exchange on the front stream
+  DevBuf<u32> d_merged_n;
+  DevBuf<float> d_xyz;                        // 3 per point
+  DevBuf<uint8_t> d_ts_send;                  // one block of Time-Surface rows, padded to 8 bytes
+  DevBuf<uint8_t> d_ts_recv;                  // [world] of them
+  DevEvent ev_map;                            // the band's export is on the back stream, the exchange on the front stream
   static size_t block_words(u32 stride) { return 2 + (size_t)stride * 13; }
 };
 
@@ -209,25 +205,19 @@ void comm_release(esvo_context* h) {
   esvo_comm* c = h->comm;
   if (!c) return;
   if (c->sc) hipStreamSynchronize(c->sc);
-  for (void* p : {(void*)c->d_empty, (void*)c->d_recv[0], (void*)c->d_recv[1], (void*)c->d_heads, (void*)c->d_map_heads, (void*)c->d_band_recv, (void*)c->d_merged, (void*)c->d_id_present, (void*)c->d_id_scan_tmp, (void*)c->d_merged_n, (void*)c->d_xyz, (void*)c->d_ts_send, (void*)c->d_ts_recv})
-    if (p) hipFree(p);
-  if (c->h_heads) hipHostFree(c->h_heads);
-  if (c->ev_map) hipEventDestroy(c->ev_map);
   if (c->events_ok) {
-    for (int i = 0; i < 2; ++i) { hipEventDestroy(c->pushed[i]); hipEventDestroy(c->gathered[i]); }
     // the handle gets its own front-stage events back (nothing is in flight: the callers drained every stream)
     for (int fp = 0; fp < 2; ++fp)
       for (int i = 0; i < EV_FRONT_STRIDE; ++i) h->evt[EV_T0 + fp * EV_FRONT_STRIDE + i] = c->orig_ev[fp][i];
-    for (OwnTick& o : c->own) {
+    for (OwnTick& o : c->own)
       for (int i = 0; i < EV_FRONT_STRIDE; ++i) hipEventDestroy(o.ev[i]);
-      if (o.d_block) hipFree(o.d_block);
-      if (o.h_cnt) hipHostFree(o.h_cnt);
-    }
   }
-  if (c->nccl && g_rccl.CommDestroy) g_rccl.CommDestroy(c->nccl);
-  if (c->sc) hipStreamDestroy(c->sc);
-  delete c;
+  const ncclComm_t nccl = c->nccl;
+  const hipStream_t sc = c->sc;
+  delete c;  // its other events and every buffer
   h->comm = nullptr;
+  if (nccl && g_rccl.CommDestroy) g_rccl.CommDestroy(nccl);
+  if (sc) hipStreamDestroy(sc);
 }
 // esvo_reset on a handle with a communicator (collective like every esvo_comm_* call): rounds in flight are dropped with
 // the window they would have entered
@@ -267,14 +257,12 @@ int comm_all_gather(esvo_context* h, const void* d_send, void* d_recv, size_t by
 
 int comm_alloc(esvo_context* h) {
   esvo_comm* c = h->comm;
-  for (void* p : {(void*)c->d_empty, (void*)c->d_recv[0], (void*)c->d_recv[1]})
-    if (p) hipFree(p);
-  c->d_empty = c->d_recv[0] = c->d_recv[1] = nullptr;
+  (void)c->d_empty.release(); (void)c->d_recv[0].release(); (void)c->d_recv[1].release();
   const size_t bw = esvo_comm::block_words(c->stride_cap);
-  HIPCHK(hipMalloc(reinterpret_cast<void**>(&c->d_empty), bw * 8));
+  HIPCHK(c->d_empty.alloc(bw));
   HIPCHK(hipMemsetAsync(c->d_empty, 0, bw * 8, c->sc));  // (on the stream that reads it: the null stream is not ordered with a non-blocking one)
-  HIPCHK(hipMalloc(reinterpret_cast<void**>(&c->d_recv[0]), bw * 8 * c->world));
-  HIPCHK(hipMalloc(reinterpret_cast<void**>(&c->d_recv[1]), bw * 8 * c->world));
+  HIPCHK(c->d_recv[0].alloc(bw * c->world));
+  HIPCHK(c->d_recv[1].alloc(bw * c->world));
   return ESVO_OK;
 }
 
@@ -296,20 +284,20 @@ int comm_setup(esvo_context* h, int rank, int world) {
   }
   int rc = comm_alloc(h);
   if (rc) return rc;
-  HIPCHK(hipMalloc(reinterpret_cast<void**>(&c->d_heads), sizeof(u64) * 2 * world));
-  HIPCHK(hipMalloc(reinterpret_cast<void**>(&c->d_map_heads), sizeof(u64) * (2 + 2 * (size_t)world)));
-  HIPCHK(hipHostMalloc(reinterpret_cast<void**>(&c->h_heads), sizeof(u64) * 2 * world));
+  HIPCHK(c->d_heads.alloc(2 * (size_t)world));
+  HIPCHK(c->d_map_heads.alloc(2 + 2 * (size_t)world));
+  HIPCHK(c->h_heads.alloc(2 * (size_t)world));
   for (OwnTick& o : c->own) {  // (a block holds a frame of any size a tick can produce: re-gathered from here when blocks grow)
-    HIPCHK(hipMalloc(reinterpret_cast<void**>(&o.d_block), esvo_comm::block_words(h->max_ev) * 8));
-    HIPCHK(hipHostMalloc(reinterpret_cast<void**>(&o.h_cnt), sizeof(u32) * CNT_ROW));
+    HIPCHK(o.d_block.alloc(esvo_comm::block_words(h->max_ev)));
+    HIPCHK(o.h_cnt.alloc(CNT_ROW));
     std::memset(o.h_cnt, 0, sizeof(u32) * CNT_ROW);
     for (int i = 0; i < EV_FRONT_STRIDE; ++i) HIPCHK(hipEventCreate(&o.ev[i]));
   }
   for (int fp = 0; fp < 2; ++fp)
     for (int i = 0; i < EV_FRONT_STRIDE; ++i) c->orig_ev[fp][i] = h->evt[EV_T0 + fp * EV_FRONT_STRIDE + i];
   for (int i = 0; i < 2; ++i) {
-    HIPCHK(hipEventCreateWithFlags(&c->pushed[i], hipEventDisableTiming));
-    HIPCHK(hipEventCreateWithFlags(&c->gathered[i], hipEventDisableTiming));
+    HIPCHK(c->pushed[i].create(hipEventDisableTiming));
+    HIPCHK(c->gathered[i].create(hipEventDisableTiming));
   }
   c->events_ok = true;
   // one untimed round trip sets up the communicator's channels (and proves the transport works)
@@ -698,10 +686,10 @@ int esvo_comm_newest_map(esvo_handle h, esvo_depth_point_t* out, size_t cap, siz
   // Every rank takes the same path from here on, whatever its `out` / `cap` and whatever its local allocations did: the
   // ranks first agree (one more 16-byte gather) that all of them could stage the exchange, and only then gather the maps --
   // a rank that skipped a collective the others make would hang them.
-  u64 *d_s = nullptr, *d_r = nullptr;
+  DevBuf<u64> d_s, d_r;
   const size_t bw = std::max<size_t>(max_n * W, 1);
-  hipError_t e = hipMalloc(reinterpret_cast<void**>(&d_s), bw * 8);
-  if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&d_r), bw * 8 * c->world);
+  hipError_t e = d_s.alloc(bw);
+  if (e == hipSuccess) e = d_r.alloc(bw * c->world);
   if (e == hipSuccess && !mine.empty())
     e = hipMemcpyAsync(d_s, mine.data(), mine.size() * sizeof(esvo_depth_point_t), hipMemcpyHostToDevice, h->stream);
   u64 ok[2] = {e == hipSuccess ? 0u : 1u, 0u};
@@ -726,8 +714,6 @@ int esvo_comm_newest_map(esvo_handle h, esvo_depth_point_t* out, size_t cap, siz
     }
   }
   if (hipStreamSynchronize(h->stream) != hipSuccess && !rc) { g_create_error = "map exchange failed"; rc = ESVO_ERR_HIP; }
-  if (d_s) hipFree(d_s);
-  if (d_r) hipFree(d_r);
   return rc;
 }
 
@@ -767,8 +753,8 @@ int gather_map_device(esvo_context* h, size_t* n_total) {
   esvo_comm* c = h->comm;
   int rc = flush_pending_tick(h);
   if (rc) return rc;
-  if (!c->ev_map) HIPCHK(hipEventCreateWithFlags(&c->ev_map, hipEventDisableTiming));
-  if (!c->d_merged_n) HIPCHK(hipMalloc(reinterpret_cast<void**>(&c->d_merged_n), sizeof(u32) * 2));
+  HIPCHK(c->ev_map.create(hipEventDisableTiming));
+  if (!c->d_merged_n) HIPCHK(c->d_merged_n.alloc(2));
   // the band's alive cells, in cell order (esvo_depth_point_t with the global creation id in seq), on the back stream
   launch_map_compact(h->d_map_cur, h->d_exp_flags, h->d_exp_prefix, h->d_cnt_b + CNTB_MAP, h->d_scan_tmp_b, h->d_export, nullptr, h->dp, h->stream_b);
   u64* d_hs = c->d_map_heads;
@@ -792,25 +778,15 @@ int gather_map_device(esvo_context* h, size_t* n_total) {
   const size_t id_need = std::max<size_t>(win_pts * 9 + 1, 1024);
   // (a failed allocation below would leave the other ranks in a collective this one skips; the buffers are small against the
   //  handle's own and grow geometrically, so it is treated like any other out-of-memory condition: the call fails)
-  if (max_n > c->band_block_pts) {
-    if (c->d_band_recv) hipFree(c->d_band_recv);
-    c->d_band_recv = nullptr;
-    c->band_block_pts = max_n + max_n / 4 + 256;
-    HIPCHK(hipMalloc(reinterpret_cast<void**>(&c->d_band_recv), sizeof(esvo_depth_point_t) * c->band_block_pts * c->world));
-  }
-  if (total > c->merged_cap) {
-    if (c->d_merged) hipFree(c->d_merged);
-    c->d_merged = nullptr;
-    c->merged_cap = total + total / 4 + 256;
-    HIPCHK(hipMalloc(reinterpret_cast<void**>(&c->d_merged), sizeof(esvo_depth_point_t) * c->merged_cap));
-  }
+  if (max_n > c->d_band_recv.cap() / c->world) HIPCHK(c->d_band_recv.alloc((max_n + max_n / 4 + 256) * c->world));
+  if (total > c->d_merged.cap()) HIPCHK(c->d_merged.alloc(total + total / 4 + 256));
   if (id_need > c->id_cap) {
-    if (c->d_id_present) hipFree(c->d_id_present);
-    if (c->d_id_scan_tmp) hipFree(c->d_id_scan_tmp);
-    c->d_id_present = c->d_id_scan_tmp = nullptr;
-    c->id_cap = id_need + id_need / 4;
-    HIPCHK(hipMalloc(reinterpret_cast<void**>(&c->d_id_present), sizeof(u32) * 3 * c->id_cap));
-    HIPCHK(hipMalloc(reinterpret_cast<void**>(&c->d_id_scan_tmp), sizeof(u32) * (scan_scratch_elems(c->id_cap) + 8)));
+    (void)c->d_id_present.release(); (void)c->d_id_scan_tmp.release();
+    c->id_cap = 0;
+    const size_t cap = id_need + id_need / 4;
+    HIPCHK(c->d_id_present.alloc(3 * cap));
+    HIPCHK(c->d_id_scan_tmp.alloc(scan_scratch_elems(cap) + 8));
+    c->id_cap = cap;
   }
   // every rank's block has the SAME length -- the largest band of this read-out -- whatever its own buffers hold
   rc = comm_all_gather(h, h->d_export, c->d_band_recv, max_n * sizeof(esvo_depth_point_t));
@@ -861,12 +837,7 @@ int esvo_comm_gather_pointcloud_xyz(esvo_handle h, float* out_xyz, size_t cap_po
   *n = total;
   if (!out_xyz || !total) { HIPCHK(hipStreamSynchronize(h->stream)); return ESVO_OK; }
   if (cap_points < total) { HIPCHK(hipStreamSynchronize(h->stream)); FAIL(ESVO_ERR_CAPACITY, "output array too small for the point cloud"); }
-  if (total > c->xyz_cap) {
-    if (c->d_xyz) hipFree(c->d_xyz);
-    c->d_xyz = nullptr;
-    c->xyz_cap = total + total / 4 + 256;
-    HIPCHK(hipMalloc(reinterpret_cast<void**>(&c->d_xyz), sizeof(float) * 3 * c->xyz_cap));
-  }
+  if (total > c->d_xyz.cap() / 3) HIPCHK(c->d_xyz.alloc(3 * (total + total / 4 + 256)));
   const double* T = h->T_world_frame;
   hipLaunchKernelGGL(esvo::band_xyz_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, h->stream, c->d_merged, c->d_merged_n, T[0], T[1], T[2], T[3],
                      T[4], T[5], T[6], T[7], T[8], T[9], T[10], T[11], c->d_xyz);
@@ -891,14 +862,11 @@ int esvo_comm_gather_ts(esvo_handle h, int cam) {
     FAIL(ESVO_ERR_UNSUPPORTED, "esvo_comm_gather_ts: the band is not rank * ceil(H / world) rows");
   if (!h->ts_valid[cam]) FAIL(ESVO_ERR_STATE, "no device-resident Time Surface: call esvo_ts_render first");
   const size_t block = ((size_t)rows * h->W + 7) / 8 * 8;
-  if (c->ts_block != block) {
-    if (c->d_ts_send) hipFree(c->d_ts_send);
-    if (c->d_ts_recv) hipFree(c->d_ts_recv);
-    c->d_ts_send = c->d_ts_recv = nullptr;
-    HIPCHK(hipMalloc(reinterpret_cast<void**>(&c->d_ts_send), block));
-    HIPCHK(hipMalloc(reinterpret_cast<void**>(&c->d_ts_recv), block * c->world));
+  if (c->d_ts_recv.cap() != block * c->world) {
+    (void)c->d_ts_send.release(); (void)c->d_ts_recv.release();
+    HIPCHK(c->d_ts_send.alloc(block));
     HIPCHK(hipMemsetAsync(c->d_ts_send, 0, block, h->stream));  // (the pad bytes; on the stream the copies below run on: hipMemset's null stream is not ordered with it)
-    c->ts_block = block;
+    HIPCHK(c->d_ts_recv.alloc(block * c->world));  // (last: its size marks the pair complete)
   }
   std::lock_guard<std::mutex> lt(h->mu_ts);
   resident_write_begin(h, cam);  // a tracker read of the previous surface may be in flight

@@ -59,26 +59,12 @@ void fill_dev_params(esvo_context* h) {
   d.ls_norm = p.ls_norm;
 }
 
-template <typename T>
-hipError_t dalloc(T** p, size_t n) { return hipMalloc(reinterpret_cast<void**>(p), (n ? n : 1) * sizeof(T)); }
-
 // compute band of the per-cell stages: the owned rows + a halo of 2 rows for the displaced-element side
 // effects (+ the regulariser's radius), see DevParams::cband_y0
 void set_compute_band(esvo_context* h) {
   const int halo = 2 + (h->prm.regularization ? h->prm.reg_radius : 0);
   h->dp.cband_y0 = std::max(0, h->dp.band_y0 - halo);
   h->dp.cband_y1 = std::min(h->H, h->dp.band_y1 + halo);
-}
-
-// pinned staging + the global-index ring of the routed band mode
-void release_routing(esvo_context* h) {
-  for (int cam = 0; cam < 2; ++cam) {
-    if (h->h_route_ev[cam]) hipHostFree(h->h_route_ev[cam]);
-    h->h_route_ev[cam] = nullptr;
-    h->route_cap[cam] = 0;
-  }
-  if (h->h_route_gidx) hipHostFree(h->h_route_gidx);
-  h->h_route_gidx = nullptr;
 }
 
 // the reference's colour tables are jet on i / 255 (Visualization.cpp:128-226): 255 * channel =
@@ -179,10 +165,10 @@ int esvo_create(const esvo_params_t* params, const esvo_calib_t* left, const esv
   CK(hipStreamCreateWithFlags(&h->stream_t, hipStreamNonBlocking));
   CK(hipStreamCreateWithFlags(&h->stream_i, hipStreamNonBlocking));
   // calibration -> device
-  CK(dalloc(&h->d_lut, npx));
+  CK(h->d_lut.alloc(npx));
   CK(hipMemcpy(h->d_lut, left->rect_lut, sizeof(float2) * npx, hipMemcpyHostToDevice));
   if (left->rect_mask) {
-    CK(dalloc(&h->d_mask, npx));
+    CK(h->d_mask.alloc(npx));
     CK(hipMemcpy(h->d_mask, left->rect_mask, npx, hipMemcpyHostToDevice));
   }
   for (int cam = 0; cam < 2; ++cam) {
@@ -192,7 +178,7 @@ int esvo_create(const esvo_params_t* params, const esvo_calib_t* left, const esv
       fm[i].x = (int)std::nearbyintf(c->map_x[i] * 32.f);
       fm[i].y = (int)std::nearbyintf(c->map_y[i] * 32.f);
     }
-    CK(dalloc(&h->d_fixmap[cam], npx));
+    CK(h->d_fixmap[cam].alloc(npx));
     CK(hipMemcpy(h->d_fixmap[cam], fm.data(), sizeof(int2) * npx, hipMemcpyHostToDevice));
     // per rectified row: the raw rows its bilinear taps reach (what a row band of the Time Surface needs of the SAE;
     // esvo_shard_set_routing).  A tap outside the image reads the constant 0 and needs nothing.
@@ -208,15 +194,15 @@ int esvo_create(const esvo_params_t* params, const esvo_calib_t* left, const esv
         h->fix_row_lo[cam][y] = std::min(h->fix_row_lo[cam][y], lo);
         h->fix_row_hi[cam][y] = std::max(h->fix_row_hi[cam][y], hi);
       }
-    CK(dalloc(&h->d_sae[cam], npx));
+    CK(h->d_sae[cam].alloc(npx));
     CK(hipMemset(h->d_sae[cam], 0, sizeof(u64) * npx));
     if (params->max_event_queue_len > 0) {  // EventQueueMat semantics: a set of <= L keys per pixel, slot-major
-      CK(dalloc(&h->d_tsq[cam], npx * (size_t)params->max_event_queue_len));
+      CK(h->d_tsq[cam].alloc(npx * (size_t)params->max_event_queue_len));
       CK(hipMemset(h->d_tsq[cam], 0, sizeof(u64) * npx * (size_t)params->max_event_queue_len));
     }
-    CK(dalloc(&h->d_ts[cam], npx + 64));
-    CK(dalloc(&h->d_obs2[0][cam], npx + 64));
-    CK(dalloc(&h->d_obs2[1][cam], npx + 64));
+    CK(h->d_ts[cam].alloc(npx + 64));
+    CK(h->d_obs2[0][cam].alloc(npx + 64));
+    CK(h->d_obs2[1][cam].alloc(npx + 64));
     h->d_obs[cam] = h->d_obs2[0][cam];
   }
   if (params->max_event_queue_len > 0) {
@@ -224,34 +210,34 @@ int esvo_create(const esvo_params_t* params, const esvo_calib_t* left, const esv
     const size_t tiles = (size_t)((h->W + 7) / 8) * ((h->H + 7) / 8);
     h->tsq_tcap = 1024;
     if (const char* e = esvo_dev_switch("ESVO_TSQ_TILE_CAP")) h->tsq_tcap = (u32)std::max(1, std::atoi(e));  // tests: force the overflow list
-    CK(dalloc(&h->d_tsq_tcount, tiles));
+    CK(h->d_tsq_tcount.alloc(tiles));
     CK(hipMemset(h->d_tsq_tcount, 0, sizeof(u32) * tiles));
-    CK(dalloc(&h->d_tsq_tlist, tiles * h->tsq_tcap));
-    CK(dalloc(&h->d_tsq_over, (size_t)esvo_context::TSQ_ROUND));
-    CK(dalloc(&h->d_tsq_over_count, 1));
+    CK(h->d_tsq_tlist.alloc(tiles * h->tsq_tcap));
+    CK(h->d_tsq_over.alloc((size_t)esvo_context::TSQ_ROUND));
+    CK(h->d_tsq_over_count.alloc(1));
   }
-  CK(dalloc(&h->d_raw, npx + 64));
-  CK(dalloc(&h->d_raw1, npx + 64));
+  CK(h->d_raw.alloc(npx + 64));
+  CK(h->d_raw1.alloc(npx + 64));
   h->h_rect_lut[0].assign(left->rect_lut, left->rect_lut + 2 * npx);
   if (right->rect_lut) h->h_rect_lut[1].assign(right->rect_lut, right->rect_lut + 2 * npx);
-  CK(dalloc(&h->d_obs_tmp, npx + 64));
+  CK(h->d_obs_tmp.alloc(npx + 64));
   h->ring_cap = (u64)std::max<int64_t>(params->event_ring_capacity, 1024);
-  for (int cam = 0; cam < 2; ++cam) CK(dalloc(&h->d_ring[cam], h->ring_cap));
+  for (int cam = 0; cam < 2; ++cam) CK(h->d_ring[cam].alloc(h->ring_cap));
   h->max_poses = (u32)std::max(params->max_poses_per_tick, 2);
-  CK(dalloc(&h->d_pose_T2[0], (size_t)h->max_poses * 17));  // [T | toSec]
-  CK(dalloc(&h->d_pose_T2[1], (size_t)h->max_poses * 17));
+  CK(h->d_pose_T2[0].alloc((size_t)h->max_poses * 17));  // [T | toSec]
+  CK(h->d_pose_T2[1].alloc((size_t)h->max_poses * 17));
   h->d_pose_T = h->d_pose_T2[0];
   // + 1: the SGM bootstrap selects up to PROCESS_EVENT_NUM + 1 events (esvo_Mapping.cpp:547: `size() <= PROCESS_EVENT_NUM_`)
   h->max_ev = (u32)std::max(params->max_events_per_tick, params->process_event_num) + 1u;
   if (h->max_ev > 4000000u) { g_create_error = "max_events_per_tick too large (scan limit 4M)"; esvo_destroy(h); return ESVO_ERR_CAPACITY; }
   if (npx > 4000000u) { g_create_error = "image too large (scan limit 4M pixels)"; esvo_destroy(h); return ESVO_ERR_CAPACITY; }
   const size_t E = h->max_ev;
-  CK(dalloc(&h->d_tick_ev, E));
-  CK(dalloc(&h->d_match_slots, E));
-  CK(dalloc(&h->d_match_flags, E));
-  CK(dalloc(&h->d_match_prefix, E));
-  CK(dalloc(&h->d_matches2[0], E));
-  CK(dalloc(&h->d_matches2[1], E));
+  CK(h->d_tick_ev.alloc(E));
+  CK(h->d_match_slots.alloc(E));
+  CK(h->d_match_flags.alloc(E));
+  CK(h->d_match_prefix.alloc(E));
+  CK(h->d_matches2[0].alloc(E));
+  CK(h->d_matches2[1].alloc(E));
   h->d_matches = h->d_matches2[0];
   // (scratch of the split launch: 7 x 16 doubles per match -- only where the launch can be used)
   if (E >= LM_SPLIT_MIN_EVENTS) {
@@ -260,27 +246,27 @@ int esvo_create(const esvo_params_t* params, const esvo_calib_t* left, const esv
     // instructions of lockstep execution, and the tick is bound by the chip's throughput at its sustained f64 clock.  It is
     // On the 1280x720 stress stream (4.9e5 events, 2.3e5 matches per tick: five times the waves) it does pay: 7.7 against
     // 8.4 ms per tick (profiles/r03_split_launch_other_workloads.txt).  So: used for launches bounded by >= 400 000 events.
-    CK(dalloc(&h->d_lm_fvec0, E * 7 * 16));
-    CK(dalloc(&h->d_lm_fnorm0, E));
-    CK(dalloc(&h->d_lm_meta, E));
-    CK(dalloc(&h->d_lm_order, E));
-    CK(dalloc(&h->d_lm_hist, 2 * 32 * 64));  // kernels_lm.hip: 2 x LM_SPLIT_STRIPES x LM_SPLIT_BINS
+    CK(h->d_lm_fvec0.alloc(E * 7 * 16));
+    CK(h->d_lm_fnorm0.alloc(E));
+    CK(h->d_lm_meta.alloc(E));
+    CK(h->d_lm_order.alloc(E));
+    CK(h->d_lm_hist.alloc(2 * 32 * 64));  // kernels_lm.hip: 2 x LM_SPLIT_STRIPES x LM_SPLIT_BINS
     CK(hipMemset(h->d_lm_hist, 0, sizeof(u32) * 2 * 32 * 64));
   }
   if (E > LM_TWO_QUEUES_MAX_EVENTS) {  // (= LM_WIDE_MAX: launches above it take the narrow layout) the processing order, context.hpp
     for (int k = 0; k < 2; ++k) {
-      CK(dalloc(&h->d_lm_pix_order2[k], E));
-      CK(dalloc(&h->d_lm_sort_rows[k], E));
+      CK(h->d_lm_pix_order2[k].alloc(E));
+      CK(h->d_lm_sort_rows[k].alloc(E));
     }
-    CK(dalloc(&h->d_lm_sort_hist, voxel_hist_words(E)));
+    CK(h->d_lm_sort_hist.alloc(voxel_hist_words(E)));
     if (const char* eo = esvo_dev_switch("ESVO_LM_ORDER")) h->lm_order_on = std::atoi(eo) != 0;
   }
   if (const char* ed = esvo_dev_switch("ESVO_BM_DEDUPE")) h->bm_dedupe_on = std::atoi(ed) != 0;
   if (const char* em = esvo_dev_switch("ESVO_BM_DEDUPE_MIN")) h->bm_dedupe_min = (u32)std::max(1L, std::atol(em));
-  if (h->bm_dedupe_on && E >= h->bm_dedupe_min) CK(dalloc(&h->d_bm_dedupe, npx + 4 + 2 * E));  // context.hpp: table | count | list | outcomes
+  if (h->bm_dedupe_on && E >= h->bm_dedupe_min) CK(h->d_bm_dedupe.alloc(npx + 4 + 2 * E));  // context.hpp: table | count | list | outcomes
   // (two blocks, one per front parity: two LM launches in flight -- the two LM queues -- must not share the probe's scratch, where
   //  a wave leaves its start stamps: a launch that read the other one's stamp added a wrapped difference to the sums)
-  CK(dalloc(&h->d_clk, 2 * clk_words(h->max_ev)));
+  CK(h->d_clk.alloc(2 * clk_words(h->max_ev)));
   CK(hipMemset(h->d_clk, 0, sizeof(u64) * 2 * clk_words(h->max_ev)));
   if (const char* ec = esvo_dev_switch("ESVO_CLK_PROBE")) h->clk_probe = std::atoi(ec) != 0;
   {
@@ -289,35 +275,35 @@ int esvo_create(const esvo_params_t* params, const esvo_calib_t* left, const esv
     h->stats.clk_ref_khz = (uint32_t)khz;
   }
   for (int k = 0; k < 2; ++k) {
-    CK(dalloc(&h->d_pt_slots2[k], E));
-    CK(dalloc(&h->d_pt_flags2[k], E));
-    CK(dalloc(&h->d_pt_prefix2[k], E));
-    CK(dalloc(&h->d_scan_tmp_l2[k], scan_scratch_elems(std::max(E, npx)) + 8));
+    CK(h->d_pt_slots2[k].alloc(E));
+    CK(h->d_pt_flags2[k].alloc(E));
+    CK(h->d_pt_prefix2[k].alloc(E));
+    CK(h->d_scan_tmp_l2[k].alloc(scan_scratch_elems(std::max(E, npx)) + 8));
   }
   h->d_pt_slots = h->d_pt_slots2[0]; h->d_pt_flags = h->d_pt_flags2[0]; h->d_pt_prefix = h->d_pt_prefix2[0];
   h->d_scan_tmp_l = h->d_scan_tmp_l2[0];
-  CK(dalloc(&h->d_pts_tmp, E));
-  CK(dalloc(&h->d_stage[0], E));
-  CK(dalloc(&h->d_stage[1], E));
-  CK(dalloc(&h->d_counters2[0], CNT_ROW));
-  CK(dalloc(&h->d_counters2[1], CNT_ROW));
+  CK(h->d_pts_tmp.alloc(E));
+  CK(h->d_stage[0].alloc(E));
+  CK(h->d_stage[1].alloc(E));
+  CK(h->d_counters2[0].alloc(CNT_ROW));
+  CK(h->d_counters2[1].alloc(CNT_ROW));
   CK(hipMemset(h->d_counters2[0], 0, sizeof(u32) * CNT_ROW));
   CK(hipMemset(h->d_counters2[1], 0, sizeof(u32) * CNT_ROW));
   h->d_counters = h->d_counters2[0];
-  CK(hipHostMalloc(reinterpret_cast<void**>(&h->h_counters), sizeof(u32) * CNT_ROW * 2));
+  CK(h->h_counters.alloc(CNT_ROW * 2));
   std::memset(h->h_counters, 0, sizeof(u32) * CNT_ROW * 2);
-  CK(hipHostMalloc(reinterpret_cast<void**>(&h->h_pin), sizeof(double) * 2 * ((size_t)h->max_poses * 17 + 16)));
-  CK(dalloc(&h->d_scan_tmp, scan_scratch_elems(std::max(E, npx)) + 8));
-  CK(dalloc(&h->d_scan_tmp_b, scan_scratch_elems(std::max(E, npx)) + 8));
-  CK(dalloc(&h->d_cnt_b, CNTB_ROW));
+  CK(h->h_pin.alloc(2 * ((size_t)h->max_poses * 17 + 16)));
+  CK(h->d_scan_tmp.alloc(scan_scratch_elems(std::max(E, npx)) + 8));
+  CK(h->d_scan_tmp_b.alloc(scan_scratch_elems(std::max(E, npx)) + 8));
+  CK(h->d_cnt_b.alloc(CNTB_ROW));
   CK(hipMemset(h->d_cnt_b, 0, sizeof(u32) * CNTB_ROW));
-  CK(hipHostMalloc(reinterpret_cast<void**>(&h->h_cnt_b), sizeof(u32) * CNTB_ROW * CNTB_ROWS));  // (common.hpp: CNTB_ROW_*)
+  CK(h->h_cnt_b.alloc(CNTB_ROW * CNTB_ROWS));  // (common.hpp: CNTB_ROW_*)
   std::memset(h->h_cnt_b, 0, sizeof(u32) * CNTB_ROW * CNTB_ROWS);
-  CK(dalloc(&h->d_halo_viol, 2));
+  CK(h->d_halo_viol.alloc(2));
   CK(hipMemset(h->d_halo_viol, 0, sizeof(u32) * 2));
   // fusion window
   h->win_cap = (u32)std::max<int64_t>((int64_t)params->max_window_points, (int64_t)E) + 2 * (u32)E;
-  CK(dalloc(&h->d_win, h->win_cap));
+  CK(h->d_win.alloc(h->win_cap));
   // CONST_POINTS keeps frames until their points exceed 1.5 maxNumFusionPoints (esvo_Mapping.cpp:346-353): every non-empty
   // frame holds at least one point, which bounds their number; empty frames are run-length records (context.hpp)
   h->max_frames = (u32)std::max(params->max_fusion_frames + 2, 512);
@@ -329,56 +315,55 @@ int esvo_create(const esvo_params_t* params, const esvo_calib_t* left, const esv
   h->slot_used.assign(h->max_frames + 1, 0);
   h->n_pose_slots = std::min<u32>(h->max_frames + 1, 1024u);
   if (const char* e0 = esvo_dev_switch("ESVO_POSE_SLOTS0")) h->n_pose_slots = std::min<u32>(h->max_frames + 1, (u32)std::max(1, std::atoi(e0)));
-  CK(dalloc(&h->d_frame_pose_T, (size_t)h->n_pose_slots * h->max_poses * 16));
-  CK(dalloc(&h->d_fr_table, 2 * (3 * (size_t)h->max_frames + 1)));
-  CK(hipHostMalloc(reinterpret_cast<void**>(&h->h_fr_table), sizeof(u32) * 2 * (3 * (size_t)h->max_frames + 1)));
+  CK(h->d_frame_pose_T.alloc((size_t)h->n_pose_slots * h->max_poses * 16));
+  CK(h->d_fr_table.alloc(2 * (3 * (size_t)h->max_frames + 1)));
+  CK(h->h_fr_table.alloc(2 * (3 * (size_t)h->max_frames + 1)));
   // map
-  CK(dalloc(&h->d_prop, h->win_cap));
+  CK(h->d_prop.alloc(h->win_cap));
   {  // the fusion front (kernels_fuse.hip): FUSE_TILE x FUSE_TILE-cell tiles
     const size_t n_tiles = (size_t)((h->W + FUSE_TILE - 1) / FUSE_TILE) * ((h->H + FUSE_TILE - 1) / FUSE_TILE);
     if (const char* et = esvo_dev_switch("ESVO_FUSE_TILE_CAP")) h->fuse_tile_cap = (u32)std::max(1L, std::atol(et));
     if (const char* ep = esvo_dev_switch("ESVO_FUSE_PMAX")) h->fuse_pmax_plus1 = (u32)std::max(0L, std::atol(ep)) + 1u;
-    CK(dalloc(&h->d_tile_pts, n_tiles * h->fuse_tile_cap));
-    CK(dalloc(&h->d_over_pts, h->win_cap));
-    CK(dalloc(&h->d_tile_count, n_tiles));
-    CK(dalloc(&h->d_cell_count, npx));
-    CK(dalloc(&h->d_cell_offset, npx));
+    CK(h->d_tile_pts.alloc(n_tiles * h->fuse_tile_cap));
+    CK(h->d_over_pts.alloc(h->win_cap));
+    CK(h->d_tile_count.alloc(n_tiles));
+    CK(h->d_cell_count.alloc(npx));
+    CK(h->d_cell_offset.alloc(npx));
     h->fuse_slice_cap = (u32)((n_tiles + 63) / 64) * FUSE_TILE * FUSE_TILE;   // the cells of the tiles t with t % 64 == slice
-    CK(dalloc(&h->d_cell_list, (size_t)16 * 64 * h->fuse_slice_cap));
-    CK(dalloc(&h->d_fuse_ctr, 2112 + 64));
+    CK(h->d_cell_list.alloc((size_t)16 * 64 * h->fuse_slice_cap));
+    CK(h->d_fuse_ctr.alloc(2112 + 64));
     CK(hipMemset(h->d_tile_count, 0, sizeof(u32) * n_tiles));  // zero between ticks: fuse_turn_kernel clears what was read
     CK(hipMemset(h->d_fuse_ctr, 0, sizeof(u32) * (2112 + 64)));
     if (const char* er = esvo_dev_switch("ESVO_FUSE_TILE_REC")) h->fuse_tile_rec = (u32)std::max(1L, std::atol(er));
-    CK(dalloc(&h->d_rec_ids, n_tiles * h->fuse_tile_rec + (size_t)h->win_cap * 9));
+    CK(h->d_rec_ids.alloc(n_tiles * h->fuse_tile_rec + (size_t)h->win_cap * 9));
   }
   if (const char* ef = esvo_dev_switch("ESVO_FUSE_LDS_CAP")) h->fuse_lds_cap = (u32)std::max(0L, std::atol(ef));
-  CK(hipMalloc(reinterpret_cast<void**>(&h->d_map), map_buffer_bytes(npx)));  // cells + their dense flags (common.hpp: map_flags)
-  CK(hipMalloc(reinterpret_cast<void**>(&h->d_map2), map_buffer_bytes(npx)));  // cells + their dense flags (common.hpp: map_flags)
+  for (int k = 0; k < 2; ++k) CK(h->d_map_mem[k].alloc(map_buffer_bytes(npx)));  // cells + their dense flags (common.hpp: map_flags)
+  h->d_map = reinterpret_cast<MapCell*>(h->d_map_mem[0].get()); h->d_map2 = reinterpret_cast<MapCell*>(h->d_map_mem[1].get());
   CK(hipMemset(h->d_map, 0, map_buffer_bytes(npx)));
   CK(hipMemset(h->d_map2, 0, map_buffer_bytes(npx)));
   h->d_map_cur = h->d_map;
-  CK(dalloc(&h->d_owner_max, npx));
-  CK(dalloc(&h->d_owner_min, npx));
-  CK(dalloc(&h->d_own_w, E));
-  CK(dalloc(&h->d_lkeep, E));
+  CK(h->d_owner_max.alloc(npx));
+  CK(h->d_owner_min.alloc(npx));
+  CK(h->d_own_w.alloc(E));
+  CK(h->d_lkeep.alloc(E));
   h->codes_bytes = (E + 7) / 8 * 8;
-  CK(dalloc(&h->d_codes, h->codes_bytes));
-  CK(dalloc(&h->d_sel, E));
-  CK(dalloc(&h->d_evmap, npx + 64));
-  CK(dalloc(&h->d_reg_ab, npx));
-  CK(dalloc(&h->d_reg_cd, npx));
-  CK(dalloc(&h->d_exp_flags, npx));
-  CK(dalloc(&h->d_exp_prefix, npx));
-  CK(dalloc(&h->d_export, npx));
-  CK(dalloc(&h->d_export_cell, npx));
+  CK(h->d_codes.alloc(h->codes_bytes));
+  CK(h->d_sel.alloc(E));
+  CK(h->d_evmap.alloc(npx + 64));
+  CK(h->d_reg_ab.alloc(npx));
+  CK(h->d_reg_cd.alloc(npx));
+  CK(h->d_exp_flags.alloc(npx));
+  CK(h->d_exp_prefix.alloc(npx));
+  CK(h->d_export.alloc(npx));
+  CK(h->d_export_cell.alloc(npx));
   for (int i = 0; i < EV_N; ++i) CK(hipEventCreate(&h->evt[i]));
-  if (h->tl_on) { CK(hipEventCreate(&h->tl_ref)); CK(hipEventRecord(h->tl_ref, h->stream)); CK(hipEventSynchronize(h->tl_ref)); }
+  if (h->tl_on) { CK(h->tl_ref.create()); CK(hipEventRecord(h->tl_ref, h->stream)); CK(hipEventSynchronize(h->tl_ref)); }
   h->evt_ok = true;
-  CK(hipEventCreateWithFlags(&h->evt_trk_read, hipEventDisableTiming));
-  for (int cam = 0; cam < 2; ++cam) CK(hipEventCreateWithFlags(&h->evt_ingest[cam], hipEventDisableTiming));
-  CK(hipHostMalloc(reinterpret_cast<void**>(&h->h_pose_pool), sizeof(double) * 16 * (size_t)h->max_poses * esvo_context::POSE_POOL));
-  for (int i = 0; i < esvo_context::POSE_POOL; ++i) CK(hipEventCreate(&h->pool_evt[i]));
-  h->pool_ok = true;
+  CK(h->evt_trk_read.create(hipEventDisableTiming));
+  for (int cam = 0; cam < 2; ++cam) CK(h->evt_ingest[cam].create(hipEventDisableTiming));
+  CK(h->h_pose_pool.alloc(16 * (size_t)h->max_poses * esvo_context::POSE_POOL));
+  for (int i = 0; i < esvo_context::POSE_POOL; ++i) CK(h->pool_evt[i].create());
   for (int i = 0; i < 16; ++i) h->T_world_obs[i] = h->T_world_frame[i] = (i % 5 == 0) ? 1.0 : 0.0;
 #undef CK
   *out = h;
@@ -395,53 +380,11 @@ int esvo_destroy(esvo_handle h) {
   comm_release(h);
   em_release(h);
   gpc_release(h);
-  void* ptrs[] = {h->d_lut, h->d_mask, h->d_fixmap[0], h->d_fixmap[1], h->d_sae[0], h->d_sae[1], h->d_raw, h->d_raw1, h->d_fwd_lut[0], h->d_fwd_lut[1], h->d_fwd_off[0], h->d_fwd_off[1],
-                  h->d_fwd_src[0], h->d_fwd_src[1], h->d_fwd_val, h->d_ts[0],
-                  h->d_ts[1], h->d_ring[0], h->d_ring[1], h->d_obs2[0][0], h->d_obs2[0][1], h->d_obs2[1][0], h->d_obs2[1][1], h->d_obs_tmp,
-                  h->d_pose_T2[0], h->d_pose_T2[1], h->d_scan_tmp_b, h->d_cnt_b, h->d_tick_ev, h->d_match_slots, h->d_match_flags, h->d_match_prefix,
-                  h->d_matches2[0], h->d_matches2[1], h->d_scan_tmp_l2[0], h->d_scan_tmp_l2[1], h->d_pt_slots2[0], h->d_pt_slots2[1], h->d_pt_flags2[0], h->d_pt_flags2[1], h->d_pt_prefix2[0], h->d_pt_prefix2[1], h->d_pts_tmp, h->d_stage[0], h->d_stage[1], h->d_counters2[0], h->d_counters2[1], h->d_scan_tmp,
-                  h->d_win, h->d_frame_pose_T, h->d_fr_table, h->d_prop, h->d_tile_pts, h->d_tile_count, h->d_over_pts,
-                  h->d_cell_count, h->d_cell_offset, h->d_cell_list, h->d_fuse_ctr, h->d_rec_ids, h->d_map, h->d_map2, h->d_owner_max, h->d_owner_min, h->d_exp_flags,
-                  h->d_exp_prefix, h->d_export, h->d_export_cell, h->d_reg_ab, h->d_reg_cd, h->d_tsq[0], h->d_tsq[1], h->d_tsq_tcount, h->d_tsq_tlist, h->d_tsq_over, h->d_tsq_over_count, h->d_own_w, h->d_lkeep, h->d_codes, h->d_codes_send, h->d_codes_all, h->d_pts_send, h->d_pts_all, h->d_rank_kept,
-                  h->d_sel, h->d_evmap, h->d_lm_fvec0, h->d_lm_fnorm0, h->d_lm_meta, h->d_lm_order, h->d_lm_hist, h->d_lm_pix_order2[0], h->d_lm_pix_order2[1], h->d_lm_sort_rows[0], h->d_lm_sort_rows[1], h->d_lm_sort_hist, h->d_bm_dedupe, h->d_clk, h->d_ring_gidx, h->d_halo_viol, h->d_dn_flags, h->d_merge_a, h->d_merge_b, h->d_merge_plan, h->d_tsq_dup};
-  for (void* p : ptrs) if (p) hipFree(p);
-  if (h->h_counters) hipHostFree(h->h_counters);
-  if (h->h_cnt_b) hipHostFree(h->h_cnt_b);
-  if (h->h_pin) hipHostFree(h->h_pin);
-  if (h->h_fr_table) hipHostFree(h->h_fr_table);
   if (h->evt_ok) for (int i = 0; i < EV_N; ++i) hipEventDestroy(h->evt[i]);
-  if (h->pool_ok) for (int i = 0; i < esvo_context::POSE_POOL; ++i) hipEventDestroy(h->pool_evt[i]);
-  if (h->h_pose_pool) hipHostFree(h->h_pose_pool);
-  if (h->h_trk_ne) hipHostFree(h->h_trk_ne);
-  if (h->h_trk_solve) hipHostFree(h->h_trk_solve);
-  if (h->h_trk_xyz) hipHostFree(h->h_trk_xyz);
-  release_routing(h);
-  for (int cam = 0; cam < 2; ++cam) if (h->d_wire[cam]) hipFree(h->d_wire[cam]);
-  if (h->evt_trk_read) hipEventDestroy(h->evt_trk_read);
-  for (void* q : {(void*)h->d_cloud_xyz[0], (void*)h->d_cloud_xyz[1], (void*)h->d_cloud_ids, (void*)h->d_cloud_scan, (void*)h->d_cloud_cnt}) if (q) hipFree(q);
-  if (h->h_cloud_cnt) hipHostFree(h->h_cloud_cnt);
-  for (int k = 0; k < 2; ++k) {
-    if (h->evt_cloud_built[k]) hipEventDestroy(h->evt_cloud_built[k]);
-    if (h->evt_cloud_read[k]) hipEventDestroy(h->evt_cloud_read[k]);
-  }
-  if (h->tl_ref) hipEventDestroy(h->tl_ref);
-  for (int cam = 0; cam < 2; ++cam) if (h->evt_ingest[cam]) hipEventDestroy(h->evt_ingest[cam]);
-  for (void* q : {(void*)h->d_viz_bgr, (void*)h->d_viz_jet, (void*)h->d_viz_owner}) if (q) hipFree(q);
-  for (void* q : {(void*)h->sgm.sobL, (void*)h->sgm.rawL, (void*)h->sgm.sobR, (void*)h->sgm.rawR, (void*)h->sgm.vol[0], (void*)h->sgm.vol[1],
-                  (void*)h->sgm.vol[2], (void*)h->sgm.vol[3], (void*)h->sgm.vol[4], (void*)h->sgm.vol[5], (void*)h->sgm.d1, (void*)h->sgm.d1b,
-                  (void*)h->sgm.d2key, (void*)h->d_sgm_img[0], (void*)h->d_sgm_img[1], (void*)h->d_sgm_disp, (void*)h->d_sgm_pair, (void*)h->d_sgm_T})
-    if (q) hipFree(q);
-  for (hipEvent_t e : h->evt_sgm) if (e) hipEventDestroy(e);
-  if (h->own_stream && h->stream) hipStreamDestroy(h->stream);
-  if (h->stream_b) hipStreamDestroy(h->stream_b);
-  if (h->stream_l) { hipStreamSynchronize(h->stream_l); hipStreamDestroy(h->stream_l); }
-  if (h->stream_l1) { hipStreamSynchronize(h->stream_l1); hipStreamDestroy(h->stream_l1); }
-  if (h->stream_t) { hipStreamSynchronize(h->stream_t); hipStreamDestroy(h->stream_t); }
-  if (h->stream_i) { hipStreamSynchronize(h->stream_i); hipStreamDestroy(h->stream_i); }
-  for (void* q : {(void*)h->d_trk_blur, (void*)h->d_trk_neg, (void*)h->d_trk_du, (void*)h->d_trk_dv, (void*)h->d_trk_xyz, (void*)h->d_trk_pts,
-                  (void*)h->d_trk_out, (void*)h->d_trk_viz_bgr, (void*)h->d_trk_viz_owner, (void*)h->d_trk_viz_jet, (void*)h->d_trk_viz_cnt})
-    if (q) hipFree(q);
+  // the handle's buffers and its own events go with it, before the streams as ever
+  const hipStream_t streams[] = {h->own_stream ? h->stream : nullptr, h->stream_b, h->stream_l, h->stream_l1, h->stream_t, h->stream_i};
   delete h;
+  for (hipStream_t s : streams) if (s) { hipStreamSynchronize(s); hipStreamDestroy(s); }
   return ESVO_OK;
 }
 
@@ -678,14 +621,13 @@ extern "C" int esvo_debug_stall(esvo_handle h, int which, unsigned microseconds)
 
 extern "C" int esvo_selftest_division(unsigned long long n, unsigned long long seed, unsigned long long* mismatches) {
   esvo_context* h = nullptr;
-  unsigned long long* d = nullptr;
-  HIPCHK(hipMalloc(reinterpret_cast<void**>(&d), sizeof(unsigned long long)));
+  DevBuf<unsigned long long> d;
+  HIPCHK(d.alloc(1));
   HIPCHK(hipMemset(d, 0, sizeof(unsigned long long)));
   const unsigned threads = 256, blocks = 1024;
   const unsigned long long per = (n + (unsigned long long)threads * blocks - 1) / ((unsigned long long)threads * blocks);
   hipLaunchKernelGGL(selftest_div_kernel, dim3(blocks), dim3(threads), 0, 0, per, seed, d);
   HIPCHK(hipDeviceSynchronize());
   HIPCHK(hipMemcpy(mismatches, d, sizeof(unsigned long long), hipMemcpyDeviceToHost));
-  hipFree(d);
   return ESVO_OK;
 }

@@ -11,7 +11,8 @@
 // Return value: a negative esvo_status_t, or the number of guard words that no longer hold the pattern (0 when all is well).
 // The exceptions are at the end, take a handle, launch nothing and copy something out: esvo_debug_fuse_cell_counts one buffer of the
 // last fusion (tests/test_gpu_fuse_cases.py), esvo_debug_bm_owner_count the owner count of the last shared block-matching launch
-// (tests/test_gpu_bm_dedupe.py).
+// (tests/test_gpu_bm_dedupe.py); esvo_debug_live_allocations and esvo_debug_devmem_selftest take no handle and read / walk
+// the ledger of devmem.hpp (tests/test_gpu_lifecycle.py).
 #include <vector>
 
 #include "context.hpp"
@@ -68,6 +69,34 @@ struct GBuf {
     return hipSuccess;
   }
 };
+
+template <bool Pinned>
+int devmem_selftest() {
+  using B = esvo::Buf<u32, Pinned>;
+  const size_t a0 = esvo::g_live_allocs.load(), b0 = esvo::g_live_bytes.load();
+  const auto at = [&](size_t allocs, size_t bytes) { return esvo::g_live_allocs.load() == a0 + allocs && esvo::g_live_bytes.load() == b0 + bytes; };
+  { B e; if (e || e.cap()) return 1; }                                          // an empty buffer and its destructor
+  if (!at(0, 0)) return 2;
+  {
+    B b;
+    if (b.alloc(100) != hipSuccess || !b || b.cap() != 100 || !at(1, 400)) return 3;
+    if ((Pinned ? (std::memset(b, 0x5a, 400), hipSuccess) : hipMemset(b, 0x5a, 400)) != hipSuccess) return 4;  // the memory is there
+    u32* const p = b;
+    if (b.grow(50) != hipSuccess || b != p || b.cap() != 100 || !at(1, 400)) return 5;   // smaller: nothing happens
+    if (b.grow(300) != hipSuccess || !b || b.cap() != 300 || !at(1, 1200)) return 6;     // larger: exactly what was asked for
+    u32* const q = b;
+    B c(std::move(b));                                                                    // move construction: no free
+    if (b || b.cap() || c != q || c.cap() != 300 || !at(1, 1200)) return 7;
+    B d;
+    if (d.alloc(10) != hipSuccess || !at(2, 1240)) return 8;
+    d = std::move(c);                                                                     // move assignment: one free, the target's
+    if (c || c.cap() || d != q || d.cap() != 300 || !at(1, 1200)) return 9;
+    if (d.release() != hipSuccess || d || d.cap() || !at(0, 0)) return 10;
+    if (d.release() != hipSuccess || !at(0, 0)) return 11;                                // twice: nothing more
+    if (d.alloc(0) != hipSuccess || d.cap() != 1 || !at(1, 4)) return 12;                 // at least one element
+  }                                                                                       // ... freed by its destructor
+  return at(0, 0) ? 0 : 13;
+}
 
 struct OwnStream {
   hipStream_t s = nullptr;
@@ -456,5 +485,16 @@ int esvo_debug_bm_owner_count(esvo_handle h, uint32_t* n_owners, int* shared) {
   HIPCHK(hipMemcpy(n_owners, h->d_bm_dedupe + (size_t)h->W * h->H, sizeof(u32), hipMemcpyDeviceToHost));
   return ESVO_OK;
 }
+
+// The ledger of devmem.hpp: live allocations and live bytes of every DevBuf / PinBuf of the process (tests/test_gpu_lifecycle.py
+// asserts on its deltas around its own handles).  The guarded buffers above and esvo_ts_alloc_pinned are not in it.
+void esvo_debug_live_allocations(size_t out[2]) {
+  out[0] = esvo::g_live_allocs.load();
+  out[1] = esvo::g_live_bytes.load();
+}
+
+// The owning type itself, a few hundred bytes at a time, each step checked against the ledger: returns 0, or the number of the
+// first step whose pointer, capacity or ledger delta is not what devmem.hpp promises.  pinned: PinBuf instead of DevBuf.
+int esvo_debug_devmem_selftest(int pinned) { return pinned ? devmem_selftest<true>() : devmem_selftest<false>(); }
 
 }  // extern "C"

@@ -16,24 +16,19 @@ struct EmSlice {
 
 struct EmState {
   // device buffers (grown on demand)
-  esvo_event_t* d_left = nullptr;
-  esvo_event_t* d_right = nullptr;
-  size_t cap_left = 0, cap_right = 0;
-  u32* d_slice_of = nullptr;
-  u32 *d_cnt_tp = nullptr, *d_cnt_ep = nullptr, *d_off = nullptr, *d_flags = nullptr, *d_prefix = nullptr;
-  esvo_match_t *d_slots = nullptr, *d_out = nullptr;
+  DevBuf<esvo_event_t> d_left, d_right;
+  DevBuf<u32> d_slice_of, d_cnt_tp, d_cnt_ep, d_off, d_flags, d_prefix;  // cap_ev elements each, as d_slots and d_out
+  DevBuf<esvo_match_t> d_slots, d_out;
   size_t cap_ev = 0;
-  double* d_T = nullptr;
-  size_t cap_T = 0;
-  u32 *d_pair_ev = nullptr, *d_pair_r = nullptr, *d_pair_ok = nullptr;
-  double* d_pair_cost = nullptr;
+  DevBuf<double> d_T;
+  DevBuf<u32> d_pair_ev, d_pair_r, d_pair_ok;  // cap_pairs elements each, as d_pair_cost
+  DevBuf<double> d_pair_cost;
   size_t cap_pairs = 0;
-  u32* d_scan = nullptr;
-  size_t cap_scan = 0;
-  u32* d_tot = nullptr;  // [0] epipolar pairs [1] unused [2] patch ok [3] matches
-  unsigned long long* d_tot64 = nullptr;  // [0] epipolar pairs [1] time + polarity pairs, 64-bit
-  float2* d_lut_r = nullptr;
-  hipEvent_t ev0 = nullptr, ev1 = nullptr;
+  DevBuf<u32> d_scan;
+  DevBuf<u32> d_tot;  // [0] epipolar pairs [1] unused [2] patch ok [3] matches
+  DevBuf<unsigned long long> d_tot64;  // [0] epipolar pairs [1] time + polarity pairs, 64-bit
+  DevBuf<float2> d_lut_r;
+  DevEvent ev0, ev1;
   // last tick
   esvo_em_selection_t sel{};
   std::vector<EmSlice> slices;
@@ -43,22 +38,8 @@ struct EmState {
 namespace esvo_host {
 
 void em_release(esvo_context* h) {
-  EmState* e = h->em;
-  if (!e) return;
-  void* ptrs[] = {e->d_left, e->d_right, e->d_slice_of, e->d_cnt_tp, e->d_cnt_ep, e->d_off, e->d_flags, e->d_prefix, e->d_slots,
-                  e->d_out, e->d_T, e->d_pair_ev, e->d_pair_r, e->d_pair_ok, e->d_pair_cost, e->d_scan, e->d_tot, e->d_tot64, e->d_lut_r};
-  for (void* p : ptrs) if (p) (void)hipFree(p);
-  if (e->ev0) (void)hipEventDestroy(e->ev0);
-  if (e->ev1) (void)hipEventDestroy(e->ev1);
-  delete e;
+  delete h->em;
   h->em = nullptr;
-}
-
-template <class T>
-static hipError_t em_grow(T** p, size_t need, size_t have) {
-  if (need <= have && *p) return hipSuccess;
-  if (*p) { hipError_t e = hipFree(*p); if (e != hipSuccess) return e; *p = nullptr; }
-  return hipMalloc(reinterpret_cast<void**>(p), sizeof(T) * std::max<size_t>(need, 1));
 }
 
 // the state, the right camera's rectification table on the device, the checks every EM call shares
@@ -74,14 +55,14 @@ static int em_prepare(esvo_context* h, const esvo_em_params_t* em) {
   if (h->h_rect_lut[1].size() != 2 * npx) FAIL(ESVO_ERR_STATE, "event matching needs the right camera's rect_lut (esvo_create)");
   if (!h->em) {
     h->em = new EmState();
-    HIPCHK(hipEventCreate(&h->em->ev0));
-    HIPCHK(hipEventCreate(&h->em->ev1));
-    HIPCHK(hipMalloc(reinterpret_cast<void**>(&h->em->d_tot), sizeof(u32) * 4));
-    HIPCHK(hipMalloc(reinterpret_cast<void**>(&h->em->d_tot64), sizeof(unsigned long long) * 2));
+    HIPCHK(h->em->ev0.create());
+    HIPCHK(h->em->ev1.create());
+    HIPCHK(h->em->d_tot.alloc(4));
+    HIPCHK(h->em->d_tot64.alloc(2));
   }
   EmState* e = h->em;
   if (!e->d_lut_r) {
-    HIPCHK(hipMalloc(reinterpret_cast<void**>(&e->d_lut_r), sizeof(float2) * npx));
+    HIPCHK(e->d_lut_r.alloc(npx));
     HIPCHK(hipMemcpy(e->d_lut_r, h->h_rect_lut[1].data(), sizeof(float2) * npx, hipMemcpyHostToDevice));
   }
   return ESVO_OK;
@@ -89,8 +70,8 @@ static int em_prepare(esvo_context* h, const esvo_em_params_t* em) {
 
 static int em_reserve_events(esvo_context* h, size_t n_left, size_t n_right) {
   EmState* e = h->em;
-  if (n_left > e->cap_left) { HIPCHK(em_grow(&e->d_left, n_left, 0)); e->cap_left = n_left; }
-  if (n_right > e->cap_right) { HIPCHK(em_grow(&e->d_right, n_right, 0)); e->cap_right = n_right; }
+  HIPCHK(e->d_left.grow(n_left));
+  HIPCHK(e->d_right.grow(n_right));
   return ESVO_OK;
 }
 
@@ -106,12 +87,12 @@ static int em_match_device(esvo_context* h, const esvo_em_params_t* em, u32 firs
   e->stats.slices = n_slices;
   if (n == 0) return ESVO_OK;
   if (n > e->cap_ev) {
-    HIPCHK(em_grow(&e->d_slice_of, n, 0)); HIPCHK(em_grow(&e->d_cnt_tp, n, 0)); HIPCHK(em_grow(&e->d_cnt_ep, n, 0));
-    HIPCHK(em_grow(&e->d_off, n, 0)); HIPCHK(em_grow(&e->d_flags, n, 0)); HIPCHK(em_grow(&e->d_prefix, n, 0));
-    HIPCHK(em_grow(&e->d_slots, n, 0)); HIPCHK(em_grow(&e->d_out, n, 0));
+    HIPCHK(e->d_slice_of.grow(n)); HIPCHK(e->d_cnt_tp.grow(n)); HIPCHK(e->d_cnt_ep.grow(n));
+    HIPCHK(e->d_off.grow(n)); HIPCHK(e->d_flags.grow(n)); HIPCHK(e->d_prefix.grow(n));
+    HIPCHK(e->d_slots.grow(n)); HIPCHK(e->d_out.grow(n));
     e->cap_ev = n;
   }
-  if (n_slices * 12 > e->cap_T) { HIPCHK(em_grow(&e->d_T, n_slices * 12, 0)); e->cap_T = n_slices * 12; }
+  HIPCHK(e->d_T.grow(n_slices * 12));
   // T_left_rv = T_obs^-1 T_slice with the rigid inverse and 4x4 product of DepthProblem's restatement (common.hpp)
   std::vector<double> T_lr(n_slices * 12);
   double Tlw[16], Tlv[16];
@@ -121,7 +102,7 @@ static int em_match_device(esvo_context* h, const esvo_em_params_t* em, u32 firs
     std::copy(Tlv, Tlv + 12, T_lr.begin() + 12 * s);
   }
   auto scan_need = [](size_t m) { return scan_scratch_elems(m); };
-  if (scan_need(n) > e->cap_scan) { HIPCHK(em_grow(&e->d_scan, scan_need(n), 0)); e->cap_scan = scan_need(n); }
+  HIPCHK(e->d_scan.grow(scan_need(n)));
   hipStream_t st = h->stream;
   HIPCHK(hipMemcpyAsync(e->d_slice_of, slice_of.data(), sizeof(u32) * n, hipMemcpyHostToDevice, st));
   HIPCHK(hipMemcpyAsync(e->d_T, T_lr.data(), sizeof(double) * 12 * n_slices, hipMemcpyHostToDevice, st));
@@ -155,11 +136,11 @@ static int em_match_device(esvo_context* h, const esvo_em_params_t* em, u32 firs
   if (tot64[0] > 0xffffffffull) FAIL(ESVO_ERR_CAPACITY, "more than 2^32 - 1 (event, candidate) pairs pass the epipolar test");
   const u32 n_pairs = (u32)tot64[0];
   if (n_pairs > e->cap_pairs) {
-    HIPCHK(em_grow(&e->d_pair_ev, n_pairs, 0)); HIPCHK(em_grow(&e->d_pair_r, n_pairs, 0));
-    HIPCHK(em_grow(&e->d_pair_ok, n_pairs, 0)); HIPCHK(em_grow(&e->d_pair_cost, n_pairs, 0));
+    HIPCHK(e->d_pair_ev.grow(n_pairs)); HIPCHK(e->d_pair_r.grow(n_pairs));
+    HIPCHK(e->d_pair_ok.grow(n_pairs)); HIPCHK(e->d_pair_cost.grow(n_pairs));
     e->cap_pairs = n_pairs;
   }
-  if (scan_need(n_pairs) > e->cap_scan) { HIPCHK(em_grow(&e->d_scan, scan_need(n_pairs), 0)); e->cap_scan = scan_need(n_pairs); }
+  HIPCHK(e->d_scan.grow(scan_need(n_pairs)));
   a.n_pairs = n_pairs; a.pair_ev = e->d_pair_ev; a.pair_r = e->d_pair_r; a.pair_cost = e->d_pair_cost; a.pair_ok = e->d_pair_ok;
   launch_em_candidates(a, 1, st);
   launch_em_pair_cost(a, st);

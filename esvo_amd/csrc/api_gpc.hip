@@ -9,45 +9,35 @@
 
 // (global namespace: esvo_context holds a GpcState*)
 struct GpcState {
-  // near cloud: ids scratch [3][id_cap] present | prefix | where, its scan scratch, the cloud itself (near_cap points)
-  u32* d_ids = nullptr;
+  // near cloud: ids scratch [3][id_cap] present | prefix | where, its scan scratch, the cloud itself (3 floats per point)
+  DevBuf<u32> d_ids;
   size_t id_cap = 0;
-  u32* d_id_scan = nullptr;
-  float* d_near = nullptr;
-  size_t near_cap = 0;
-  u32* d_cnt = nullptr;          // [0] near elements [1] cells whose id was outside the bound
+  DevBuf<u32> d_id_scan;
+  DevBuf<float> d_near;
+  DevBuf<u32> d_cnt;             // [0] near elements [1] cells whose id was outside the bound
   // voxel filter, for vox_cap rows
-  u64* d_pairs[2] = {nullptr, nullptr};
-  u32* d_heads = nullptr;        // [2][vox_cap] heads | rank
-  u32* d_hist = nullptr;
-  u32* d_vox_scan = nullptr;
-  float* d_cent = nullptr;
+  DevBuf<u64> d_pairs[2];
+  DevBuf<u32> d_heads;           // [2][vox_cap] heads | rank
+  DevBuf<u32> d_hist;
+  DevBuf<u32> d_vox_scan;
+  DevBuf<float> d_cent;
   size_t vox_cap = 0;
-  float* d_in = nullptr;         // esvo_map_voxel_filter's upload
-  size_t in_cap = 0;
-  VoxelGrid* d_grid = nullptr;
-  struct Pinned { VoxelGrid grid; u32 cnt[2]; }* h_pin = nullptr;
+  DevBuf<float> d_in;            // esvo_map_voxel_filter's upload
+  DevBuf<VoxelGrid> d_grid;
+  struct Pinned { VoxelGrid grid; u32 cnt[2]; };
+  PinBuf<Pinned> h_pin;
   // the global cloud
   bool configured = false;
   esvo_gpc_params_t prm{};
-  float* d_global = nullptr;
-  size_t global_cap = 0;
-  hipEvent_t ev0 = nullptr, ev1 = nullptr;
+  DevBuf<float> d_global;        // 3 floats per point of the capacity
+  DevEvent ev0, ev1;
   esvo_gpc_stats_t stats{};
 };
 
 namespace esvo_host {
 
 void gpc_release(esvo_context* h) {
-  GpcState* g = h->gpc;
-  if (!g) return;
-  void* ptrs[] = {g->d_ids, g->d_id_scan, g->d_near, g->d_cnt, g->d_pairs[0], g->d_pairs[1], g->d_heads, g->d_hist, g->d_vox_scan,
-                  g->d_cent, g->d_in, g->d_grid, g->d_global};
-  for (void* p : ptrs) if (p) (void)hipFree(p);
-  if (g->h_pin) (void)hipHostFree(g->h_pin);
-  if (g->ev0) (void)hipEventDestroy(g->ev0);
-  if (g->ev1) (void)hipEventDestroy(g->ev1);
-  delete g;
+  delete h->gpc;
   h->gpc = nullptr;
 }
 
@@ -57,24 +47,17 @@ void gpc_reset(esvo_context* h) {
   h->gpc->stats.total_points = 0;
 }
 
-template <class T>
-static hipError_t gpc_grow(T** p, size_t need, size_t have) {
-  if (need <= have && *p) return hipSuccess;
-  if (*p) { hipError_t e = hipFree(*p); *p = nullptr; if (e != hipSuccess) return e; }
-  return hipMalloc(reinterpret_cast<void**>(p), sizeof(T) * std::max<size_t>(need, 1));
-}
-
 static int gpc_state(esvo_context* h) {
   if (h->sharded || h->comm) FAIL(ESVO_ERR_STATE, "handle is band-sharded or tick-interleaved: the global cloud is a single-GPU read-out");
   HIPCHK(hipSetDevice(h->device));
   if (h->gpc) return ESVO_OK;
   GpcState* g = new GpcState();
   h->gpc = g;  // (released by esvo_destroy whatever fails below)
-  HIPCHK(hipMalloc(reinterpret_cast<void**>(&g->d_cnt), sizeof(u32) * 2));
-  HIPCHK(hipMalloc(reinterpret_cast<void**>(&g->d_grid), sizeof(VoxelGrid)));
-  HIPCHK(hipHostMalloc(reinterpret_cast<void**>(&g->h_pin), sizeof(GpcState::Pinned)));
-  HIPCHK(hipEventCreate(&g->ev0));
-  HIPCHK(hipEventCreate(&g->ev1));
+  HIPCHK(g->d_cnt.alloc(2));
+  HIPCHK(g->d_grid.alloc(1));
+  HIPCHK(g->h_pin.alloc(1));
+  HIPCHK(g->ev0.create());
+  HIPCHK(g->ev1.create());
   return ESVO_OK;
 }
 
@@ -82,13 +65,12 @@ static int gpc_state(esvo_context* h) {
 static int gpc_reserve_near(esvo_context* h, size_t id_n) {
   GpcState* g = h->gpc;
   const size_t npx = (size_t)h->W * h->H;
-  HIPCHK(gpc_grow(&g->d_near, npx * 3, g->near_cap * 3));
-  g->near_cap = npx;
+  HIPCHK(g->d_near.grow(npx * 3));
   if (id_n > g->id_cap || !g->d_ids) {
     const size_t cap = std::max<size_t>(id_n, 4096);
     g->id_cap = 0;
-    HIPCHK(gpc_grow(&g->d_ids, 3 * cap, 0));
-    HIPCHK(gpc_grow(&g->d_id_scan, scan_scratch_elems(cap) + 8, 0));
+    HIPCHK(g->d_ids.grow(3 * cap));
+    HIPCHK(g->d_id_scan.grow(scan_scratch_elems(cap) + 8));
     g->id_cap = cap;
   }
   return ESVO_OK;
@@ -99,12 +81,12 @@ static int gpc_reserve_voxel(esvo_context* h, size_t n) {
   if (n <= g->vox_cap && g->d_cent) return ESVO_OK;
   const size_t cap = std::max<size_t>(n, 4096);
   g->vox_cap = 0;
-  HIPCHK(gpc_grow(&g->d_pairs[0], cap, 0));
-  HIPCHK(gpc_grow(&g->d_pairs[1], cap, 0));
-  HIPCHK(gpc_grow(&g->d_heads, 2 * cap, 0));
-  HIPCHK(gpc_grow(&g->d_hist, voxel_hist_words(cap), 0));
-  HIPCHK(gpc_grow(&g->d_vox_scan, scan_scratch_elems(std::max(cap, voxel_hist_words(cap))) + 8, 0));
-  HIPCHK(gpc_grow(&g->d_cent, cap * 3, 0));
+  HIPCHK(g->d_pairs[0].grow(cap));
+  HIPCHK(g->d_pairs[1].grow(cap));
+  HIPCHK(g->d_heads.grow(2 * cap));
+  HIPCHK(g->d_hist.grow(voxel_hist_words(cap)));
+  HIPCHK(g->d_vox_scan.grow(scan_scratch_elems(std::max(cap, voxel_hist_words(cap))) + 8));
+  HIPCHK(g->d_cent.grow(cap * 3));
   g->vox_cap = cap;
   return ESVO_OK;
 }
@@ -115,7 +97,7 @@ static int gpc_near(esvo_context* h, double range, size_t* n_near) {
   const u32 id_n = h->map_id_bound;
   u32* present = g->d_ids;
   launch_map_cloud_near(h->d_map_cur, id_n, range, present, present + g->id_cap, present + 2 * g->id_cap, g->d_cnt, g->d_id_scan,
-                        h->T_world_frame, g->d_near, (u32)g->near_cap, h->dp, h->stream_b);
+                        h->T_world_frame, g->d_near, (u32)(g->d_near.cap() / 3), h->dp, h->stream_b);
   HIPCHK(hipGetLastError());
   HIPCHK(hipMemcpyAsync(g->h_pin->cnt, g->d_cnt, sizeof(u32) * 2, hipMemcpyDeviceToHost, h->stream_b));
   HIPCHK(esvo_wait_stream(h->stream_b, true));
@@ -139,7 +121,8 @@ static int gpc_voxel(esvo_context* h, const float* d_xyz, size_t n, float leaf, 
   if (grid.n_finite == 0) return ESVO_OK;
   if (grid.too_large) FAIL(ESVO_ERR_CAPACITY, "leaf size too small for the extent of the cloud (voxel index overflows, as in pcl::VoxelGrid)");
   const u32 n_finite = grid.n_finite;
-  const u64* sorted = launch_voxel_sort(d_xyz, (u32)n, g->d_grid, grid.key_bits, g->d_pairs, g->d_hist, g->d_vox_scan, s);
+  u64* const pairs[2] = {g->d_pairs[0], g->d_pairs[1]};
+  const u64* sorted = launch_voxel_sort(d_xyz, (u32)n, g->d_grid, grid.key_bits, pairs, g->d_hist, g->d_vox_scan, s);
   launch_voxel_centroids(d_xyz, sorted, n_finite, g->d_heads, g->d_heads + g->vox_cap, g->d_grid, g->d_vox_scan, g->d_cent, (u32)g->vox_cap, s);
   HIPCHK(hipGetLastError());
   HIPCHK(hipMemcpyAsync(&g->h_pin->grid.n_voxels, &g->d_grid->n_voxels, sizeof(u32), hipMemcpyDeviceToHost, s));
@@ -175,8 +158,7 @@ int esvo_map_voxel_filter(esvo_handle h, const float* xyz, size_t n, float leaf,
   *n_out = 0;
   if (n == 0) return ESVO_OK;
   GpcState* g = h->gpc;
-  HIPCHK(gpc_grow(&g->d_in, n * 3, g->in_cap * 3));
-  g->in_cap = std::max(g->in_cap, n);
+  HIPCHK(g->d_in.grow(n * 3));
   { int rc = gpc_reserve_voxel(h, n); if (rc) return rc; }
   HIPCHK(hipMemcpyAsync(g->d_in, xyz, n * 3 * sizeof(float), hipMemcpyHostToDevice, h->stream_b));
   size_t k = 0;
@@ -203,11 +185,7 @@ int esvo_map_gpc_configure(esvo_handle h, const esvo_gpc_params_t* prm) {
   { int rc = gpc_reserve_near(h, 9 * (size_t)h->win_cap); if (rc) return rc; }
   { int rc = gpc_reserve_voxel(h, npx); if (rc) return rc; }
   const size_t cap = prm->capacity_points ? (size_t)prm->capacity_points : (size_t)5000000;
-  if (cap != g->global_cap || !g->d_global) {
-    g->global_cap = 0;
-    HIPCHK(gpc_grow(&g->d_global, cap * 3, 0));
-    g->global_cap = cap;
-  }
+  if (cap * 3 != g->d_global.cap()) HIPCHK(g->d_global.alloc(cap * 3));
   g->prm = *prm;
   g->prm.capacity_points = cap;
   g->stats = esvo_gpc_stats_t{};  // (t_last_pub = 0.0, esvo_Mapping.cpp:152)
@@ -238,7 +216,7 @@ int esvo_map_gpc_update(esvo_handle h, uint64_t t_ns, int* refreshed) {
   // :966-969: the last min(L, NumGPC_added_per_refresh) - 1 centroids
   const size_t add = L ? (size_t)std::min<u64>((u64)L, g->prm.num_added_per_refresh) - 1 : 0;
   const size_t total = (size_t)g->stats.total_points;
-  if (total + add > g->global_cap) FAIL(ESVO_ERR_CAPACITY, "the global cloud is full (esvo_gpc_params_t::capacity_points)");
+  if (total + add > g->d_global.cap() / 3) FAIL(ESVO_ERR_CAPACITY, "the global cloud is full (esvo_gpc_params_t::capacity_points)");
   if (add)
     HIPCHK(hipMemcpyAsync(g->d_global + 3 * total, g->d_cent + 3 * (L - add), add * 3 * sizeof(float), hipMemcpyDeviceToDevice, h->stream_b));
   HIPCHK(hipEventRecord(g->ev1, h->stream_b));

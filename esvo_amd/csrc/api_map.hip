@@ -126,7 +126,8 @@ static const u32* run_lm_order(esvo_context* h, u32 max_matches) {
   const bool split = h->d_lm_fvec0 != nullptr && max_matches >= esvo::LM_SPLIT_MIN_EVENTS;
   if (!h->lm_order_on || !h->d_lm_pix_order2[0] || !lm_launch_is_ordered(max_matches, false, false, split, h->dp)) return nullptr;
   u32* order = h->d_lm_pix_order2[h->fpar];
-  launch_lm_pixel_order(h->d_matches, h->d_counters + CNT_MATCHES, max_matches, 0, h->d_obs[0], h->d_obs[1], h->dp, h->d_lm_sort_rows, h->d_lm_sort_hist,
+  u64* const rows[2] = {h->d_lm_sort_rows[0], h->d_lm_sort_rows[1]};
+  launch_lm_pixel_order(h->d_matches, h->d_counters + CNT_MATCHES, max_matches, 0, h->d_obs[0], h->d_obs[1], h->dp, rows, h->d_lm_sort_hist,
                         h->d_scan_tmp, order, h->stream);
   return order;
 }

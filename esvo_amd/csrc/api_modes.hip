@@ -115,18 +115,20 @@ static int sgm_alloc(esvo_context* h) {
   const size_t npx = (size_t)h->W * h->H;
   if (!h->sgm_ok) {
     const size_t nvol = (size_t)h->H * (h->W - 48) * 48;
-    uint8_t** planes[4] = {&h->sgm.sobL, &h->sgm.rawL, &h->sgm.sobR, &h->sgm.rawR};
-    for (auto pp : planes) HIPCHK(hipMalloc(reinterpret_cast<void**>(pp), npx));
-    for (int i = 0; i < 6; ++i) HIPCHK(hipMalloc(reinterpret_cast<void**>(&h->sgm.vol[i]), nvol * sizeof(int16_t)));
-    HIPCHK(hipMalloc(reinterpret_cast<void**>(&h->sgm.d1), npx * sizeof(int16_t)));
-    HIPCHK(hipMalloc(reinterpret_cast<void**>(&h->sgm.d1b), npx * sizeof(int16_t)));
-    HIPCHK(hipMalloc(reinterpret_cast<void**>(&h->sgm.d2key), npx * sizeof(u32)));
-    HIPCHK(hipMalloc(reinterpret_cast<void**>(&h->d_sgm_img[0]), npx));
-    HIPCHK(hipMalloc(reinterpret_cast<void**>(&h->d_sgm_img[1]), npx));
-    HIPCHK(hipMalloc(reinterpret_cast<void**>(&h->d_sgm_disp), npx * sizeof(int16_t)));
-    HIPCHK(hipMalloc(reinterpret_cast<void**>(&h->d_sgm_pair), sizeof(u32) * 8 * (size_t)h->max_ev));
-    HIPCHK(hipMalloc(reinterpret_cast<void**>(&h->d_sgm_T), sizeof(double) * 16));
-    for (hipEvent_t& e : h->evt_sgm) HIPCHK(hipEventCreate(&e));
+    for (auto& b : h->d_sgm_plane) HIPCHK(b.alloc(npx));
+    for (auto& b : h->d_sgm_vol) HIPCHK(b.alloc(nvol));
+    HIPCHK(h->d_sgm_d1.alloc(npx));
+    HIPCHK(h->d_sgm_d1b.alloc(npx));
+    HIPCHK(h->d_sgm_d2key.alloc(npx));
+    h->sgm = SgmScratch{h->d_sgm_plane[0], h->d_sgm_plane[1], h->d_sgm_plane[2], h->d_sgm_plane[3],
+                        {h->d_sgm_vol[0], h->d_sgm_vol[1], h->d_sgm_vol[2], h->d_sgm_vol[3], h->d_sgm_vol[4], h->d_sgm_vol[5]},
+                        h->d_sgm_d1, h->d_sgm_d1b, h->d_sgm_d2key};
+    HIPCHK(h->d_sgm_img[0].alloc(npx));
+    HIPCHK(h->d_sgm_img[1].alloc(npx));
+    HIPCHK(h->d_sgm_disp.alloc(npx));
+    HIPCHK(h->d_sgm_pair.alloc(8 * (size_t)h->max_ev));
+    HIPCHK(h->d_sgm_T.alloc(16));
+    for (DevEvent& e : h->evt_sgm) HIPCHK(e.create());
     h->sgm_ok = true;
   }
   return ESVO_OK;

@@ -67,22 +67,20 @@ int esvo_map_cloud_build(esvo_handle h, size_t* n) {
   const size_t npx = (size_t)h->W * h->H;
   if (!h->d_cloud_xyz[1]) {  // first build: nothing of this state is in use yet
     for (int k = 0; k < 2; ++k) {
-      if (!h->d_cloud_xyz[k]) HIPCHK(hipMalloc(reinterpret_cast<void**>(&h->d_cloud_xyz[k]), npx * 3 * sizeof(float)));
-      if (!h->evt_cloud_built[k]) HIPCHK(hipEventCreateWithFlags(&h->evt_cloud_built[k], hipEventDisableTiming));
-      if (!h->evt_cloud_read[k]) HIPCHK(hipEventCreateWithFlags(&h->evt_cloud_read[k], hipEventDisableTiming));
+      if (!h->d_cloud_xyz[k]) HIPCHK(h->d_cloud_xyz[k].alloc(npx * 3));
+      HIPCHK(h->evt_cloud_built[k].create(hipEventDisableTiming));
+      HIPCHK(h->evt_cloud_read[k].create(hipEventDisableTiming));
     }
-    if (!h->d_cloud_cnt) HIPCHK(hipMalloc(reinterpret_cast<void**>(&h->d_cloud_cnt), sizeof(u32) * 2));
-    if (!h->h_cloud_cnt) HIPCHK(hipHostMalloc(reinterpret_cast<void**>(&h->h_cloud_cnt), sizeof(u32) * 2));
+    if (!h->d_cloud_cnt) HIPCHK(h->d_cloud_cnt.alloc(2));
+    if (!h->h_cloud_cnt) HIPCHK(h->h_cloud_cnt.alloc(2));
   }
   const u32 id_n = h->map_id_bound;
   if (id_n > h->cloud_id_cap) {  // (the id arrays are read on the back stream only, by earlier builds: all complete -- every build waits for its count)
-    if (h->d_cloud_ids) hipFree(h->d_cloud_ids);
-    if (h->d_cloud_scan) hipFree(h->d_cloud_scan);
-    h->d_cloud_ids = h->d_cloud_scan = nullptr;
+    (void)h->d_cloud_ids.release(); (void)h->d_cloud_scan.release();
     h->cloud_id_cap = 0;
     const size_t cap = std::max<size_t>((size_t)id_n + id_n / 4, 4096);
-    HIPCHK(hipMalloc(reinterpret_cast<void**>(&h->d_cloud_ids), sizeof(u32) * 3 * cap));
-    HIPCHK(hipMalloc(reinterpret_cast<void**>(&h->d_cloud_scan), sizeof(u32) * (scan_scratch_elems(cap) + 8)));
+    HIPCHK(h->d_cloud_ids.alloc(3 * cap));
+    HIPCHK(h->d_cloud_scan.alloc(scan_scratch_elems(cap) + 8));
     h->cloud_id_cap = cap;
   }
   int w;
@@ -224,9 +222,9 @@ int esvo_map_get_debug_images(esvo_handle h, double age_max_range, uint8_t* inv_
   { int rcp = flush_pending_tick(h); if (rcp) return rcp; }
   const size_t npx = (size_t)h->W * h->H;
   if (!h->d_viz_bgr) {
-    HIPCHK(hipMalloc(reinterpret_cast<void**>(&h->d_viz_bgr), npx * 3));
-    HIPCHK(hipMalloc(reinterpret_cast<void**>(&h->d_viz_owner), npx * sizeof(u32)));
-    HIPCHK(hipMalloc(reinterpret_cast<void**>(&h->d_viz_jet), 768));
+    HIPCHK(h->d_viz_bgr.alloc(npx * 3));
+    HIPCHK(h->d_viz_owner.alloc(npx));
+    HIPCHK(h->d_viz_jet.alloc(768));
     uint8_t jet[768];
     jet256_bgr(jet);
     HIPCHK(hipMemcpy(h->d_viz_jet, jet, 768, hipMemcpyHostToDevice));

@@ -100,7 +100,7 @@ static int routed_front(esvo_context* h, esvo_context::TickState& tk, u32 n, con
   const size_t nb = shard_codes_block_routed(n);
   HIPCHK(hipMemsetAsync(h->d_codes_send, 0, nb, h->stream));
   launch_shard_codes_routed(h->d_matches, h->d_lkeep, h->d_counters + CNT_OWN_MATCHES, n_own, n, (u32)h->dp.num_threads, h->d_own_w,
-                            reinterpret_cast<u32*>(h->d_codes_send), h->stream);
+                            reinterpret_cast<u32*>(h->d_codes_send.get()), h->stream);
   HIPCHK(hipGetLastError());
   h->xchg_send = h->d_codes_send;
   h->xchg_recv = N > 1 ? h->d_codes_all : h->d_codes_send;
@@ -118,7 +118,7 @@ static int routed_denoise_begin(esvo_context* h, esvo_context::TickState& tk) {
   const size_t nb = denoise_bits_block(tk.n);
   HIPCHK(hipMemsetAsync(h->d_codes_send, 0, nb, h->stream));
   launch_denoise_bits_routed(h->d_ring[0], h->sh_first, h->ring_cap, tk.n_loc, h->d_ring_gidx, tk.g_first, tk.n, h->d_evmap, h->W, h->H,
-                             h->dp.band_y0, h->dp.band_y1, reinterpret_cast<u32*>(h->d_codes_send), h->stream);
+                             h->dp.band_y0, h->dp.band_y1, reinterpret_cast<u32*>(h->d_codes_send.get()), h->stream);
   HIPCHK(hipGetLastError());
   h->xchg_send = h->d_codes_send;
   h->xchg_recv = N > 1 ? h->d_codes_all : h->d_codes_send;
@@ -131,11 +131,11 @@ int routed_denoise_resume(esvo_context* h) {
   esvo_context::TickState& tk = h->tk[h->fpar];
   const u32 N = (u32)h->dp.ev_nshards, n_raw = tk.n;
   if (!h->d_dn_flags) {
-    HIPCHK(hipMalloc(reinterpret_cast<void**>(&h->d_dn_flags), sizeof(u32) * 2 * (size_t)h->max_ev));
+    HIPCHK(h->d_dn_flags.alloc(2 * (size_t)h->max_ev));
   }
   u32* flags = h->d_dn_flags;
   u32* prefix = h->d_dn_flags + h->max_ev;
-  launch_denoise_bits_unpack(reinterpret_cast<const u32*>(N > 1 ? h->d_codes_all : h->d_codes_send), (u32)(denoise_bits_block(n_raw) / 4), N, n_raw,
+  launch_denoise_bits_unpack(reinterpret_cast<const u32*>((N > 1 ? h->d_codes_all : h->d_codes_send).get()), (u32)(denoise_bits_block(n_raw) / 4), N, n_raw,
                              flags, h->stream);
   launch_exclusive_scan_u32(flags, prefix, h->d_counters + CNT_DENOISE_KEPT, h->d_scan_tmp, n_raw, h->stream);
   int rc = read_counters(h);  // the kept count sizes everything behind it (as on one GPU: one read-back)
@@ -188,7 +188,7 @@ int shard_order_points(esvo_context* h, esvo_context::TickState& tk) {
   // part of a band-mode tick that does not shrink.
   const bool tiled = h->routed && !scan_is_small(n);
   if (h->routed)
-    launch_shard_unpack_routed(reinterpret_cast<const u32*>(N > 1 ? h->d_codes_all : h->d_codes_send), (u32)(shard_codes_block_routed(n) / 4), N,
+    launch_shard_unpack_routed(reinterpret_cast<const u32*>((N > 1 ? h->d_codes_all : h->d_codes_send).get()), (u32)(shard_codes_block_routed(n) / 4), N,
                                n, h->d_codes, h->d_rank_kept, tiled ? h->d_scan_tmp : nullptr, h->stream);
   else
     launch_shard_unpack_codes(N > 1 ? h->d_codes_all : h->d_codes_send, (u32)shard_codes_block(n, N), N, n, h->d_codes, h->d_rank_kept,
@@ -244,10 +244,6 @@ bool rings_empty(esvo_context* h) {
   std::lock_guard<std::mutex> lr(h->mu_ring);
   return h->ring_next[0] == 0 && h->ring_next[1] == 0 && h->glob_ts.empty();
 }
-void free_shard_blocks(esvo_context* h) {
-  for (void** p : {(void**)&h->d_codes_send, (void**)&h->d_codes_all, (void**)&h->d_pts_send, (void**)&h->d_pts_all, (void**)&h->d_rank_kept, (void**)&h->d_ring_gidx})
-    if (*p) { (void)hipFree(*p); *p = nullptr; }
-}
 }  // namespace
 
 int esvo_shard_set_band(esvo_handle h, int row_begin, int row_end, int shard, int n_shards) {
@@ -268,12 +264,12 @@ int esvo_shard_set_band(esvo_handle h, int row_begin, int row_end, int shard, in
   if (h->sharded && !h->d_rank_kept) {  // exchange blocks, sized for any rank count up to SHARD_MAX_RANKS (lazily: unsharded handles never pay)
     const size_t E = h->max_ev, R = esvo_context::SHARD_MAX_RANKS, WP = sizeof(DevPoint) / 8;
     HIPCHK(hipSetDevice(h->device));
-    auto alloc = [&](auto** p, size_t bytes) { return hipMalloc(reinterpret_cast<void**>(p), bytes) == hipSuccess; };
     // (d_rank_kept, the guard above, is allocated LAST: a failure in the chain frees what came before and leaves the guard null)
-    if (!alloc(&h->d_codes_send, (E + 7) / 8 * 8) || !alloc(&h->d_codes_all, E + 8 * R) || !alloc(&h->d_pts_send, 8 * (1 + E * WP)) ||
-        !alloc(&h->d_pts_all, 8 * (R + (E + R) * WP)) || !alloc(&h->d_rank_kept, sizeof(u32) * R)) {
+    if (h->d_codes_send.alloc((E + 7) / 8 * 8) || h->d_codes_all.alloc(E + 8 * R) || h->d_pts_send.alloc(1 + E * WP) ||
+        h->d_pts_all.alloc(R + (E + R) * WP) || h->d_rank_kept.alloc(R)) {
       (void)hipGetLastError();
-      free_shard_blocks(h);
+      (void)h->d_codes_send.release(); (void)h->d_codes_all.release(); (void)h->d_pts_send.release(); (void)h->d_pts_all.release();
+      (void)h->d_rank_kept.release(); (void)h->d_ring_gidx.release();
       h->sharded = false;
       h->dp.ev_shard = 0; h->dp.ev_nshards = 1; h->dp.band_y0 = 0; h->dp.band_y1 = h->H;
       set_compute_band(h);
@@ -326,15 +322,14 @@ int esvo_shard_set_routing(esvo_handle h, int mode, int ts_halo_rows) {
       h->keep_px[(size_t)y * W + x] = f;
     }
   HIPCHK(hipSetDevice(h->device));
-  if (!h->d_ring_gidx) HIPCHK(hipMalloc(reinterpret_cast<void**>(&h->d_ring_gidx), sizeof(u32) * h->ring_cap));
+  if (!h->d_ring_gidx) HIPCHK(h->d_ring_gidx.alloc(h->ring_cap));
   {  // exchange 1 spans the whole tick in this mode: n_shards blocks of two bits per slot
     const size_t need = (size_t)h->dp.ev_nshards * shard_codes_block_routed(h->max_ev);
     if (need > (size_t)h->max_ev + 8 * esvo_context::SHARD_MAX_RANKS) {
       HIPCHK(hipStreamSynchronize(h->stream));
-      uint8_t* d_new = nullptr;
-      if (hipMalloc(reinterpret_cast<void**>(&d_new), need) != hipSuccess) { (void)hipGetLastError(); FAIL(ESVO_ERR_CAPACITY, "out of device memory for the routed exchange blocks"); }
-      (void)hipFree(h->d_codes_all);
-      h->d_codes_all = d_new;
+      DevBuf<uint8_t> d_new;  // (allocated before the old blocks go: they stay intact where this fails)
+      if (d_new.alloc(need) != hipSuccess) { (void)hipGetLastError(); FAIL(ESVO_ERR_CAPACITY, "out of device memory for the routed exchange blocks"); }
+      h->d_codes_all = std::move(d_new);
     }
   }
   h->ts_halo = halo;

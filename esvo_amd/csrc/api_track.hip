@@ -12,10 +12,10 @@ int esvo_track_set_current(esvo_handle h, const uint8_t* ts_left, int kernel_siz
   HIPCHK(hipSetDevice(h->device));
   const size_t npx = (size_t)h->W * h->H;
   if (!h->d_trk_neg) {
-    HIPCHK(hipMalloc(reinterpret_cast<void**>(&h->d_trk_blur), npx));
-    HIPCHK(hipMalloc(reinterpret_cast<void**>(&h->d_trk_neg), npx));
-    HIPCHK(hipMalloc(reinterpret_cast<void**>(&h->d_trk_du), npx * sizeof(int16_t)));
-    HIPCHK(hipMalloc(reinterpret_cast<void**>(&h->d_trk_dv), npx * sizeof(int16_t)));
+    HIPCHK(h->d_trk_blur.alloc(npx));
+    HIPCHK(h->d_trk_neg.alloc(npx));
+    HIPCHK(h->d_trk_du.alloc(npx));
+    HIPCHK(h->d_trk_dv.alloc(npx));
   }
   const uint8_t* src = h->d_ts[0];
   if (ts_left) {  // host image (TS node in another process)
@@ -62,15 +62,13 @@ int esvo_track_get_images(esvo_handle h, uint8_t* neg, int16_t* du, int16_t* dv)
 static int track_reserve(esvo_context* h, size_t n) {
   if (n > h->trk_cap) {
     HIPCHK(hipStreamSynchronize(h->stream_t));
-    for (void* q : {(void*)h->d_trk_xyz, (void*)h->d_trk_pts, (void*)h->d_trk_out}) if (q) hipFree(q);
-    if (h->h_trk_xyz) hipHostFree(h->h_trk_xyz);
-    h->d_trk_xyz = nullptr; h->d_trk_pts = nullptr; h->d_trk_out = nullptr; h->h_trk_xyz = nullptr;
+    (void)h->d_trk_xyz.release(); (void)h->d_trk_pts.release(); (void)h->d_trk_out.release(); (void)h->h_trk_xyz.release();
     h->trk_cap = 0; h->trk_n = 0;
     const size_t cap = std::max<size_t>(n, 4096);
-    HIPCHK(hipHostMalloc(reinterpret_cast<void**>(&h->h_trk_xyz), cap * 3 * sizeof(float)));
-    HIPCHK(hipMalloc(reinterpret_cast<void**>(&h->d_trk_xyz), cap * 3 * sizeof(float)));
-    HIPCHK(hipMalloc(reinterpret_cast<void**>(&h->d_trk_pts), cap * 3 * sizeof(double)));
-    HIPCHK(hipMalloc(reinterpret_cast<void**>(&h->d_trk_out), cap * 6 * sizeof(double)));
+    HIPCHK(h->h_trk_xyz.alloc(cap * 3));
+    HIPCHK(h->d_trk_xyz.alloc(cap * 3));
+    HIPCHK(h->d_trk_pts.alloc(cap * 3));
+    HIPCHK(h->d_trk_out.alloc(cap * 6));
     h->trk_cap = cap;
   }
   return ESVO_OK;
@@ -144,7 +142,7 @@ int esvo_track_set_reference_from_cloud(esvo_handle h, const uint32_t* order, si
     std::memcpy(h->h_trk_xyz, order, n * sizeof(u32));
     h->trk_xyz_inflight = true;
     HIPCHK(hipMemcpyAsync(h->d_trk_xyz, h->h_trk_xyz, n * sizeof(u32), hipMemcpyHostToDevice, h->stream_t));
-    d_order = reinterpret_cast<const u32*>(h->d_trk_xyz);
+    d_order = reinterpret_cast<const u32*>(h->d_trk_xyz.get());
   }
   HIPCHK(hipStreamWaitEvent(h->stream_t, h->evt_cloud_built[cb], 0));
   launch_track_reference_gather(h->d_cloud_xyz[cb], d_order, (u32)n, r, h->d_trk_pts, h->stream_t);
@@ -244,7 +242,7 @@ int esvo_track_normal_equations_batch(esvo_handle h, int n_poses, const double* 
   std::memset(b, 0, sizeof(double) * 6 * n_poses);
   if (cost) std::memset(cost, 0, sizeof(double) * n_poses);
   if (m == 0) return ESVO_OK;
-  if (!h->h_trk_ne) HIPCHK(hipHostMalloc(reinterpret_cast<void**>(&h->h_trk_ne), sizeof(double) * TRK_NE_TERMS * TRK_NE_MAX_POSES));
+  if (!h->h_trk_ne) HIPCHK(h->h_trk_ne.alloc(TRK_NE_TERMS * TRK_NE_MAX_POSES));
   TrackArgs a;
   fill_track_args(h, a);
   TrackPoseSet set;  // as esvo_track_jacobian: T_left_ref = [R^T | -R^T t] (RegProblemLM.cpp:203-205), J_constPart (:189-194)
@@ -343,7 +341,7 @@ int esvo_track_solve(esvo_handle h, const esvo_track_solve_params_t* prm, double
   if (!h->trk_cur) FAIL(ESVO_ERR_STATE, "esvo_track_set_current has not been called");
   HIPCHK(hipSetDevice(h->device));
   N = std::min<size_t>(prm->n_points, h->trk_n);  // (a reference set between the two locks)
-  if (!h->h_trk_solve) HIPCHK(hipHostMalloc(reinterpret_cast<void**>(&h->h_trk_solve), sizeof(TrackSolveOut)));
+  if (!h->h_trk_solve) HIPCHK(h->h_trk_solve.alloc(1));
   TrackArgs a;
   fill_track_args(h, a);
   TrackSolveArgs s;
@@ -376,15 +374,15 @@ int esvo_track_reprojection_map(esvo_handle h, const double R[9], const double t
   HIPCHK(hipSetDevice(h->device));
   const size_t npx = (size_t)h->W * h->H;
   if (!h->d_trk_viz_cnt) {
-    if (!h->d_trk_viz_bgr) HIPCHK(hipMalloc(reinterpret_cast<void**>(&h->d_trk_viz_bgr), (npx + 3) / 4 * 12));
-    if (!h->d_trk_viz_owner) HIPCHK(hipMalloc(reinterpret_cast<void**>(&h->d_trk_viz_owner), (npx + 3) / 4 * 4 * sizeof(u32)));
-    if (!h->d_trk_viz_jet) HIPCHK(hipMalloc(reinterpret_cast<void**>(&h->d_trk_viz_jet), 768));
+    if (!h->d_trk_viz_bgr) HIPCHK(h->d_trk_viz_bgr.alloc((npx + 3) / 4 * 12));
+    if (!h->d_trk_viz_owner) HIPCHK(h->d_trk_viz_owner.alloc((npx + 3) / 4 * 4));
+    if (!h->d_trk_viz_jet) HIPCHK(h->d_trk_viz_jet.alloc(768));
     uint8_t jet[768];
     jet256_bgr(jet);
     HIPCHK(hipMemsetAsync(h->d_trk_viz_owner, 0, (npx + 3) / 4 * 4 * sizeof(u32), h->stream_t));  // the only clear: every call leaves it 0
     HIPCHK(hipMemcpyAsync(h->d_trk_viz_jet, jet, 768, hipMemcpyHostToDevice, h->stream_t));
     HIPCHK(hipStreamSynchronize(h->stream_t));  // (jet lives on this frame)
-    HIPCHK(hipMalloc(reinterpret_cast<void**>(&h->d_trk_viz_cnt), sizeof(u32)));  // last: marks the set complete
+    HIPCHK(h->d_trk_viz_cnt.alloc(1));  // last: marks the set complete
   }
   TrackArgs a;
   fill_track_args(h, a);

@@ -104,11 +104,9 @@ void queue_prepare(esvo_context* h, int cam, u64 t_ns) {
   }
   if (!h->tsq_dup[cam].empty()) {  // what eventsCallback inserted in place of late events: copies of the then-newest event (push_unsorted)
     auto& dup = h->tsq_dup[cam];
-    if (dup.size() > h->tsq_dup_cap) {
+    if (dup.size() > h->d_tsq_dup.cap()) {
       hipStreamSynchronize(h->stream);
-      if (h->d_tsq_dup) hipFree(h->d_tsq_dup);
-      h->tsq_dup_cap = std::max<size_t>(dup.size(), 4096);
-      if (hipMalloc(reinterpret_cast<void**>(&h->d_tsq_dup), sizeof(esvo_event_t) * h->tsq_dup_cap) != hipSuccess) { h->d_tsq_dup = nullptr; h->tsq_dup_cap = 0; }
+      (void)h->d_tsq_dup.alloc(std::max<size_t>(dup.size(), 4096));  // (on failure the buffer is empty: the copies are dropped below)
     }
     if (h->d_tsq_dup) {
       for (size_t a0 = 0; a0 < dup.size(); a0 += esvo_context::TSQ_ROUND) {
@@ -277,10 +275,10 @@ int push_routed(esvo_context* h, int cam, size_t n, GetEv get) {
   }
   if (n > h->route_cap[cam]) {  // (idle: every routed push ends with a wait for its copies)
     const size_t cap = std::max<size_t>(n, (size_t)1 << 16);
-    if (h->h_route_ev[cam]) { hipHostFree(h->h_route_ev[cam]); h->h_route_ev[cam] = nullptr; h->route_cap[cam] = 0; }
-    if (cam == 0 && h->h_route_gidx) { hipHostFree(h->h_route_gidx); h->h_route_gidx = nullptr; }
-    HIPCHK(hipHostMalloc(reinterpret_cast<void**>(&h->h_route_ev[cam]), sizeof(esvo_event_t) * cap, hipHostMallocDefault));
-    if (cam == 0) HIPCHK(hipHostMalloc(reinterpret_cast<void**>(&h->h_route_gidx), sizeof(u32) * cap, hipHostMallocDefault));
+    (void)h->h_route_ev[cam].release(); h->route_cap[cam] = 0;
+    if (cam == 0) (void)h->h_route_gidx.release();
+    HIPCHK(h->h_route_ev[cam].alloc(cap));
+    if (cam == 0) HIPCHK(h->h_route_gidx.alloc(cap));
     h->route_cap[cam] = cap;
   }
   esvo_event_t* kept = h->h_route_ev[cam];
@@ -433,17 +431,11 @@ int push_unsorted(esvo_context* h, int cam, size_t n, GetEv get) {
     ts_tail.assign(tsq.begin() + pos_rel, tsq.end());
     h->ring_reserved[cam] = ring_next + n;
   }
-  auto grow = [&](auto** p, size_t& cap, size_t need, size_t elem) {
-    if (need <= cap) return true;
-    if (*p) (void)hipFree(*p);
-    *p = nullptr; cap = 0;
-    const size_t c = std::max<size_t>(need + need / 2, 4096);
-    if (hipMalloc(reinterpret_cast<void**>(p), c * elem) != hipSuccess) { (void)hipGetLastError(); return false; }
-    cap = c;
-    return true;
+  const auto room = [](auto& buf, size_t need) {  // a scratch that is too small is replaced by one with half as much again
+    return need <= buf.cap() || buf.alloc(std::max<size_t>(need + need / 2, 4096)) == hipSuccess;
   };
-  if (!grow(&h->d_merge_a, h->merge_cap_a, K, sizeof(esvo_event_t)) || !grow(&h->d_merge_b, h->merge_cap_b, n, sizeof(esvo_event_t)) ||
-      !grow(&h->d_merge_plan, h->merge_cap_plan, K + n, sizeof(u32))) {
+  if (!room(h->d_merge_a, K) || !room(h->d_merge_b, n) || !room(h->d_merge_plan, K + n)) {
+    (void)hipGetLastError();
     push_abort(h, cam);
     FAIL(ESVO_ERR_CAPACITY, "out of device memory for the out-of-order merge");
   }
@@ -622,11 +614,8 @@ int esvo_ts_push_event_array(esvo_handle h, int cam, const uint8_t* msg, size_t 
   std::lock_guard<std::mutex> lp(h->mu_push[cam]);
   HIPCHK(hipSetDevice(h->device));
   if (h->routed) return push_routed(h, cam, n, widen);
-  if ((size_t)n * 13 > h->wire_cap[cam]) {  // this camera's staging buffer: its pusher is the only user (mu_push)
-    if (h->d_wire[cam]) { hipFree(h->d_wire[cam]); h->d_wire[cam] = nullptr; }
-    h->wire_cap[cam] = std::max<size_t>((size_t)n * 13, (size_t)1 << 20);
-    HIPCHK(hipMalloc(reinterpret_cast<void**>(&h->d_wire[cam]), h->wire_cap[cam]));
-  }
+  if ((size_t)n * 13 > h->d_wire[cam].cap())  // this camera's staging buffer: its pusher is the only user (mu_push)
+    HIPCHK(h->d_wire[cam].alloc(std::max<size_t>((size_t)n * 13, (size_t)1 << 20)));
   PushTicket tk;
   { int rc = push_begin(h, cam, n, stamp(0), tk); if (rc) return rc; }
   { int rc = push_drain(h, cam, tk); if (rc) return rc; }
@@ -669,10 +658,10 @@ int build_forward_lists(esvo_context* h, int cam) {
   for (size_t s = 0; s < npx; ++s)
     if (corners(s, dst))
       for (int c = 0; c < 4; ++c) src[fill[dst[c]]++] = (u32)s | ((u32)c << 30);
-  HIPCHK(hipMalloc(reinterpret_cast<void**>(&h->d_fwd_off[cam]), sizeof(u32) * (npx + 1)));
-  HIPCHK(hipMalloc(reinterpret_cast<void**>(&h->d_fwd_src[cam]), sizeof(u32) * src.size()));
-  HIPCHK(hipMalloc(reinterpret_cast<void**>(&h->d_fwd_lut[cam]), sizeof(float2) * npx));
-  if (!h->d_fwd_val) HIPCHK(hipMalloc(reinterpret_cast<void**>(&h->d_fwd_val), sizeof(double) * npx));
+  HIPCHK(h->d_fwd_off[cam].alloc(npx + 1));
+  HIPCHK(h->d_fwd_src[cam].alloc(src.size()));
+  HIPCHK(h->d_fwd_lut[cam].alloc(npx));
+  if (!h->d_fwd_val) HIPCHK(h->d_fwd_val.alloc(npx));
   HIPCHK(hipMemcpy(h->d_fwd_off[cam], off.data(), sizeof(u32) * (npx + 1), hipMemcpyHostToDevice));
   HIPCHK(hipMemcpy(h->d_fwd_src[cam], src.data(), sizeof(u32) * src.size(), hipMemcpyHostToDevice));
   HIPCHK(hipMemcpy(h->d_fwd_lut[cam], lut.data(), sizeof(float2) * npx, hipMemcpyHostToDevice));

@@ -97,20 +97,18 @@ static int alloc_pose_slot(esvo_context* h, u32* slot) {
   HIPCHK(hipStreamSynchronize(h->stream));
   int rc = drain_lm_and_back(h);
   if (rc) return rc;
-  double* d_new = nullptr;
-  const size_t per = (size_t)h->max_poses * 16 * sizeof(double);
-  if (hipMalloc(reinterpret_cast<void**>(&d_new), per * n_new) != hipSuccess) {
+  DevBuf<double> d_new;
+  const size_t per = (size_t)h->max_poses * 16;
+  if (d_new.alloc(per * n_new) != hipSuccess) {
     (void)hipGetLastError();
     FAIL(ESVO_ERR_CAPACITY, "out of device memory growing the pose-table slots");
   }
-  if (hipMemcpy(d_new, h->d_frame_pose_T, per * h->n_pose_slots, hipMemcpyDeviceToDevice) != hipSuccess) {
-    (void)hipGetLastError();
-    (void)hipFree(d_new);  // the old table stays in place and in use
+  if (hipMemcpy(d_new, h->d_frame_pose_T, sizeof(double) * per * h->n_pose_slots, hipMemcpyDeviceToDevice) != hipSuccess) {
+    (void)hipGetLastError();  // (d_new goes with this scope: the old table stays in place and in use)
     FAIL(ESVO_ERR_HIP, "copying the pose-table slots into the grown table failed");
   }
-  double* d_old = h->d_frame_pose_T;
-  h->d_frame_pose_T = d_new;  // the copy succeeded: from here on the handle owns the new table whatever the free says
-  HIPCHK(hipFree(d_old));
+  std::swap(d_new, h->d_frame_pose_T);  // the copy succeeded: from here on the handle owns the new table whatever the free says
+  HIPCHK(d_new.release());
   *slot = h->n_pose_slots;
   h->slot_used[*slot] = 1;
   h->n_pose_slots = n_new;

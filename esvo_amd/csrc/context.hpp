@@ -1,9 +1,12 @@
 // context.hpp — the state behind an esvo_handle and what the api_*.hip translation units share.
 //
 // One esvo_context owns every device buffer of one GPU: SAE + staged event rings (Time Surface), the observation pair,
-// per-tick BM/LM scratch, the fusion window ring and the dense DepthMap.  Each entry point replays, on the handle's HIP
-// streams, the call sequence of the reference seam it replaces (cited in include/esvo_hip.h); nothing computes on the
-// CPU except bookkeeping (time-stamp binary searches, window policy, output ordering).
+// per-tick BM/LM scratch, the fusion window ring and the dense DepthMap.  It owns them through DevBuf / PinBuf members
+// (devmem.hpp): a member that is a buffer is freed with the handle, a raw pointer member owns nothing (the views are listed
+// together below) -- esvo_destroy has no list to keep.  Single-owner events are DevEvent members in the same way; the evt[]
+// table and the streams stay raw handles, created and destroyed by esvo_create / esvo_destroy.  Each entry point replays, on
+// the handle's HIP streams, the call sequence of the reference seam it replaces (cited in include/esvo_hip.h); nothing
+// computes on the CPU except bookkeeping (time-stamp binary searches, window policy, output ordering).
 //   api_core.hip   lifecycle, parameters, self-tests           api_ts.hip     event ingest, Time-Surface render
 //   api_map.hip    mapper: stage launches, the tick pipeline   api_window.hip fusion window, back stage, map export
 //   api_modes.hip  synchronous MVStereo modes 1 and 4, SGM     api_shard.hip  band mode: routed front, phases, configuration
@@ -25,6 +28,7 @@
 #include <vector>
 
 #include "common.hpp"
+#include "devmem.hpp"
 
 using namespace esvo;
 
@@ -78,7 +82,7 @@ struct esvo_context {
   bool lm_two_on = false;
   // ESVO_TIMELINE=1 (tools/regime_probe.py): when every stage of every tick ran, collected from the HIP events as they complete
   bool tl_on = false;
-  hipEvent_t tl_ref = nullptr;
+  DevEvent tl_ref;
   std::vector<std::array<float, 8>> tl_front;
   std::vector<std::array<float, 4>> tl_back;
   // the pipeline's way back from its slow operating point (api_map.hip, pipeline_resync)
@@ -119,12 +123,10 @@ struct esvo_context {
     const u32* a_flags = nullptr; const u32* a_prefix = nullptr; u32 a_slots = 0;          // gather mode: a_src = the solver slots
     const void* b_src = nullptr; void* b_dst = nullptr; size_t b_bytes = 0; int ev_b = -1;  // pose table
   } pro;
-  uint8_t* d_obs2[2][2] = {{nullptr, nullptr}, {nullptr, nullptr}};
+  DevBuf<uint8_t> d_obs2[2][2];
   int obs_par = 0;
-  esvo_match_t* d_matches2[2] = {nullptr, nullptr};
-  u32* d_counters2[2] = {nullptr, nullptr};
-  u32* d_scan_tmp_l = nullptr;    // scan scratch of the LM stage (of the current parity)
-  u32* d_scan_tmp_l2[2] = {nullptr, nullptr};
+  DevBuf<esvo_match_t> d_matches2[2];
+  DevBuf<u32> d_counters2[2], d_scan_tmp_l2[2];
   hipStream_t stream_i = nullptr;  // event ingest (H2D into the ring): staging new events never waits for a running tick
   bool own_stream = false;
   int par = 0;                    // parity of the tick being assembled
@@ -153,27 +155,41 @@ struct esvo_context {
   // mu_ts, mu_ring in that order, and no tracker-group call takes mu_api.  mu_cloud is innermost for both groups (mapper:
   // mu_api -> mu_cloud; tracker: mu_track -> mu_cloud; esvo_reset holds all of them) and nothing is locked under it.
 
+  // ---- VIEWS: raw pointers that own nothing and are never freed.  Each aliases one buffer of a double-buffered set (or a
+  // part of one) and is re-pointed by a swap; kernels capture the pointer at launch, so work in flight keeps its own.
+  uint8_t* d_obs[2] = {nullptr, nullptr};  // d_obs2[obs_par][cam]: the observation pair of the current parity
+  esvo_match_t* d_matches = nullptr;       // d_matches2[fpar]
+  u32* d_counters = nullptr;               // d_counters2[fpar]: the front stage's counter row (common.hpp: CNT_*)
+  DevPoint* d_pt_slots = nullptr;          // d_pt_slots2 / d_pt_flags2 / d_pt_prefix2 [fpar]: LM output by slot + keep flags + their scan
+  u32* d_pt_flags = nullptr;
+  u32* d_pt_prefix = nullptr;
+  u32* d_scan_tmp_l = nullptr;             // d_scan_tmp_l2[fpar]: scan scratch of the LM stage
+  double* d_pose_T = nullptr;              // d_pose_T2[pose_buf]: the tick's pose table
+  double* d_pose_sec = nullptr;            // its tail (d_pose_T + 16 m): toSec() of the stamps
+  MapCell* d_map = nullptr;                // the cells of d_map_mem[0]
+  MapCell* d_map2 = nullptr;               // the cells of d_map_mem[1]
+  MapCell* d_map_cur = nullptr;            // d_map or d_map2: the DepthMap that is current
+  void* xchg_send = nullptr;               // the send / receive block of the exchange that is due (d_codes_* or d_pts_*);
+  void* xchg_recv = nullptr;               //   one rank: recv aliases send
+
   // calibration
-  float2* d_lut = nullptr;
-  uint8_t* d_mask = nullptr;
-  int2* d_fixmap[2] = {nullptr, nullptr};
+  DevBuf<float2> d_lut;
+  DevBuf<uint8_t> d_mask;
+  DevBuf<int2> d_fixmap[2];
 
   // Time Surface
-  u64* d_sae[2] = {nullptr, nullptr};
-  uint8_t* d_raw = nullptr;
-  uint8_t* d_raw1 = nullptr;
+  DevBuf<u64> d_sae[2];
+  DevBuf<uint8_t> d_raw, d_raw1;
   // FORWARD-mode Time Surface (esvo_ts_render_forward): host copy of each camera's rect_lut, and -- built on first use --
   // its device copy, the per-destination contribution lists (CSR: offsets, source index | corner << 30) and a f64 scratch
   std::vector<float> h_rect_lut[2];
-  float2* d_fwd_lut[2] = {nullptr, nullptr};
-  uint32_t* d_fwd_off[2] = {nullptr, nullptr};
-  uint32_t* d_fwd_src[2] = {nullptr, nullptr};
-  double* d_fwd_val = nullptr;  // the right camera's raw surface when both cameras render in one launch (esvo_map_tick_resident)
-  uint8_t* d_ts[2] = {nullptr, nullptr};
+  DevBuf<float2> d_fwd_lut[2];
+  DevBuf<uint32_t> d_fwd_off[2], d_fwd_src[2];
+  DevBuf<double> d_fwd_val;  // the right camera's raw surface when both cameras render in one launch (esvo_map_tick_resident)
+  DevBuf<uint8_t> d_ts[2];
   bool ts_valid[2] = {false, false};
-  esvo_event_t* d_ring[2] = {nullptr, nullptr};
-  uint8_t* d_wire[2] = {nullptr, nullptr};  // staging of serialised 13-byte event records (esvo_ts_push_event_array), per camera
-  size_t wire_cap[2] = {0, 0};
+  DevBuf<esvo_event_t> d_ring[2];
+  DevBuf<uint8_t> d_wire[2];  // staging of serialised 13-byte event records (esvo_ts_push_event_array), per camera
   u64 ring_cap = 0;
   std::deque<u64> ts_host[2];   // time stamps of staged events [ring_base, ring_base + size)
   u64 ring_base[2] = {0, 0};    // absolute index of ts_host[cam].front()
@@ -186,124 +202,103 @@ struct esvo_context {
   u64 scatter_pending_lo[2] = {~0ull, ~0ull};  // oldest event a possibly still running scatter kernel reads
   // esvo_ts_push_events_async: the newest enqueued (not awaited) copy of a camera; consumers of the ring on the front stream
   // queue behind it (ingest_fence, api_ts.hip) -- under mu_ring
-  hipEvent_t evt_ingest[2] = {nullptr, nullptr};
+  DevEvent evt_ingest[2];
   bool ingest_pending[2] = {false, false};
 
   // observation
-  uint8_t* d_obs[2] = {nullptr, nullptr};
-  uint8_t* d_obs_tmp = nullptr;
+  DevBuf<uint8_t> d_obs_tmp;
   double T_world_obs[16];
   u64 obs_t_ns = 0;
   bool obs_set = false;
 
   // pose table of the tick
-  double* d_pose_sec = nullptr;   // toSec() of the stamps: the tail of the tick's table (d_pose_T + 16 m)
-  double* d_pose_T = nullptr;     // the tick's table (one of d_pose_T2, alternating)
-  double* d_pose_T2[2] = {nullptr, nullptr};
+  DevBuf<double> d_pose_T2[2];
   int pose_buf = 0;
   std::vector<double> h_pose_T;
-  double* h_pin = nullptr;        // pinned staging: 2 slots x (max_poses x 17 + 16) doubles
+  PinBuf<double> h_pin;        // pinned staging: 2 slots x (max_poses x 17 + 16) doubles
   int pin_slot = 0;
   bool stats_pending = false;     // the last tick's counters / timings have not been read back yet
   u32 n_pose = 0;
 
   // per-tick scratch
   u32 max_ev = 0;
-  esvo_event_t* d_tick_ev = nullptr;
-  esvo_match_t* d_match_slots = nullptr;
-  u32* d_match_flags = nullptr;
-  u32* d_match_prefix = nullptr;
-  esvo_match_t* d_matches = nullptr;
+  DevBuf<esvo_event_t> d_tick_ev;
+  DevBuf<esvo_match_t> d_match_slots;
+  DevBuf<u32> d_match_flags, d_match_prefix;
   // split LM launch (kernels_lm.hip): F(x0) of every match, its cost, the processing order; allocated when the handle can see
   // launches above the wide layout's bound
-  double* d_lm_fvec0 = nullptr;
-  double* d_lm_fnorm0 = nullptr;
-  u32* d_lm_meta = nullptr;
-  u32* d_lm_order = nullptr;
-  u32* d_lm_hist = nullptr;
+  DevBuf<double> d_lm_fvec0, d_lm_fnorm0;
+  DevBuf<u32> d_lm_meta, d_lm_order, d_lm_hist;
   // the processing order of the narrow LM launch (kernels_lm.hip): built on the front queue behind the match compaction, read by
   // the LM launch on its own queue while the next tick's front stage runs -- so the order exists per front parity (as d_matches2
   // does); the sort's rows and histogram are the front queue's alone.  Allocated when the handle can see narrow launches.
-  u32* d_lm_pix_order2[2] = {nullptr, nullptr};
-  u64* d_lm_sort_rows[2] = {nullptr, nullptr};
-  u32* d_lm_sort_hist = nullptr;
+  DevBuf<u32> d_lm_pix_order2[2];
+  DevBuf<u64> d_lm_sort_rows[2];
+  DevBuf<u32> d_lm_sort_hist;
   bool lm_order_on = true;        // ESVO_LM_ORDER=0 (test / A/B only): the launch takes its slots in grid order
   // block matching once per distinct raw pixel (kernels_bm.hip, launch_bm_match_dedupe): one allocation -- the owner table
   // [W * H], the owner count (4 words, the first is used), the owner list [max_ev], the search outcomes [max_ev] -- on the front
   // queue alone, the next tick's block matching is behind its readers.  Allocated when the handle can see launches of
   // bm_dedupe_min events; run_bm takes the path for those.
-  u32* d_bm_dedupe = nullptr;
+  DevBuf<u32> d_bm_dedupe;
   bool bm_dedupe_on = true;       // ESVO_BM_DEDUPE=0 (test / A/B only): one search per event
   u32 bm_dedupe_min = esvo::BM_DEDUPE_MIN_EVENTS;  // ESVO_BM_DEDUPE_MIN=<n> (tests): the smallest launch bound that shares
-  u64* d_clk = nullptr;           // in-run shader-clock probe of the LM kernel (LmArgs::clk, common.hpp); read by esvo_get_stats
+  DevBuf<u64> d_clk;           // in-run shader-clock probe of the LM kernel (LmArgs::clk, common.hpp); read by esvo_get_stats
   bool clk_probe = true;          // ESVO_CLK_PROBE=0 (A/B only) launches the LM kernel without it
-  DevPoint* d_pt_slots = nullptr;   // LM output by slot + keep flags + their scan: alias one of two sets (front parity)
-  u32* d_pt_flags = nullptr;
-  u32* d_pt_prefix = nullptr;
-  DevPoint* d_pt_slots2[2] = {nullptr, nullptr};
-  u32* d_pt_flags2[2] = {nullptr, nullptr};
-  u32* d_pt_prefix2[2] = {nullptr, nullptr};
-  DevPoint* d_pts_tmp = nullptr;  // stage-wise refine output
-  DevPoint* d_stage[2] = {nullptr, nullptr};  // a lazily completed tick's frame (by parity) until its count is known
-  u32* d_counters = nullptr;      // the front stage's counter row of the current parity (common.hpp: CNT_*)
-  u32* h_counters = nullptr;      // pinned
-  u32* d_scan_tmp = nullptr;
-  u32* d_cnt_b = nullptr;         // the back stage's counter row (common.hpp: CNTB_*)
-  u32* h_cnt_b = nullptr;         // pinned, CNTB_ROWS rows of it (CNTB_ROW_*)
-  u32* d_scan_tmp_b = nullptr;
+  DevBuf<DevPoint> d_pt_slots2[2];
+  DevBuf<u32> d_pt_flags2[2], d_pt_prefix2[2];
+  DevBuf<DevPoint> d_pts_tmp;  // stage-wise refine output
+  DevBuf<DevPoint> d_stage[2];  // a lazily completed tick's frame (by parity) until its count is known
+  PinBuf<u32> h_counters;      // pinned
+  DevBuf<u32> d_scan_tmp;
+  DevBuf<u32> d_cnt_b;         // the back stage's counter row (common.hpp: CNTB_*)
+  PinBuf<u32> h_cnt_b;         // pinned, CNTB_ROWS rows of it (CNTB_ROW_*)
+  DevBuf<u32> d_scan_tmp_b;
 
   // fusion window
-  DevPoint* d_win = nullptr;
+  DevBuf<DevPoint> d_win;
   u32 win_cap = 0;
   std::deque<FrameRec> frames;    // oldest first
   u32 n_pose_slots = 0;
   std::vector<char> slot_used;
-  double* d_frame_pose_T = nullptr;
+  DevBuf<double> d_frame_pose_T;
   u32 max_poses = 0;
-  u32* d_fr_table = nullptr;      // fr_cum | fr_off | fr_slot
-  u32* h_fr_table = nullptr;      // pinned
+  DevBuf<u32> d_fr_table;      // fr_cum | fr_off | fr_slot
+  PinBuf<u32> h_fr_table;      // pinned
   u32 max_frames = 0;             // capacity in NON-EMPTY frames (pose slots, frame tables)
   size_t n_window_frames = 0;     // frames of the window as the reference counts them (empty ones included)
 
   // DepthMap
-  DevPoint* d_prop = nullptr;
+  DevBuf<DevPoint> d_prop;
   // fusion front (kernels_fuse.hip): per tile a fixed-capacity list of point ids + one shared overflow list; per cell the
   // (offset, count) of its sorted record list; the touched cells by length class; counters (class sizes, cursors)
-  u32* d_tile_count = nullptr;
-  uint2* d_tile_pts = nullptr;
-  uint2* d_over_pts = nullptr;
-  u32* d_cell_count = nullptr;
-  u32* d_cell_offset = nullptr;
-  u32* d_cell_list = nullptr;
-  u32* d_fuse_ctr = nullptr;      // class_count | class_total | rec_cursor | over_count (common.hpp: FUSE_CTR_*)
+  DevBuf<u32> d_tile_count;
+  DevBuf<uint2> d_tile_pts, d_over_pts;
+  DevBuf<u32> d_cell_count, d_cell_offset, d_cell_list;
+  DevBuf<u32> d_fuse_ctr;      // class_count | class_total | rec_cursor | over_count (common.hpp: FUSE_CTR_*)
   u32 fuse_tile_rec = 4096;       // entries of a tile's own region of d_rec_ids (ESVO_FUSE_TILE_REC: tests)
   u32 fuse_slice_cap = 0;         // entries of one (class, slice) segment of d_cell_list
   u32 fuse_tile_cap = 1024;       // ESVO_FUSE_TILE_CAP (tests): entries per tile list
   u32 fuse_pmax_plus1 = 0;        // ESVO_FUSE_PMAX (tests) + 1: candidates up to which a tile takes the bit-row path
-  u32* d_rec_ids = nullptr;       // record ids of cells whose list does not fit LDS (degenerate scenes)
+  DevBuf<u32> d_rec_ids;       // record ids of cells whose list does not fit LDS (degenerate scenes)
   u32 fuse_lds_cap = 0;           // ESVO_FUSE_LDS_CAP (tests): record ids per tile kept in LDS; 0 = the maximum
-  MapCell* d_map = nullptr;
-  MapCell* d_map2 = nullptr;
-  MapCell* d_map_cur = nullptr;
-  u32* d_owner_max = nullptr;
-  u32* d_owner_min = nullptr;
-  u32* d_sel = nullptr;           // denoising: walk positions of the kept events
-  uint8_t* d_evmap = nullptr;     // denoising: binary event map
+  DevBuf<uint8_t> d_map_mem[2];  // each: the cells + their dense flags (common.hpp: map_buffer_bytes); d_map / d_map2 view them
+  DevBuf<u32> d_owner_max, d_owner_min;
+  DevBuf<u32> d_sel;           // denoising: walk positions of the kept events
+  DevBuf<uint8_t> d_evmap;     // denoising: binary event map
   // sharded mode (kernels_shard.hip): dense local lists + the (matched, kept) byte per slot that is exchanged
-  u32* d_own_w = nullptr;         // slot w of the k-th own match
-  u32* d_lkeep = nullptr;         // keep flag of the k-th own match after LM + culling
-  uint8_t* d_codes = nullptr;     // [codes_bytes] one byte per slot (all ranks' slots, after exchange 1)
+  DevBuf<u32> d_own_w;         // slot w of the k-th own match
+  DevBuf<u32> d_lkeep;         // keep flag of the k-th own match after LM + culling
+  DevBuf<uint8_t> d_codes;     // [codes_bytes] one byte per slot (all ranks' slots, after exchange 1)
   size_t codes_bytes = 0;
   // what the caller must all-gather across the ranks before the next phase (esvo_shard_exchange): xchg_block bytes from
   // xchg_send of every rank into xchg_recv, rank-major.  One rank (n_shards == 1): recv aliases send, nothing to exchange.
-  void* xchg_send = nullptr;
-  void* xchg_recv = nullptr;
   size_t xchg_block = 0;
-  uint8_t* d_codes_send = nullptr;             // exchange 1: [roundup8(ceil(n / N))] the bytes of the own slots r, r + N ...
-  uint8_t* d_codes_all = nullptr;              //             [N][that]
-  unsigned long long* d_pts_send = nullptr;    // exchange 2: [1 + own * 13] count | kept points (final index in seq)
-  unsigned long long* d_pts_all = nullptr;     //             [N][1 + max_kept * 13]
-  u32* d_rank_kept = nullptr;                  // [SHARD_MAX_RANKS] kept count of every rank (from exchange 1)
+  DevBuf<uint8_t> d_codes_send;             // exchange 1: [roundup8(ceil(n / N))] the bytes of the own slots r, r + N ...
+  DevBuf<uint8_t> d_codes_all;              //             [N][that]
+  DevBuf<unsigned long long> d_pts_send;    // exchange 2: [1 + own * 13] count | kept points (final index in seq)
+  DevBuf<unsigned long long> d_pts_all;     //             [N][1 + max_kept * 13]
+  DevBuf<u32> d_rank_kept;                  // [SHARD_MAX_RANKS] kept count of every rank (from exchange 1)
   static constexpr u32 SHARD_MAX_RANKS = 1024;
   bool sharded = false;
   // ---- routed band mode (esvo_shard_set_routing): events are routed by image row at ingest, the Time Surfaces are
@@ -323,23 +318,20 @@ struct esvo_context {
   std::deque<u64> own_before;            // how many OWN events (floor(y_rect) in the band) were kept before this one: the count of a
   u64 own_total = 0;                     //   selection's own events bounds its LM launch (the ring also holds the raster's halo events)
   u64 last_stamp[2] = {0, 0};            // newest stamp seen per camera (kept or not): the order check of the push calls
-  u32* d_ring_gidx = nullptr;            // [ring_cap] low 32 bits of the global index of the left ring's events
-  esvo_event_t* h_route_ev[2] = {nullptr, nullptr};  // pinned staging of the kept events of one push, per camera
-  u32* h_route_gidx = nullptr;
+  DevBuf<u32> d_ring_gidx;            // [ring_cap] low 32 bits of the global index of the left ring's events
+  PinBuf<esvo_event_t> h_route_ev[2];  // pinned staging of the kept events of one push, per camera
+  PinBuf<u32> h_route_gidx;
   size_t route_cap[2] = {0, 0};
   // out-of-order packets (api_ts.hip, push_unsorted): scratch of the ring merge; queue mode: the copies of the then-newest event
   // that take a late event's place in the per-pixel queues, inserted with the next batch
-  esvo_event_t* d_merge_a = nullptr;
-  esvo_event_t* d_merge_b = nullptr;
-  u32* d_merge_plan = nullptr;
-  size_t merge_cap_a = 0, merge_cap_b = 0, merge_cap_plan = 0;
+  DevBuf<esvo_event_t> d_merge_a, d_merge_b;
+  DevBuf<u32> d_merge_plan;
   std::vector<esvo_event_t> tsq_dup[2];
-  esvo_event_t* d_tsq_dup = nullptr;
-  size_t tsq_dup_cap = 0;
-  u32* d_halo_viol = nullptr;            // [2] matches whose refinement read outside oband, all ranks, summed over the ticks | scratch
+  DevBuf<esvo_event_t> d_tsq_dup;
+  DevBuf<u32> d_halo_viol;            // [2] matches whose refinement read outside oband, all ranks, summed over the ticks | scratch
   bool halo_error = false;               // sticky (esvo_reset clears it): ticks are refused with ESVO_ERR_HALO
   bool dn_pending = false;               // Denoising on a routed handle: phase 0 returned ESVO_AGAIN, the mask bits are being exchanged
-  u32* d_dn_flags = nullptr;             // [2][max_ev] kept flag + exclusive prefix per walk position of the raw selection (lazily)
+  DevBuf<u32> d_dn_flags;             // [2][max_ev] kept flag + exclusive prefix per walk position of the raw selection (lazily)
   // A tick's state between its phases.  Unsharded ticks are finished lazily: esvo_map_tick(k) enqueues the front
   // stage of tick k and only then completes tick k-1 (point count -> window policy -> back stage), so the host
   // never waits on the front stream while it still has work to enqueue there.
@@ -378,24 +370,21 @@ struct esvo_context {
   u64 committed_t_ns = 0;         // stamp of the newest tick whose back stage is enqueued (0: none)
   // per-pixel event queues (max_event_queue_len > 0; kernels_ts.hip): key sets of both cameras + the batch's tile lists
   int tsq_len = 0;
-  u64* d_tsq[2] = {nullptr, nullptr};
-  u32* d_tsq_tcount = nullptr;
-  uint4* d_tsq_tlist = nullptr;
-  uint4* d_tsq_over = nullptr;
-  u32* d_tsq_over_count = nullptr;
+  DevBuf<u64> d_tsq[2];
+  DevBuf<u32> d_tsq_tcount;
+  DevBuf<uint4> d_tsq_tlist, d_tsq_over;
+  DevBuf<u32> d_tsq_over_count;
   u32 tsq_tcap = 0;
   static constexpr u64 TSQ_ROUND = 1ull << 20;  // events per insertion round = capacity of the overflow list
   u64 sh_first = 0;
   u64 sh_first_prev = 0;  // the selection before it (two ticks may be in flight)
   u64 em_guard_lo[2] = {~0ull, ~0ull};  // oldest ring event an esvo_map_tick_em gather may still read, per camera (api_em.hip)
-  double2* d_reg_ab = nullptr;
-  double2* d_reg_cd = nullptr;
+  DevBuf<double2> d_reg_ab, d_reg_cd;
   double T_world_frame[16];
   // export
-  u32* d_exp_flags = nullptr;
-  u32* d_exp_prefix = nullptr;
-  esvo_depth_point_t* d_export = nullptr;
-  u32* d_export_cell = nullptr;
+  DevBuf<u32> d_exp_flags, d_exp_prefix;
+  DevBuf<esvo_depth_point_t> d_export;
+  DevBuf<u32> d_export_cell;
   // The map's point cloud kept on the device (esvo_map_cloud_build; kernels_cloud.hip): a SNAPSHOT in one of two buffers of W*H
   // points (allocated by the first build).  A build fills the buffer that is not current, on the back stream and behind the
   // event of the tracker's last gather out of it (evt_cloud_read), records evt_cloud_built, reads the count -- its one host
@@ -404,68 +393,66 @@ struct esvo_context {
   u32 map_id_bound = 0;           // creation ids of d_map_cur are below this: what the fusion that built it numbered (run_fuse:
                                   // points x records per point; esvo_map_init_sgm: 4 x points).  Recorded where the ids are
                                   // assigned: the window may shrink afterwards without a fusion (esvo_map_push_frame).
-  float* d_cloud_xyz[2] = {nullptr, nullptr};
+  DevBuf<float> d_cloud_xyz[2];
   int cloud_cur = -1;             // the buffer that holds the snapshot (-1: none -- before the first build, after a reset)
   size_t cloud_n = 0;
   u64 cloud_t_ns = 0;             // committed_t_ns at the build
-  u32* d_cloud_ids = nullptr;     // [3][cloud_id_cap] present | prefix | where, by creation id
+  DevBuf<u32> d_cloud_ids;     // [3][cloud_id_cap] present | prefix | where, by creation id
   size_t cloud_id_cap = 0;
-  u32* d_cloud_scan = nullptr;    // scan scratch for cloud_id_cap ids
-  u32* d_cloud_cnt = nullptr;     // [0] elements [1] cells whose id was outside the bound (must stay 0)
-  u32* h_cloud_cnt = nullptr;     // pinned copy of it
-  hipEvent_t evt_cloud_built[2] = {nullptr, nullptr};
-  hipEvent_t evt_cloud_read[2] = {nullptr, nullptr};   // the tracker stream's newest gather out of that buffer
+  DevBuf<u32> d_cloud_scan;    // scan scratch for cloud_id_cap ids
+  DevBuf<u32> d_cloud_cnt;     // [0] elements [1] cells whose id was outside the bound (must stay 0)
+  PinBuf<u32> h_cloud_cnt;     // pinned copy of it
+  DevEvent evt_cloud_built[2];
+  DevEvent evt_cloud_read[2];   // the tracker stream's newest gather out of that buffer
   bool cloud_read_pending[2] = {false, false};
 
   // tracker residual / Jacobian evaluation (kernels_track.hip): own stream, own images, synchronous calls
   hipStream_t stream_t = nullptr;
-  uint8_t* d_trk_blur = nullptr;
-  uint8_t* d_trk_neg = nullptr;
-  int16_t* d_trk_du = nullptr;
-  int16_t* d_trk_dv = nullptr;
-  float* d_trk_xyz = nullptr;
-  double* d_trk_pts = nullptr;
-  double* d_trk_out = nullptr;
-  double* h_trk_ne = nullptr;     // pinned: the 28 sums of esvo_track_normal_equations
-  TrackSolveOut* h_trk_solve = nullptr;  // pinned: what track_solve_kernel writes (esvo_track_solve, on_device)
-  float* h_trk_xyz = nullptr;     // pinned staging of esvo_track_set_reference's point cloud
+  DevBuf<uint8_t> d_trk_blur, d_trk_neg;
+  DevBuf<int16_t> d_trk_du, d_trk_dv;
+  DevBuf<float> d_trk_xyz;
+  DevBuf<double> d_trk_pts, d_trk_out;
+  PinBuf<double> h_trk_ne;     // pinned: the 28 sums of esvo_track_normal_equations
+  PinBuf<TrackSolveOut> h_trk_solve;  // pinned: what track_solve_kernel writes (esvo_track_solve, on_device)
+  PinBuf<float> h_trk_xyz;     // pinned staging of esvo_track_set_reference's point cloud
   bool trk_xyz_inflight = false;  // an upload out of it has been enqueued and no call has waited for the tracker stream since
   size_t trk_cap = 0, trk_n = 0;
   bool trk_cur = false;
-  hipEvent_t evt_trk_read = nullptr;  // the tracker stream has read the resident left Time Surface (mu_ts)
+  DevEvent evt_trk_read;  // the tracker stream has read the resident left Time Surface (mu_ts)
   // the reprojection map (kernels_track_viz.hip): the tracker group's own image, owner words, jet table and counter, allocated
   // on first use under mu_track -- the d_viz_* buffers below are the mapper group's
-  uint8_t* d_trk_viz_bgr = nullptr;
-  u32* d_trk_viz_owner = nullptr;   // all 0 between calls (the paint pass clears what the mark pass set)
-  uint8_t* d_trk_viz_jet = nullptr;
-  u32* d_trk_viz_cnt = nullptr;
+  DevBuf<uint8_t> d_trk_viz_bgr;
+  DevBuf<u32> d_trk_viz_owner;   // all 0 between calls (the paint pass clears what the mark pass set)
+  DevBuf<uint8_t> d_trk_viz_jet;
+  DevBuf<u32> d_trk_viz_cnt;
   bool trk_viz_valid = false;       // d_trk_viz_bgr holds the image of a call
   bool trk_read_pending = false;
 
   // pinned staging slots for frame pose tables that arrive from the host (push_frame variants): a slot is reused only
   // after the back stream has consumed it
   static constexpr int POSE_POOL = 32;
-  double* h_pose_pool = nullptr;
-  hipEvent_t pool_evt[POSE_POOL];
-  bool pool_ok = false;
+  PinBuf<double> h_pose_pool;
+  DevEvent pool_evt[POSE_POOL];
   int pool_next = 0;
 
   // SGM initialisation (kernels_sgm.hip): allocated on first use, released by esvo_destroy
-  SgmScratch sgm = {};
+  SgmScratch sgm = {};            // what the launchers take by value: raw pointers into the buffers of the next three lines
+  DevBuf<uint8_t> d_sgm_plane[4];  // sobL, rawL, sobR, rawR
+  DevBuf<int16_t> d_sgm_vol[6], d_sgm_d1, d_sgm_d1b;
+  DevBuf<u32> d_sgm_d2key;
   bool sgm_ok = false;
-  uint8_t* d_sgm_img[2] = {nullptr, nullptr};
-  int16_t* d_sgm_disp = nullptr;
-  u32* d_sgm_pair = nullptr;      // [2][4 * max_ev] winner flags / ranks of naive_propagation
-  double* d_sgm_T = nullptr;
+  DevBuf<uint8_t> d_sgm_img[2];
+  DevBuf<int16_t> d_sgm_disp;
+  DevBuf<u32> d_sgm_pair;      // [2][4 * max_ev] winner flags / ranks of naive_propagation
+  DevBuf<double> d_sgm_T;
   // the per-tick SGM mode (esvo_map_tick_sgm / esvo_map_push_disparity_frame)
   bool sgm_disp_valid = false;    // d_sgm_disp holds a disparity image
-  hipEvent_t evt_sgm[3] = {nullptr, nullptr, nullptr};  // before / behind the SGM chain, behind the point stage
+  DevEvent evt_sgm[3];  // before / behind the SGM chain, behind the point stage
   esvo_sgm_stats_t sgm_stats = {};
 
   // debug images (kernels_viz.hip): allocated on first use
-  uint8_t* d_viz_bgr = nullptr;
-  uint8_t* d_viz_jet = nullptr;
-  u32* d_viz_owner = nullptr;
+  DevBuf<uint8_t> d_viz_bgr, d_viz_jet;
+  DevBuf<u32> d_viz_owner;
 
   struct esvo_comm* comm = nullptr;  // multi-GPU exchange (api_comm.hip), null on single-GPU handles
 
@@ -483,7 +470,6 @@ extern thread_local std::string g_create_error;
 // api_core.hip
 void fill_dev_params(esvo_context* h);
 void set_compute_band(esvo_context* h);
-void release_routing(esvo_context* h);
 void jet256_bgr(uint8_t jet[768]);  // DrawPoint's 256 BGR triples: the mapper's debug images and the tracker's reprojection map
 // api_ts.hip
 void collect_ts_timing(esvo_context* h, int only = -1);

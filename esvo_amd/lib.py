@@ -515,6 +515,20 @@ def debug_sqrt_moderate(x):
     return out, g
 
 
+def debug_live_allocations():
+    """(live allocations, live bytes) of the process: every device / pinned buffer a handle owns (devmem.hpp)"""
+    out = (C.c_size_t * 2)()
+    fn = getattr(load(), "esvo_debug_live_allocations")
+    fn.argtypes, fn.restype = [C.c_void_p], None
+    fn(out)
+    return int(out[0]), int(out[1])
+
+
+def debug_devmem_selftest(pinned=False):
+    """the owning buffer type step by step against its ledger: 0, or the number of the first step that failed"""
+    return _dbg_rc(_dbg_fn("esvo_debug_devmem_selftest", [C.c_int])(1 if pinned else 0), "esvo_debug_devmem_selftest")
+
+
 class BagReader:
     """rosbag format 2.0 reader of the C-ABI (esvo_bag_*): iterates (topic, bag stamp ns, serialised EventArray bytes)"""
 
