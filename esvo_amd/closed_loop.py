@@ -289,3 +289,111 @@ def run_bands(G, routing="y_rect", n_ticks=15, reref=10**9, speed=1.0, seed=2025
     out["ranks_agree"] = all(np.array_equal(np.array(o["poses"]), np.array(out["poses"])) and np.array_equal(o["map"], out["map"]) for o in outs)
     out["events_staged_max_frac"] = max(o["events_staged"][0] for o in outs) / max(len(st.ev_left), 1)
     return out
+
+
+def run_node_rates(n_frames=20, map_every=5, resident=True, history=100, speed=1.0, seed=20250419, verbose=False):
+    """The loop at the reference's own rates on ONE handle: the Time Surfaces are rendered every 10 ms, the tracker registers
+    every frame against the NEWEST retained frame (esvo_Tracking.cpp:241-247), the mapper ticks every `map_every` frames on the
+    pair dataTransferring would take (esvo_Mapping.cpp:497-534): the second newest for which "a pose is known", i.e. that the
+    tracker has registered -- nothing while fewer than eleven pairs are retained.  Each mapper tick is followed by a
+    re-reference of the tracker to the new map.
+    resident=True: the frames stay on the device (ts_history_configure; track_set_current_at, ts_history_select_observation,
+    set_observation_at).  resident=False: the same loop the way it has to be done without the history -- every render is
+    downloaded, the pairs are kept in a host dict with the same eviction, and the chosen ones are handed back with
+    set_observation(t, left, right, T) and track_set_current(left, 5).  Both compute the same bits."""
+    rig, st, p, t0 = _scene(seed, speed)
+    if t0 + n_frames * TICK_NS > st.t1_ns:
+        raise ValueError(f"the scene's stream ends after {(st.t1_ns - t0) // TICK_NS} frames")
+    dev = lib.Esvo(p, rig)
+    if resident:
+        dev.ts_history_configure(history)
+    dev.ts_push_events(0, st.ev_left)
+    dev.ts_push_events(1, st.ev_right)
+    host_ts = {}                           # resident=False: stamp -> (left, right), the node's TS_history_
+    pair = (dev.ts_render(0, t0, download=not resident), dev.ts_render(1, t0, download=not resident))
+    if not resident:
+        host_ts[t0] = pair
+    T0 = st.pose(t0)                       # bootstrap pose given, as the reference's identity at start-up
+    dev.set_observation(t0, None, None, T0)
+    n_sgm, _ = dev.init_sgm(None, None, min_points=100)
+    T_est = {t0: T0}
+    out = {"pos_err": [], "rot_err_deg": [], "points": [], "tick_frames": [], "tick_stamps": [], "track_ms": [], "map_ms": [],
+           "poses": [], "n_inside": [], "sgm_points": n_sgm}
+    rng = np.random.default_rng(0)
+    xyz = dev.get_pointcloud()
+    sel = rng.permutation(len(xyz))[:2000]
+    t_ref, R_, t_ = t0, np.eye(3), np.zeros(3)
+    for k in range(1, n_frames + 1):
+        t = t0 + k * TICK_NS
+        c0 = time.perf_counter()
+        pair = (dev.ts_render(0, t, download=not resident), dev.ts_render(1, t, download=not resident))
+        if resident:
+            dev.track_set_current_at(t, 5)
+        else:
+            host_ts[t] = pair
+            while len(host_ts) > history:
+                del host_ts[min(host_ts)]
+            dev.track_set_current(host_ts[max(host_ts)][0], 5)
+        dev.track_set_reference(xyz[sel], T_est[t_ref])
+        R_, t_, rms = register(dev, len(sel), R_, t_)
+        Tw = np.eye(4)
+        Tw[:3, :3] = T_est[t_ref][:3, :3] @ R_
+        Tw[:3, 3] = T_est[t_ref][:3, :3] @ t_ + T_est[t_ref][:3, 3]
+        T_est[t] = Tw
+        c1 = time.perf_counter()
+        out["track_ms"].append((c1 - c0) * 1e3)                # both renders (+ their download) + the registration
+        out["n_inside"].append(dev.track_reprojection_map(R_, t_, 2000, p.invdepth_min, p.invdepth_max, download=False)[1])
+        gt = st.pose(t)
+        out["pos_err"].append(float(np.linalg.norm(Tw[:3, 3] - gt[:3, 3])))
+        out["rot_err_deg"].append(float(np.degrees(np.arccos(np.clip((np.trace(Tw[:3, :3].T @ gt[:3, :3]) - 1) / 2, -1, 1)))))
+        out["poses"].append(Tw.copy())
+        if k % map_every:
+            continue
+        c2 = time.perf_counter()
+        if resident:
+            chosen = dev.ts_history_select_observation(T_est.get)
+        else:
+            stamps_h = sorted(host_ts)
+            chosen = lib.ts_history_select(stamps_h, T_est.get)
+            chosen = None if chosen is None else (stamps_h[chosen[0]], chosen[1])
+        if chosen is None:                                     # the node's dataTransferring returns false: no tick
+            continue
+        t_obs, T_obs = chosen
+
+        def pose_at(tq, a=T_est[t_obs - TICK_NS], b=T_obs, ta=t_obs - TICK_NS):
+            w = (tq - ta) / TICK_NS                            # tf-style interpolation between tracked poses
+            T = np.eye(4)
+            T[:3, 3] = (1 - w) * a[:3, 3] + w * b[:3, 3]
+            T[:3, :3] = orth((1 - w) * a[:3, :3] + w * b[:3, :3])
+            return T
+        c2b = time.perf_counter()
+        stamps, poses = rostime.pose_table(pose_at, t_obs, p.bm_half_slice_thickness)
+        c2c = time.perf_counter()
+        if resident:
+            dev.set_observation_at(t_obs, T_obs)
+        else:
+            dev.set_observation(t_obs, host_ts[t_obs][0], host_ts[t_obs][1], T_obs)
+        dev.tick(t_obs, stamps, poses)
+        out["points"].append(int(dev.stats().last_points))     # (reading the statistics completes the tick)
+        c3 = time.perf_counter()
+        out["map_ms"].append((c2b - c2 + c3 - c2c) * 1e3)       # the choice of the pair, the observation and the tick
+        out["tick_frames"].append(k)
+        out["tick_stamps"].append(int(t_obs))
+        xyz = dev.get_pointcloud()                             # re-reference: the tracker registers against the new map
+        sel = rng.permutation(len(xyz))[:2000]
+        t_ref, R_, t_ = t, np.eye(3), np.zeros(3)
+        if verbose:
+            print(f"frame {k}: mapper tick at frame {(t_obs - t0) // TICK_NS}, {out['points'][-1]} points, pos err "
+                  f"{out['pos_err'][-1] * 1e3:.2f} mm")
+    mp = dev.get_map()
+    t_map = out["tick_stamps"][-1] if out["tick_stamps"] else t0
+    u, v, rho = st.true_inv_depth_image(t_map)
+    ok = (u >= 0) & (u < rig.width) & (v >= 0) & (v < rig.height)
+    gtimg = {(int(b), int(a)): c for a, b, c in zip(u[ok], v[ok], rho[ok])}
+    err = np.array([m["inv_depth"] - gtimg[(int(m["row"]), int(m["col"]))] for m in mp
+                    if (int(m["row"]), int(m["col"])) in gtimg and m["inv_depth"] > 0])
+    out["map"] = mp
+    out["map_cells"] = len(mp)
+    out["map_median_abs_err"] = float(np.median(np.abs(err))) if len(err) else float("nan")
+    dev.close()
+    return out

@@ -562,6 +562,7 @@ int esvo_comm_init(esvo_handle h, const uint8_t id[ESVO_COMM_ID_BYTES], int rank
   if (!h || !id || world < 1 || rank < 0 || rank >= world) return ESVO_ERR_INVALID_ARG;
   API_LOCK(h);
   if (h->comm) FAIL(ESVO_ERR_STATE, "the handle already has a communicator");
+  if (h->hist_len) FAIL(ESVO_ERR_UNSUPPORTED, "the handle keeps a Time-Surface history: esvo_ts_history_configure(h, 0) before giving it a communicator");
   if (const char* e = load_rccl()) FAIL(ESVO_ERR_UNSUPPORTED, e);
   HIPCHK(hipSetDevice(h->device));
   { int rcp = flush_pending_tick(h); if (rcp) return rcp; }
@@ -584,6 +585,7 @@ int esvo_comm_init_callbacks(esvo_handle h, int rank, int world, esvo_all_gather
   if (!h || !all_gather || world < 1 || rank < 0 || rank >= world) return ESVO_ERR_INVALID_ARG;
   API_LOCK(h);
   if (h->comm) FAIL(ESVO_ERR_STATE, "the handle already has a communicator");
+  if (h->hist_len) FAIL(ESVO_ERR_UNSUPPORTED, "the handle keeps a Time-Surface history: esvo_ts_history_configure(h, 0) before giving it a communicator");
   HIPCHK(hipSetDevice(h->device));
   { int rcp = flush_pending_tick(h); if (rcp) return rcp; }
   h->comm = new esvo_comm();

@@ -426,6 +426,7 @@ int esvo_reset(esvo_handle h) {
   h->sh_first = 0;
   h->sh_first_prev = 0;
   h->trk_read_pending = false;
+  hist_clear(h);  // esvo_Mapping::reset clears TS_history_ (:764-804); the slots stay allocated
   h->ema_lm_ms = h->ema_back_ms = 0.f;
   h->lm_two_on = false;
   std::memset(h->lm_pair_ms, 0, sizeof(h->lm_pair_ms));

@@ -186,6 +186,7 @@ int ts_render_pair(esvo_context* h, uint64_t t_ns, uint8_t* const obs_out[2]) {
     if (timed || h->trk_used.load()) hipEventRecord(h->evt[EV_R1], h->stream);  // (also what esvo_track_set_current waits for)
     HIPCHK(hipGetLastError());
     h->ts_valid[0] = h->ts_valid[1] = true;
+    for (int cam = 0; cam < 2; ++cam) { int rch = hist_store(h, cam, t_ns, h->d_ts[cam], false); if (rch) return rch; }  // (history off: nothing)
   }
   h->ts_timing_pending[0] = timed;
   h->ts_pair_sample = timed;
@@ -707,6 +708,7 @@ int esvo_ts_render_forward(esvo_handle h, int cam, uint64_t t_ns, uint8_t* out_m
     if (cam == 0) hipEventRecord(h->evt[EV_R1], h->stream);  // what esvo_track_set_current waits for
     HIPCHK(hipGetLastError());
     h->ts_valid[cam] = true;
+    { int rch = hist_store(h, cam, t_ns, h->d_ts[cam], false); if (rch) return rch; }  // the Time-Surface history (off: nothing)
   }
   if (cam == 0) h->ts_timing_pending[0] = false;  // EV_R1 no longer belongs to a timed scatter / render pair
   h->stats.ts_frames[cam]++;
@@ -762,6 +764,7 @@ int esvo_ts_render(esvo_handle h, int cam, uint64_t t_ns, uint8_t* out_mono8) {
     if (timed || (cam == 0 && h->trk_used.load())) hipEventRecord(h->evt[EV_R1 + evo], h->stream);
     HIPCHK(hipGetLastError());
     h->ts_valid[cam] = true;
+    { int rch = hist_store(h, cam, t_ns, h->d_ts[cam], false); if (rch) return rch; }  // the Time-Surface history (off: nothing)
   }
   h->ts_timing_pending[cam] = timed;
   h->stats.ts_frames[cam]++;

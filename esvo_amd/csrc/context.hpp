@@ -13,6 +13,7 @@
 //   api_out.hip    DepthMap / cloud / image outputs, stats     api_comm.hip   tick-interleaved multi-GPU exchange
 //   api_em.hip     event-to-event matching (modes 0 and 2)     api_gpc.hip    the global point cloud
 //   api_track.hip  tracker residual / Jacobian evaluation      api_bag.hip, api_dev.hip  bag reader, development hooks
+//   api_history.hip  Time-Surface history: frames by stamp, the mapper's and the tracker's pick
 #pragma once
 #include <algorithm>
 #include <array>
@@ -145,7 +146,7 @@ struct esvo_context {
   std::mutex mu_push[2];        // one pusher per camera at a time (held across its host-to-device copy)
   std::mutex mu_track;          // tracker-group calls
   std::mutex mu_ts;             // the resident left Time Surface (d_ts[0], ts_valid[0], EV_R1) between a render and a
-                                // tracker read (esvo_track_set_current without a host image)
+                                // tracker read (esvo_track_set_current without a host image); the Time-Surface history's table
   std::mutex mu_cloud;          // the device-resident point cloud between a build (mapper group) and a tracker gather
                                 // (esvo_track_set_reference_from_cloud): cloud_cur, cloud_n, cloud_t_ns, evt_cloud_built,
                                 // evt_cloud_read and cloud_read_pending.  Held only while those change or while work that reads
@@ -188,6 +189,16 @@ struct esvo_context {
   DevBuf<double> d_fwd_val;  // the right camera's raw surface when both cameras render in one launch (esvo_map_tick_resident)
   DevBuf<uint8_t> d_ts[2];
   bool ts_valid[2] = {false, false};
+  // Time-Surface history (api_history.hip; the nodes' TS_history_): hist_len entries of two frames each, frame (slot, cam) at
+  // d_hist + (2 * slot + cam) * hist_stride.  The stride is W * H rounded up to 256 bytes, so every frame starts as an allocation
+  // does.  The table (stamp -> slot, ascending stamps), the free slots and evt_hist are guarded by mu_ts; every store is
+  // enqueued on the front stream under that lock, every tracker read on the tracker stream behind evt_hist.  0: off.
+  struct HistEntry { u64 t_ns; u32 slot; uint8_t cams; };  // cams: bit 0 left present, bit 1 right present
+  size_t hist_len = 0, hist_stride = 0;
+  DevBuf<uint8_t> d_hist;
+  std::vector<HistEntry> hist;
+  std::vector<u32> hist_free;
+  DevEvent evt_hist;            // the front stream behind the newest store (a later record implies the earlier stores)
   DevBuf<esvo_event_t> d_ring[2];
   DevBuf<uint8_t> d_wire[2];  // staging of serialised 13-byte event records (esvo_ts_push_event_array), per camera
   u64 ring_cap = 0;
@@ -477,6 +488,9 @@ void ingest_fence(esvo_context* h, int cam);  // caller holds mu_ring
 int ts_scatter_ahead(esvo_context* h, uint64_t t_ns);
 void resident_write_begin(esvo_context* h, int cam);
 int ts_render_pair(esvo_context* h, uint64_t t_ns, uint8_t* const obs_out[2]);
+// api_history.hip
+int hist_store(esvo_context* h, int cam, uint64_t t_ns, const uint8_t* src, bool from_host);  // caller holds mu_ts
+void hist_clear(esvo_context* h);                                                             // caller holds mu_ts
 // api_em.hip
 void em_release(esvo_context* h);  // frees the event-matching state (esvo_destroy)
 // api_gpc.hip

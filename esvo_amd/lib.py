@@ -17,7 +17,7 @@ from .abi import (DEPTH_POINT_DTYPE, EM_POSE_FN, ERR_CAPACITY, ERR_INVALID_ARG, 
 _CSRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc")
 # ESVO_HIP_LIB: another build of the same library (A/B measurements of kernel variants, tools/ab_build.py); never a fallback
 _LIB_PATH = os.environ.get("ESVO_HIP_LIB") or os.path.join(_CSRC, "libesvo_hip.so")
-_SOURCES = ["api_core.hip", "api_ts.hip", "api_map.hip", "api_window.hip", "api_modes.hip", "api_shard.hip", "api_out.hip", "api_comm.hip", "api_bag.hip", "api_track.hip", "scan.hip", "kernels_ts.hip", "kernels_bm.hip", "kernels_lm.hip", "kernels_lm_any.hip", "kernels_fuse.hip", "kernels_shard.hip", "kernels_track.hip", "kernels_track_viz.hip", "kernels_viz.hip", "kernels_sgm.hip", "api_em.hip", "kernels_em.hip", "kernels_cloud.hip", "api_dev.hip", "api_gpc.hip", "kernels_voxel.hip"]
+_SOURCES = ["api_core.hip", "api_ts.hip", "api_map.hip", "api_window.hip", "api_modes.hip", "api_shard.hip", "api_out.hip", "api_comm.hip", "api_bag.hip", "api_track.hip", "scan.hip", "kernels_ts.hip", "kernels_bm.hip", "kernels_lm.hip", "kernels_lm_any.hip", "kernels_fuse.hip", "kernels_shard.hip", "kernels_track.hip", "kernels_track_viz.hip", "kernels_viz.hip", "kernels_sgm.hip", "api_em.hip", "kernels_em.hip", "kernels_cloud.hip", "api_dev.hip", "api_gpc.hip", "kernels_voxel.hip", "api_history.hip"]
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared",
                "-Wno-unused-value", "-Wno-unused-result", "-ldl"]
 
@@ -41,6 +41,8 @@ SYMBOLS = [
     "esvo_map_cloud_near", "esvo_map_voxel_filter", "esvo_map_gpc_configure", "esvo_map_gpc_update", "esvo_map_gpc_get", "esvo_map_gpc_device",
     "esvo_map_gpc_stats", "esvo_gpc_sizes",
     "esvo_track_reprojection_map", "esvo_track_reprojection_map_device",
+    "esvo_ts_history_configure", "esvo_ts_history_list", "esvo_ts_history_get", "esvo_ts_history_put", "esvo_map_set_observation_at",
+    "esvo_track_set_current_at", "esvo_ts_history_select", "esvo_ts_history_select_observation",
 ]
 
 ALL_GATHER_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p)
@@ -238,6 +240,14 @@ def load():
     lib.esvo_gpc_sizes.restype = None
     lib.esvo_track_reprojection_map.argtypes = [vp, vp, vp, sz, C.c_double, C.c_double, vp, psz]
     lib.esvo_track_reprojection_map_device.argtypes = [vp, C.POINTER(vp)]
+    lib.esvo_ts_history_configure.argtypes = [vp, sz]
+    lib.esvo_ts_history_list.argtypes = [vp, vp, vp, sz, psz]
+    lib.esvo_ts_history_get.argtypes = [vp, u64, i32, vp]
+    lib.esvo_ts_history_put.argtypes = [vp, u64, i32, vp]
+    lib.esvo_map_set_observation_at.argtypes = [vp, u64, vp]
+    lib.esvo_track_set_current_at.argtypes = [vp, u64, i32]
+    lib.esvo_ts_history_select.argtypes = [vp, sz, i32, EM_POSE_FN, vp, psz, vp]
+    lib.esvo_ts_history_select_observation.argtypes = [vp, i32, EM_POSE_FN, vp, C.POINTER(C.c_uint64), vp]
     for s in SYMBOLS:
         if s not in ("esvo_default_params", "esvo_last_error", "esvo_abi_sizes", "esvo_bag_last_error", "esvo_em_sizes", "esvo_sgm_sizes",
                      "esvo_track_sizes", "esvo_gpc_sizes"):
@@ -247,6 +257,45 @@ def load():
     lib.esvo_bag_last_error.restype = C.c_char_p
     _lib = lib
     return lib
+
+
+def _pose_trampoline(pose_fn):
+    """pose_fn(t_ns) -> 4x4 T_world_cam or None, as an esvo_em_pose_fn.  An exception must not unwind through the C frames: it is
+    kept (the second value, a list) and the stamp counts as one without a pose."""
+    raised = []
+
+    def trampoline(user, t_ns, out):
+        try:
+            T = None if pose_fn is None else pose_fn(int(t_ns))
+            if T is None:
+                return 0
+            T = np.asarray(T, np.float64).reshape(16)
+            for k in range(16):
+                out[k] = float(T[k])
+            return 1
+        except BaseException as e:  # noqa: BLE001
+            raised.append(e)
+            return 0
+    return EM_POSE_FN(trampoline), raised
+
+
+def ts_history_select(stamps, pose_fn=None, initialization=False):
+    """dataTransferring's choice among the stamps of complete pairs, ascending (esvo_ts_history_select; host code, no GPU):
+    (index, 4x4 T_world_cam), or None where the node would return false.  pose_fn(t_ns) -> 4x4 pose, or None where no pose is
+    known; it is not consulted while the system initialises."""
+    lib = load()
+    st = np.ascontiguousarray(stamps, np.uint64)
+    cb, raised = _pose_trampoline(pose_fn)
+    idx, T = C.c_size_t(0), np.zeros(16, np.float64)
+    rc = lib.esvo_ts_history_select(st.ctypes.data if len(st) else None, len(st), 1 if initialization else 0, cb, None, C.byref(idx),
+                                    T.ctypes.data)
+    if raised:
+        raise raised[0]
+    if rc == ESVO_AGAIN:
+        return None
+    if rc != 0:
+        raise EsvoError(f"esvo_ts_history_select failed ({rc}): {lib.esvo_last_error(None).decode(errors='replace')}", code=rc)
+    return int(idx.value), T.reshape(4, 4)
 
 
 def stochastic_order(n_cloud, n_take, draws):
@@ -720,6 +769,52 @@ class Esvo:
         out = np.empty((self.H, self.W), np.uint8) if download else None
         self._ck(self.lib.esvo_ts_render(self.h, int(cam), int(t_ns), _p(out)))
         return out
+
+    # ---- Time-Surface history (the nodes' TS_history_ on the device)
+    def ts_history_configure(self, length):
+        """retain `length` pairs by stamp (TS_HISTORY_LENGTH: 100); 0 switches the history off.  Empties it."""
+        self._ck(self.lib.esvo_ts_history_configure(self.h, int(length)))
+
+    def ts_history(self):
+        """(stamps uint64 ascending, cams uint8: bit 0 left present, bit 1 right present)"""
+        n = C.c_size_t(0)
+        self._ck(self.lib.esvo_ts_history_list(self.h, None, None, 0, C.byref(n)))
+        t, cams = np.zeros(max(n.value, 1), np.uint64), np.zeros(max(n.value, 1), np.uint8)
+        self._ck(self.lib.esvo_ts_history_list(self.h, t.ctypes.data, cams.ctypes.data, len(t), C.byref(n)))
+        return t[: n.value].copy(), cams[: n.value].copy()
+
+    def ts_history_get(self, t_ns, cam):
+        out = np.empty((self.H, self.W), np.uint8)
+        self._ck(self.lib.esvo_ts_history_get(self.h, int(t_ns), int(cam), out.ctypes.data))
+        return out
+
+    def ts_history_put(self, t_ns, cam, img):
+        img = np.ascontiguousarray(img, np.uint8)
+        if img.size != self.W * self.H:
+            raise ValueError(f"a {self.W} x {self.H} mono8 image is expected, not {img.shape}")
+        self._ck(self.lib.esvo_ts_history_put(self.h, int(t_ns), int(cam), img.ctypes.data))
+
+    def set_observation_at(self, t_ns, T_world_cam):
+        """set_observation(t_ns, left, right, T) on the retained pair of that stamp"""
+        T = np.ascontiguousarray(T_world_cam, np.float64).reshape(16)
+        self._ck(self.lib.esvo_map_set_observation_at(self.h, int(t_ns), T.ctypes.data))
+
+    def track_set_current_at(self, t_ns, kernel_size=5):
+        """track_set_current(left, kernel_size) on the retained left frame of that stamp"""
+        self._ck(self.lib.esvo_track_set_current_at(self.h, int(t_ns), int(kernel_size)))
+
+    def ts_history_select_observation(self, pose_fn=None, initialization=False):
+        """dataTransferring's choice among the retained complete pairs: (t_ns, 4x4 T_world_cam), or None where the node would
+        return false.  pose_fn as for ts_history_select."""
+        cb, raised = _pose_trampoline(pose_fn)
+        t, T = C.c_uint64(0), np.zeros(16, np.float64)
+        rc = self.lib.esvo_ts_history_select_observation(self.h, 1 if initialization else 0, cb, None, C.byref(t), T.ctypes.data)
+        if raised:
+            raise raised[0]
+        if rc == ESVO_AGAIN:
+            return None
+        self._ck(rc)
+        return int(t.value), T.reshape(4, 4)
 
     # ---- mapper, stage-wise (EventBM / DepthProblemSolver / DepthFusion seams)
     def ts_render_forward(self, cam, t_ns, download=True):

@@ -22,6 +22,7 @@
  *       TRACKER  esvo_track_*
  *       MAPPER   every other call that takes the handle (renders, observation, ticks, stage-wise calls, outputs,
  *                parameters, esvo_comm_*, esvo_reset -- which excludes the other two groups while it runs)
+ *       (esvo_ts_history_list and esvo_ts_history_select_observation belong to no group: any thread may call them)
  *     Calls of the same group are serialised by the library (safe from several threads, never concurrent).  The node's
  *     data_mutex_ is therefore NOT needed around these calls.  What the caller still owns is causality: a render or
  *     tick at time t sees the events staged when it is called, exactly like the reference's TS_history_/events_left_
@@ -554,6 +555,70 @@ int esvo_map_push_disparity_frame(esvo_handle h, const int16_t* disp16, const es
 int esvo_map_sgm_stats(esvo_handle h, esvo_sgm_stats_t* out);
 /* sizeof() of {esvo_sgm_stats_t}, numDisparities (48), 0, 0. */
 void esvo_sgm_sizes(size_t out[4]);
+
+/* ---- Time-Surface history ------------------------------------------------------------ */
+
+/* The nodes' TS_history_ (a std::map of stereo pairs by stamp, TS_HISTORY_LENGTH 100) on the device.  The tracker registers
+ * against the newest pair (esvo_Tracking.cpp:241-247), the mapper observes the second newest pair that has a pose
+ * (esvo_Mapping.cpp:497-534): on one handle neither is "the last render", so the frames are kept by stamp and both pick theirs
+ * without a Time Surface crossing the bus.  Off by default; with the history off no other call changes in any way.
+ *
+ * Retained, once the history is on: every frame that becomes a camera's resident frame -- esvo_ts_render,
+ * esvo_ts_render_forward, both cameras of esvo_map_tick_resident -- and the frames given with esvo_ts_history_put, each under
+ * its stamp.  Host images handed to esvo_map_set_observation or esvo_track_set_current are NOT retained.  An entry is a stamp
+ * with up to two frames; it is complete when both cameras are present.  The reference's ExactTime synchroniser only ever
+ * inserts pairs, so esvo_map_set_observation_at and both select calls see complete pairs only; esvo_track_set_current_at
+ * needs the left frame only.
+ * Eviction is the reference's (timeSurfaceCallback, esvo_Mapping.cpp:757-761): the entry is inserted in stamp order, then the
+ * smallest stamps are erased while there are more than `length`.  A new stamp below every retained one on a full history is
+ * therefore not retained (the render itself succeeds).  With per-pixel queues (max_event_queue_len > 0) stamps may arrive in
+ * any order.
+ * Deviation: a stamp and camera that is retained already is OVERWRITTEN by a new frame; the reference's emplace keeps the
+ * first one, but a node cannot receive one stamp twice.
+ * esvo_reset empties the history (esvo_Mapping::reset, :764-804), the slots stay allocated; esvo_set_params leaves it alone.
+ * Every call below returns ESVO_ERR_STATE while the history is off, ESVO_ERR_INVALID_ARG for a NULL argument (where not
+ * stated otherwise) or a cam outside 0..1.  A stamp that is not retained -- or not complete where a pair is needed -- is
+ * ESVO_ERR_STATE with no change of state: the previous observation / current frame stays in place, and esvo_last_error names
+ * the stamp and the retained range.
+ * Not on band-sharded or tick-interleaved handles: esvo_ts_history_configure(length > 0) returns ESVO_ERR_UNSUPPORTED there,
+ * and esvo_shard_set_band / esvo_comm_init / esvo_comm_init_callbacks return ESVO_ERR_UNSUPPORTED on a handle with the history on
+ * (the band mode keeps esvo_comm_gather_ts).
+ * Threads: the calls belong to the mapper group, except esvo_track_set_current_at (tracker group) and esvo_ts_history_list /
+ * esvo_ts_history_select_observation, which any thread may call; esvo_ts_history_select takes no handle. */
+
+/* TS_HISTORY_LENGTH (esvo_Mapping.h / esvo_Tracking.h: 100): `length` pairs are retained; 0 = off (the default).  The
+ * slots -- length x 2 frames of W * H bytes, each starting on a multiple of 256 bytes -- are allocated here and freed by
+ * length = 0, a reconfiguration or esvo_destroy.  Reconfiguring empties the history. */
+int esvo_ts_history_configure(esvo_handle h, size_t length);
+/* TS_history_'s keys: the retained stamps in ascending order; cams[i]: bit 0 left present, bit 1 right present.  *n receives
+ * the count; t_ns and cams may be NULL (both NULL: count only), otherwise cap < count is ESVO_ERR_CAPACITY. */
+int esvo_ts_history_list(esvo_handle h, uint64_t* t_ns, uint8_t* cams, size_t cap, size_t* n);
+/* A retained frame copied out (W * H bytes) ... */
+int esvo_ts_history_get(esvo_handle h, uint64_t t_ns, int cam, uint8_t* out_mono8);
+/* ... and a host frame put in, as timeSurfaceCallback's TS_history_.emplace does (esvo_Mapping.cpp:737-761) for a
+ * Time-Surface node in another process: one upload on arrival instead of one per use. */
+int esvo_ts_history_put(esvo_handle h, uint64_t t_ns, int cam, const uint8_t* mono8);
+/* esvo_map_set_observation on the retained pair of that stamp (TS_obs_ = *it_end, esvo_Mapping.cpp:512-519): equal, bit for
+ * bit, to esvo_map_set_observation(h, t_ns, left, right, T_world_cam) with the host images of the two frames, SmoothTimeSurface
+ * included (the blur reads the slot directly, as it reads the resident frame). */
+int esvo_map_set_observation_at(esvo_handle h, uint64_t t_ns, const double T_world_cam[16]);
+/* esvo_track_set_current on the retained left frame of that stamp (curDataTransferring's TS_history_.rbegin(),
+ * esvo_Tracking.cpp:241-247, for the newest stamp): equal, bit for bit, to esvo_track_set_current(h, left, kernel_size) with
+ * the host image, kernel_size 0 or 5.  No host wait: the read queues behind the frame's store on the device. */
+int esvo_track_set_current_at(esvo_handle h, uint64_t t_ns, int kernel_size);
+/* dataTransferring's choice of TS_obs_ (esvo_Mapping.cpp:497-534; the same in esvo_MVStereo.cpp:559-576).  Host code, no
+ * handle: t_ns are the stamps of the complete pairs, ascending.  n <= 10: ESVO_AGAIN (:497, "to assure the
+ * esvo_time_surface node has been working").  The walk starts at the second newest stamp (:503, "in case that the tf is
+ * behind the most current TS") and goes down to the oldest inclusive; the newest is never taken.  initialization != 0
+ * (ESVO_System_Status_ == "INITIALIZATION"): the second newest, T_world_cam = identity, pose_fn is not called (may be NULL).
+ * Otherwise the first stamp for which pose_fn returns 1 (getPoseAt), with the pose it filled in.  Returns ESVO_OK and
+ * *index, or ESVO_AGAIN where the node returns false. */
+int esvo_ts_history_select(const uint64_t* t_ns, size_t n, int initialization, esvo_em_pose_fn pose_fn, void* user, size_t* index,
+                           double T_world_cam[16]);
+/* The same on the handle's retained complete pairs; *t_ns receives the chosen stamp (for esvo_map_set_observation_at).
+ * pose_fn runs on the calling thread with none of the handle's locks held. */
+int esvo_ts_history_select_observation(esvo_handle h, int initialization, esvo_em_pose_fn pose_fn, void* user, uint64_t* t_ns,
+                                       double T_world_cam[16]);
 
 /* ---- Outputs ------------------------------------------------------------------------ */
 

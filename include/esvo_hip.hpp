@@ -25,6 +25,7 @@
 #include <algorithm>
 #include <cmath>
 #include <cstdint>
+#include <functional>
 #include <memory>
 #include <stdexcept>
 #include <string>
@@ -109,6 +110,62 @@ class TimeSurface {
  private:
   ContextPtr ctx_;
   int cam_;
+};
+
+// TS_history_ of the mapper and tracker nodes (std::map<ros::Time, TimeSurfaceObservation>, TS_HISTORY_LENGTH pairs) kept on
+// the device: every frame createTimeSurfaceAtTime renders is retained under its stamp; DepthFusion::setObservationAt and
+// RegProblemLM::setCurrentAt pick theirs by stamp.  One per Context.
+class TimeSurfaceHistory {
+ public:
+  // pose(t_ns, T_world_cam) -> whether a pose is known at that stamp (getPoseAt)
+  using PoseLookup = std::function<bool(uint64_t, double*)>;
+  explicit TimeSurfaceHistory(ContextPtr ctx) : ctx_(std::move(ctx)) {}
+  // TS_HISTORY_LENGTH pairs are retained from here on; 0 switches the history off.  Empties it.
+  void configure(size_t TS_HISTORY_LENGTH) {
+    ctx_->check(esvo_ts_history_configure(ctx_->handle(), TS_HISTORY_LENGTH), "esvo_ts_history_configure");
+  }
+  // the retained stamps, ascending; cams (nullable): bit 0 left present, bit 1 right present
+  std::vector<uint64_t> stamps(std::vector<uint8_t>* cams = nullptr) const {
+    size_t n = 0;
+    ctx_->check(esvo_ts_history_list(ctx_->handle(), nullptr, nullptr, 0, &n), "esvo_ts_history_list");
+    std::vector<uint64_t> t(n);
+    std::vector<uint8_t> c(n);
+    if (n) ctx_->check(esvo_ts_history_list(ctx_->handle(), t.data(), c.data(), n, &n), "esvo_ts_history_list");
+    t.resize(n); c.resize(n);
+    if (cams) *cams = c;
+    return t;
+  }
+  void get(uint64_t t_ns, int cam, std::vector<uint8_t>& mono8) const {
+    mono8.resize((size_t)ctx_->width() * ctx_->height());
+    ctx_->check(esvo_ts_history_get(ctx_->handle(), t_ns, cam, mono8.data()), "esvo_ts_history_get");
+  }
+  // timeSurfaceCallback's emplace for a Time-Surface node in another process (esvo_Mapping.cpp:737-761)
+  void put(uint64_t t_ns, int cam, const uint8_t* mono8) {
+    ctx_->check(esvo_ts_history_put(ctx_->handle(), t_ns, cam, mono8), "esvo_ts_history_put");
+  }
+  // dataTransferring's choice of TS_obs_ (esvo_Mapping.cpp:497-534) among the retained complete pairs: false where the node
+  // returns false; otherwise obs.t_ns and obs.T_world_cam are filled in (TS_left / TS_right stay null: the frames are on the
+  // device, DepthFusion::setObservationAt takes them).  initialization: ESVO_System_Status_ == "INITIALIZATION".
+  bool selectObservation(bool initialization, const PoseLookup& pose, StampedTimeSurfaceObs& obs) const {
+    struct Tramp {
+      static int call(void* user, uint64_t t_ns, double T[16]) { return (*static_cast<const PoseLookup*>(user))(t_ns, T) ? 1 : 0; }
+    };
+    const bool have = static_cast<bool>(pose);
+    if (!initialization && !have) throw Error(ESVO_ERR_INVALID_ARG, "selectObservation: no pose lookup");
+    uint64_t t = 0;
+    double T[16];
+    const int rc = esvo_ts_history_select_observation(ctx_->handle(), initialization ? 1 : 0, have ? &Tramp::call : nullptr,
+                                                      const_cast<PoseLookup*>(&pose), &t, T);
+    if (rc == ESVO_AGAIN) return false;
+    ctx_->check(rc, "esvo_ts_history_select_observation");
+    obs.t_ns = t;
+    obs.TS_left = obs.TS_right = nullptr;
+    std::copy(T, T + 16, obs.T_world_cam);
+    return true;
+  }
+
+ private:
+  ContextPtr ctx_;
 };
 
 // esvo_core::core::EventBM
@@ -259,6 +316,11 @@ class DepthFusion {
     ctx_->check(esvo_map_push_disparity_frame(ctx_->handle(), dispMap, vEventsSGM.data(), vEventsSGM.size(), &n),
                 "esvo_map_push_disparity_frame");
     return n;
+  }
+  // TS_obs_ = the retained pair of that stamp (TimeSurfaceHistory; esvo_Mapping.cpp:512-519): what EventBM::createMatchProblem
+  // does with the host images of the pair, without the images leaving the device
+  void setObservationAt(uint64_t t_ns, const double T_world_cam[16]) {
+    ctx_->check(esvo_map_set_observation_at(ctx_->handle(), t_ns, T_world_cam), "esvo_map_set_observation_at");
   }
   // returns numFusionCount
   size_t update() {
@@ -678,6 +740,11 @@ class RegProblemLM {
     ctx_->check(esvo_track_set_current(ctx_->handle(), cur_TS_left, cfg_.kernelSize), "esvo_track_set_current");
     numBatches_ = std::max(numPoints_ / cfg_.BATCH_SIZE, (size_t)1);
     setStochasticSampling(0, numPoints_);
+  }
+  // the current frame = the retained left Time Surface of that stamp (TimeSurfaceHistory; curDataTransferring's
+  // TS_history_.rbegin(), esvo_Tracking.cpp:241-247): replaces the frame setProblem / setProblemFromMap set, keeps the reference
+  void setCurrentAt(uint64_t t_ns) {
+    ctx_->check(esvo_track_set_current_at(ctx_->handle(), t_ns, cfg_.kernelSize), "esvo_track_set_current_at");
   }
   void setStochasticSampling(size_t offset, size_t N) { offset_ = offset; count_ = N; }
   // operator(): fvec for the warp T_left_ref the caller derived from x; returns the number of values
