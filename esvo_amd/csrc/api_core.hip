@@ -33,6 +33,248 @@ int validate_params(const esvo_params_t* p, std::string& why) {
   return ESVO_OK;
 }
 
+// ---- esvo_create in steps (each returns a status; esvo_create destroys the half-built handle on the first that fails) ----------
+#define CK(call) do { hipError_t _e = (call); if (_e != hipSuccess) { g_create_error = std::string(#call) + ": " + hipGetErrorString(_e); return ESVO_ERR_HIP; } } while (0)
+
+// tiles of the fusion front (kernels_fuse.hip): FUSE_TILE x FUSE_TILE cells each
+size_t fuse_front_tiles(const esvo_context* h) { return (size_t)((h->W + FUSE_TILE - 1) / FUSE_TILE) * ((h->H + FUSE_TILE - 1) / FUSE_TILE); }
+
+// The device side of "as created": what esvo_create leaves behind, on the front stream, and esvo_reset puts back.  Everything else a
+// tick reads it has written before, or (d_clk, esvo_reset) is cleared where it is read.
+int zero_session_buffers(esvo_context* h, hipStream_t st) {
+  const size_t npx = (size_t)h->W * h->H;
+  for (int cam = 0; cam < 2; ++cam) {
+    HIPCHK(hipMemsetAsync(h->d_sae[cam], 0, sizeof(u64) * npx, st));
+    if (h->d_tsq[cam]) HIPCHK(hipMemsetAsync(h->d_tsq[cam], 0, sizeof(u64) * npx * (size_t)h->tsq_len, st));  // EventQueueMat semantics: a set of <= L keys per pixel, slot-major
+  }
+  HIPCHK(hipMemsetAsync(h->d_halo_viol, 0, sizeof(u32) * 2, st));
+  HIPCHK(hipMemsetAsync(h->d_map, 0, map_buffer_bytes(npx), st));
+  HIPCHK(hipMemsetAsync(h->d_map2, 0, map_buffer_bytes(npx), st));
+  HIPCHK(hipMemsetAsync(h->d_tile_count, 0, sizeof(u32) * fuse_front_tiles(h), st));  // zero between ticks: fuse_turn_kernel clears what was read
+  HIPCHK(hipMemsetAsync(h->d_fuse_ctr, 0, sizeof(u32) * 2112, st));
+  if (h->d_rank_kept) HIPCHK(hipMemsetAsync(h->d_rank_kept, 0, sizeof(u32) * esvo_context::SHARD_MAX_RANKS, st));  // (band mode: allocated by its configuration)
+  h->d_map_cur = h->d_map;
+  return ESVO_OK;
+}
+
+// every development switch the handle reads (common.hpp, esvo_dev_switch: only with ESVO_DEV_SWITCHES=1), one line each
+void read_dev_switches(esvo_context* h) {
+  const char* e;
+  if ((e = esvo_dev_switch("ESVO_LM_PAIR"))) h->lm_pair_forced = std::atoi(e) == 1 ? 1 : (std::atoi(e) == 0 ? 0 : -1);
+  if ((e = esvo_dev_switch("ESVO_LM_QUEUES"))) h->lm_queues = std::atoi(e) == 1 ? 1 : (std::atoi(e) == 2 ? 2 : 0);
+  if ((e = esvo_dev_switch("ESVO_TIMELINE"))) h->tl_on = std::atoi(e) != 0;
+  if ((e = esvo_dev_switch("ESVO_LOWLAT"))) h->lat_mode = std::atoi(e) != 0;
+  if ((e = esvo_dev_switch("ESVO_LOWLAT_TIMED_EVERY"))) h->lat_timed_every = std::max(1, std::atoi(e));
+  if ((e = esvo_dev_switch("ESVO_REG_SPARSE"))) h->reg_sparse_forced = std::atoi(e) != 0 ? 1 : 0;
+  if ((e = esvo_dev_switch("ESVO_PIPE_TIMED_EVERY"))) h->pipe_timed_every = std::max(1, std::atoi(e));
+  if ((e = esvo_dev_switch("ESVO_LOWLAT_MAX_EVENTS"))) h->lat_max_events = (u32)std::strtoul(e, nullptr, 10);
+  if (h->tsq_len > 0) h->tsq_tcap = (e = esvo_dev_switch("ESVO_TSQ_TILE_CAP")) ? (u32)std::max(1, std::atoi(e)) : 1024u;  // tests: force the overflow list
+  if (h->max_ev > LM_TWO_QUEUES_MAX_EVENTS && (e = esvo_dev_switch("ESVO_LM_ORDER"))) h->lm_order_on = std::atoi(e) != 0;  // (only where the order buffers exist)
+  if ((e = esvo_dev_switch("ESVO_BM_DEDUPE"))) h->bm_dedupe_on = std::atoi(e) != 0;
+  if ((e = esvo_dev_switch("ESVO_BM_DEDUPE_MIN"))) h->bm_dedupe_min = (u32)std::max(1L, std::atol(e));
+  if ((e = esvo_dev_switch("ESVO_CLK_PROBE"))) h->clk_probe = std::atoi(e) != 0;
+  h->n_pose_slots = (e = esvo_dev_switch("ESVO_POSE_SLOTS0")) ? (u32)std::max(1, std::atoi(e)) : 1024u;  // tests: a smaller first allocation (alloc_window_and_map)
+  if ((e = esvo_dev_switch("ESVO_FUSE_TILE_CAP"))) h->fuse_tile_cap = (u32)std::max(1L, std::atol(e));
+  if ((e = esvo_dev_switch("ESVO_FUSE_PMAX"))) h->fuse_pmax_plus1 = (u32)std::max(0L, std::atol(e)) + 1u;
+  if ((e = esvo_dev_switch("ESVO_FUSE_TILE_REC"))) h->fuse_tile_rec = (u32)std::max(1L, std::atol(e));
+  if ((e = esvo_dev_switch("ESVO_FUSE_LDS_CAP"))) h->fuse_lds_cap = (u32)std::max(0L, std::atol(e));
+}
+
+int create_streams(esvo_context* h) {
+  int prio_lo = 0, prio_hi = 0;  // numerically lower = higher priority
+  CK(hipDeviceGetStreamPriorityRange(&prio_lo, &prio_hi));
+  // Three stages on three streams share the chip.  The LM kernel is the bulk of the vector-ALU work and tolerates waiting
+  // (two dense waves per SIMD); the matching stage and the fusion stage are short, latency-bound kernels that run one wave
+  // per SIMD beside it.  They get the HIGH priority and the LM stream the LOWEST: whenever one of their waves is ready it
+  // issues, the LM waves fill every other slot.  Measured in round 3: 1.40 ms per tick against 1.70 ms with the LM stream
+  // high and the fusion stream low.  (Other priority assignments and a SPATIAL partition of the compute units by
+  // hipExtStreamCreateWithCUMask were measured in rounds 3-4 -- all slower, 1.5-4 ms for the partition; profiles/HISTORY.md.)
+  CK(hipStreamCreateWithPriority(&h->stream, hipStreamNonBlocking, prio_hi));
+  CK(hipStreamCreateWithPriority(&h->stream_b, hipStreamNonBlocking, prio_hi));
+  h->own_stream = true;
+  CK(hipStreamCreateWithPriority(&h->stream_l, hipStreamNonBlocking, prio_lo));
+  CK(hipStreamCreateWithPriority(&h->stream_l1, hipStreamNonBlocking, prio_lo));
+  CK(hipStreamCreateWithFlags(&h->stream_t, hipStreamNonBlocking));
+  CK(hipStreamCreateWithFlags(&h->stream_i, hipStreamNonBlocking));
+  return ESVO_OK;
+}
+
+// one camera: calibration -> device (the left camera's rectification table and mask, the fixed-point remap), then its Time Surface
+int alloc_camera(esvo_context* h, int cam, const esvo_calib_t* c) {
+  const size_t npx = (size_t)h->W * h->H;
+  if (cam == 0) {
+    CK(h->d_lut.alloc(npx));
+    CK(hipMemcpy(h->d_lut, c->rect_lut, sizeof(float2) * npx, hipMemcpyHostToDevice));
+    if (c->rect_mask) {
+      CK(h->d_mask.alloc(npx));
+      CK(hipMemcpy(h->d_mask, c->rect_mask, npx, hipMemcpyHostToDevice));
+    }
+  }
+  std::vector<int2> fm(npx);
+  for (size_t i = 0; i < npx; ++i) {  // OpenCV remap's INTER_BITS=5 coordinate quantisation (Appendix B.2)
+    fm[i].x = (int)std::nearbyintf(c->map_x[i] * 32.f);
+    fm[i].y = (int)std::nearbyintf(c->map_y[i] * 32.f);
+  }
+  CK(h->d_fixmap[cam].alloc(npx));
+  CK(hipMemcpy(h->d_fixmap[cam], fm.data(), sizeof(int2) * npx, hipMemcpyHostToDevice));
+  // per rectified row: the raw rows its bilinear taps reach (what a row band of the Time Surface needs of the SAE;
+  // esvo_shard_set_routing).  A tap outside the image reads the constant 0 and needs nothing.
+  h->fix_row_lo[cam].assign(h->H, h->H);
+  h->fix_row_hi[cam].assign(h->H, -1);
+  for (int y = 0; y < h->H; ++y)
+    for (int x = 0; x < h->W; ++x) {
+      const int2 m = fm[(size_t)y * h->W + x];
+      const int ix = m.x >> 5, iy = m.y >> 5, fx = m.x & 31, fy = m.y & 31;
+      if (ix + (fx ? 1 : 0) < 0 || ix >= h->W) continue;
+      const int lo = std::max(iy, 0), hi = std::min(iy + (fy ? 1 : 0), h->H - 1);
+      if (lo > hi) continue;
+      h->fix_row_lo[cam][y] = std::min(h->fix_row_lo[cam][y], lo);
+      h->fix_row_hi[cam][y] = std::max(h->fix_row_hi[cam][y], hi);
+    }
+  CK(h->d_sae[cam].alloc(npx));  // (the SAE and the queues are zeroed by zero_session_buffers)
+  if (h->tsq_len > 0) CK(h->d_tsq[cam].alloc(npx * (size_t)h->tsq_len));
+  CK(h->d_ts[cam].alloc(npx + 64));
+  for (int k = 0; k < 2; ++k) CK(h->d_obs2[k][cam].alloc(npx + 64));
+  h->d_obs[cam] = h->d_obs2[0][cam];
+  return ESVO_OK;
+}
+
+// what the two cameras share: the queues' tile lists, raw surfaces, event rings, the tick's pose tables
+int alloc_rings(esvo_context* h, const esvo_calib_t* left, const esvo_calib_t* right) {
+  const size_t npx = (size_t)h->W * h->H;
+  if (h->tsq_len > 0) {
+    const size_t tiles = (size_t)((h->W + 7) / 8) * ((h->H + 7) / 8);
+    CK(h->d_tsq_tcount.alloc(tiles)); CK(hipMemset(h->d_tsq_tcount, 0, sizeof(u32) * tiles));
+    CK(h->d_tsq_tlist.alloc(tiles * h->tsq_tcap));
+    CK(h->d_tsq_over.alloc((size_t)esvo_context::TSQ_ROUND));
+    CK(h->d_tsq_over_count.alloc(1));
+  }
+  CK(h->d_raw.alloc(npx + 64)); CK(h->d_raw1.alloc(npx + 64));
+  h->h_rect_lut[0].assign(left->rect_lut, left->rect_lut + 2 * npx);
+  if (right->rect_lut) h->h_rect_lut[1].assign(right->rect_lut, right->rect_lut + 2 * npx);
+  CK(h->d_obs_tmp.alloc(npx + 64));
+  h->ring_cap = (u64)std::max<int64_t>(h->prm.event_ring_capacity, 1024);
+  for (int cam = 0; cam < 2; ++cam) CK(h->d_ring[cam].alloc(h->ring_cap));
+  h->max_poses = (u32)std::max(h->prm.max_poses_per_tick, 2);
+  for (int k = 0; k < 2; ++k) CK(h->d_pose_T2[k].alloc((size_t)h->max_poses * 17));  // [T | toSec]
+  h->d_pose_T = h->d_pose_T2[0];
+  return ESVO_OK;
+}
+
+int alloc_tick_scratch(esvo_context* h) {
+  const size_t npx = (size_t)h->W * h->H, E = h->max_ev;
+  if (h->max_ev > 4000000u) FAIL(ESVO_ERR_CAPACITY, "max_events_per_tick too large (scan limit 4M)");
+  if (npx > 4000000u) FAIL(ESVO_ERR_CAPACITY, "image too large (scan limit 4M pixels)");
+  CK(h->d_tick_ev.alloc(E));
+  CK(h->d_match_slots.alloc(E));
+  CK(h->d_match_flags.alloc(E)); CK(h->d_match_prefix.alloc(E));
+  for (int k = 0; k < 2; ++k) CK(h->d_matches2[k].alloc(E));
+  h->d_matches = h->d_matches2[0];
+  // (scratch of the split launch: 7 x 16 doubles per match -- only where the launch can be used)
+  if (E >= LM_SPLIT_MIN_EVENTS) {
+    // The split LM launch (kernels_lm.hip, LmSplit) executes 10 % fewer vector instructions (3.47e8 against 3.85e8 per launch
+    // of the bench workload) but does not shorten the tick (1.40 against 1.38 ms): what it removes are the partially masked
+    // instructions of lockstep execution, and the tick is bound by the chip's throughput at its sustained f64 clock.  It is
+    // On the 1280x720 stress stream (4.9e5 events, 2.3e5 matches per tick: five times the waves) it does pay: 7.7 against
+    // 8.4 ms per tick (profiles/r03_split_launch_other_workloads.txt).  So: used for launches bounded by >= 400 000 events.
+    CK(h->d_lm_fvec0.alloc(E * 7 * 16)); CK(h->d_lm_fnorm0.alloc(E));
+    CK(h->d_lm_meta.alloc(E)); CK(h->d_lm_order.alloc(E));
+    CK(h->d_lm_hist.alloc(2 * 32 * 64));  // kernels_lm.hip: 2 x LM_SPLIT_STRIPES x LM_SPLIT_BINS
+    CK(hipMemset(h->d_lm_hist, 0, sizeof(u32) * 2 * 32 * 64));
+  }
+  if (E > LM_TWO_QUEUES_MAX_EVENTS) {  // (= LM_WIDE_MAX: launches above it take the narrow layout) the processing order, context.hpp
+    for (int k = 0; k < 2; ++k) { CK(h->d_lm_pix_order2[k].alloc(E)); CK(h->d_lm_sort_rows[k].alloc(E)); }
+    CK(h->d_lm_sort_hist.alloc(voxel_hist_words(E)));
+  }
+  if (h->bm_dedupe_on && E >= h->bm_dedupe_min) CK(h->d_bm_dedupe.alloc(npx + 4 + 2 * E));  // context.hpp: table | count | list | outcomes
+  // (two blocks, one per front parity: two LM launches in flight -- the two LM queues -- must not share the probe's scratch, where
+  //  a wave leaves its start stamps: a launch that read the other one's stamp added a wrapped difference to the sums)
+  CK(h->d_clk.alloc(2 * clk_words(h->max_ev)));
+  // All of it, once, so that no word is undefined; esvo_reset clears the CLK_SCRATCH sums at the head of each block only: the start
+  // stamps behind them are written by the wave that reads them back (kernels_lm.hip), in every launch
+  CK(hipMemset(h->d_clk, 0, sizeof(u64) * 2 * clk_words(h->max_ev)));
+  int khz = 0;  // rate of s_memrealtime (wall_clock64): the constant reference clock the probe divides by
+  if (hipDeviceGetAttribute(&khz, hipDeviceAttributeWallClockRate, h->device) != hipSuccess || khz <= 0) khz = 100000;
+  h->stats.clk_ref_khz = (uint32_t)khz;
+  for (int k = 0; k < 2; ++k) {
+    CK(h->d_pt_slots2[k].alloc(E));
+    CK(h->d_pt_flags2[k].alloc(E)); CK(h->d_pt_prefix2[k].alloc(E));
+    CK(h->d_scan_tmp_l2[k].alloc(scan_scratch_elems(std::max(E, npx)) + 8));
+  }
+  h->d_pt_slots = h->d_pt_slots2[0]; h->d_pt_flags = h->d_pt_flags2[0]; h->d_pt_prefix = h->d_pt_prefix2[0];
+  h->d_scan_tmp_l = h->d_scan_tmp_l2[0];
+  CK(h->d_pts_tmp.alloc(E));
+  for (int k = 0; k < 2; ++k) CK(h->d_stage[k].alloc(E));
+  for (int k = 0; k < 2; ++k) CK(h->d_counters2[k].alloc(CNT_ROW));
+  for (int k = 0; k < 2; ++k) CK(hipMemset(h->d_counters2[k], 0, sizeof(u32) * CNT_ROW));
+  h->d_counters = h->d_counters2[0];
+  CK(h->h_counters.alloc(CNT_ROW * 2));
+  std::memset(h->h_counters, 0, sizeof(u32) * CNT_ROW * 2);
+  CK(h->h_pin.alloc(2 * ((size_t)h->max_poses * 17 + 16)));
+  CK(h->d_scan_tmp.alloc(scan_scratch_elems(std::max(E, npx)) + 8)); CK(h->d_scan_tmp_b.alloc(scan_scratch_elems(std::max(E, npx)) + 8));
+  CK(h->d_cnt_b.alloc(CNTB_ROW)); CK(hipMemset(h->d_cnt_b, 0, sizeof(u32) * CNTB_ROW));
+  CK(h->h_cnt_b.alloc(CNTB_ROW * CNTB_ROWS));  // (common.hpp: CNTB_ROW_*)
+  std::memset(h->h_cnt_b, 0, sizeof(u32) * CNTB_ROW * CNTB_ROWS);
+  CK(h->d_halo_viol.alloc(2));
+  return ESVO_OK;
+}
+
+int alloc_window_and_map(esvo_context* h) {
+  const size_t npx = (size_t)h->W * h->H, E = h->max_ev;
+  h->win_cap = (u32)std::max<int64_t>((int64_t)h->prm.max_window_points, (int64_t)E) + 2 * (u32)E;
+  CK(h->d_win.alloc(h->win_cap));
+  // CONST_POINTS keeps frames until their points exceed 1.5 maxNumFusionPoints (esvo_Mapping.cpp:346-353): every non-empty
+  // frame holds at least one point, which bounds their number; empty frames are run-length records (context.hpp)
+  h->max_frames = (u32)std::max(h->prm.max_fusion_frames + 2, 512);
+  if (h->prm.fusion_strategy == ESVO_FUSION_CONST_POINTS)
+    h->max_frames = std::max(h->max_frames, (u32)(1.5 * h->prm.max_fusion_points) + 4u);
+  // pose-table slots of the window's non-empty frames: max_frames + 1 in the worst case (CONST_POINTS with one point per
+  // frame: 1 GB of tables at 20 000 points x 256 poses), a handful in practice -- allocated for 1024 frames (read_dev_switches) and
+  // doubled on demand (alloc_pose_slot, api_window.hip)
+  h->slot_used.assign(h->max_frames + 1, 0);
+  h->n_pose_slots = std::min<u32>(h->max_frames + 1, h->n_pose_slots);
+  CK(h->d_frame_pose_T.alloc((size_t)h->n_pose_slots * h->max_poses * 16));
+  CK(h->d_fr_table.alloc(2 * (3 * (size_t)h->max_frames + 1))); CK(h->h_fr_table.alloc(2 * (3 * (size_t)h->max_frames + 1)));
+  // map
+  CK(h->d_prop.alloc(h->win_cap));
+  const size_t n_tiles = fuse_front_tiles(h);
+  CK(h->d_tile_pts.alloc(n_tiles * h->fuse_tile_cap)); CK(h->d_over_pts.alloc(h->win_cap));
+  CK(h->d_tile_count.alloc(n_tiles));
+  CK(h->d_cell_count.alloc(npx)); CK(h->d_cell_offset.alloc(npx));
+  h->fuse_slice_cap = (u32)((n_tiles + 63) / 64) * FUSE_TILE * FUSE_TILE;   // the cells of the tiles t with t % 64 == slice
+  CK(h->d_cell_list.alloc((size_t)16 * 64 * h->fuse_slice_cap));
+  CK(h->d_fuse_ctr.alloc(2112 + 64));
+  // the 64 words behind the counters (common.hpp: FUSE_CTR_*, the last one at 2081) are padding no kernel addresses: zeroed here,
+  // once, so that no word is undefined; the counters themselves by zero_session_buffers
+  CK(hipMemset(h->d_fuse_ctr + 2112, 0, sizeof(u32) * 64));
+  CK(h->d_rec_ids.alloc(n_tiles * h->fuse_tile_rec + (size_t)h->win_cap * 9));
+  for (int k = 0; k < 2; ++k) CK(h->d_map_mem[k].alloc(map_buffer_bytes(npx)));  // cells + their dense flags (common.hpp: map_flags)
+  h->d_map = reinterpret_cast<MapCell*>(h->d_map_mem[0].get()); h->d_map2 = reinterpret_cast<MapCell*>(h->d_map_mem[1].get());
+  CK(h->d_owner_max.alloc(npx)); CK(h->d_owner_min.alloc(npx));
+  CK(h->d_own_w.alloc(E)); CK(h->d_lkeep.alloc(E));
+  h->codes_bytes = (E + 7) / 8 * 8;
+  CK(h->d_codes.alloc(h->codes_bytes));
+  CK(h->d_sel.alloc(E));
+  CK(h->d_evmap.alloc(npx + 64));
+  CK(h->d_reg_ab.alloc(npx)); CK(h->d_reg_cd.alloc(npx));
+  CK(h->d_exp_flags.alloc(npx)); CK(h->d_exp_prefix.alloc(npx));
+  CK(h->d_export.alloc(npx)); CK(h->d_export_cell.alloc(npx));
+  return ESVO_OK;
+}
+
+int create_events_and_pools(esvo_context* h) {
+  for (int i = 0; i < EV_N; ++i) CK(hipEventCreate(&h->evt[i]));
+  if (h->tl_on) { CK(h->tl_ref.create()); CK(hipEventRecord(h->tl_ref, h->stream)); CK(hipEventSynchronize(h->tl_ref)); }
+  h->evt_ok = true;
+  CK(h->evt_trk_read.create(hipEventDisableTiming));
+  for (int cam = 0; cam < 2; ++cam) CK(h->evt_ingest[cam].create(hipEventDisableTiming));
+  CK(h->h_pose_pool.alloc(16 * (size_t)h->max_poses * esvo_context::POSE_POOL));
+  for (int i = 0; i < esvo_context::POSE_POOL; ++i) CK(h->pool_evt[i].create());
+  for (int i = 0; i < 16; ++i) h->T_world_obs[i] = h->T_world_frame[i] = (i % 5 == 0) ? 1.0 : 0.0;
+  return ESVO_OK;
+}
+#undef CK
+
 }  // namespace
 
 namespace esvo_host {
@@ -123,7 +365,6 @@ int esvo_create(const esvo_params_t* params, const esvo_calib_t* left, const esv
   h->prm = *params;
   h->device = device;
   h->W = left->width; h->H = left->height;
-  const size_t npx = (size_t)h->W * h->H;
   std::memset(&h->stats, 0, sizeof(h->stats));
   std::memcpy(h->dp.camL.P, left->P, sizeof(double) * 12);
   std::memcpy(h->dp.camR.P, right->P, sizeof(double) * 12);
@@ -137,235 +378,19 @@ int esvo_create(const esvo_params_t* params, const esvo_calib_t* left, const esv
   h->dp.cband_y0 = 0; h->dp.cband_y1 = h->H;
   h->dp.ev_shard = 0; h->dp.ev_nshards = 1;
   fill_dev_params(h);
-
-#define CK(call) do { hipError_t _e = (call); if (_e != hipSuccess) { g_create_error = std::string(#call) + ": " + hipGetErrorString(_e); esvo_destroy(h); return ESVO_ERR_HIP; } } while (0)
-  {
-    int prio_lo = 0, prio_hi = 0;  // numerically lower = higher priority
-    CK(hipDeviceGetStreamPriorityRange(&prio_lo, &prio_hi));
-    // Three stages on three streams share the chip.  The LM kernel is the bulk of the vector-ALU work and tolerates waiting
-    // (two dense waves per SIMD); the matching stage and the fusion stage are short, latency-bound kernels that run one wave
-    // per SIMD beside it.  They get the HIGH priority and the LM stream the LOWEST: whenever one of their waves is ready it
-    // issues, the LM waves fill every other slot.  Measured in round 3: 1.40 ms per tick against 1.70 ms with the LM stream
-    // high and the fusion stream low.  (Other priority assignments and a SPATIAL partition of the compute units by
-    // hipExtStreamCreateWithCUMask were measured in rounds 3-4 -- all slower, 1.5-4 ms for the partition; profiles/HISTORY.md.)
-    CK(hipStreamCreateWithPriority(&h->stream, hipStreamNonBlocking, prio_hi));
-    CK(hipStreamCreateWithPriority(&h->stream_b, hipStreamNonBlocking, prio_hi));
-    h->own_stream = true;
-    CK(hipStreamCreateWithPriority(&h->stream_l, hipStreamNonBlocking, prio_lo));
-    CK(hipStreamCreateWithPriority(&h->stream_l1, hipStreamNonBlocking, prio_lo));
-    if (const char* ep = esvo_dev_switch("ESVO_LM_PAIR")) h->lm_pair_forced = std::atoi(ep) == 1 ? 1 : (std::atoi(ep) == 0 ? 0 : -1);
-    if (const char* eq = esvo_dev_switch("ESVO_LM_QUEUES")) h->lm_queues = std::atoi(eq) == 1 ? 1 : (std::atoi(eq) == 2 ? 2 : 0);
-  }
-  if (const char* et = esvo_dev_switch("ESVO_TIMELINE")) h->tl_on = std::atoi(et) != 0;
-  if (const char* el = esvo_dev_switch("ESVO_LOWLAT")) h->lat_mode = std::atoi(el) != 0;
-  if (const char* el = esvo_dev_switch("ESVO_LOWLAT_TIMED_EVERY")) h->lat_timed_every = std::max(1, std::atoi(el));
-  if (const char* el = esvo_dev_switch("ESVO_REG_SPARSE")) h->reg_sparse_forced = std::atoi(el) != 0 ? 1 : 0;
-  if (const char* el = esvo_dev_switch("ESVO_PIPE_TIMED_EVERY")) h->pipe_timed_every = std::max(1, std::atoi(el));
-  if (const char* el = esvo_dev_switch("ESVO_LOWLAT_MAX_EVENTS")) h->lat_max_events = (u32)std::strtoul(el, nullptr, 10);
-  CK(hipStreamCreateWithFlags(&h->stream_t, hipStreamNonBlocking));
-  CK(hipStreamCreateWithFlags(&h->stream_i, hipStreamNonBlocking));
-  // calibration -> device
-  CK(h->d_lut.alloc(npx));
-  CK(hipMemcpy(h->d_lut, left->rect_lut, sizeof(float2) * npx, hipMemcpyHostToDevice));
-  if (left->rect_mask) {
-    CK(h->d_mask.alloc(npx));
-    CK(hipMemcpy(h->d_mask, left->rect_mask, npx, hipMemcpyHostToDevice));
-  }
-  for (int cam = 0; cam < 2; ++cam) {
-    const esvo_calib_t* c = cam ? right : left;
-    std::vector<int2> fm(npx);
-    for (size_t i = 0; i < npx; ++i) {  // OpenCV remap's INTER_BITS=5 coordinate quantisation (Appendix B.2)
-      fm[i].x = (int)std::nearbyintf(c->map_x[i] * 32.f);
-      fm[i].y = (int)std::nearbyintf(c->map_y[i] * 32.f);
-    }
-    CK(h->d_fixmap[cam].alloc(npx));
-    CK(hipMemcpy(h->d_fixmap[cam], fm.data(), sizeof(int2) * npx, hipMemcpyHostToDevice));
-    // per rectified row: the raw rows its bilinear taps reach (what a row band of the Time Surface needs of the SAE;
-    // esvo_shard_set_routing).  A tap outside the image reads the constant 0 and needs nothing.
-    h->fix_row_lo[cam].assign(h->H, h->H);
-    h->fix_row_hi[cam].assign(h->H, -1);
-    for (int y = 0; y < h->H; ++y)
-      for (int x = 0; x < h->W; ++x) {
-        const int2 m = fm[(size_t)y * h->W + x];
-        const int ix = m.x >> 5, iy = m.y >> 5, fx = m.x & 31, fy = m.y & 31;
-        if (ix + (fx ? 1 : 0) < 0 || ix >= h->W) continue;
-        const int lo = std::max(iy, 0), hi = std::min(iy + (fy ? 1 : 0), h->H - 1);
-        if (lo > hi) continue;
-        h->fix_row_lo[cam][y] = std::min(h->fix_row_lo[cam][y], lo);
-        h->fix_row_hi[cam][y] = std::max(h->fix_row_hi[cam][y], hi);
-      }
-    CK(h->d_sae[cam].alloc(npx));
-    CK(hipMemset(h->d_sae[cam], 0, sizeof(u64) * npx));
-    if (params->max_event_queue_len > 0) {  // EventQueueMat semantics: a set of <= L keys per pixel, slot-major
-      CK(h->d_tsq[cam].alloc(npx * (size_t)params->max_event_queue_len));
-      CK(hipMemset(h->d_tsq[cam], 0, sizeof(u64) * npx * (size_t)params->max_event_queue_len));
-    }
-    CK(h->d_ts[cam].alloc(npx + 64));
-    CK(h->d_obs2[0][cam].alloc(npx + 64));
-    CK(h->d_obs2[1][cam].alloc(npx + 64));
-    h->d_obs[cam] = h->d_obs2[0][cam];
-  }
-  if (params->max_event_queue_len > 0) {
-    h->tsq_len = params->max_event_queue_len;
-    const size_t tiles = (size_t)((h->W + 7) / 8) * ((h->H + 7) / 8);
-    h->tsq_tcap = 1024;
-    if (const char* e = esvo_dev_switch("ESVO_TSQ_TILE_CAP")) h->tsq_tcap = (u32)std::max(1, std::atoi(e));  // tests: force the overflow list
-    CK(h->d_tsq_tcount.alloc(tiles));
-    CK(hipMemset(h->d_tsq_tcount, 0, sizeof(u32) * tiles));
-    CK(h->d_tsq_tlist.alloc(tiles * h->tsq_tcap));
-    CK(h->d_tsq_over.alloc((size_t)esvo_context::TSQ_ROUND));
-    CK(h->d_tsq_over_count.alloc(1));
-  }
-  CK(h->d_raw.alloc(npx + 64));
-  CK(h->d_raw1.alloc(npx + 64));
-  h->h_rect_lut[0].assign(left->rect_lut, left->rect_lut + 2 * npx);
-  if (right->rect_lut) h->h_rect_lut[1].assign(right->rect_lut, right->rect_lut + 2 * npx);
-  CK(h->d_obs_tmp.alloc(npx + 64));
-  h->ring_cap = (u64)std::max<int64_t>(params->event_ring_capacity, 1024);
-  for (int cam = 0; cam < 2; ++cam) CK(h->d_ring[cam].alloc(h->ring_cap));
-  h->max_poses = (u32)std::max(params->max_poses_per_tick, 2);
-  CK(h->d_pose_T2[0].alloc((size_t)h->max_poses * 17));  // [T | toSec]
-  CK(h->d_pose_T2[1].alloc((size_t)h->max_poses * 17));
-  h->d_pose_T = h->d_pose_T2[0];
+  h->tsq_len = params->max_event_queue_len;  // (0: one stamp per pixel)
   // + 1: the SGM bootstrap selects up to PROCESS_EVENT_NUM + 1 events (esvo_Mapping.cpp:547: `size() <= PROCESS_EVENT_NUM_`)
   h->max_ev = (u32)std::max(params->max_events_per_tick, params->process_event_num) + 1u;
-  if (h->max_ev > 4000000u) { g_create_error = "max_events_per_tick too large (scan limit 4M)"; esvo_destroy(h); return ESVO_ERR_CAPACITY; }
-  if (npx > 4000000u) { g_create_error = "image too large (scan limit 4M pixels)"; esvo_destroy(h); return ESVO_ERR_CAPACITY; }
-  const size_t E = h->max_ev;
-  CK(h->d_tick_ev.alloc(E));
-  CK(h->d_match_slots.alloc(E));
-  CK(h->d_match_flags.alloc(E));
-  CK(h->d_match_prefix.alloc(E));
-  CK(h->d_matches2[0].alloc(E));
-  CK(h->d_matches2[1].alloc(E));
-  h->d_matches = h->d_matches2[0];
-  // (scratch of the split launch: 7 x 16 doubles per match -- only where the launch can be used)
-  if (E >= LM_SPLIT_MIN_EVENTS) {
-    // The split LM launch (kernels_lm.hip, LmSplit) executes 10 % fewer vector instructions (3.47e8 against 3.85e8 per launch
-    // of the bench workload) but does not shorten the tick (1.40 against 1.38 ms): what it removes are the partially masked
-    // instructions of lockstep execution, and the tick is bound by the chip's throughput at its sustained f64 clock.  It is
-    // On the 1280x720 stress stream (4.9e5 events, 2.3e5 matches per tick: five times the waves) it does pay: 7.7 against
-    // 8.4 ms per tick (profiles/r03_split_launch_other_workloads.txt).  So: used for launches bounded by >= 400 000 events.
-    CK(h->d_lm_fvec0.alloc(E * 7 * 16));
-    CK(h->d_lm_fnorm0.alloc(E));
-    CK(h->d_lm_meta.alloc(E));
-    CK(h->d_lm_order.alloc(E));
-    CK(h->d_lm_hist.alloc(2 * 32 * 64));  // kernels_lm.hip: 2 x LM_SPLIT_STRIPES x LM_SPLIT_BINS
-    CK(hipMemset(h->d_lm_hist, 0, sizeof(u32) * 2 * 32 * 64));
-  }
-  if (E > LM_TWO_QUEUES_MAX_EVENTS) {  // (= LM_WIDE_MAX: launches above it take the narrow layout) the processing order, context.hpp
-    for (int k = 0; k < 2; ++k) {
-      CK(h->d_lm_pix_order2[k].alloc(E));
-      CK(h->d_lm_sort_rows[k].alloc(E));
-    }
-    CK(h->d_lm_sort_hist.alloc(voxel_hist_words(E)));
-    if (const char* eo = esvo_dev_switch("ESVO_LM_ORDER")) h->lm_order_on = std::atoi(eo) != 0;
-  }
-  if (const char* ed = esvo_dev_switch("ESVO_BM_DEDUPE")) h->bm_dedupe_on = std::atoi(ed) != 0;
-  if (const char* em = esvo_dev_switch("ESVO_BM_DEDUPE_MIN")) h->bm_dedupe_min = (u32)std::max(1L, std::atol(em));
-  if (h->bm_dedupe_on && E >= h->bm_dedupe_min) CK(h->d_bm_dedupe.alloc(npx + 4 + 2 * E));  // context.hpp: table | count | list | outcomes
-  // (two blocks, one per front parity: two LM launches in flight -- the two LM queues -- must not share the probe's scratch, where
-  //  a wave leaves its start stamps: a launch that read the other one's stamp added a wrapped difference to the sums)
-  CK(h->d_clk.alloc(2 * clk_words(h->max_ev)));
-  CK(hipMemset(h->d_clk, 0, sizeof(u64) * 2 * clk_words(h->max_ev)));
-  if (const char* ec = esvo_dev_switch("ESVO_CLK_PROBE")) h->clk_probe = std::atoi(ec) != 0;
-  {
-    int khz = 0;  // rate of s_memrealtime (wall_clock64): the constant reference clock the probe divides by
-    if (hipDeviceGetAttribute(&khz, hipDeviceAttributeWallClockRate, device) != hipSuccess || khz <= 0) khz = 100000;
-    h->stats.clk_ref_khz = (uint32_t)khz;
-  }
-  for (int k = 0; k < 2; ++k) {
-    CK(h->d_pt_slots2[k].alloc(E));
-    CK(h->d_pt_flags2[k].alloc(E));
-    CK(h->d_pt_prefix2[k].alloc(E));
-    CK(h->d_scan_tmp_l2[k].alloc(scan_scratch_elems(std::max(E, npx)) + 8));
-  }
-  h->d_pt_slots = h->d_pt_slots2[0]; h->d_pt_flags = h->d_pt_flags2[0]; h->d_pt_prefix = h->d_pt_prefix2[0];
-  h->d_scan_tmp_l = h->d_scan_tmp_l2[0];
-  CK(h->d_pts_tmp.alloc(E));
-  CK(h->d_stage[0].alloc(E));
-  CK(h->d_stage[1].alloc(E));
-  CK(h->d_counters2[0].alloc(CNT_ROW));
-  CK(h->d_counters2[1].alloc(CNT_ROW));
-  CK(hipMemset(h->d_counters2[0], 0, sizeof(u32) * CNT_ROW));
-  CK(hipMemset(h->d_counters2[1], 0, sizeof(u32) * CNT_ROW));
-  h->d_counters = h->d_counters2[0];
-  CK(h->h_counters.alloc(CNT_ROW * 2));
-  std::memset(h->h_counters, 0, sizeof(u32) * CNT_ROW * 2);
-  CK(h->h_pin.alloc(2 * ((size_t)h->max_poses * 17 + 16)));
-  CK(h->d_scan_tmp.alloc(scan_scratch_elems(std::max(E, npx)) + 8));
-  CK(h->d_scan_tmp_b.alloc(scan_scratch_elems(std::max(E, npx)) + 8));
-  CK(h->d_cnt_b.alloc(CNTB_ROW));
-  CK(hipMemset(h->d_cnt_b, 0, sizeof(u32) * CNTB_ROW));
-  CK(h->h_cnt_b.alloc(CNTB_ROW * CNTB_ROWS));  // (common.hpp: CNTB_ROW_*)
-  std::memset(h->h_cnt_b, 0, sizeof(u32) * CNTB_ROW * CNTB_ROWS);
-  CK(h->d_halo_viol.alloc(2));
-  CK(hipMemset(h->d_halo_viol, 0, sizeof(u32) * 2));
-  // fusion window
-  h->win_cap = (u32)std::max<int64_t>((int64_t)params->max_window_points, (int64_t)E) + 2 * (u32)E;
-  CK(h->d_win.alloc(h->win_cap));
-  // CONST_POINTS keeps frames until their points exceed 1.5 maxNumFusionPoints (esvo_Mapping.cpp:346-353): every non-empty
-  // frame holds at least one point, which bounds their number; empty frames are run-length records (context.hpp)
-  h->max_frames = (u32)std::max(params->max_fusion_frames + 2, 512);
-  if (params->fusion_strategy == ESVO_FUSION_CONST_POINTS)
-    h->max_frames = std::max(h->max_frames, (u32)(1.5 * params->max_fusion_points) + 4u);
-  // pose-table slots of the window's non-empty frames: max_frames + 1 in the worst case (CONST_POINTS with one point per
-  // frame: 1 GB of tables at 20 000 points x 256 poses), a handful in practice -- allocated for 1024 frames and doubled on
-  // demand (alloc_pose_slot, api_window.hip).  ESVO_POSE_SLOTS0 (tests): a smaller first allocation.
-  h->slot_used.assign(h->max_frames + 1, 0);
-  h->n_pose_slots = std::min<u32>(h->max_frames + 1, 1024u);
-  if (const char* e0 = esvo_dev_switch("ESVO_POSE_SLOTS0")) h->n_pose_slots = std::min<u32>(h->max_frames + 1, (u32)std::max(1, std::atoi(e0)));
-  CK(h->d_frame_pose_T.alloc((size_t)h->n_pose_slots * h->max_poses * 16));
-  CK(h->d_fr_table.alloc(2 * (3 * (size_t)h->max_frames + 1)));
-  CK(h->h_fr_table.alloc(2 * (3 * (size_t)h->max_frames + 1)));
-  // map
-  CK(h->d_prop.alloc(h->win_cap));
-  {  // the fusion front (kernels_fuse.hip): FUSE_TILE x FUSE_TILE-cell tiles
-    const size_t n_tiles = (size_t)((h->W + FUSE_TILE - 1) / FUSE_TILE) * ((h->H + FUSE_TILE - 1) / FUSE_TILE);
-    if (const char* et = esvo_dev_switch("ESVO_FUSE_TILE_CAP")) h->fuse_tile_cap = (u32)std::max(1L, std::atol(et));
-    if (const char* ep = esvo_dev_switch("ESVO_FUSE_PMAX")) h->fuse_pmax_plus1 = (u32)std::max(0L, std::atol(ep)) + 1u;
-    CK(h->d_tile_pts.alloc(n_tiles * h->fuse_tile_cap));
-    CK(h->d_over_pts.alloc(h->win_cap));
-    CK(h->d_tile_count.alloc(n_tiles));
-    CK(h->d_cell_count.alloc(npx));
-    CK(h->d_cell_offset.alloc(npx));
-    h->fuse_slice_cap = (u32)((n_tiles + 63) / 64) * FUSE_TILE * FUSE_TILE;   // the cells of the tiles t with t % 64 == slice
-    CK(h->d_cell_list.alloc((size_t)16 * 64 * h->fuse_slice_cap));
-    CK(h->d_fuse_ctr.alloc(2112 + 64));
-    CK(hipMemset(h->d_tile_count, 0, sizeof(u32) * n_tiles));  // zero between ticks: fuse_turn_kernel clears what was read
-    CK(hipMemset(h->d_fuse_ctr, 0, sizeof(u32) * (2112 + 64)));
-    if (const char* er = esvo_dev_switch("ESVO_FUSE_TILE_REC")) h->fuse_tile_rec = (u32)std::max(1L, std::atol(er));
-    CK(h->d_rec_ids.alloc(n_tiles * h->fuse_tile_rec + (size_t)h->win_cap * 9));
-  }
-  if (const char* ef = esvo_dev_switch("ESVO_FUSE_LDS_CAP")) h->fuse_lds_cap = (u32)std::max(0L, std::atol(ef));
-  for (int k = 0; k < 2; ++k) CK(h->d_map_mem[k].alloc(map_buffer_bytes(npx)));  // cells + their dense flags (common.hpp: map_flags)
-  h->d_map = reinterpret_cast<MapCell*>(h->d_map_mem[0].get()); h->d_map2 = reinterpret_cast<MapCell*>(h->d_map_mem[1].get());
-  CK(hipMemset(h->d_map, 0, map_buffer_bytes(npx)));
-  CK(hipMemset(h->d_map2, 0, map_buffer_bytes(npx)));
-  h->d_map_cur = h->d_map;
-  CK(h->d_owner_max.alloc(npx));
-  CK(h->d_owner_min.alloc(npx));
-  CK(h->d_own_w.alloc(E));
-  CK(h->d_lkeep.alloc(E));
-  h->codes_bytes = (E + 7) / 8 * 8;
-  CK(h->d_codes.alloc(h->codes_bytes));
-  CK(h->d_sel.alloc(E));
-  CK(h->d_evmap.alloc(npx + 64));
-  CK(h->d_reg_ab.alloc(npx));
-  CK(h->d_reg_cd.alloc(npx));
-  CK(h->d_exp_flags.alloc(npx));
-  CK(h->d_exp_prefix.alloc(npx));
-  CK(h->d_export.alloc(npx));
-  CK(h->d_export_cell.alloc(npx));
-  for (int i = 0; i < EV_N; ++i) CK(hipEventCreate(&h->evt[i]));
-  if (h->tl_on) { CK(h->tl_ref.create()); CK(hipEventRecord(h->tl_ref, h->stream)); CK(hipEventSynchronize(h->tl_ref)); }
-  h->evt_ok = true;
-  CK(h->evt_trk_read.create(hipEventDisableTiming));
-  for (int cam = 0; cam < 2; ++cam) CK(h->evt_ingest[cam].create(hipEventDisableTiming));
-  CK(h->h_pose_pool.alloc(16 * (size_t)h->max_poses * esvo_context::POSE_POOL));
-  for (int i = 0; i < esvo_context::POSE_POOL; ++i) CK(h->pool_evt[i].create());
-  for (int i = 0; i < 16; ++i) h->T_world_obs[i] = h->T_world_frame[i] = (i % 5 == 0) ? 1.0 : 0.0;
-#undef CK
+  read_dev_switches(h);
+  int rc = create_streams(h);
+  for (int cam = 0; cam < 2 && !rc; ++cam) rc = alloc_camera(h, cam, cam ? right : left);
+  if (!rc) rc = alloc_rings(h, left, right);
+  if (!rc) rc = alloc_tick_scratch(h);
+  if (!rc) rc = alloc_window_and_map(h);
+  if (!rc) rc = create_events_and_pools(h);
+  if (!rc) rc = zero_session_buffers(h, h->stream);
+  if (!rc && hipStreamSynchronize(h->stream) != hipSuccess) { g_create_error = "draining the front stream failed"; rc = ESVO_ERR_HIP; }
+  if (rc) { esvo_destroy(h); return rc; }
   *out = h;
   return ESVO_OK;
 }
@@ -391,81 +416,36 @@ int esvo_destroy(esvo_handle h) {
 int esvo_reset(esvo_handle h) {
   if (!h) return ESVO_ERR_INVALID_ARG;
   API_LOCK(h);
-  // a reset excludes the other two groups as well: pushers in flight finish first, the tracker's images go
+  // a reset excludes the other two groups as well: pushers in flight finish first (the tracker's images and reference stay:
+  // context.hpp, "survives a reset")
   std::lock_guard<std::mutex> lp0(h->mu_push[0]), lp1(h->mu_push[1]), ltk(h->mu_track), lts(h->mu_ts), lr(h->mu_ring), lcl(h->mu_cloud);
   HIPCHK(hipSetDevice(h->device));
   { int rcp = flush_pending_tick(h); if (rcp) return rcp; }
-  const size_t npx = (size_t)h->W * h->H;
   HIPCHK(hipStreamSynchronize(h->stream));
   HIPCHK(hipStreamSynchronize(h->stream_l)); HIPCHK(hipStreamSynchronize(h->stream_l1));
   HIPCHK(hipStreamSynchronize(h->stream_b));
   HIPCHK(hipStreamSynchronize(h->stream_t));
   HIPCHK(hipStreamSynchronize(h->stream_i));
   comm_reset(h);  // (drains the exchange stream of a handle with a communicator)
-  for (int cam = 0; cam < 2; ++cam) {
-    HIPCHK(hipMemsetAsync(h->d_sae[cam], 0, sizeof(u64) * npx, h->stream));
-    if (h->d_tsq[cam]) HIPCHK(hipMemsetAsync(h->d_tsq[cam], 0, sizeof(u64) * npx * (size_t)h->tsq_len, h->stream));
-    h->ts_host[cam].clear();
-    h->ring_base[cam] = h->ring_next[cam] = h->ring_reserved[cam] = h->scattered[cam] = 0;
-    h->scatter_pending_lo[cam] = ~0ull;
-    h->ingest_pending[cam] = false;
-    h->ts_valid[cam] = false;
-    h->last_stamp[cam] = 0;
-    h->tsq_dup[cam].clear();
-  }
-  h->glob_ts.clear();
-  h->kept_g.clear();
-  h->own_before.clear();
-  h->own_total = 0;
-  h->glob_base = 0;
-  h->halo_error = false;
-  h->dn_pending = false;
-  h->resync = esvo_context::Resync();
-  HIPCHK(hipMemsetAsync(h->d_halo_viol, 0, sizeof(u32) * 2, h->stream));
+  // the session state (context.hpp): what is declared in these structs, and nothing else, starts again
+  static_cast<IngestSession&>(*h) = IngestSession{};
+  static_cast<TsSession&>(*h) = TsSession{};
+  static_cast<SchedSession&>(*h) = SchedSession{};
+  static_cast<MapSession&>(*h) = MapSession{};
+  static_cast<CloudSession&>(*h) = CloudSession{};  // (every stream was drained above: no gather is in flight)
+  // ... and what no default initialiser can say
+  std::fill(h->slot_used.begin(), h->slot_used.end(), 0);  // (its size is fixed at esvo_create)
   std::memset(h->h_cnt_b + CNTB_ROW * CNTB_ROW_HALO, 0, sizeof(u32) * CNTB_ROW);
-  h->sh_first = 0;
-  h->sh_first_prev = 0;
-  h->trk_read_pending = false;
   hist_clear(h);  // esvo_Mapping::reset clears TS_history_ (:764-804); the slots stay allocated
-  h->ema_lm_ms = h->ema_back_ms = 0.f;
-  h->lm_two_on = false;
-  std::memset(h->lm_pair_ms, 0, sizeof(h->lm_pair_ms));
-  h->lm_pair_n[0] = h->lm_pair_n[1] = 0u;
-  h->lm_pair_decisions = 0;
-  h->lm_pair_current = -1;
-  h->sgm_disp_valid = false;
-  h->sgm_stats = esvo_sgm_stats_t{};
-  h->frames.clear();
-  h->n_window_frames = 0;
-  std::fill(h->slot_used.begin(), h->slot_used.end(), 0);
-  HIPCHK(hipMemsetAsync(h->d_map, 0, map_buffer_bytes(npx), h->stream));
-  HIPCHK(hipMemsetAsync(h->d_map2, 0, map_buffer_bytes(npx), h->stream));
-  HIPCHK(hipMemsetAsync(h->d_tile_count, 0, sizeof(u32) * (size_t)((h->W + FUSE_TILE - 1) / FUSE_TILE) * ((h->H + FUSE_TILE - 1) / FUSE_TILE), h->stream));
-  HIPCHK(hipMemsetAsync(h->d_fuse_ctr, 0, sizeof(u32) * 2112, h->stream));
-  if (h->d_rank_kept) HIPCHK(hipMemsetAsync(h->d_rank_kept, 0, sizeof(u32) * esvo_context::SHARD_MAX_RANKS, h->stream));
-  h->d_map_cur = h->d_map;
-  h->map_id_bound = 0;
-  h->cloud_cur = -1;  // the device-resident cloud is emptied (every stream was drained above: no gather is in flight)
-  h->cloud_n = 0;
-  h->cloud_t_ns = 0;
-  h->cloud_read_pending[0] = h->cloud_read_pending[1] = false;
   gpc_reset(h);
-  h->obs_set = false;
-  h->n_pose = 0;
+  { int rcz = zero_session_buffers(h, h->stream); if (rcz) return rcz; }
   HIPCHK(hipStreamSynchronize(h->stream));
   HIPCHK(hipStreamSynchronize(h->stream_l)); HIPCHK(hipStreamSynchronize(h->stream_l1));
   HIPCHK(hipStreamSynchronize(h->stream_b));
-  h->back_pending[0] = h->back_pending[1] = false;
-  h->committed_t_ns = 0;
-  h->ts_timing_pending[0] = h->ts_timing_pending[1] = false;
-  h->ts_pair_sample = false;
-  h->stats_pending = false;
-  {
-    const uint32_t khz = h->stats.clk_ref_khz;
-    std::memset(&h->stats, 0, sizeof(h->stats));
-    h->stats.clk_ref_khz = khz;
-  }
-  HIPCHK(hipMemset(h->d_clk, 0, sizeof(u64) * CLK_SCRATCH));
+  const uint32_t khz = h->stats.clk_ref_khz;  // (a property of the device: kept)
+  std::memset(&h->stats, 0, sizeof(h->stats));
+  h->stats.clk_ref_khz = khz;
+  HIPCHK(hipMemset(h->d_clk, 0, sizeof(u64) * CLK_SCRATCH));  // the probe's sums of both front parities (alloc_tick_scratch)
   HIPCHK(hipMemset(h->d_clk + clk_words(h->max_ev), 0, sizeof(u64) * CLK_SCRATCH));
   return ESVO_OK;
 }

@@ -51,7 +51,74 @@ struct FrameRec {
 };
 enum : u32 { NO_SLOT = 0xffffffffu };
 
-struct esvo_context {
+// ---- SESSION STATE: the bookkeeping of what a handle has been fed since esvo_create or the last esvo_reset.  The rule: a member
+// declared inside one of the *Session structs below is put back to its initial value by esvo_reset, by assignment of a fresh struct,
+// and is never named there; a member declared anywhere else survives a reset.  One struct per lock that guards its members (esvo_reset
+// holds them all); esvo_context derives from them, so a use site reads h->ring_base[cam] as ever.
+struct IngestSession {  // under mu_ring: the event rings
+  std::deque<u64> ts_host[2];   // time stamps of staged events [ring_base, ring_base + size)
+  u64 ring_base[2] = {0, 0};    // absolute index of ts_host[cam].front()
+  u64 ring_next[2] = {0, 0};    // absolute index of the next event to stage
+  u64 ring_reserved[2] = {0, 0};  // >= ring_next: end of the block a pusher is copying right now (its slots are being
+                                  // overwritten: selections are validated against THIS, not against ring_next)
+  u64 scattered[2] = {0, 0};    // absolute index of the first event not yet in the SAE
+  u64 scatter_pending_lo[2] = {~0ull, ~0ull};  // oldest event a possibly still running scatter kernel reads
+  bool ingest_pending[2] = {false, false};     // esvo_context::evt_ingest of that camera stands for a copy nobody has awaited
+  u64 sh_first = 0;             // the newest selection's first event
+  u64 sh_first_prev = 0;        // the selection before it (two ticks may be in flight)
+  // routed band mode: event selection stays GLOBAL (dataTransferring walks the whole left stream): every left stamp is kept on the
+  // host, each kept event remembers its index in that sequence
+  std::deque<u64> glob_ts;      // stamps of ALL left events [glob_base, glob_base + size)
+  u64 glob_base = 0;
+  std::deque<u64> kept_g;       // global index of each kept left event, aligned with ts_host[0]
+  std::deque<u64> own_before;   // how many OWN events (floor(y_rect) in the band) were kept before this one: the count of a
+  u64 own_total = 0;            //   selection's own events bounds its LM launch (the ring also holds the raster's halo events)
+  u64 last_stamp[2] = {0, 0};   // newest stamp seen per camera (kept or not): the order check of the push calls
+  // queue mode, out-of-order packets (api_ts.hip, push_unsorted): the copies of the then-newest event that take a late event's place
+  // in the per-pixel queues, inserted with the next batch
+  std::vector<esvo_event_t> tsq_dup[2];
+};
+struct TsSession {  // under mu_ts (the right camera's flag: mapper group only)
+  bool ts_valid[2] = {false, false};  // d_ts[cam] holds a render
+  bool trk_read_pending = false;      // evt_trk_read stands for a tracker read of d_ts[0] the next render has to wait for
+};
+struct SchedSession {  // mapper group (mu_api): what the scheduling policies have learnt -- results do not depend on any of it
+  float ema_lm_ms = 0.f, ema_back_ms = 0.f;  // the second LM queue (esvo_context::lm_queues): smoothed stage timings, the decision
+  bool lm_two_on = false;
+  // the pipeline's way back from its slow operating point (api_map.hip, pipeline_resync)
+  struct Resync { double last_ms = 0; float period_ema = 0, period_before = 0; u32 streak = 0, cooldown = 0, check_in = 0; bool lm_wait_back = false; } resync;
+  // pair layout of the LM kernel (esvo_context::lm_pair_forced): the last four launch times per layout, their count, the decisions
+  float lm_pair_ms[2][4] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
+  u32 lm_pair_n[2] = {0u, 0u};
+  u32 lm_pair_decisions = 0;
+  int lm_pair_current = -1;     // the layout the policy settled on (-1: still exploring)
+};
+struct MapSession {  // mapper group (mu_api): observation, window, DepthMap, what is still to be collected
+  bool obs_set = false;
+  u32 n_pose = 0;
+  std::deque<FrameRec> frames;  // the fusion window, oldest first
+  size_t n_window_frames = 0;   // frames of the window as the reference counts them (empty ones included)
+  u32 map_id_bound = 0;         // creation ids of d_map_cur are below this: what the fusion that built it numbered (run_fuse:
+                                // points x records per point; esvo_map_init_sgm: 4 x points).  Recorded where the ids are
+                                // assigned: the window may shrink afterwards without a fusion (esvo_map_push_frame).
+  u64 committed_t_ns = 0;       // stamp of the newest tick whose back stage is enqueued (0: none)
+  bool stats_pending = false;   // the last tick's counters / timings have not been read back yet
+  bool back_pending[2] = {false, false};  // back-stage timings / counters of that parity not collected yet
+  bool ts_timing_pending[2] = {false, false};
+  bool ts_pair_sample = false;  // the pending sample of camera 0 covers both cameras (pair render)
+  bool halo_error = false;      // routed band mode, sticky until a reset: ticks are refused with ESVO_ERR_HALO
+  bool dn_pending = false;      // Denoising on a routed handle: phase 0 returned ESVO_AGAIN, the mask bits are being exchanged
+  bool sgm_disp_valid = false;  // the per-tick SGM mode (esvo_map_tick_sgm / esvo_map_push_disparity_frame): d_sgm_disp holds an image
+  esvo_sgm_stats_t sgm_stats = {};
+};
+struct CloudSession {  // under mu_cloud: the device-resident point cloud (esvo_context::d_cloud_xyz)
+  int cloud_cur = -1;           // the buffer that holds the snapshot (-1: none -- before the first build, after a reset)
+  size_t cloud_n = 0;
+  u64 cloud_t_ns = 0;           // committed_t_ns at the build
+  bool cloud_read_pending[2] = {false, false};
+};
+
+struct esvo_context : IngestSession, TsSession, SchedSession, MapSession, CloudSession {
   esvo_params_t prm;
   DevParams dp;
   int W = 0, H = 0, device = 0;
@@ -79,15 +146,11 @@ struct esvo_context {
   // (0.289 -> 0.264 ms per overlapping tick; 346x260 1000 events 0.203 -> 0.191): on above 0.9 x, off below 0.7 x
   // (profiles/r06_lowlat_tick.txt).
   int lm_queues = 0;              // 0 auto, 1 never, 2 always
-  float ema_lm_ms = 0.f, ema_back_ms = 0.f;
-  bool lm_two_on = false;
   // ESVO_TIMELINE=1 (tools/regime_probe.py): when every stage of every tick ran, collected from the HIP events as they complete
   bool tl_on = false;
   DevEvent tl_ref;
   std::vector<std::array<float, 8>> tl_front;
   std::vector<std::array<float, 4>> tl_back;
-  // the pipeline's way back from its slow operating point (api_map.hip, pipeline_resync)
-  struct Resync { double last_ms = 0; float period_ema = 0, period_before = 0; u32 streak = 0, cooldown = 0, check_in = 0; bool lm_wait_back = false; } resync;
   // Latency mode (round 6, api_map.hip): a tick that arrives while nothing of the previous one is pending -- the caller reads every
   // tick's result before it hands in the next, as the ROS node does -- has nothing to overlap with.  Its LM launch stays in the
   // front queue (no cross-queue hand-off: ~25 us) and the host polls for its counters and its end instead of sleeping on the
@@ -102,19 +165,14 @@ struct esvo_context {
   // sample, sum_ms_kernel[] sums the samples, stats.stage_timing_samples counts them.  The LM layout policy (lm_pair_*) lives on LM
   // launch times: the two events around the LM launch are recorded as well whenever the policy is exploring or trying the layout it
   // is not using (TickState::timed_lm).  Ticks that overlap (the throughput path) record all of them as before.
-  u32 lat_ticks = 0;              // ticks enqueued with nothing pending before them (band-sharded ticks: all of them -- every
-                                  // phase of such a tick is waited for by the exchange that follows it)
   // Overlapping SMALL ticks (at most lat_max_events events; two in flight, nobody waits) are paced by the host: ~45 runtime calls per
   // tick, a third of them event records.  They sample their stage timings one tick in pipe_timed_every; the throughput path (larger
   // ticks, paced by the LM kernel) keeps recording every tick: sampling one in four measured -0.5 % on one box and +0.3 % on
   // another, a four-way A/B with the one-launch back prologue nothing at all (profiles/r06_throughput_ab.txt).
-  u32 pipe_seq = 0;
   u32 pipe_timed_every = 4;       // ESVO_PIPE_TIMED_EVERY (A/B; 1 = every tick)
   u32 lat_timed_every = 31;       // ESVO_LOWLAT_TIMED_EVERY (A/B; 1 = every tick)
   int reg_sparse_forced = -1;     // ESVO_REG_SPARSE (A/B): the regulariser's sparse-map layout never (0) / always (1); -1: by the element count
-  bool gather_guard[2] = {false, false};  // the solver-slot buffers of that parity are read by a back stage's first launch (EV_STG releases them)
   bool stage_events_on = true;    // false while a tick whose stage timings are not sampled is being enqueued (api_map.hip)
-  bool back_timed[2] = {true, true};  // the back stage of that parity recorded its stage events
   std::atomic<bool> trk_used{false};  // esvo_track_set_current has read the resident surface: renders record EV_R1 for it
   // ... and the copies that open its back stage (frame into the ring, pose table into the frame's slot) are not enqueued one by one
   // but handed to run_fuse, whose frame-table upload carries them in the same launch (scan.hip, back_prologue_kernel)
@@ -131,8 +189,6 @@ struct esvo_context {
   hipStream_t stream_i = nullptr;  // event ingest (H2D into the ring): staging new events never waits for a running tick
   bool own_stream = false;
   int par = 0;                    // parity of the tick being assembled
-  bool back_pending[2] = {false, false};  // back-stage timings / counters of that parity not collected yet
-  u32 back_frames[2] = {0, 0};
   double baseline = 0;
   struct EmState* em = nullptr;  // event-to-event matching (api_em.hip): buffers, last selection and counts; created on first use
   struct GpcState* gpc = nullptr;  // the global point cloud (api_gpc.hip): near-cloud and voxel-filter scratch, pc_global_, its stats
@@ -141,15 +197,13 @@ struct esvo_context {
   // INGEST (esvo_ts_push_events / _event_array / _bag: the ROS spinner's eventsCallback), TRACKER (esvo_track_*) and
   // everything else (the MAPPER group: renders, ticks, outputs, parameters).
   std::recursive_mutex mu_api;  // held by every mapper-group call for its duration (they call each other: recursive)
-  std::mutex mu_ring;           // event-ring bookkeeping: ts_host, ring_base / _next / _reserved, scattered, scatter_pending_lo,
-                                // scatter_seq, sh_first, stats.events_staged / _scattered.  Never held across a host wait.
+  std::mutex mu_ring;           // IngestSession, scatter_seq, stats.events_staged / _scattered.  Never held across a host wait.
   std::mutex mu_push[2];        // one pusher per camera at a time (held across its host-to-device copy)
   std::mutex mu_track;          // tracker-group calls
   std::mutex mu_ts;             // the resident left Time Surface (d_ts[0], ts_valid[0], EV_R1) between a render and a
                                 // tracker read (esvo_track_set_current without a host image); the Time-Surface history's table
   std::mutex mu_cloud;          // the device-resident point cloud between a build (mapper group) and a tracker gather
-                                // (esvo_track_set_reference_from_cloud): cloud_cur, cloud_n, cloud_t_ns, evt_cloud_built,
-                                // evt_cloud_read and cloud_read_pending.  Held only while those change or while work that reads
+                                // (esvo_track_set_reference_from_cloud): CloudSession, evt_cloud_built, evt_cloud_read.  Held only while those change or while work that reads
                                 // or writes a buffer is ENQUEUED -- never across a host wait, so neither group waits on the host
                                 // for the other: the build fills the buffer that is NOT current and publishes it afterwards.
   // Lock order: mu_api (API_LOCK) comes before mu_track, never after it -- esvo_reset takes mu_api, mu_push[0..1], mu_track,
@@ -188,7 +242,6 @@ struct esvo_context {
   DevBuf<uint32_t> d_fwd_off[2], d_fwd_src[2];
   DevBuf<double> d_fwd_val;  // the right camera's raw surface when both cameras render in one launch (esvo_map_tick_resident)
   DevBuf<uint8_t> d_ts[2];
-  bool ts_valid[2] = {false, false};
   // Time-Surface history (api_history.hip; the nodes' TS_history_): hist_len entries of two frames each, frame (slot, cam) at
   // d_hist + (2 * slot + cam) * hist_stride.  The stride is W * H rounded up to 256 bytes, so every frame starts as an allocation
   // does.  The table (stamp -> slot, ascending stamps), the free slots and evt_hist are guarded by mu_ts; every store is
@@ -202,34 +255,18 @@ struct esvo_context {
   DevBuf<esvo_event_t> d_ring[2];
   DevBuf<uint8_t> d_wire[2];  // staging of serialised 13-byte event records (esvo_ts_push_event_array), per camera
   u64 ring_cap = 0;
-  std::deque<u64> ts_host[2];   // time stamps of staged events [ring_base, ring_base + size)
-  u64 ring_base[2] = {0, 0};    // absolute index of ts_host[cam].front()
-  u64 ring_next[2] = {0, 0};    // absolute index of the next event to stage
-  u64 ring_reserved[2] = {0, 0};  // >= ring_next: end of the block a pusher is copying right now (its slots are being
-                                  // overwritten: selections are validated against THIS, not against ring_next)
-  u64 scatter_seq = 0;          // scatter launches so far (a pusher that drained the front stream resets scatter_pending_lo
-                                // only if no scatter was enqueued meanwhile)
-  u64 scattered[2] = {0, 0};    // absolute index of the first event not yet in the SAE
-  u64 scatter_pending_lo[2] = {~0ull, ~0ull};  // oldest event a possibly still running scatter kernel reads
   // esvo_ts_push_events_async: the newest enqueued (not awaited) copy of a camera; consumers of the ring on the front stream
-  // queue behind it (ingest_fence, api_ts.hip) -- under mu_ring
+  // queue behind it (ingest_fence, api_ts.hip) -- under mu_ring, with IngestSession::ingest_pending
   DevEvent evt_ingest[2];
-  bool ingest_pending[2] = {false, false};
 
   // observation
   DevBuf<uint8_t> d_obs_tmp;
-  double T_world_obs[16];
-  u64 obs_t_ns = 0;
-  bool obs_set = false;
 
   // pose table of the tick
   DevBuf<double> d_pose_T2[2];
   int pose_buf = 0;
   std::vector<double> h_pose_T;
   PinBuf<double> h_pin;        // pinned staging: 2 slots x (max_poses x 17 + 16) doubles
-  int pin_slot = 0;
-  bool stats_pending = false;     // the last tick's counters / timings have not been read back yet
-  u32 n_pose = 0;
 
   // per-tick scratch
   u32 max_ev = 0;
@@ -269,7 +306,6 @@ struct esvo_context {
   // fusion window
   DevBuf<DevPoint> d_win;
   u32 win_cap = 0;
-  std::deque<FrameRec> frames;    // oldest first
   u32 n_pose_slots = 0;
   std::vector<char> slot_used;
   DevBuf<double> d_frame_pose_T;
@@ -277,7 +313,6 @@ struct esvo_context {
   DevBuf<u32> d_fr_table;      // fr_cum | fr_off | fr_slot
   PinBuf<u32> h_fr_table;      // pinned
   u32 max_frames = 0;             // capacity in NON-EMPTY frames (pose slots, frame tables)
-  size_t n_window_frames = 0;     // frames of the window as the reference counts them (empty ones included)
 
   // DepthMap
   DevBuf<DevPoint> d_prop;
@@ -304,7 +339,6 @@ struct esvo_context {
   size_t codes_bytes = 0;
   // what the caller must all-gather across the ranks before the next phase (esvo_shard_exchange): xchg_block bytes from
   // xchg_send of every rank into xchg_recv, rank-major.  One rank (n_shards == 1): recv aliases send, nothing to exchange.
-  size_t xchg_block = 0;
   DevBuf<uint8_t> d_codes_send;             // exchange 1: [roundup8(ceil(n / N))] the bytes of the own slots r, r + N ...
   DevBuf<uint8_t> d_codes_all;              //             [N][that]
   DevBuf<unsigned long long> d_pts_send;    // exchange 2: [1 + own * 13] count | kept points (final index in seq)
@@ -321,27 +355,15 @@ struct esvo_context {
   int sband_y0[2] = {0, 0}, sband_y1[2] = {0, 0};  // RAW rows whose events a camera's SAE needs for rband (remap + median taps)
   std::vector<int> fix_row_lo[2], fix_row_hi[2];   // per rectified row: the raw rows its remap taps reach (from the fixed-point maps)
   std::vector<uint8_t> keep_px;          // left camera, [W * H]: bit 0 the SAE needs the pixel's events, bit 1 floor(y_rect) is in the band
-  // event selection stays GLOBAL (dataTransferring walks the whole left stream): every left stamp is kept on the host, each
-  // kept event remembers its index in that sequence -- under mu_ring like ts_host
-  std::deque<u64> glob_ts;               // stamps of ALL left events [glob_base, glob_base + size)
-  u64 glob_base = 0;
-  std::deque<u64> kept_g;                // global index of each kept left event, aligned with ts_host[0]
-  std::deque<u64> own_before;            // how many OWN events (floor(y_rect) in the band) were kept before this one: the count of a
-  u64 own_total = 0;                     //   selection's own events bounds its LM launch (the ring also holds the raster's halo events)
-  u64 last_stamp[2] = {0, 0};            // newest stamp seen per camera (kept or not): the order check of the push calls
   DevBuf<u32> d_ring_gidx;            // [ring_cap] low 32 bits of the global index of the left ring's events
   PinBuf<esvo_event_t> h_route_ev[2];  // pinned staging of the kept events of one push, per camera
   PinBuf<u32> h_route_gidx;
   size_t route_cap[2] = {0, 0};
-  // out-of-order packets (api_ts.hip, push_unsorted): scratch of the ring merge; queue mode: the copies of the then-newest event
-  // that take a late event's place in the per-pixel queues, inserted with the next batch
+  // out-of-order packets (api_ts.hip, push_unsorted): scratch of the ring merge; queue mode: the device copy of tsq_dup
   DevBuf<esvo_event_t> d_merge_a, d_merge_b;
   DevBuf<u32> d_merge_plan;
-  std::vector<esvo_event_t> tsq_dup[2];
   DevBuf<esvo_event_t> d_tsq_dup;
   DevBuf<u32> d_halo_viol;            // [2] matches whose refinement read outside oband, all ranks, summed over the ticks | scratch
-  bool halo_error = false;               // sticky (esvo_reset clears it): ticks are refused with ESVO_ERR_HALO
-  bool dn_pending = false;               // Denoising on a routed handle: phase 0 returned ESVO_AGAIN, the mask bits are being exchanged
   DevBuf<u32> d_dn_flags;             // [2][max_ev] kept flag + exclusive prefix per walk position of the raw selection (lazily)
   // A tick's state between its phases.  Unsharded ticks are finished lazily: esvo_map_tick(k) enqueues the front
   // stage of tick k and only then completes tick k-1 (point count -> window policy -> back stage), so the host
@@ -372,13 +394,8 @@ struct esvo_context {
   // (the first ticks of a handle are slow whatever the layout).  ESVO_LM_PAIR = 0 / 1 forces never / always.  Scheduling
   // only: same bits either way.
   int lm_pair_forced = -1;
-  float lm_pair_ms[2][4] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
-  u32 lm_pair_n[2] = {0u, 0u};
-  u32 lm_pair_decisions = 0;
-  int lm_pair_current = -1;       // the layout the policy settled on (-1: still exploring)
   int fpar = 0;                   // parity of the newest front stage
   bool tick_pending = false;      // tk[fpar] has its front stage enqueued but is not committed yet
-  u64 committed_t_ns = 0;         // stamp of the newest tick whose back stage is enqueued (0: none)
   // per-pixel event queues (max_event_queue_len > 0; kernels_ts.hip): key sets of both cameras + the batch's tile lists
   int tsq_len = 0;
   DevBuf<u64> d_tsq[2];
@@ -387,9 +404,6 @@ struct esvo_context {
   DevBuf<u32> d_tsq_over_count;
   u32 tsq_tcap = 0;
   static constexpr u64 TSQ_ROUND = 1ull << 20;  // events per insertion round = capacity of the overflow list
-  u64 sh_first = 0;
-  u64 sh_first_prev = 0;  // the selection before it (two ticks may be in flight)
-  u64 em_guard_lo[2] = {~0ull, ~0ull};  // oldest ring event an esvo_map_tick_em gather may still read, per camera (api_em.hip)
   DevBuf<double2> d_reg_ab, d_reg_cd;
   double T_world_frame[16];
   // export
@@ -401,13 +415,7 @@ struct esvo_context {
   // event of the tracker's last gather out of it (evt_cloud_read), records evt_cloud_built, reads the count -- its one host
   // read -- and only then makes the buffer current, under mu_cloud.  The tracker's gather runs on its own stream behind
   // evt_cloud_built.  Ticks never touch the buffers; esvo_reset empties them (cloud_cur = -1).
-  u32 map_id_bound = 0;           // creation ids of d_map_cur are below this: what the fusion that built it numbered (run_fuse:
-                                  // points x records per point; esvo_map_init_sgm: 4 x points).  Recorded where the ids are
-                                  // assigned: the window may shrink afterwards without a fusion (esvo_map_push_frame).
   DevBuf<float> d_cloud_xyz[2];
-  int cloud_cur = -1;             // the buffer that holds the snapshot (-1: none -- before the first build, after a reset)
-  size_t cloud_n = 0;
-  u64 cloud_t_ns = 0;             // committed_t_ns at the build
   DevBuf<u32> d_cloud_ids;     // [3][cloud_id_cap] present | prefix | where, by creation id
   size_t cloud_id_cap = 0;
   DevBuf<u32> d_cloud_scan;    // scan scratch for cloud_id_cap ids
@@ -415,7 +423,6 @@ struct esvo_context {
   PinBuf<u32> h_cloud_cnt;     // pinned copy of it
   DevEvent evt_cloud_built[2];
   DevEvent evt_cloud_read[2];   // the tracker stream's newest gather out of that buffer
-  bool cloud_read_pending[2] = {false, false};
 
   // tracker residual / Jacobian evaluation (kernels_track.hip): own stream, own images, synchronous calls
   hipStream_t stream_t = nullptr;
@@ -427,8 +434,7 @@ struct esvo_context {
   PinBuf<TrackSolveOut> h_trk_solve;  // pinned: what track_solve_kernel writes (esvo_track_solve, on_device)
   PinBuf<float> h_trk_xyz;     // pinned staging of esvo_track_set_reference's point cloud
   bool trk_xyz_inflight = false;  // an upload out of it has been enqueued and no call has waited for the tracker stream since
-  size_t trk_cap = 0, trk_n = 0;
-  bool trk_cur = false;
+  size_t trk_cap = 0;
   DevEvent evt_trk_read;  // the tracker stream has read the resident left Time Surface (mu_ts)
   // the reprojection map (kernels_track_viz.hip): the tracker group's own image, owner words, jet table and counter, allocated
   // on first use under mu_track -- the d_viz_* buffers below are the mapper group's
@@ -436,15 +442,12 @@ struct esvo_context {
   DevBuf<u32> d_trk_viz_owner;   // all 0 between calls (the paint pass clears what the mark pass set)
   DevBuf<uint8_t> d_trk_viz_jet;
   DevBuf<u32> d_trk_viz_cnt;
-  bool trk_viz_valid = false;       // d_trk_viz_bgr holds the image of a call
-  bool trk_read_pending = false;
 
   // pinned staging slots for frame pose tables that arrive from the host (push_frame variants): a slot is reused only
   // after the back stream has consumed it
   static constexpr int POSE_POOL = 32;
   PinBuf<double> h_pose_pool;
   DevEvent pool_evt[POSE_POOL];
-  int pool_next = 0;
 
   // SGM initialisation (kernels_sgm.hip): allocated on first use, released by esvo_destroy
   SgmScratch sgm = {};            // what the launchers take by value: raw pointers into the buffers of the next three lines
@@ -456,10 +459,7 @@ struct esvo_context {
   DevBuf<int16_t> d_sgm_disp;
   DevBuf<u32> d_sgm_pair;      // [2][4 * max_ev] winner flags / ranks of naive_propagation
   DevBuf<double> d_sgm_T;
-  // the per-tick SGM mode (esvo_map_tick_sgm / esvo_map_push_disparity_frame)
-  bool sgm_disp_valid = false;    // d_sgm_disp holds a disparity image
-  DevEvent evt_sgm[3];  // before / behind the SGM chain, behind the point stage
-  esvo_sgm_stats_t sgm_stats = {};
+  DevEvent evt_sgm[3];  // the per-tick SGM mode: before / behind the SGM chain, behind the point stage
 
   // debug images (kernels_viz.hip): allocated on first use
   DevBuf<uint8_t> d_viz_bgr, d_viz_jet;
@@ -470,8 +470,28 @@ struct esvo_context {
   hipEvent_t evt[EV_N];
   bool evt_ok = false;
   esvo_stats_t stats;
-  bool ts_timing_pending[2] = {false, false};
-  bool ts_pair_sample = false;  // the pending sample of camera 0 covers both cameras (pair render)
+
+  // ---- SURVIVES A RESET although it belongs to the session (everything outside the *Session structs survives; what is fixed at
+  // esvo_create, configuration, buffers and events do so by nature).  Left in place above: par / fpar / obs_par / pose_buf and the
+  // views that follow them (the double-buffered sets are symmetric: work resumes on whichever half is current); tk[] (read only
+  // while tick_pending, which flush_pending_tick clears); pro (active inside one tick_phase2); the tools' timeline; (?) em, which
+  // has no reset hook.  (?): the code shows no reason -- a reset handle keeps it as it always has, a later change decides.
+  u32 lat_ticks = 0;            // ticks enqueued with nothing pending before them (band-sharded ticks: all of them -- every phase of such a
+  u32 pipe_seq = 0;             // tick is waited for by an exchange) / overlapping small ticks: they pace the SAMPLING of stage timings, no result
+  bool gather_guard[2] = {false, false};  // a back stage's first launch reads that parity's solver slots until EV_STG: complete after a reset's drains
+  bool back_timed[2] = {true, true};  // the back stage of that parity recorded its stage events: describes evt[], which survives
+  u32 back_frames[2] = {0, 0};  // (written and read by nobody)
+  u64 scatter_seq = 0;          // scatter launches so far, under mu_ring (a pusher that drained the front stream resets scatter_pending_lo
+                                // only if no scatter was enqueued meanwhile): compared for equality only
+  u64 em_guard_lo[2] = {~0ull, ~0ull};  // oldest ring event an esvo_map_tick_em gather may still read (api_em.hip): lifted before that call returns
+  int pin_slot = 0;             // which half of h_pin the next pose table takes: either will do
+  int pool_next = 0;            // ... which slot of h_pose_pool (pool_evt[] says when a slot is free again)
+  double T_world_obs[16];       // the observation's pose and stamp: every tick checks obs_set before it reads them
+  u64 obs_t_ns = 0;
+  size_t xchg_block = 0;        // 0 behind a tick's last phase, like xchg_send / xchg_recv; (?) a reset between two phases keeps the three
+  size_t trk_n = 0;             // (?) points of the tracker's reference
+  bool trk_cur = false;         // (?) esvo_track_set_current has run: the tracker keeps its images
+  bool trk_viz_valid = false;   // (?) d_trk_viz_bgr holds the image of a call
 };
 
 namespace esvo_host {
