@@ -685,8 +685,41 @@ def make_fuse_cases():
     print("ref_fuse_cases.npz", os.path.getsize(path) // 1024, "KiB")
 
 
+def run_lm_case(c):
+    """the reference's DepthProblemSolver on one crafted case (tests/lm_cases.py), without the matches on which the reference
+    itself is undefined: (points of solve() before culling, in its thread-stride order; per match whether
+    solve_single_problem_numerical returned true)"""
+    import lm_cases as LC
+    m = R.RefMapper(LC.case_params(c), LC.rig())
+    LC.observe_on(m, c)
+    mt = LC.pinned_matches(c)
+    solved = np.array([m.solve_single(q["x_left"], q["pose_idx"], q["inv_depth"])[1] for q in mt], np.uint8)
+    return m.refine(mt, cull=False), solved
+
+
+def make_lm_cases():
+    """tests/lm_cases.py: crafted matches at the switch points of the residual evaluator and of the solver around it, refined by the
+    reference's own DepthProblem / DepthProblemSolver.  Recorded results only: per case the matches, the points, the per-match
+    solved flags and a digest of the inputs."""
+    import lm_cases as LC
+    out = {}
+    for name in LC.NAMES:
+        c = LC.case(name)
+        pts, solved = run_lm_case(c)
+        assert len(pts) == int(solved.sum()), name
+        out[f"{name}_matches"], out[f"{name}_points"], out[f"{name}_solved"] = LC.pinned_matches(c), pts, solved
+        out[f"{name}_sha"] = LC.input_digest(c)
+        print("lm case", name, len(solved), "matches", len(pts), "points")
+    path = os.path.join(HERE, "ref_lm_cases.npz")
+    np.savez_compressed(path, **out)
+    print("ref_lm_cases.npz", os.path.getsize(path) // 1024, "KiB")
+
+
 if __name__ == "__main__":
     assert R.available(), "needs /root/reference (build container only)"
+    if "--lm-cases" in sys.argv:   # only the crafted refinement cases: ref_lm_cases.npz
+        make_lm_cases()
+        sys.exit(0)
     if "--fuse-cases" in sys.argv:   # only the crafted back-stage cases: ref_fuse_cases.npz
         make_fuse_cases()
         sys.exit(0)
@@ -715,3 +748,4 @@ if __name__ == "__main__":
     make_l2()
     make_node()
     make_fuse_cases()
+    make_lm_cases()
