@@ -26,6 +26,14 @@ int validate_params(const esvo_params_t* p, std::string& why) {
   if (p->median_blur_kernel_size < 0 || p->median_blur_kernel_size > 3) { why = "median_blur_kernel_size must be 0..3 (kernel 2k + 1)"; return ESVO_ERR_UNSUPPORTED; }
   if (p->max_event_queue_len < 0 || p->max_event_queue_len > TSQ_LMAX) { why = "max_event_queue_len must be 0 (one stamp per pixel) or 1..32"; return ESVO_ERR_UNSUPPORTED; }
   if (p->bm_max_disparity < p->bm_min_disparity || p->bm_min_disparity < 0) { why = "bad disparity range"; return ESVO_ERR_INVALID_ARG; }
+  {  // both block-matching launchers size dynamic LDS from the range; past what a workgroup can be given the launch itself would fail
+    const unsigned long long lds = esvo::bm_match_lds_bytes(p->patch_size_x, p->patch_size_y, p->bm_min_disparity, p->bm_max_disparity, p->bm_step, p->bm_updown);
+    if (lds > esvo::BM_LDS_MAX_BYTES) {
+      why = "disparity range too wide: block matching would need " + std::to_string(lds) + " bytes of LDS per workgroup for its strip of " +
+            std::to_string((long long)p->bm_max_disparity - p->bm_min_disparity + 1) + " candidates, a workgroup gets " + std::to_string(esvo::BM_LDS_MAX_BYTES) + " at the most";
+      return ESVO_ERR_UNSUPPORTED;
+    }
+  }
   if (p->td_nu <= 2.0 || p->td_scale <= 0) { why = "Tdist_nu must be > 2 and Tdist_scale > 0"; return ESVO_ERR_INVALID_ARG; }
   if (p->num_threads < 1 || p->num_threads > 64) { why = "num_threads out of range"; return ESVO_ERR_INVALID_ARG; }
   if (p->lm_max_iteration < 1) { why = "lm_max_iteration must be >= 1"; return ESVO_ERR_INVALID_ARG; }

@@ -297,6 +297,11 @@ struct BmArgs {
   u32* search_rec = nullptr;
 };
 void launch_bm_match(const BmArgs& a, const DevParams& p, hipStream_t s);
+// dynamic LDS of one block-matching workgroup under these parameters (it grows with the disparity range: the staged strip, and the
+// cost row under BM_step > 1), exactly as launch_bm_match sizes its launch.  A workgroup can be given no more than the LDS of one
+// compute unit -- 160 KiB on gfx950 --, a launch that asks for more fails: esvo_create / esvo_set_params refuse such a range.
+constexpr unsigned long long BM_LDS_MAX_BYTES = 160ull * 1024ull;
+unsigned long long bm_match_lds_bytes(int wx, int wy, int dmin, int dmax, int step, int updown);
 // Everything block matching computes but event_idx and pose_idx follows from the event's raw pixel, and a throughput slice hits a
 // third of its pixels more than once: the search runs once per distinct raw pixel of the selection, every other event at the pixel
 // copies the result (own event_idx, own pose look-up, the owner's failure reason counted once more).  out_slots, out_flags and the

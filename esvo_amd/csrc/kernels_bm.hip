@@ -586,11 +586,39 @@ __global__ void __launch_bounds__(64) bm_match_any_kernel(BmArgs a, DevParams p,
       atomicAdd(a.fail_counters + CNT_BM_FAIL + (reason - 1) * CNT_STRIPES + (blockIdx.x % CNT_STRIPES), 1u);
   }
 }
+// ---- dynamic LDS of one workgroup, in one place: the launchers size their launches with it and esvo_create / esvo_set_params refuse
+// a disparity range that needs more than a workgroup can be given (common.hpp: bm_match_lds_bytes, BM_LDS_MAX_BYTES) ----
+static long long bm_strip_dwords(long long nd) { return ((((nd + 2) >> 2) + 5) + 3) & ~3LL; }  // dwords staged per strip row (16-byte pieces)
+static int bm_group_width(long long nd) {  // lanes per event: the group size that wastes the fewest candidate slots (ties -> wider)
+  int bestG = 64;
+  long long bestSlots = 1LL << 62;
+  for (int G = 64; G >= 8; G >>= 1) {
+    const long long slots = ((nd + G - 1) / G) * G;
+    if (slots < bestSlots) { bestSlots = slots; bestG = G; }
+  }
+  return bestG;
+}
+static long long bm_any_strip_bytes(long long wx, long long wy, long long nd, bool updown) {
+  return ((updown ? (wy + nd - 1) * wx : wy * (wx + nd - 1)) + 7) & ~7LL;
+}
+static long long bm_15x7_event_bytes(long long nd, bool coarse, bool updown) {
+  return (28 + (updown ? (nd + 6) * 4 : 7 * bm_strip_dwords(nd))) * 4 + (coarse ? ((nd + 1) & ~1LL) * 8 : 0);
+}
+unsigned long long bm_match_lds_bytes(int wx, int wy, int dmin, int dmax, int step, int updown) {
+  const long long nd = (long long)dmax - dmin + 1;
+  const bool coarse = step > 1;
+  if (wx != 15 || wy != 7) {
+    const long long N = (long long)wx * wy;
+    return (unsigned long long)(((N + 7) & ~7LL) + bm_any_strip_bytes(wx, wy, nd, updown != 0) + (coarse ? nd * 8 : 0));
+  }
+  return (unsigned long long)(bm_15x7_event_bytes(nd, coarse, updown != 0) * (BM_BLOCK / bm_group_width(nd)));
+}
+
 template <bool COARSE, bool UPDOWN>
 static void launch_bm_any(const BmArgs& a, const DevParams& p, hipStream_t s) {
-  const int nd = p.dmax - p.dmin + 1, N = p.wx * p.wy;
-  const int strip = ((UPDOWN ? (p.wy + nd - 1) * p.wx : p.wy * (p.wx + nd - 1)) + 7) & ~7;
-  const size_t lds = (size_t)((N + 7) & ~7) + strip + (COARSE ? (size_t)nd * 8 : 0);
+  const int nd = p.dmax - p.dmin + 1;
+  const int strip = (int)bm_any_strip_bytes(p.wx, p.wy, nd, UPDOWN);
+  const size_t lds = (size_t)bm_match_lds_bytes(p.wx, p.wy, p.dmin, p.dmax, COARSE ? 2 : 1, UPDOWN);
   const u32 own = a.gidx ? a.n_loc : ((a.n > (u32)p.ev_shard) ? (a.n - (u32)p.ev_shard + (u32)p.ev_nshards - 1) / (u32)p.ev_nshards : 0);
   if (own == 0) return;
   hipLaunchKernelGGL((bm_match_any_kernel<COARSE, UPDOWN>), dim3(own), dim3(64), lds, s, a, p, strip);
@@ -599,7 +627,7 @@ static void launch_bm_any(const BmArgs& a, const DevParams& p, hipStream_t s) {
 template <int G, bool COARSE, bool UPDOWN>
 static void launch_bm_g(const BmArgs& a, const DevParams& p, int RD, hipStream_t s) {
   const int nd = p.dmax - p.dmin + 1;
-  const int per_event = (28 + (UPDOWN ? (nd + 6) * 4 : 7 * RD)) * 4 + (COARSE ? ((nd + 1) & ~1) * 8 : 0);
+  const int per_event = (int)bm_15x7_event_bytes(nd, COARSE, UPDOWN);
   const int epb = BM_BLOCK / G;
   const u32 own = a.gidx ? a.n_loc : ((a.n > (u32)p.ev_shard) ? (a.n - (u32)p.ev_shard + (u32)p.ev_nshards - 1) / (u32)p.ev_nshards : 0);
   if (own == 0) return;
@@ -619,13 +647,8 @@ static void launch_bm_mode(int G, const BmArgs& a, const DevParams& p, int RD, h
 void launch_bm_match(const BmArgs& a, const DevParams& p, hipStream_t s) {
   if (a.n == 0) return;
   const int nd = p.dmax - p.dmin + 1;
-  const int RD = ((((nd + 2) >> 2) + 5) + 3) & ~3;  // dwords staged per strip row (16-byte pieces)
-  // lanes per event: the group size that wastes the fewest candidate slots (ties -> wider)
-  int bestG = 64, bestSlots = 1 << 30;
-  for (int G = 64; G >= 8; G >>= 1) {
-    const int slots = ((nd + G - 1) / G) * G;
-    if (slots < bestSlots) { bestSlots = slots; bestG = G; }
-  }
+  const int RD = (int)bm_strip_dwords(nd);
+  const int bestG = bm_group_width(nd);
   const bool coarse = p.step > 1;
   if (p.wx != 15 || p.wy != 7) {  // any other patch size: the general kernel
     if (p.updown) { if (coarse) launch_bm_any<true, true>(a, p, s); else launch_bm_any<false, true>(a, p, s); }

@@ -464,6 +464,7 @@ struct orc_mapper {
   Mat4 T_world_frame;
   // counters
   uint64_t n_replace = 0, n_replace_displaced = 0, max_scale_iters = 0, n_evals = 0;
+  uint64_t bm_fail[3] = {0, 0, 0};  // the last orc_mapper_match's infoNoiseRatioLowNum_, coarseSearchingFailNum_, fineSearchingFailNum_
 
   int W() const { return camL.W; }
   int H() const { return camL.H; }
@@ -599,7 +600,10 @@ struct BM {
   }
   // EventBM::match_an_event, EventBM.cpp:80-168
   bool match_an_event(const esvo_event_t& e, uint32_t event_idx, esvo_match_t& out,
-                      double* all_costs = nullptr, int exact_int = 0) const {
+                      double* all_costs = nullptr, int exact_int = 0, int* reason = nullptr) const {
+    // reason: which of the reference's failure counters the event adds to (EventBM.h:89): 1 infoNoiseRatioLowNum_ (:107),
+    // 2 coarseSearchingFailNum_ (:124), 3 fineSearchingFailNum_ (:135); 0: none of them
+    if (reason) *reason = 0;
     const Camera& cam = M->camL;
     if (e.x >= W || e.y >= H) return false;  // (the reference would index out of bounds)
     const size_t li = ((size_t)e.y * W + e.x) * 2;
@@ -613,7 +617,7 @@ struct BM {
     block(M->tsL, ltx, lty, patch_src.data());  // :101
     size_t cnt = 0;
     for (double v : patch_src) cnt += (v < 1);
-    if ((double)cnt > 0.95 * (double)patch_src.size()) return false;  // :104-109
+    if ((double)cnt > 0.95 * (double)patch_src.size()) { if (reason) *reason = 1; return false; }  // :104-109
     double min_cost = 1.0;
     int bx = 0, by = 0;
     size_t bestDisp = 0;
@@ -626,16 +630,20 @@ struct BM {
       //  stays 1.0 and the search fails for step==1.  For step>1 the oracle also fails.)
       size_t bd = (size_t)-1;
       double mc = min_cost;
-      if (!epipolarSearching(mc, bx, by, bd, lo, hi, step, x1x, x1y, patch_src.data(), all_costs, exact_int))
+      if (!epipolarSearching(mc, bx, by, bd, lo, hi, step, x1x, x1y, patch_src.data(), all_costs, exact_int)) {
+        if (reason) *reason = 2;
         return false;
+      }
       min_cost = mc; bestDisp = bd; any = true;
     }
     (void)any;
     // fine :128-138   (size_t arithmetic; `>= 0` is always true, Appendix A-9)
     size_t fine_start = bestDisp - (step - 1);
     if (!epipolarSearching(min_cost, bx, by, bestDisp, fine_start, bestDisp + (step - 1), 1, x1x, x1y,
-                           patch_src.data(), nullptr, exact_int))
+                           patch_src.data(), nullptr, exact_int)) {
+      if (reason) *reason = 3;
       return false;
+    }
     if (min_cost <= M->prm.bm_zncc_threshold) {  // :141
       const double disparity = M->prm.bm_updown ? (double)(x1y - by) : (double)(x1x - bx);  // :146-151
       const double depth = M->baseline * cam.P[0] / disparity;  // :152
@@ -1254,10 +1262,13 @@ extern "C" size_t orc_mapper_match(orc_mapper_handle h, const esvo_event_t* ev, 
   BM bm{h, h->prm.patch_size_x, h->prm.patch_size_y, h->W(), h->H()};
   const int T = std::max(1, h->prm.num_threads);
   std::vector<std::vector<esvo_match_t>> per(T);
+  std::vector<uint8_t> why(n, 0);  // per event, so that real threads share nothing
   auto job = [&](int t) {
     for (size_t i = t; i < n; i += T) {
       esvo_match_t m;
-      if (bm.match_an_event(ev[i], (uint32_t)i, m, nullptr, h->bm_exact_int)) per[t].push_back(m);
+      int r = 0;
+      if (bm.match_an_event(ev[i], (uint32_t)i, m, nullptr, h->bm_exact_int, &r)) per[t].push_back(m);
+      why[i] = (uint8_t)r;
     }
   };
   if (h->real_threads > 1) {
@@ -1274,7 +1285,9 @@ extern "C" size_t orc_mapper_match(orc_mapper_handle h, const esvo_event_t* ev, 
           for (size_t k = b; k < e; ++k) {
             size_t i = t + k * T;
             esvo_match_t m;
-            if (bm.match_an_event(ev[i], (uint32_t)i, m, nullptr, h->bm_exact_int)) parts[t][rt].push_back(m);
+            int r = 0;
+            if (bm.match_an_event(ev[i], (uint32_t)i, m, nullptr, h->bm_exact_int, &r)) parts[t][rt].push_back(m);
+            why[i] = (uint8_t)r;
           }
         }
       });
@@ -1283,9 +1296,15 @@ extern "C" size_t orc_mapper_match(orc_mapper_handle h, const esvo_event_t* ev, 
   } else {
     for (int t = 0; t < T; ++t) job(t);
   }
+  h->bm_fail[0] = h->bm_fail[1] = h->bm_fail[2] = 0;
+  for (size_t i = 0; i < n; ++i) if (why[i]) h->bm_fail[why[i] - 1]++;
   size_t cnt = 0;
   for (int t = 0; t < T; ++t) for (auto& m : per[t]) { if (cnt < cap) out[cnt] = m; cnt++; }
   return cnt;
+}
+
+extern "C" void orc_mapper_bm_fail_counts(orc_mapper_handle h, uint64_t out[3]) {
+  for (int r = 0; r < 3; ++r) out[r] = h->bm_fail[r];
 }
 
 extern "C" int orc_mapper_match_costs(orc_mapper_handle h, const esvo_event_t* ev, double* costs, int exact_int) {

@@ -91,6 +91,9 @@ size_t orc_denoise_events(const esvo_event_t* ev, const uint32_t* idx, size_t n,
  * thread-stride order).  Uses the current observation + pose table. */
 size_t orc_mapper_match(orc_mapper_handle h, const esvo_event_t* ev, size_t n, esvo_match_t* out,
                         size_t cap);
+/* the reference's failure counters (EventBM.h:89) over the last orc_mapper_match: infoNoiseRatioLowNum_,
+ * coarseSearchingFailNum_, fineSearchingFailNum_ */
+void orc_mapper_bm_fail_counts(orc_mapper_handle h, uint64_t out[3]);
 /* per-event diagnostic: all candidate costs of one event (for near-tie analysis).
  * costs[d - dmin]; returns 0 if the event is rejected before the search. */
 int orc_mapper_match_costs(orc_mapper_handle h, const esvo_event_t* ev, double* costs,

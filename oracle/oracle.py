@@ -67,6 +67,7 @@ def load(fast=False):
     lib.orc_denoise_events.argtypes = [vp, vp, sz, i32, i32, sz, vp]
     lib.orc_mapper_match.restype = sz
     lib.orc_mapper_match.argtypes = [vp, vp, sz, vp, sz]
+    lib.orc_mapper_bm_fail_counts.argtypes = [vp, vp]
     lib.orc_mapper_match_costs.restype = i32
     lib.orc_mapper_match_costs.argtypes = [vp, vp, vp, i32]
     lib.orc_mapper_refine.restype = sz
@@ -339,6 +340,12 @@ class OracleMapper:
         out = np.zeros(max(ev.shape[0], 1), MATCH_DTYPE)
         n = self.lib.orc_mapper_match(self.h, ev.ctypes.data, ev.shape[0], out.ctypes.data, out.shape[0])
         return out[:n]
+
+    def bm_fail_counts(self):
+        """the reference's failure counters over the last match(): (info-noise ratio low, coarse search, fine search)"""
+        c = np.zeros(3, np.uint64)
+        self.lib.orc_mapper_bm_fail_counts(self.h, c.ctypes.data)
+        return tuple(int(v) for v in c)
 
     def match_costs(self, ev_one, exact_int=False):
         ev = np.ascontiguousarray(ev_one, dtype=EVENT_DTYPE).reshape(1)

@@ -715,8 +715,38 @@ def make_lm_cases():
     print("ref_lm_cases.npz", os.path.getsize(path) // 1024, "KiB")
 
 
+def run_bm_case(c):
+    """the reference's EventBM on one crafted case (tests/bm_cases.py), without the events outside the image: its matches in its
+    thread-stride order"""
+    import bm_cases as BC
+    m = R.RefMapper(BC.case_params(c), c["rig"])
+    m.set_observation(BC.T0_NS, c["left"], c["right"], np.eye(4))
+    m.set_poses(c["stamps"], c["poses"])
+    return m.match(BC.pinned_events(c))
+
+
+def make_bm_cases():
+    """tests/bm_cases.py: crafted events at the switch points of the disparity search, matched by the reference's own EventBM.
+    Recorded results only: per case a digest of the inputs and, for the cases that are held to the reference, the matches."""
+    import bm_cases as BC
+    out = {}
+    for name in BC.NAMES:
+        c = BC.case(name)
+        out[f"{name}_sha"] = BC.input_digest(c)
+        if name in BC.UNPINNED:
+            continue
+        out[f"{name}_matches"] = run_bm_case(c)
+        print("bm case", name, len(BC.pinned_events(c)), "events", len(out[f"{name}_matches"]), "matches")
+    path = os.path.join(HERE, "ref_bm_cases.npz")
+    np.savez_compressed(path, **out)
+    print("ref_bm_cases.npz", os.path.getsize(path) // 1024, "KiB")
+
+
 if __name__ == "__main__":
     assert R.available(), "needs /root/reference (build container only)"
+    if "--bm-cases" in sys.argv:   # only the crafted block-matching cases: ref_bm_cases.npz
+        make_bm_cases()
+        sys.exit(0)
     if "--lm-cases" in sys.argv:   # only the crafted refinement cases: ref_lm_cases.npz
         make_lm_cases()
         sys.exit(0)
@@ -749,3 +779,4 @@ if __name__ == "__main__":
     make_node()
     make_fuse_cases()
     make_lm_cases()
+    make_bm_cases()

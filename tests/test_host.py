@@ -68,6 +68,29 @@ def test_unsupported_params_are_rejected_not_approximated():
         assert rc == -5, (kw, rc, so.esvo_last_error(None))
 
 
+def test_disparity_range_beyond_the_lds_of_a_workgroup_is_refused():
+    """Both block-matching launchers size dynamic LDS from the disparity range (the staged strip; the cost row under BM_step > 1).
+    A workgroup gets 160 KiB at the most, a launch that asks for more fails: create refuses the range, with the reason.  Both sides
+    of the limit for the 15 x 7 kernel (64 lanes per event: (28 + 7 RD) dwords), its up-down instance (16 bytes per strip row) and
+    the general kernel at 64 x 40 (40 strip rows of 63 + nd bytes behind the 2560-byte patch)."""
+    from esvo_amd import lib
+    so = lib.load()
+    so.esvo_last_error.restype = ctypes.c_char_p
+    rig = calib.ideal_rig(64, 48, 100.0, 0.1)
+    cases = [(dict(), 23296, 23360), (dict(bm_updown=1), 10176, 10240), (dict(patch_size_x=64, patch_size_y=40), 3968, 3970),
+             (dict(bm_step=2), 10880, 10944)]
+    for kw, fits, too_wide in cases:
+        for nd, refused in ((fits, False), (too_wide, True)):
+            p, _ = params.make_params(params.PRESETS["mvstereo_upenn"], rig, bm_min_disparity=1, bm_max_disparity=nd, **kw)
+            h = ctypes.c_void_p()
+            cl, cr = rig.left.as_struct(), rig.right.as_struct()
+            rc = so.esvo_create(ctypes.addressof(p), ctypes.addressof(cl), ctypes.addressof(cr), 0, ctypes.byref(h))
+            why = so.esvo_last_error(None).decode()
+            assert (rc == -5 and "disparity range too wide" in why and str(nd) + " candidates" in why) == refused, (kw, nd, rc, why)
+            if rc == 0:
+                so.esvo_destroy(h)
+
+
 def test_disparity_ranges_of_shipped_configs():
     """effective BM ranges after the clamp of esvo_Mapping.cpp:110-116."""
     cases = [("mvstereo_rpg", 156.925, 0.14805, (4, 40)), ("mvstereo_upenn", 199.653, 0.09988, (3, 20)),

@@ -406,6 +406,25 @@ def test_coarse_to_fine_block_matching_equals_reference_source(name, step, updow
     assert 0 < len(ref) < len(m1.match(tk["ev"]))   # the coarse pass and its neighbour rule reject matches the dense search keeps
 
 
+def _bm_case_names():
+    import bm_cases as BC
+    return [n for n in BC.NAMES if n not in BC.UNPINNED]
+
+
+@pytest.mark.parametrize("name", _bm_case_names())
+def test_block_matching_on_crafted_cases_equals_reference_source(name):
+    """the oracle (literal mode) against the reference's EventBM on the crafted events of tests/bm_cases.py -- gates, borders,
+    the info-noise bar, ties from periodic strips, zero-variance patches, the coarse rule, the up-down search, other patch sizes,
+    pose stamps (tests/golden/ref_bm_cases.npz): same matched events, order, disparities, poses and costs, the bars of
+    test_oracle_stages_match_reference.  bm_cases.UNPINNED lists the cases left out, with the reason."""
+    import bm_cases as BC
+    g = np.load(os.path.join(GOLDEN, "ref_bm_cases.npz"))
+    c = BC.case(name)
+    assert np.array_equal(BC.input_digest(c), g[f"{name}_sha"])
+    m = BC.oracle_for(c, exact=False)
+    check_matches(m.match(BC.pinned_events(c)), g[f"{name}_matches"])
+
+
 @pytest.mark.parametrize("name", ["upenn", "hkust"])
 def test_gaussian_model_l2_equals_reference_source(name):
     """LSnorm: l2 in the oracle against the reference's classes configured with it (tests/golden/ref_l2.npz), stage by stage
