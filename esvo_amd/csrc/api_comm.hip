@@ -152,10 +152,9 @@ struct CommRound {
 struct OwnTick {
   DevBuf<u64> d_block;                 // [2 + max_ev * 13] header + frame
   PinBuf<u32> h_cnt;                   // pinned, CNT_ROW
-  hipEvent_t ev[EV_FRONT_STRIDE];      // raw handles, lent: installed into h->evt[EV_T0 + fp * EV_FRONT_STRIDE ...] while the tick's front stage is enqueued
-  esvo_context::TickState tk;
-  int fp = 0;
-  bool live = false;                   // enqueued; EV_CNT of this slot marks "frame, header and counters ready"
+  FrontEvents ev;                      // lent: h->front[fp].ev points here while (and after) the tick's front stage is enqueued
+  TickState tk;
+  bool live = false;                   // enqueued; FE_CNT of this slot marks "frame, header and counters ready"
 };
 struct esvo_comm {
   int rank = 0, world = 1;
@@ -174,7 +173,6 @@ struct esvo_comm {
   OwnTick own[4];
   u64 own_seq = 0;                 // own ticks so far
   int last_slot_of_fp[2] = {-1, -1};
-  hipEvent_t orig_ev[2][EV_FRONT_STRIDE];  // the handle's own front-stage events, put back by esvo_comm_destroy
   DevBuf<u64> d_empty;             // the block of a round without an own tick (a flushed partial round): zeros
   DevBuf<u64> d_recv[2];
   DevBuf<u64> d_heads;             // [2][world] point counts of the gathered blocks
@@ -183,7 +181,6 @@ struct esvo_comm {
   PinBuf<u64> h_heads;             // pinned, [2][world]
   DevEvent gathered[2];            // the gather into d_recv[i] and the copy of its counts have completed
   DevEvent pushed[2];              // the back stream has copied every frame out of d_recv[i]
-  bool events_ok = false;          // the OwnTick events exist and the handle's own are kept in orig_ev
   u64 rounds = 0;                  // rounds whose gather has been enqueued
   esvo_comm_stats_t st = {};
   // band mode: all-gather of the band maps, merged on the device; of the Time-Surface bands
@@ -205,16 +202,10 @@ void comm_release(esvo_context* h) {
   esvo_comm* c = h->comm;
   if (!c) return;
   if (c->sc) hipStreamSynchronize(c->sc);
-  if (c->events_ok) {
-    // the handle gets its own front-stage events back (nothing is in flight: the callers drained every stream)
-    for (int fp = 0; fp < 2; ++fp)
-      for (int i = 0; i < EV_FRONT_STRIDE; ++i) h->evt[EV_T0 + fp * EV_FRONT_STRIDE + i] = c->orig_ev[fp][i];
-    for (OwnTick& o : c->own)
-      for (int i = 0; i < EV_FRONT_STRIDE; ++i) hipEventDestroy(o.ev[i]);
-  }
+  for (FrontSlot& F : h->front) F.ev = &F.own_ev;  // their own events again (nothing is in flight: the callers drained every stream)
   const ncclComm_t nccl = c->nccl;
   const hipStream_t sc = c->sc;
-  delete c;  // its other events and every buffer
+  delete c;  // its events, the lent sets among them, and every buffer
   h->comm = nullptr;
   if (nccl && g_rccl.CommDestroy) g_rccl.CommDestroy(nccl);
   if (sc) hipStreamDestroy(sc);
@@ -291,15 +282,12 @@ int comm_setup(esvo_context* h, int rank, int world) {
     HIPCHK(o.d_block.alloc(esvo_comm::block_words(h->max_ev)));
     HIPCHK(o.h_cnt.alloc(CNT_ROW));
     std::memset(o.h_cnt, 0, sizeof(u32) * CNT_ROW);
-    for (int i = 0; i < EV_FRONT_STRIDE; ++i) HIPCHK(hipEventCreate(&o.ev[i]));
+    HIPCHK(o.ev.create());
   }
-  for (int fp = 0; fp < 2; ++fp)
-    for (int i = 0; i < EV_FRONT_STRIDE; ++i) c->orig_ev[fp][i] = h->evt[EV_T0 + fp * EV_FRONT_STRIDE + i];
   for (int i = 0; i < 2; ++i) {
     HIPCHK(c->pushed[i].create(hipEventDisableTiming));
     HIPCHK(c->gathered[i].create(hipEventDisableTiming));
   }
-  c->events_ok = true;
   // one untimed round trip sets up the communicator's channels (and proves the transport works)
   rc = comm_all_gather(h, c->d_empty, c->d_recv[0], 16, c->sc);
   if (rc) return rc;
@@ -327,7 +315,7 @@ int round_gather(esvo_context* h, CommRound& R) {
   HIPCHK(hipStreamWaitEvent(c->sc, c->pushed[buf], 0));
   const u64* d_send = c->d_empty;
   if (R.own_slot >= 0) {  // frame, header and count: behind the LM launch on that tick's queues
-    HIPCHK(hipStreamWaitEvent(c->sc, c->own[R.own_slot].ev[EV_CNT - EV_T0], 0));
+    HIPCHK(hipStreamWaitEvent(c->sc, c->own[R.own_slot].ev.e[FE_CNT], 0));
     d_send = c->own[R.own_slot].d_block;
   }
   const size_t bw = esvo_comm::block_words(R.stride);
@@ -458,8 +446,8 @@ int own_front(esvo_context* h, uint64_t t_ns, const double T_world_cam[16], cons
   if (o.live) FAIL(ESVO_ERR_STATE, "four own ticks in flight");  // (cannot happen: a round is collected before the one two later goes out)
   // This front stage rewrites what the own tick two rounds ago (same parity) used -- observation pair, pose table, match list,
   // counter row, LM output -- and that tick's round may not have been collected yet: behind its frame on the DEVICE.
-  if (c->last_slot_of_fp[nfp] >= 0) HIPCHK(hipStreamWaitEvent(h->stream, c->own[c->last_slot_of_fp[nfp]].ev[EV_CNT - EV_T0], 0));
-  for (int i = 0; i < EV_FRONT_STRIDE; ++i) h->evt[EV_T0 + nfp * EV_FRONT_STRIDE + i] = o.ev[i];
+  if (c->last_slot_of_fp[nfp] >= 0) HIPCHK(hipStreamWaitEvent(h->stream, c->own[c->last_slot_of_fp[nfp]].ev.e[FE_CNT], 0));
+  h->front[nfp].ev = &o.ev;
   int rc;
   if (render) {  // = esvo_map_tick_resident's front: both cameras in one launch per kernel, the observation written by the remap
     begin_observation(h);
@@ -481,22 +469,22 @@ int own_front(esvo_context* h, uint64_t t_ns, const double T_world_cam[16], cons
   const bool split = !h->prm.denoising;
   rc = tick_phase0(h, t_ns, pose_t_ns, pose_T, m, FrontOpts{split, false, false});
   if (rc) return rc;
-  const esvo_context::TickState& tk = h->tk[h->fpar];
+  FrontSlot& F = h->front_cur();
+  const TickState& tk = F.tk;
   // frame compaction, header and counters: on the idle second LM queue when there is one (the next LM launch then follows this
   // one directly on its queue), behind the LM kernel
   hipStream_t sl = tk.n ? tk.lm_stream : h->stream;
   hipStream_t sn = sl;
   if (tk.n && split && !tk.lm_two && (sl == h->stream_l || sl == h->stream_l1)) {
     sn = sl == h->stream_l ? h->stream_l1 : h->stream_l;
-    HIPCHK(hipStreamWaitEvent(sn, h->evt[EV_LM1 + h->fpar * EV_FRONT_STRIDE], 0));
+    HIPCHK(hipStreamWaitEvent(sn, F.ev->e[FE_LM1], 0));
   }
   if (tk.n) { rc = run_order_points(h, tk.n, reinterpret_cast<DevPoint*>(o.d_block + 2), sn); if (rc) return rc; }
-  hipLaunchKernelGGL(esvo::comm_block_header_kernel, dim3(1), dim3(1), 0, sn, h->d_counters + CNT_POINTS, o.d_block);
-  HIPCHK(hipMemcpyAsync(o.h_cnt, h->d_counters, sizeof(u32) * CNT_ROW, hipMemcpyDeviceToHost, sn));
-  HIPCHK(hipEventRecord(h->evt[EV_CNT + h->fpar * EV_FRONT_STRIDE], sn));
+  hipLaunchKernelGGL(esvo::comm_block_header_kernel, dim3(1), dim3(1), 0, sn, F.d_counters + CNT_POINTS, o.d_block);
+  HIPCHK(hipMemcpyAsync(o.h_cnt, F.d_counters, sizeof(u32) * CNT_ROW, hipMemcpyDeviceToHost, sn));
+  HIPCHK(hipEventRecord(F.ev->e[FE_CNT], sn));
   HIPCHK(hipGetLastError());
   o.tk = tk;
-  o.fp = h->fpar;
   o.live = true;
   c->last_slot_of_fp[h->fpar] = slot;
   c->own_seq++;
@@ -880,7 +868,7 @@ int esvo_comm_gather_ts(esvo_handle h, int cam) {
   hipLaunchKernelGGL(esvo::ts_bands_scatter_kernel, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, h->stream, c->d_ts_recv, block, c->world, rows, h->W,
                      h->H, c->rank, h->d_ts[cam]);
   HIPCHK(hipGetLastError());
-  if (cam == 0) HIPCHK(hipEventRecord(h->evt[EV_R1], h->stream));  // what esvo_track_set_current waits for
+  if (cam == 0) HIPCHK(hipEventRecord(h->ts_ev[0].e[TE_R1], h->stream));  // what esvo_track_set_current waits for
   return ESVO_OK;
 }
 

@@ -164,8 +164,8 @@ int alloc_rings(esvo_context* h, const esvo_calib_t* left, const esvo_calib_t* r
   h->ring_cap = (u64)std::max<int64_t>(h->prm.event_ring_capacity, 1024);
   for (int cam = 0; cam < 2; ++cam) CK(h->d_ring[cam].alloc(h->ring_cap));
   h->max_poses = (u32)std::max(h->prm.max_poses_per_tick, 2);
-  for (int k = 0; k < 2; ++k) CK(h->d_pose_T2[k].alloc((size_t)h->max_poses * 17));  // [T | toSec]
-  h->d_pose_T = h->d_pose_T2[0];
+  for (int k = 0; k < 2; ++k) CK(h->pose[k].d_T.alloc((size_t)h->max_poses * 17));  // [T | toSec]
+  h->d_pose_T = h->pose[0].d_T;  // (pose_buf == 0; upload_poses re-points it)
   return ESVO_OK;
 }
 
@@ -176,8 +176,7 @@ int alloc_tick_scratch(esvo_context* h) {
   CK(h->d_tick_ev.alloc(E));
   CK(h->d_match_slots.alloc(E));
   CK(h->d_match_flags.alloc(E)); CK(h->d_match_prefix.alloc(E));
-  for (int k = 0; k < 2; ++k) CK(h->d_matches2[k].alloc(E));
-  h->d_matches = h->d_matches2[0];
+  for (int k = 0; k < 2; ++k) CK(h->front[k].d_matches.alloc(E));
   // (scratch of the split launch: 7 x 16 doubles per match -- only where the launch can be used)
   if (E >= LM_SPLIT_MIN_EVENTS) {
     // The split LM launch (kernels_lm.hip, LmSplit) executes 10 % fewer vector instructions (3.47e8 against 3.85e8 per launch
@@ -191,7 +190,7 @@ int alloc_tick_scratch(esvo_context* h) {
     CK(hipMemset(h->d_lm_hist, 0, sizeof(u32) * 2 * 32 * 64));
   }
   if (E > LM_TWO_QUEUES_MAX_EVENTS) {  // (= LM_WIDE_MAX: launches above it take the narrow layout) the processing order, context.hpp
-    for (int k = 0; k < 2; ++k) { CK(h->d_lm_pix_order2[k].alloc(E)); CK(h->d_lm_sort_rows[k].alloc(E)); }
+    for (int k = 0; k < 2; ++k) { CK(h->front[k].d_lm_pix_order.alloc(E)); CK(h->d_lm_sort_rows[k].alloc(E)); }
     CK(h->d_lm_sort_hist.alloc(voxel_hist_words(E)));
   }
   if (h->bm_dedupe_on && E >= h->bm_dedupe_min) CK(h->d_bm_dedupe.alloc(npx + 4 + 2 * E));  // context.hpp: table | count | list | outcomes
@@ -205,17 +204,14 @@ int alloc_tick_scratch(esvo_context* h) {
   if (hipDeviceGetAttribute(&khz, hipDeviceAttributeWallClockRate, h->device) != hipSuccess || khz <= 0) khz = 100000;
   h->stats.clk_ref_khz = (uint32_t)khz;
   for (int k = 0; k < 2; ++k) {
-    CK(h->d_pt_slots2[k].alloc(E));
-    CK(h->d_pt_flags2[k].alloc(E)); CK(h->d_pt_prefix2[k].alloc(E));
-    CK(h->d_scan_tmp_l2[k].alloc(scan_scratch_elems(std::max(E, npx)) + 8));
+    CK(h->front[k].d_pt_slots.alloc(E));
+    CK(h->front[k].d_pt_flags.alloc(E)); CK(h->front[k].d_pt_prefix.alloc(E));
+    CK(h->front[k].d_scan_tmp_l.alloc(scan_scratch_elems(std::max(E, npx)) + 8));
   }
-  h->d_pt_slots = h->d_pt_slots2[0]; h->d_pt_flags = h->d_pt_flags2[0]; h->d_pt_prefix = h->d_pt_prefix2[0];
-  h->d_scan_tmp_l = h->d_scan_tmp_l2[0];
   CK(h->d_pts_tmp.alloc(E));
-  for (int k = 0; k < 2; ++k) CK(h->d_stage[k].alloc(E));
-  for (int k = 0; k < 2; ++k) CK(h->d_counters2[k].alloc(CNT_ROW));
-  for (int k = 0; k < 2; ++k) CK(hipMemset(h->d_counters2[k], 0, sizeof(u32) * CNT_ROW));
-  h->d_counters = h->d_counters2[0];
+  for (int k = 0; k < 2; ++k) CK(h->front[k].d_stage.alloc(E));
+  for (int k = 0; k < 2; ++k) CK(h->front[k].d_counters.alloc(CNT_ROW));
+  for (int k = 0; k < 2; ++k) CK(hipMemset(h->front[k].d_counters, 0, sizeof(u32) * CNT_ROW));
   CK(h->h_counters.alloc(CNT_ROW * 2));
   std::memset(h->h_counters, 0, sizeof(u32) * CNT_ROW * 2);
   CK(h->h_pin.alloc(2 * ((size_t)h->max_poses * 17 + 16)));
@@ -223,6 +219,7 @@ int alloc_tick_scratch(esvo_context* h) {
   CK(h->d_cnt_b.alloc(CNTB_ROW)); CK(hipMemset(h->d_cnt_b, 0, sizeof(u32) * CNTB_ROW));
   CK(h->h_cnt_b.alloc(CNTB_ROW * CNTB_ROWS));  // (common.hpp: CNTB_ROW_*)
   std::memset(h->h_cnt_b, 0, sizeof(u32) * CNTB_ROW * CNTB_ROWS);
+  for (int k = 0; k < 2; ++k) { h->front[k].d_clk = h->d_clk + (size_t)k * clk_words(h->max_ev); h->front[k].h_counters = h->h_counters + CNT_ROW * k; h->back[k].h_cnt = h->h_cnt_b + CNTB_ROW * k; }  // the slots' views
   CK(h->d_halo_viol.alloc(2));
   return ESVO_OK;
 }
@@ -243,6 +240,7 @@ int alloc_window_and_map(esvo_context* h) {
   h->n_pose_slots = std::min<u32>(h->max_frames + 1, h->n_pose_slots);
   CK(h->d_frame_pose_T.alloc((size_t)h->n_pose_slots * h->max_poses * 16));
   CK(h->d_fr_table.alloc(2 * (3 * (size_t)h->max_frames + 1))); CK(h->h_fr_table.alloc(2 * (3 * (size_t)h->max_frames + 1)));
+  for (int k = 0; k < 2; ++k) { h->back[k].d_fr_table = h->d_fr_table + k * (h->d_fr_table.cap() / 2); h->back[k].h_fr_table = h->h_fr_table + k * (h->h_fr_table.cap() / 2); }  // a half each
   // map
   CK(h->d_prop.alloc(h->win_cap));
   const size_t n_tiles = fuse_front_tiles(h);
@@ -271,9 +269,11 @@ int alloc_window_and_map(esvo_context* h) {
 }
 
 int create_events_and_pools(esvo_context* h) {
-  for (int i = 0; i < EV_N; ++i) CK(hipEventCreate(&h->evt[i]));
+  for (int k = 0; k < 2; ++k) CK(h->ts_ev[k].create());
+  CK(h->ev_frame.create());  // (all of them, now: BE_RG1, FE_STG and a pose buffer's are waited for before they are first recorded)
+  for (int k = 0; k < 2; ++k) CK(h->front[k].own_ev.create());
+  for (int k = 0; k < 2; ++k) { CK(h->back[k].ev.create()); CK(h->pose[k].released.create()); }
   if (h->tl_on) { CK(h->tl_ref.create()); CK(hipEventRecord(h->tl_ref, h->stream)); CK(hipEventSynchronize(h->tl_ref)); }
-  h->evt_ok = true;
   CK(h->evt_trk_read.create(hipEventDisableTiming));
   for (int cam = 0; cam < 2; ++cam) CK(h->evt_ingest[cam].create(hipEventDisableTiming));
   CK(h->h_pose_pool.alloc(16 * (size_t)h->max_poses * esvo_context::POSE_POOL));
@@ -413,7 +413,6 @@ int esvo_destroy(esvo_handle h) {
   comm_release(h);
   em_release(h);
   gpc_release(h);
-  if (h->evt_ok) for (int i = 0; i < EV_N; ++i) hipEventDestroy(h->evt[i]);
   // the handle's buffers and its own events go with it, before the streams as ever
   const hipStream_t streams[] = {h->own_stream ? h->stream : nullptr, h->stream_b, h->stream_l, h->stream_l1, h->stream_t, h->stream_i};
   delete h;
@@ -453,8 +452,7 @@ int esvo_reset(esvo_handle h) {
   const uint32_t khz = h->stats.clk_ref_khz;  // (a property of the device: kept)
   std::memset(&h->stats, 0, sizeof(h->stats));
   h->stats.clk_ref_khz = khz;
-  HIPCHK(hipMemset(h->d_clk, 0, sizeof(u64) * CLK_SCRATCH));  // the probe's sums of both front parities (alloc_tick_scratch)
-  HIPCHK(hipMemset(h->d_clk + clk_words(h->max_ev), 0, sizeof(u64) * CLK_SCRATCH));
+  for (const FrontSlot& F : h->front) HIPCHK(hipMemset(F.d_clk, 0, sizeof(u64) * CLK_SCRATCH));  // the probe's sums (alloc_tick_scratch)
   return ESVO_OK;
 }
 

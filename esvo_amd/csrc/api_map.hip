@@ -38,8 +38,8 @@ int upload_poses(esvo_context* h, const uint64_t* pose_t_ns, const double* pose_
   h->n_pose = (u32)m;
   // the back stage copies the previous table of this buffer into its frame slot: not before that is done
   h->pose_buf ^= 1;
-  h->d_pose_T = h->d_pose_T2[h->pose_buf];
-  HIPCHK(hipStreamWaitEvent(h->stream, h->evt[EV_POSE + h->pose_buf * EV_BACK_STRIDE], 0));
+  h->d_pose_T = h->pose[h->pose_buf].d_T;
+  HIPCHK(hipStreamWaitEvent(h->stream, h->pose[h->pose_buf].released, 0));
   h->d_pose_sec = h->d_pose_T + 16 * m;
   // d_zero_row: the counter row of the tick that follows, cleared by the same launch
   launch_upload_words(T, h->d_pose_T, sizeof(double) * 17 * m, h->stream, d_zero_row, CNT_ROW);
@@ -49,14 +49,15 @@ int upload_poses(esvo_context* h, const uint64_t* pose_t_ns, const double* pose_
 // BM over n events starting at absolute ring index `first` (reverse walk) or over d_tick_ev:
 // flags + match records in slot (thread-stride) order
 int run_bm(esvo_context* h, const esvo_event_t* d_ev, u64 first, u64 cap, int reverse, u32 n, const u32* sel) {
+  FrontSlot& F = h->front_cur();
   BmArgs a;
   a.ev = d_ev; a.n = n; a.ev_first = first; a.ev_cap = cap; a.ev_reverse = reverse; a.sel = sel;
   a.tsL = h->d_obs[0]; a.tsR = h->d_obs[1];
   a.lut = h->d_lut; a.mask = h->d_mask;
   a.pose_sec = h->d_pose_sec; a.n_pose = h->n_pose;
   a.out_slots = h->d_match_slots; a.out_flags = h->d_match_flags;
-  a.fail_counters = h->d_counters;
-  if (h->stage_events_on) hipEventRecord(h->evt[EV_BM0 + h->fpar * EV_FRONT_STRIDE], h->stream);
+  a.fail_counters = F.d_counters;
+  if (h->stage_events_on) hipEventRecord(F.ev->e[FE_BM0], h->stream);
   // a throughput slice: one search per distinct raw pixel (kernels_bm.hip; the lone-tick latency path gains no launch)
   if (h->d_bm_dedupe && n >= h->bm_dedupe_min && n <= h->max_ev && !h->sharded && bm_dedupe_applies(a, h->dp)) {
     u32* owner = h->d_bm_dedupe;
@@ -66,7 +67,7 @@ int run_bm(esvo_context* h, const esvo_event_t* d_ev, u64 first, u64 cap, int re
   } else {
     launch_bm_match(a, h->dp, h->stream);
   }
-  if (h->stage_events_on) hipEventRecord(h->evt[EV_BM1 + h->fpar * EV_FRONT_STRIDE], h->stream);
+  if (h->stage_events_on) hipEventRecord(F.ev->e[FE_BM1], h->stream);
   HIPCHK(hipGetLastError());
   return ESVO_OK;
 }
@@ -74,16 +75,17 @@ int run_bm(esvo_context* h, const esvo_event_t* d_ev, u64 first, u64 cap, int re
 // ones, the list is its dense local list (count -> CNT_OWN_MATCHES) and slot_of remembers each entry's slot.
 // by_index (latency mode): the list as indices into the slots -- d_own_w -- which the wide LM layout reads; no record is copied
 int run_order_matches(esvo_context* h, u32 n, bool local, bool by_index) {
+  FrontSlot& F = h->front_cur();
   if (scan_compact_is_small(n)) {  // a small tick: one launch (scan.hip)
     by_index = by_index && !local;
-    launch_scan_compact_matches_small(h->d_match_flags, h->d_match_prefix, h->d_counters + (local ? CNT_OWN_MATCHES : CNT_MATCHES), n, h->d_match_slots,
-                                      by_index ? nullptr : h->d_matches, (local || by_index) ? h->d_own_w : nullptr, h->stream);
+    launch_scan_compact_matches_small(h->d_match_flags, h->d_match_prefix, F.d_counters + (local ? CNT_OWN_MATCHES : CNT_MATCHES), n, h->d_match_slots,
+                                      by_index ? nullptr : F.d_matches, (local || by_index) ? h->d_own_w : nullptr, h->stream);
   } else {
-    launch_exclusive_scan_u32(h->d_match_flags, h->d_match_prefix, h->d_counters + (local ? CNT_OWN_MATCHES : CNT_MATCHES), h->d_scan_tmp, n, h->stream);
-    launch_compact_matches(h->d_match_slots, h->d_match_flags, h->d_match_prefix, n, h->d_matches, local ? h->d_own_w : nullptr,
+    launch_exclusive_scan_u32(h->d_match_flags, h->d_match_prefix, F.d_counters + (local ? CNT_OWN_MATCHES : CNT_MATCHES), h->d_scan_tmp, n, h->stream);
+    launch_compact_matches(h->d_match_slots, h->d_match_flags, h->d_match_prefix, n, F.d_matches, local ? h->d_own_w : nullptr,
                            h->stream);
   }
-  if (h->stage_events_on) hipEventRecord(h->evt[EV_S1 + h->fpar * EV_FRONT_STRIDE], h->stream);
+  if (h->stage_events_on) hipEventRecord(F.ev->e[FE_S1], h->stream);
   HIPCHK(hipGetLastError());
   return ESVO_OK;
 }
@@ -93,15 +95,6 @@ int run_match(esvo_context* h, const esvo_event_t* d_ev, u64 first, u64 cap, int
   return run_order_matches(h, n, false);
 }
 
-// A new front stage takes the other parity: its own match list and counters (the LM stage of the previous tick may still be
-// running on its own), and the LM stage's own buffers, which follow the front parity (context.hpp: two LM queues)
-void switch_front_parity(esvo_context* h) {
-  h->fpar ^= 1;
-  h->d_matches = h->d_matches2[h->fpar];
-  h->d_counters = h->d_counters2[h->fpar];
-  h->d_pt_slots = h->d_pt_slots2[h->fpar]; h->d_pt_flags = h->d_pt_flags2[h->fpar]; h->d_pt_prefix = h->d_pt_prefix2[h->fpar];
-  h->d_scan_tmp_l = h->d_scan_tmp_l2[h->fpar];
-}
 // which LM layout the next lazy tick uses (context.hpp: lm_pair_*): -1 not a candidate, else 0 wide / 1 pair
 static int lm_pair_policy(esvo_context* h, u32 n_events) {
   if (n_events == 0 || n_events > esvo::LM_PAIR_MAX_EVENTS || h->prm.ls_norm == ESVO_LSNORM_L2) return -1;
@@ -113,7 +106,7 @@ static int lm_pair_policy(esvo_context* h, u32 n_events) {
     for (u32 i = 0; i < 4u && i < h->lm_pair_n[mode]; ++i) m = std::min(m, h->lm_pair_ms[mode][i]);
     return m;
   };
-  // The samples are EV_LM0..EV_LM1 intervals on the lowest-priority stream: contention with the other stages only ever ADDS
+  // The samples are FE_LM0..FE_LM1 intervals on the lowest-priority stream: contention with the other stages only ever ADDS
   // time, so the minimum of the recent four is the estimate least touched by it; and the layout in use is left only for one
   // that is 5 % faster by that estimate (hysteresis: two layouts within noise of each other do not alternate run to run).
   if (h->lm_pair_current < 0) h->lm_pair_current = recent_min(1) < recent_min(0) ? 1 : 0;
@@ -123,64 +116,67 @@ static int lm_pair_policy(esvo_context* h, u32 n_events) {
 // The processing order of the LM launch that follows (kernels_lm.hip): on the front queue, behind the match compaction of the
 // tick -- the count stays on the device.  Launches that do not read an order (wide, pair, dense, band, split) get none (nullptr).
 static const u32* run_lm_order(esvo_context* h, u32 max_matches) {
+  FrontSlot& F = h->front_cur();
   const bool split = h->d_lm_fvec0 != nullptr && max_matches >= esvo::LM_SPLIT_MIN_EVENTS;
-  if (!h->lm_order_on || !h->d_lm_pix_order2[0] || !lm_launch_is_ordered(max_matches, false, false, split, h->dp)) return nullptr;
-  u32* order = h->d_lm_pix_order2[h->fpar];
+  if (!h->lm_order_on || !h->front[0].d_lm_pix_order || !lm_launch_is_ordered(max_matches, false, false, split, h->dp)) return nullptr;
+  u32* order = F.d_lm_pix_order;
   u64* const rows[2] = {h->d_lm_sort_rows[0], h->d_lm_sort_rows[1]};
-  launch_lm_pixel_order(h->d_matches, h->d_counters + CNT_MATCHES, max_matches, 0, h->d_obs[0], h->d_obs[1], h->dp, rows, h->d_lm_sort_hist,
+  launch_lm_pixel_order(F.d_matches, F.d_counters + CNT_MATCHES, max_matches, 0, h->d_obs[0], h->d_obs[1], h->dp, rows, h->d_lm_sort_hist,
                         h->d_scan_tmp, order, h->stream);
   return order;
 }
 // order: what run_lm_order built for this launch; by_index: the match list is d_own_w (indices into d_match_slots), not d_matches
 int run_lm(esvo_context* h, u32 max_matches, int cull, bool dense, hipStream_t st, int pair, const u32* order, bool by_index) {
+  FrontSlot& F = h->front_cur();
   if (!st) st = h->stream;
-  if (h->gather_guard[h->fpar]) {  // a back stage's first launch reads this parity's solver slots (latency mode, tick_phase2): not
-    h->gather_guard[h->fpar] = false;  // before it is done (an event long complete when ticks are waited for one by one)
-    HIPCHK(hipStreamWaitEvent(st, h->evt[EV_STG + h->fpar * EV_FRONT_STRIDE], 0));
+  if (F.gather_guard) {  // a back stage's first launch reads this parity's solver slots (latency mode, tick_phase2): not
+    F.gather_guard = false;  // before it is done (an event long complete when ticks are waited for one by one)
+    HIPCHK(hipStreamWaitEvent(st, F.ev->e[FE_STG], 0));
   }
-  u32* flags = dense ? h->d_lkeep : h->d_pt_flags;  // the kernel writes every flag of its launch range
+  u32* flags = dense ? h->d_lkeep : F.d_pt_flags;  // the kernel writes every flag of its launch range
   LmArgs a;
-  a.matches = h->d_matches; a.n_matches = h->d_counters + (dense ? CNT_OWN_MATCHES : CNT_MATCHES); a.max_matches = max_matches;
+  a.matches = F.d_matches; a.n_matches = F.d_counters + (dense ? CNT_OWN_MATCHES : CNT_MATCHES); a.max_matches = max_matches;
   a.match_index = nullptr;
   a.order = dense ? nullptr : order;
   if (by_index && !dense) { a.matches = h->d_match_slots; a.match_index = h->d_own_w; }
   a.tsL = h->d_obs[0]; a.tsR = h->d_obs[1];
   a.pose_T = h->d_pose_T; std::memcpy(a.T_world_obs, h->T_world_obs, sizeof(double) * 16);
-  a.out_slots = h->d_pt_slots; a.out_flags = flags; a.cull = cull; a.dense = dense ? 1 : 0;
+  a.out_slots = F.d_pt_slots; a.out_flags = flags; a.cull = cull; a.dense = dense ? 1 : 0;
   const bool split = h->d_lm_fvec0 != nullptr && max_matches >= esvo::LM_SPLIT_MIN_EVENTS;
   a.split_fvec0 = split ? h->d_lm_fvec0 : nullptr; a.split_fnorm0 = h->d_lm_fnorm0; a.split_meta = h->d_lm_meta;
   a.split_order = h->d_lm_order; a.split_hist = h->d_lm_hist;
   a.pair = pair >= 0 ? pair : (h->lm_pair_forced == 1 && max_matches <= esvo::LM_PAIR_MAX_EVENTS ? 1 : 0);
-  a.clk = h->clk_probe ? h->d_clk + (size_t)h->fpar * clk_words(h->max_ev) : nullptr;  // (a block per front parity: api_core.hip)
-  if (h->routed && dense) { a.halo_viol = h->d_counters + CNT_SCRATCH; a.vy0 = h->oband_y0; a.vy1 = h->oband_y1; }
-  const bool timed_lm = h->stage_events_on || h->tk[h->fpar].timed_lm;
-  if (timed_lm) hipEventRecord(h->evt[EV_LM0 + h->fpar * EV_FRONT_STRIDE], st);
-  launch_lm_refine(a, h->dp, h->d_counters + CNT_SOLVED, st);
-  // (EV_LM1 is also what the point compaction waits for when it runs on the other LM queue: tick_phase0)
-  if (timed_lm || h->tk[h->fpar].cnt_stream != st) hipEventRecord(h->evt[EV_LM1 + h->fpar * EV_FRONT_STRIDE], st);
+  a.clk = h->clk_probe ? F.d_clk : nullptr;  // (a block per front parity: api_core.hip)
+  if (h->routed && dense) { a.halo_viol = F.d_counters + CNT_SCRATCH; a.vy0 = h->oband_y0; a.vy1 = h->oband_y1; }
+  const bool timed_lm = h->stage_events_on || F.tk.timed_lm;
+  if (timed_lm) hipEventRecord(F.ev->e[FE_LM0], st);
+  launch_lm_refine(a, h->dp, F.d_counters + CNT_SOLVED, st);
+  // (FE_LM1 is also what the point compaction waits for when it runs on the other LM queue: tick_phase0)
+  if (timed_lm || F.tk.cnt_stream != st) hipEventRecord(F.ev->e[FE_LM1], st);
   HIPCHK(hipGetLastError());
   return ESVO_OK;
 }
 // stable compaction of the solver slots: the culled points go to `dst` in the reference's order
 // host_row (latency mode): where the small compaction leaves the tick's counter row itself (TickState::host_row_sent)
 int run_order_points(esvo_context* h, u32 max_matches, DevPoint* dst, hipStream_t st, u32* host_row) {
-  u32* scratch = (st && st != h->stream) ? h->d_scan_tmp_l : h->d_scan_tmp;  // the LM stage scans beside the next tick's BM
+  FrontSlot& F = h->front_cur();
+  u32* scratch = (st && st != h->stream) ? F.d_scan_tmp_l : h->d_scan_tmp;  // the LM stage scans beside the next tick's BM
   if (!st) st = h->stream;
   if (scan_compact_is_small(max_matches)) {
     // (the refinement kernel writes a flag for every slot of its launch, 0 beyond the match count: no count to clip to)
-    launch_scan_compact_points_small(h->d_pt_flags, h->d_pt_prefix, h->d_counters + CNT_POINTS, max_matches, h->d_pt_slots, dst, st,
-                                     h->d_counters, host_row, host_row ? (u32)CNT_ROW : 0u);
-    h->tk[h->fpar].host_row_sent = host_row != nullptr;
+    launch_scan_compact_points_small(F.d_pt_flags, F.d_pt_prefix, F.d_counters + CNT_POINTS, max_matches, F.d_pt_slots, dst, st,
+                                     F.d_counters, host_row, host_row ? (u32)CNT_ROW : 0u);
+    F.tk.host_row_sent = host_row != nullptr;
   } else {
-    launch_exclusive_scan_u32(h->d_pt_flags, h->d_pt_prefix, h->d_counters + CNT_POINTS, scratch, max_matches, st);
-    launch_compact_points(h->d_pt_slots, h->d_pt_flags, h->d_pt_prefix, h->d_counters + CNT_MATCHES, max_matches, dst, st);
+    launch_exclusive_scan_u32(F.d_pt_flags, F.d_pt_prefix, F.d_counters + CNT_POINTS, scratch, max_matches, st);
+    launch_compact_points(F.d_pt_slots, F.d_pt_flags, F.d_pt_prefix, F.d_counters + CNT_MATCHES, max_matches, dst, st);
   }
-  if (h->stage_events_on) hipEventRecord(h->evt[EV_S2 + h->fpar * EV_FRONT_STRIDE], st);
+  if (h->stage_events_on) hipEventRecord(F.ev->e[FE_S2], st);
   HIPCHK(hipGetLastError());
   return ESVO_OK;
 }
 int run_refine(esvo_context* h, u32 max_matches, int cull, DevPoint* dst) {
-  HIPCHK(hipMemsetAsync(h->d_counters + CNT_SOLVED, 0, sizeof(u32), h->stream));  // n_solved (a tick zeroes all counters at once)
+  HIPCHK(hipMemsetAsync(h->front_cur().d_counters + CNT_SOLVED, 0, sizeof(u32), h->stream));  // n_solved (a tick zeroes all counters at once)
   const u32* order = run_lm_order(h, max_matches);
   int rc = run_lm(h, max_matches, cull, false, nullptr, -1, order);
   if (rc) return rc;
@@ -197,7 +193,7 @@ void collect_bm_failures(esvo_context* h, const u32* row, bool accumulate) {
   if (accumulate) { s.total_bm_info_noise_low += r[0]; s.total_bm_coarse_fail += r[1]; s.total_bm_fine_fail += r[2]; }
 }
 int read_counters(esvo_context* h) {
-  HIPCHK(hipMemcpyAsync(h->h_counters, h->d_counters, sizeof(u32) * CNT_ROW, hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipMemcpyAsync(h->h_counters, h->front_cur().d_counters, sizeof(u32) * CNT_ROW, hipMemcpyDeviceToHost, h->stream));  // (row 0, whatever the parity)
   HIPCHK(hipStreamSynchronize(h->stream));
   return ESVO_OK;
 }
@@ -209,8 +205,8 @@ void begin_observation(esvo_context* h) {
   h->d_obs[0] = h->d_obs2[h->obs_par][0];
   h->d_obs[1] = h->d_obs2[h->obs_par][1];
   // (observations set twice between two ticks: the pending tick's LM stage reads this very pair -- write behind it)
-  if (h->tick_pending && h->tk[h->fpar].obs_par == h->obs_par)
-    hipStreamWaitEvent(h->stream, h->evt[EV_CNT + h->fpar * EV_FRONT_STRIDE], 0);
+  if (h->tick_pending && h->front_cur().tk.obs_par == h->obs_par)
+    hipStreamWaitEvent(h->stream, h->front_cur().ev->e[FE_CNT], 0);
 }
 // nothing was rendered into the pair begin_observation switched to: the previous observation stays current
 void revert_observation(esvo_context* h) {
@@ -267,10 +263,11 @@ int esvo_map_match(esvo_handle h, const esvo_event_t* ev, size_t n, const uint64
   HIPCHK(hipSetDevice(h->device));
   { int rcp = flush_pending_tick(h); if (rcp) return rcp; }
   if (pose_t_ns) { int rc = upload_poses(h, pose_t_ns, pose_T, m); if (rc) return rc; }
+  FrontSlot& F = h->front_cur();
   *n_out = 0;
-  if (n == 0) { HIPCHK(hipMemsetAsync(h->d_counters, 0, sizeof(u32), h->stream)); return ESVO_OK; }
+  if (n == 0) { HIPCHK(hipMemsetAsync(F.d_counters, 0, sizeof(u32), h->stream)); return ESVO_OK; }
   HIPCHK(hipMemcpyAsync(h->d_tick_ev, ev, sizeof(esvo_event_t) * n, hipMemcpyHostToDevice, h->stream));
-  HIPCHK(hipMemsetAsync(h->d_counters + CNT_BM_FAIL, 0, sizeof(u32) * 3 * CNT_STRIPES, h->stream));
+  HIPCHK(hipMemsetAsync(F.d_counters + CNT_BM_FAIL, 0, sizeof(u32) * 3 * CNT_STRIPES, h->stream));
   int rc = run_match(h, h->d_tick_ev, 0, (u64)h->max_ev, 0, (u32)n);
   if (rc) return rc;
   rc = read_counters(h);
@@ -282,7 +279,7 @@ int esvo_map_match(esvo_handle h, const esvo_event_t* ev, size_t n, const uint64
   collect_bm_failures(h, h->h_counters, false);
   if (out && nm) {
     if (nm > cap) FAIL(ESVO_ERR_CAPACITY, "output array too small for the matches");
-    HIPCHK(hipMemcpy(out, h->d_matches, sizeof(esvo_match_t) * nm, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(out, F.d_matches, sizeof(esvo_match_t) * nm, hipMemcpyDeviceToHost));
   }
   return ESVO_OK;
 }
@@ -300,8 +297,8 @@ int esvo_map_refine(esvo_handle h, const esvo_match_t* matches, size_t n, int cu
   *n_out = 0;
   if (n == 0) return ESVO_OK;
   const u32 n32 = (u32)n;
-  HIPCHK(hipMemcpyAsync(h->d_matches, matches, sizeof(esvo_match_t) * n, hipMemcpyHostToDevice, h->stream));
-  HIPCHK(hipMemcpyAsync(h->d_counters, &n32, sizeof(u32), hipMemcpyHostToDevice, h->stream));
+  HIPCHK(hipMemcpyAsync(h->front_cur().d_matches, matches, sizeof(esvo_match_t) * n, hipMemcpyHostToDevice, h->stream));
+  HIPCHK(hipMemcpyAsync(h->front_cur().d_counters, &n32, sizeof(u32), hipMemcpyHostToDevice, h->stream));
   HIPCHK(hipStreamSynchronize(h->stream));
   int rc = run_refine(h, n32, cull, h->d_pts_tmp);
   if (rc) return rc;
@@ -352,7 +349,7 @@ int select_events(esvo_context* h, uint64_t t_ns, u64* first_out, u32* n_out) {
 // One extra read-back (the kept count sizes the BM launch); only the small DAVIS configs use it.
 int denoise_select(esvo_context* h, u32 n, u32* n_kept) {
   launch_denoise_flags(h->d_ring[0], h->sh_first, h->ring_cap, n, h->d_evmap, h->d_match_flags, h->W, h->H, h->stream);
-  launch_exclusive_scan_u32(h->d_match_flags, h->d_match_prefix, h->d_counters + CNT_DENOISE_KEPT, h->d_scan_tmp, n, h->stream);
+  launch_exclusive_scan_u32(h->d_match_flags, h->d_match_prefix, h->front_cur().d_counters + CNT_DENOISE_KEPT, h->d_scan_tmp, n, h->stream);
   launch_denoise_select(h->d_match_flags, h->d_match_prefix, n, h->d_sel, h->stream);
   int rc = read_counters(h);
   if (rc) return rc;
@@ -367,7 +364,7 @@ int tick_phase0(esvo_context* h, uint64_t t_ns, const uint64_t* pose_t_ns, const
   // the pose-table double buffer, which the LM stage of a still pending tick reads and whose content the back stage
   // copies into that tick's frame slot.
   if (h->dn_pending) {  // phase 0 called again behind the exchange of the denoising bits (ESVO_AGAIN)
-    h->stage_events_on = h->tk[h->fpar].timed;
+    h->stage_events_on = h->front_cur().tk.timed;
     return routed_denoise_resume(h);
   }
   if (m > h->max_poses) FAIL(ESVO_ERR_CAPACITY, "pose table larger than max_poses_per_tick");
@@ -379,10 +376,11 @@ int tick_phase0(esvo_context* h, uint64_t t_ns, const uint64_t* pose_t_ns, const
   int rc = h->routed ? select_events_routed(h, t_ns, &n, &g_first, &first, &n_loc, &n_own) : select_events(h, t_ns, &first, &n);
   if (rc) return rc;
   // (the counter row of this tick's parity -- last used two ticks ago, collected since -- is cleared with the pose upload)
-  rc = upload_poses(h, pose_t_ns, pose_T, m, h->d_counters2[h->fpar ^ 1]);
+  rc = upload_poses(h, pose_t_ns, pose_T, m, h->front[h->fpar ^ 1].d_counters);
   if (rc) return rc;
   switch_front_parity(h);
-  esvo_context::TickState& tk = h->tk[h->fpar];
+  FrontSlot& F = h->front_cur();
+  TickState& tk = F.tk;
   tk.n = n; tk.off = 0; tk.points = 0; tk.t_ns = t_ns;
   tk.n_loc = n_loc; tk.n_own = n_own; tk.g_first = g_first;
   tk.lm_stream = tk.cnt_stream = h->stream;
@@ -407,11 +405,11 @@ int tick_phase0(esvo_context* h, uint64_t t_ns, const uint64_t* pose_t_ns, const
   // two ticks in flight at most: what this tick's front stage overwrites (ring space of popped frames, the pose
   // table buffer) was last read by the back stage two ticks ago.
   // (For the ordinary tick this device-side wait is only a throttle: the tick writes parity buffers that are released by events of
-  // their own -- EV_STG, EV_POSE, the collected EV_CNT -- and the host never runs more than two back stages ahead.  Off since
+  // their own -- FE_STG, PoseBuf::released, the collected FE_CNT -- and the host never runs more than two back stages ahead.  Off since
   // round 5: it ties every front stage to the END of a back stage, which is what makes a lagging back chain stay behind -- see
   // pipeline_resync.  Sharded ticks keep it: their frame goes straight into the ring.)
-  if (h->sharded) HIPCHK(hipStreamWaitEvent(h->stream, h->evt[EV_RG1 + h->par * EV_BACK_STRIDE], 0));
-  if (tk.timed) hipEventRecord(h->evt[EV_T0 + h->fpar * EV_FRONT_STRIDE], h->stream);
+  if (h->sharded) HIPCHK(hipStreamWaitEvent(h->stream, h->back[h->par].ev.e[BE_RG1], 0));
+  if (tk.timed) hipEventRecord(F.ev->e[FE_T0], h->stream);
   const u32* sel = nullptr;
   if (h->prm.denoising && n && !h->routed) {
     rc = denoise_select(h, n, &n);
@@ -432,7 +430,7 @@ int tick_phase0(esvo_context* h, uint64_t t_ns, const uint64_t* pose_t_ns, const
     const u32* order = run_lm_order(h, n);
     hipStream_t sl = h->stream;
     if (opt.split && !tk.lat) {  // the LM stage on its own stream, behind this tick's matches
-      HIPCHK(hipEventRecord(h->evt[EV_A1 + h->fpar * EV_FRONT_STRIDE], h->stream));
+      HIPCHK(hipEventRecord(F.ev->e[FE_A1], h->stream));
       // launches in the latency-bound (wide) layout alternate between the two LM queues; the split launch's scratch and
       // the throughput layout (which fills the chip by itself) stay on one
       const bool split_scratch = h->d_lm_fvec0 != nullptr && n >= esvo::LM_SPLIT_MIN_EVENTS;
@@ -440,11 +438,11 @@ int tick_phase0(esvo_context* h, uint64_t t_ns, const uint64_t* pose_t_ns, const
         h->lm_two_on = h->ema_lm_ms > (h->lm_two_on ? 0.7f : 0.9f) * h->ema_back_ms;  // (context.hpp: round 6's thresholds)
       tk.lm_two = (h->lm_queues == 2 || (h->lm_queues == 0 && h->lm_two_on)) && n <= esvo::LM_TWO_QUEUES_MAX_EVENTS && !split_scratch;
       sl = (tk.lm_two && h->fpar) ? h->stream_l1 : h->stream_l;
-      HIPCHK(hipStreamWaitEvent(sl, h->evt[EV_A1 + h->fpar * EV_FRONT_STRIDE], 0));
+      HIPCHK(hipStreamWaitEvent(sl, F.ev->e[FE_A1], 0));
     }
     if (h->resync.lm_wait_back) {  // pipeline_resync: this LM launch starts together with the back stage after the newest enqueued one
       h->resync.lm_wait_back = false;
-      HIPCHK(hipStreamWaitEvent(sl, h->evt[EV_RG1 + (h->par ^ 1) * EV_BACK_STRIDE], 0));
+      HIPCHK(hipStreamWaitEvent(sl, h->back[h->par ^ 1].ev.e[BE_RG1], 0));
     }
     tk.lm_stream = tk.cnt_stream = sl;
     // With ONE LM queue, what follows the launch on the device (point compaction, counters) goes to the idle second queue: the
@@ -466,9 +464,10 @@ int tick_phase0(esvo_context* h, uint64_t t_ns, const uint64_t* pose_t_ns, const
 }
 // phase 1a (front stage, enqueue only): the tick's frame (culled points in the reference's order) goes straight
 // into the window ring (capacity for the worst case: n points); the counters follow into the pinned row of the
-// tick's parity and EV_CNT marks "frame and counters ready"
+// tick's parity and FE_CNT marks "frame and counters ready"
 int tick_phase1_enqueue(esvo_context* h) {
-  esvo_context::TickState& tk = h->tk[h->fpar];
+  FrontSlot& F = h->front_cur();
+  TickState& tk = F.tk;
   const u32 n = tk.n;
   int rc = ESVO_OK;
   tk.host_row_sent = false;
@@ -481,14 +480,14 @@ int tick_phase1_enqueue(esvo_context* h) {
   if (n && !h->sharded) {
     // the frame waits in the staging buffer of its parity until the tick is committed and its size is known; the
     // buffer's previous frame (two ticks ago) has been copied into the ring by then
-    if (tk.cnt_stream != tk.lm_stream) HIPCHK(hipStreamWaitEvent(tk.cnt_stream, h->evt[EV_LM1 + h->fpar * EV_FRONT_STRIDE], 0));
-    HIPCHK(hipStreamWaitEvent(tk.cnt_stream, h->evt[EV_STG + h->fpar * EV_FRONT_STRIDE], 0));
+    if (tk.cnt_stream != tk.lm_stream) HIPCHK(hipStreamWaitEvent(tk.cnt_stream, F.ev->e[FE_LM1], 0));
+    HIPCHK(hipStreamWaitEvent(tk.cnt_stream, F.ev->e[FE_STG], 0));
     // latency mode: the compaction kernel leaves the counter row in the pinned host row itself (no copy operation behind it)
-    u32* host_row = tk.lat ? h->h_counters + CNT_ROW * h->fpar : nullptr;
+    u32* host_row = tk.lat ? F.h_counters : nullptr;
     // ... and only scans: the frame stays in the solver slots until the back stage's first launch -- which knows where in the window
     // ring it goes -- compacts it straight into place (one copy of the records instead of two, and that one over the whole grid)
     tk.gather = tk.lat && scan_compact_is_small(n);
-    rc = run_order_points(h, n, tk.gather ? nullptr : h->d_stage[h->fpar], tk.cnt_stream, host_row);
+    rc = run_order_points(h, n, tk.gather ? nullptr : F.d_stage, tk.cnt_stream, host_row);
     if (rc) return rc;
   } else if (n) {  // the band mode's frame order (api_shard.hip); the frame itself is filled after exchange 2 (tick_phase2)
     rc = shard_order_points(h, tk);
@@ -496,22 +495,21 @@ int tick_phase1_enqueue(esvo_context* h) {
   }
   hipStream_t sc = (n && !h->sharded) ? tk.cnt_stream : h->stream;
   if (!tk.host_row_sent)
-    HIPCHK(hipMemcpyAsync(h->h_counters + CNT_ROW * h->fpar, h->d_counters, sizeof(u32) * CNT_ROW, hipMemcpyDeviceToHost, sc));
-  HIPCHK(hipEventRecord(h->evt[EV_CNT + h->fpar * EV_FRONT_STRIDE], sc));
+    HIPCHK(hipMemcpyAsync(F.h_counters, F.d_counters, sizeof(u32) * CNT_ROW, hipMemcpyDeviceToHost, sc));
+  HIPCHK(hipEventRecord(F.ev->e[FE_CNT], sc));
   h->tick_pending = true;
   return ESVO_OK;
 }
 // phase 1b (host): wait for the counters of the tick of parity fp (one small D2H per tick: the window policy
 // needs the point count), book-keeping, front-stage timings
 int tick_phase1_collect(esvo_context* h, int fp) {
-  return collect_front_stats(h, h->tk[fp], h->h_counters + CNT_ROW * fp, &h->evt[EV_T0 + fp * EV_FRONT_STRIDE]);
+  return collect_front_stats(h, h->front[fp].tk, h->front[fp].h_counters, *h->front[fp].ev);
 }
-// the same for a front stage whose counters and events live elsewhere (`ev`: its EV_T0 .. EV_A1 set, indexed EV_x - EV_T0) --
+// the same for a front stage whose counters and events live elsewhere --
 // the tick-interleaved mode keeps them per own tick, four deep, so that a tick can be collected after the front stage two
 // own ticks later has been enqueued on the same parity
-int collect_front_stats(esvo_context* h, esvo_context::TickState& tk, const u32* cnt, const hipEvent_t* ev) {
-  auto E = [&](int id) { return ev[id - EV_T0]; };
-  HIPCHK(esvo_wait_event(E(EV_CNT), tk.lat));
+int collect_front_stats(esvo_context* h, TickState& tk, const u32* cnt, const FrontEvents& ev) {
+  HIPCHK(esvo_wait_event(ev.e[FE_CNT], tk.lat));
   const u32 n = tk.n;
   const u32 n_points = n ? cnt[CNT_POINTS] : 0;
   esvo_stats_t& s = h->stats;
@@ -530,7 +528,7 @@ int collect_front_stats(esvo_context* h, esvo_context::TickState& tk, const u32*
   }
   if (n && !tk.timed && tk.timed_lm && tk.lm_pair >= 0) {  // an unsampled tick whose LM launch was timed for the layout policy alone
     float lm = 0.f;
-    if (hipEventElapsedTime(&lm, E(EV_LM0), E(EV_LM1)) == hipSuccess && lm > 0.f) {
+    if (hipEventElapsedTime(&lm, ev.e[FE_LM0], ev.e[FE_LM1]) == hipSuccess && lm > 0.f) {
       h->lm_pair_ms[tk.lm_pair][h->lm_pair_n[tk.lm_pair] & 3u] = lm;
       h->lm_pair_n[tk.lm_pair]++;
     } else {
@@ -539,10 +537,10 @@ int collect_front_stats(esvo_context* h, esvo_context::TickState& tk, const u32*
   }
   if (n && tk.timed) {
     s.stage_timing_samples++;
-    hipEventElapsedTime(&s.ms_bm, E(EV_T0), E(EV_S1));
-    hipEventElapsedTime(&s.ms_refine, E(EV_S1), E(EV_S2));
-    hipEventElapsedTime(&s.ms_kernel[2], E(EV_BM0), E(EV_BM1));
-    hipEventElapsedTime(&s.ms_kernel[3], E(EV_LM0), E(EV_LM1));
+    hipEventElapsedTime(&s.ms_bm, ev.e[FE_T0], ev.e[FE_S1]);
+    hipEventElapsedTime(&s.ms_refine, ev.e[FE_S1], ev.e[FE_S2]);
+    hipEventElapsedTime(&s.ms_kernel[2], ev.e[FE_BM0], ev.e[FE_BM1]);
+    hipEventElapsedTime(&s.ms_kernel[3], ev.e[FE_LM0], ev.e[FE_LM1]);
     s.sum_ms_kernel[2] += s.ms_kernel[2];
     s.sum_ms_kernel[3] += s.ms_kernel[3];
     h->ema_lm_ms = h->ema_lm_ms > 0.f ? 0.75f * h->ema_lm_ms + 0.25f * s.ms_kernel[3] : s.ms_kernel[3];
@@ -552,9 +550,8 @@ int collect_front_stats(esvo_context* h, esvo_context::TickState& tk, const u32*
     }
   }
   if (h->tl_on && h->tl_ref && n && tk.timed) {
-    const int fr[8] = {EV_T0, EV_BM0, EV_BM1, EV_S1, EV_LM0, EV_LM1, EV_S2, EV_CNT};
-    std::array<float, 8> row;
-    for (int i = 0; i < 8; ++i) { row[i] = -1.f; if (hipEventElapsedTime(&row[i], h->tl_ref, E(fr[i])) != hipSuccess) (void)hipGetLastError(); }
+    std::array<float, 8> row;  // FE_T0 .. FE_CNT
+    for (int i = 0; i < 8; ++i) { row[i] = -1.f; if (hipEventElapsedTime(&row[i], h->tl_ref, ev.e[i]) != hipSuccess) (void)hipGetLastError(); }
     h->tl_front.push_back(row);
   }
   tk.max_kept = (h->sharded && n) ? cnt[CNT_MAX_KEPT] : 0;
@@ -606,19 +603,20 @@ static int pipeline_resync(esvo_context* h, float wait_ms, double now_ms) {
 // the back stage of two ticks ago (long finished), whose pinned table and event set are reused; its timings are
 // collected then.
 int tick_phase2(esvo_context* h, int fp) {
-  esvo_context::TickState& tk = h->tk[fp];
+  FrontSlot& F = h->front[fp];
+  TickState& tk = F.tk;
   h->xchg_send = h->xchg_recv = nullptr;
   h->xchg_block = 0;
   if (h->sharded) {  // the band mode's frame out of exchange 2, the back stream behind it (api_shard.hip)
     int rc = shard_scatter_frame(h, tk);
     if (rc) return rc;
   } else {
-    HIPCHK(hipStreamWaitEvent(h->stream_b, h->evt[EV_CNT + fp * EV_FRONT_STRIDE], 0));
+    HIPCHK(hipStreamWaitEvent(h->stream_b, F.ev->e[FE_CNT], 0));
   }
   const int par = h->par;
   h->par ^= 1;
   const auto t_wait0 = std::chrono::steady_clock::now();
-  HIPCHK(hipEventSynchronize(h->evt[EV_RG1 + par * EV_BACK_STRIDE]));
+  HIPCHK(hipEventSynchronize(h->back[par].ev.e[BE_RG1]));
   if (!h->sharded) {
     const auto t_wait1 = std::chrono::steady_clock::now();
     int rcr = pipeline_resync(h, std::chrono::duration<float, std::milli>(t_wait1 - t_wait0).count(),
@@ -633,16 +631,16 @@ int tick_phase2(esvo_context* h, int fp) {
     if (tk.lat) {  // the copy rides on run_fuse's first launch (context.hpp, DeferredCopies)
       h->pro = esvo_context::DeferredCopies();
       h->pro.active = true;
-      h->pro.a_src = h->d_stage[fp]; h->pro.a_dst = h->d_win + tk.off; h->pro.a_bytes = sizeof(DevPoint) * tk.points;
-      h->pro.ev_a = EV_STG + fp * EV_FRONT_STRIDE;
+      h->pro.a_src = F.d_stage; h->pro.a_dst = h->d_win + tk.off; h->pro.a_bytes = sizeof(DevPoint) * tk.points;
+      h->pro.ev_a = F.ev->e[FE_STG];
       if (tk.gather && tk.points) {
-        h->pro.a_src = h->d_pt_slots2[fp]; h->pro.a_flags = h->d_pt_flags2[fp]; h->pro.a_prefix = h->d_pt_prefix2[fp]; h->pro.a_slots = tk.n;
-        h->gather_guard[fp] = true;  // the next LM launch of this parity waits for EV_STG (tick_phase0)
+        h->pro.a_src = F.d_pt_slots; h->pro.a_flags = F.d_pt_flags; h->pro.a_prefix = F.d_pt_prefix; h->pro.a_slots = tk.n;
+        F.gather_guard = true;  // the next LM launch of this parity waits for FE_STG (tick_phase0)
       }
     } else {
       if (tk.points)
-        HIPCHK(hipMemcpyAsync(h->d_win + tk.off, h->d_stage[fp], sizeof(DevPoint) * tk.points, hipMemcpyDeviceToDevice, h->stream_b));
-      HIPCHK(hipEventRecord(h->evt[EV_STG + fp * EV_FRONT_STRIDE], h->stream_b));
+        HIPCHK(hipMemcpyAsync(h->d_win + tk.off, F.d_stage, sizeof(DevPoint) * tk.points, hipMemcpyDeviceToDevice, h->stream_b));
+      HIPCHK(hipEventRecord(F.ev->e[FE_STG], h->stream_b));
     }
   }
   rc = commit_frame(h, tk.off, tk.points, nullptr, tk.n_pose, tk.pose_buf);
@@ -683,7 +681,7 @@ int finalize_tick_stats(esvo_context* h) {
   collect_ts_timing(h);
   collect_back(h, h->par);
   collect_back(h, h->par ^ 1);
-  if (tick_done && h->tk[h->fpar].timed && h->back_timed[h->par ^ 1]) hipEventElapsedTime(&h->stats.ms_tick_total, h->evt[EV_T0 + h->fpar * EV_FRONT_STRIDE], h->evt[EV_RG1 + (h->par ^ 1) * EV_BACK_STRIDE]);
+  if (tick_done && h->front_cur().tk.timed && h->back[h->par ^ 1].timed) hipEventElapsedTime(&h->stats.ms_tick_total, h->front_cur().ev->e[FE_T0], h->back[h->par ^ 1].ev.e[BE_RG1]);
   return ESVO_OK;
 }
 }  // namespace esvo_host
@@ -728,7 +726,7 @@ extern "C" int esvo_map_tick(esvo_handle h, uint64_t t_ns, const uint64_t* pose_
   if (!rc) rc = tick_phase1_enqueue(h);
   h->stage_events_on = true;
   if (!rc) {
-    h->lat_last = h->tk[h->fpar].lat;
+    h->lat_last = h->front_cur().tk.lat;
     if (!prev) h->lat_ticks++;
   }
   if (rc) {  // the failed tick leaves no trace: the previous one (if pending) stays pending on ITS parity and is
@@ -759,13 +757,14 @@ extern "C" int esvo_map_front(esvo_handle h, uint64_t t_ns, const uint64_t* pose
   if (rc) return rc;
   rc = tick_phase0(h, t_ns, pose_t_ns, pose_T, m);
   if (rc) return rc;
-  const u32 n = h->tk[h->fpar].n;
+  FrontSlot& F = h->front_cur();
+  const u32 n = F.tk.n;
   if (n) { rc = run_order_points(h, n, h->d_pts_tmp); if (rc) return rc; }
-  HIPCHK(hipMemcpyAsync(h->h_counters + CNT_ROW * h->fpar, h->d_counters, sizeof(u32) * CNT_ROW, hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(hipEventRecord(h->evt[EV_CNT + h->fpar * EV_FRONT_STRIDE], h->stream));
+  HIPCHK(hipMemcpyAsync(F.h_counters, F.d_counters, sizeof(u32) * CNT_ROW, hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipEventRecord(F.ev->e[FE_CNT], h->stream));
   rc = tick_phase1_collect(h, h->fpar);
   if (rc) return rc;
-  *n_points = h->tk[h->fpar].points;
+  *n_points = F.tk.points;
   return ESVO_OK;
 }
 

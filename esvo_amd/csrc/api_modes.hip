@@ -20,7 +20,7 @@ extern "C" int esvo_map_tick_bm_only(esvo_handle h, uint64_t t_ns, const uint64_
   u32 n = 0;
   u64 first = 0;
   rc = select_events(h, t_ns, &first, &n);
-  if (!rc) rc = upload_poses(h, pose_t_ns, pose_T, m, h->d_counters2[h->fpar ^ 1]);
+  if (!rc) rc = upload_poses(h, pose_t_ns, pose_T, m, h->front[h->fpar ^ 1].d_counters);
   if (rc) return rc;
   // This mode keeps maxNumFusionFrames frames of up to PROCESS_EVENT_NUM un-culled matches whatever the fusion strategy, while
   // the window ring is sized for the normal policy (max_window_points): a CONST_POINTS preset with a small point budget and
@@ -33,8 +33,9 @@ extern "C" int esvo_map_tick_bm_only(esvo_handle h, uint64_t t_ns, const uint64_
     FAIL(ESVO_ERR_CAPACITY, "PURE_BLOCK_MATCHING window (maxNumFusionFrames frames of up to PROCESS_EVENT_NUM matches) "
                             "does not fit the fusion window ring: raise max_window_points");
   switch_front_parity(h);
-  HIPCHK(hipStreamWaitEvent(h->stream, h->evt[EV_RG1 + h->par * EV_BACK_STRIDE], 0));
-  hipEventRecord(h->evt[EV_T0 + h->fpar * EV_FRONT_STRIDE], h->stream);
+  FrontSlot& F = h->front_cur();
+  HIPCHK(hipStreamWaitEvent(h->stream, h->back[h->par].ev.e[BE_RG1], 0));
+  hipEventRecord(F.ev->e[FE_T0], h->stream);
   const u32* sel = nullptr;
   if (h->prm.denoising && n) {
     rc = denoise_select(h, n, &n);
@@ -47,7 +48,7 @@ extern "C" int esvo_map_tick_bm_only(esvo_handle h, uint64_t t_ns, const uint64_
     if (rc) return rc;
     rc = run_order_matches(h, n, false);
     if (rc) return rc;
-    launch_matches_to_points(h->d_matches, h->d_counters + CNT_MATCHES, n, h->d_pts_tmp, h->dp, h->stream);
+    launch_matches_to_points(F.d_matches, F.d_counters + CNT_MATCHES, n, h->d_pts_tmp, h->dp, h->stream);
     HIPCHK(hipGetLastError());
     rc = read_counters(h);
     if (rc) return rc;
@@ -87,11 +88,12 @@ extern "C" int esvo_map_fuse_matches_naive(esvo_handle h, const esvo_match_t* ma
   rc = drain_lm_and_back(h);  // the staging buffers and the ring may still be read by work in flight
   if (rc) return rc;
   const u32 n32 = (u32)n;
+  FrontSlot& F = h->front_cur();
   if (n) {
-    HIPCHK(hipMemcpyAsync(h->d_matches, matches, sizeof(esvo_match_t) * n, hipMemcpyHostToDevice, h->stream));
-    HIPCHK(hipMemcpyAsync(h->d_counters, &n32, sizeof(u32), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(hipMemcpyAsync(F.d_matches, matches, sizeof(esvo_match_t) * n, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(hipMemcpyAsync(F.d_counters, &n32, sizeof(u32), hipMemcpyHostToDevice, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));  // n32 / matches are borrowed
-    launch_matches_to_points(h->d_matches, h->d_counters + CNT_MATCHES, n32, h->d_pts_tmp, h->dp, h->stream);
+    launch_matches_to_points(F.d_matches, F.d_counters + CNT_MATCHES, n32, h->d_pts_tmp, h->dp, h->stream);
     HIPCHK(hipGetLastError());
   }
   // the frame that leaves at this call leaves first (its ring space is free: stream_b was drained above) -- probed on a copy
@@ -209,14 +211,15 @@ extern "C" int esvo_map_init_sgm(esvo_handle h, const uint8_t* ts_left, const ui
   u32 n = 0;
   rc = sgm_select(h, &first, &n);
   if (rc) return rc;
-  HIPCHK(hipMemsetAsync(h->d_counters, 0, sizeof(u32) * CNT_ROW, h->stream));
+  FrontSlot& F = h->front_cur();
+  HIPCHK(hipMemsetAsync(F.d_counters, 0, sizeof(u32) * CNT_ROW, h->stream));
   u32 count = 0;
   if (n) {
-    HIPCHK(hipStreamWaitEvent(h->stream, h->evt[EV_RG1 + h->par * EV_BACK_STRIDE], 0));
-    launch_sgm_points(h->d_ring[0], first, h->ring_cap, n, h->d_lut, h->d_sgm_disp, h->d_pt_slots, h->d_pt_flags, h->dp, h->stream);
-    launch_exclusive_scan_u32(h->d_pt_flags, h->d_pt_prefix, h->d_counters + CNT_POINTS, h->d_scan_tmp, n, h->stream);
-    HIPCHK(hipMemcpyAsync(h->d_counters + CNT_MATCHES, &n, sizeof(u32), hipMemcpyHostToDevice, h->stream));  // compaction bound (n_in of compact_points), behind the memset above
-    launch_compact_points(h->d_pt_slots, h->d_pt_flags, h->d_pt_prefix, h->d_counters + CNT_MATCHES, n, h->d_pts_tmp, h->stream);
+    HIPCHK(hipStreamWaitEvent(h->stream, h->back[h->par].ev.e[BE_RG1], 0));
+    launch_sgm_points(h->d_ring[0], first, h->ring_cap, n, h->d_lut, h->d_sgm_disp, F.d_pt_slots, F.d_pt_flags, h->dp, h->stream);
+    launch_exclusive_scan_u32(F.d_pt_flags, F.d_pt_prefix, F.d_counters + CNT_POINTS, h->d_scan_tmp, n, h->stream);
+    HIPCHK(hipMemcpyAsync(F.d_counters + CNT_MATCHES, &n, sizeof(u32), hipMemcpyHostToDevice, h->stream));  // compaction bound (n_in of compact_points), behind the memset above
+    launch_compact_points(F.d_pt_slots, F.d_pt_flags, F.d_pt_prefix, F.d_counters + CNT_MATCHES, n, h->d_pts_tmp, h->stream);
     rc = read_counters(h);
     if (rc) return rc;
     count = h->h_counters[CNT_POINTS];
@@ -261,18 +264,19 @@ namespace esvo_host {
 // dqvDepthPoints_.push_back + pop to maxNumFusionFrames_ (:357-359), naive_propagation of every frame, newest first, into a new
 // DepthFrame at the observation's pose (:360-361).  The caller has drained the other streams and probed the window ring for n points.
 static int sgm_frame_and_propagate(esvo_context* h, const esvo_event_t* d_ev, u64 first, u64 cap, int reverse, u32 n, u32* count_out) {
-  u32* cnt = h->d_counters + CNT_SCRATCH;  // the mode's four statistics words (common.hpp)
-  HIPCHK(hipMemsetAsync(h->d_counters, 0, sizeof(u32) * CNT_ROW, h->stream));
+  FrontSlot& F = h->front_cur();
+  u32* cnt = F.d_counters + CNT_SCRATCH;  // the mode's four statistics words (common.hpp)
+  HIPCHK(hipMemsetAsync(F.d_counters, 0, sizeof(u32) * CNT_ROW, h->stream));
   HIPCHK(hipEventRecord(h->evt_sgm[1], h->stream));
   u32 count = 0;
   esvo_sgm_stats_t& g = h->sgm_stats;
   g.events = n; g.on_image = g.matched_columns = g.disp_ok = g.points = g.zero_disp = 0;
   int rc;
   if (n) {
-    launch_sgm_tick_points(d_ev, first, cap, reverse, n, h->d_lut, h->d_sgm_disp, h->d_pt_slots, h->d_pt_flags, cnt, h->dp, h->stream);
-    launch_exclusive_scan_u32(h->d_pt_flags, h->d_pt_prefix, h->d_counters + CNT_POINTS, h->d_scan_tmp, n, h->stream);
-    HIPCHK(hipMemcpyAsync(h->d_counters + CNT_MATCHES, &n, sizeof(u32), hipMemcpyHostToDevice, h->stream));  // compaction bound (n_in of compact_points), behind the memset above
-    launch_compact_points(h->d_pt_slots, h->d_pt_flags, h->d_pt_prefix, h->d_counters + CNT_MATCHES, n, h->d_pts_tmp, h->stream);
+    launch_sgm_tick_points(d_ev, first, cap, reverse, n, h->d_lut, h->d_sgm_disp, F.d_pt_slots, F.d_pt_flags, cnt, h->dp, h->stream);
+    launch_exclusive_scan_u32(F.d_pt_flags, F.d_pt_prefix, F.d_counters + CNT_POINTS, h->d_scan_tmp, n, h->stream);
+    HIPCHK(hipMemcpyAsync(F.d_counters + CNT_MATCHES, &n, sizeof(u32), hipMemcpyHostToDevice, h->stream));  // compaction bound (n_in of compact_points), behind the memset above
+    launch_compact_points(F.d_pt_slots, F.d_pt_flags, F.d_pt_prefix, F.d_counters + CNT_MATCHES, n, h->d_pts_tmp, h->stream);
     HIPCHK(hipGetLastError());
     HIPCHK(hipEventRecord(h->evt_sgm[2], h->stream));
     rc = read_counters(h);  // the one host read of the tick
@@ -289,7 +293,7 @@ static int sgm_frame_and_propagate(esvo_context* h, const esvo_event_t* d_ev, u6
   // count <= n, for which the caller probed the ring; dp.updatePose(T_world_cam) of the observation: one pose per frame
   rc = commit_naive_frame(h, h->d_pts_tmp, count, h->T_world_obs, 1, 0);
   if (rc) return rc;
-  const bool timed = h->back_timed[h->par ^ 1];  // (the parity that fusion took)
+  const bool timed = h->back[h->par ^ 1].timed;  // (the parity that fusion took)
   h->committed_t_ns = h->obs_t_ns;
   g.ms_points = g.ms_propagate = 0.f;
   if (hipEventElapsedTime(&g.ms_points, h->evt_sgm[1], h->evt_sgm[2]) != hipSuccess) (void)hipGetLastError();

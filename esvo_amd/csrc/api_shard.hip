@@ -61,7 +61,8 @@ static inline size_t shard_codes_block_routed(u32 n) { return (((size_t)n + 15) 
 // matches, LM + cull on it, then the (matched, kept) bits of the own slots in a block that spans the whole tick.
 // keep_flags / keep_prefix (Denoising): per walk position of the RAW selection (n_raw events) whether the event is kept and how
 // many kept ones precede it -- the slots are those of the kept sequence (n of them), as on one GPU.
-static int routed_front(esvo_context* h, esvo_context::TickState& tk, u32 n, const u32* keep_flags, const u32* keep_prefix, u32 n_raw = 0) {
+static int routed_front(esvo_context* h, TickState& tk, u32 n, const u32* keep_flags, const u32* keep_prefix, u32 n_raw = 0) {
+  FrontSlot& F = h->front_cur();
   const u32 N = (u32)h->dp.ev_nshards;
   const u32 n_loc = tk.n_loc, n_own = tk.n_own;
   int rc;
@@ -74,20 +75,20 @@ static int routed_front(esvo_context* h, esvo_context::TickState& tk, u32 n, con
     a.lut = h->d_lut; a.mask = h->d_mask;
     a.pose_sec = h->d_pose_sec; a.n_pose = h->n_pose;
     a.out_slots = h->d_match_slots; a.out_flags = h->d_match_flags;
-    a.fail_counters = h->d_counters;
-    if (h->stage_events_on) hipEventRecord(h->evt[EV_BM0 + h->fpar * EV_FRONT_STRIDE], h->stream);
+    a.fail_counters = F.d_counters;
+    if (h->stage_events_on) hipEventRecord(F.ev->e[FE_BM0], h->stream);
     launch_bm_match(a, h->dp, h->stream);
-    if (h->stage_events_on) hipEventRecord(h->evt[EV_BM1 + h->fpar * EV_FRONT_STRIDE], h->stream);
+    if (h->stage_events_on) hipEventRecord(F.ev->e[FE_BM1], h->stream);
     HIPCHK(hipGetLastError());
     // dense list of the own matches (count -> CNT_OWN_MATCHES); the slot of each follows from its walk position (shard_codes_routed)
     if (scan_compact_is_small(n_loc)) {
-      launch_scan_compact_matches_small(h->d_match_flags, h->d_match_prefix, h->d_counters + CNT_OWN_MATCHES, n_loc, h->d_match_slots, h->d_matches, nullptr,
+      launch_scan_compact_matches_small(h->d_match_flags, h->d_match_prefix, F.d_counters + CNT_OWN_MATCHES, n_loc, h->d_match_slots, F.d_matches, nullptr,
                                         h->stream);
     } else {
-      launch_exclusive_scan_u32(h->d_match_flags, h->d_match_prefix, h->d_counters + CNT_OWN_MATCHES, h->d_scan_tmp, n_loc, h->stream);
-      launch_compact_matches(h->d_match_slots, h->d_match_flags, h->d_match_prefix, n_loc, h->d_matches, nullptr, h->stream);
+      launch_exclusive_scan_u32(h->d_match_flags, h->d_match_prefix, F.d_counters + CNT_OWN_MATCHES, h->d_scan_tmp, n_loc, h->stream);
+      launch_compact_matches(h->d_match_slots, h->d_match_flags, h->d_match_prefix, n_loc, F.d_matches, nullptr, h->stream);
     }
-    if (h->stage_events_on) hipEventRecord(h->evt[EV_S1 + h->fpar * EV_FRONT_STRIDE], h->stream);
+    if (h->stage_events_on) hipEventRecord(F.ev->e[FE_S1], h->stream);
     HIPCHK(hipGetLastError());
     // (the ring also holds the raster's halo events: the launch -- and with it the kernel's layout -- is bounded by the OWN
     //  events of the selection, counted at ingest)
@@ -95,11 +96,11 @@ static int routed_front(esvo_context* h, esvo_context::TickState& tk, u32 n, con
     if (rc) return rc;
   } else {  // no event of this tick in the band: the stage events the statistics read are still recorded
     if (h->stage_events_on)
-      for (int e : {EV_BM0, EV_BM1, EV_S1, EV_LM0, EV_LM1}) hipEventRecord(h->evt[e + h->fpar * EV_FRONT_STRIDE], h->stream);
+      for (int e : {FE_BM0, FE_BM1, FE_S1, FE_LM0, FE_LM1}) hipEventRecord(F.ev->e[e], h->stream);
   }
   const size_t nb = shard_codes_block_routed(n);
   HIPCHK(hipMemsetAsync(h->d_codes_send, 0, nb, h->stream));
-  launch_shard_codes_routed(h->d_matches, h->d_lkeep, h->d_counters + CNT_OWN_MATCHES, n_own, n, (u32)h->dp.num_threads, h->d_own_w,
+  launch_shard_codes_routed(F.d_matches, h->d_lkeep, F.d_counters + CNT_OWN_MATCHES, n_own, n, (u32)h->dp.num_threads, h->d_own_w,
                             reinterpret_cast<u32*>(h->d_codes_send.get()), h->stream);
   HIPCHK(hipGetLastError());
   h->xchg_send = h->d_codes_send;
@@ -113,7 +114,7 @@ static int routed_front(esvo_context* h, esvo_context::TickState& tk, u32 n, con
 // whose RAW row lies in its band -- every selected event has exactly one such rank -- and the ranks all-gather them as one bit per
 // walk position of the selection.  The kept sequence (which events, in which order, how many) is then the one-GPU one on every rank.
 static inline size_t denoise_bits_block(u32 n) { return (((size_t)n + 31) / 32 * 4 + 7) / 8 * 8; }
-static int routed_denoise_begin(esvo_context* h, esvo_context::TickState& tk) {
+static int routed_denoise_begin(esvo_context* h, TickState& tk) {
   const u32 N = (u32)h->dp.ev_nshards;
   const size_t nb = denoise_bits_block(tk.n);
   HIPCHK(hipMemsetAsync(h->d_codes_send, 0, nb, h->stream));
@@ -128,7 +129,7 @@ static int routed_denoise_begin(esvo_context* h, esvo_context::TickState& tk) {
 }
 int routed_denoise_resume(esvo_context* h) {
   h->dn_pending = false;
-  esvo_context::TickState& tk = h->tk[h->fpar];
+  TickState& tk = h->front_cur().tk;
   const u32 N = (u32)h->dp.ev_nshards, n_raw = tk.n;
   if (!h->d_dn_flags) {
     HIPCHK(h->d_dn_flags.alloc(2 * (size_t)h->max_ev));
@@ -137,7 +138,7 @@ int routed_denoise_resume(esvo_context* h) {
   u32* prefix = h->d_dn_flags + h->max_ev;
   launch_denoise_bits_unpack(reinterpret_cast<const u32*>((N > 1 ? h->d_codes_all : h->d_codes_send).get()), (u32)(denoise_bits_block(n_raw) / 4), N, n_raw,
                              flags, h->stream);
-  launch_exclusive_scan_u32(flags, prefix, h->d_counters + CNT_DENOISE_KEPT, h->d_scan_tmp, n_raw, h->stream);
+  launch_exclusive_scan_u32(flags, prefix, h->front_cur().d_counters + CNT_DENOISE_KEPT, h->d_scan_tmp, n_raw, h->stream);
   int rc = read_counters(h);  // the kept count sizes everything behind it (as on one GPU: one read-back)
   if (rc) return rc;
   const u32 n = tk.n = h->h_counters[CNT_DENOISE_KEPT];
@@ -148,7 +149,7 @@ int routed_denoise_resume(esvo_context* h) {
 }
 
 // phase 0 of a sharded tick behind the event selection (tick_phase0): the routed front stage, or:
-int shard_front(esvo_context* h, esvo_context::TickState& tk, u32 n, const u32* sel) {
+int shard_front(esvo_context* h, TickState& tk, u32 n, const u32* sel) {
   int rc;
   if (h->routed) {
     if (h->prm.denoising) {  // the denoising mask first: its bits are exchanged, phase 0 is called again behind that (ESVO_AGAIN)
@@ -170,7 +171,7 @@ int shard_front(esvo_context* h, esvo_context::TickState& tk, u32 n, const u32* 
   if (rc) return rc;
   const size_t nb = shard_codes_block(n, N);
   HIPCHK(hipMemsetAsync(h->d_codes_send, 0, nb, h->stream));
-  launch_shard_codes(h->d_own_w, h->d_lkeep, h->d_counters + CNT_OWN_MATCHES, own, N, h->d_codes_send, h->stream);
+  launch_shard_codes(h->d_own_w, h->d_lkeep, h->front_cur().d_counters + CNT_OWN_MATCHES, own, N, h->d_codes_send, h->stream);
   HIPCHK(hipGetLastError());
   h->xchg_send = h->d_codes_send;
   h->xchg_recv = N > 1 ? h->d_codes_all : h->d_codes_send;
@@ -178,7 +179,8 @@ int shard_front(esvo_context* h, esvo_context::TickState& tk, u32 n, const u32* 
   return ESVO_OK;
 }
 // phase 1 of a sharded tick (tick_phase1_enqueue): the frame's order from the exchanged codes, the rank's block of exchange 2
-int shard_order_points(esvo_context* h, esvo_context::TickState& tk) {
+int shard_order_points(esvo_context* h, TickState& tk) {
+  FrontSlot& F = h->front_cur();
   const u32 n = tk.n;
   const u32 N = (u32)h->dp.ev_nshards, r = (u32)h->dp.ev_shard, T = (u32)h->dp.num_threads;
   const u32 own = h->routed ? tk.n_own : (n > r ? (n - r + N - 1) / N : 0);
@@ -193,19 +195,19 @@ int shard_order_points(esvo_context* h, esvo_context::TickState& tk) {
   else
     launch_shard_unpack_codes(N > 1 ? h->d_codes_all : h->d_codes_send, (u32)shard_codes_block(n, N), N, n, h->d_codes, h->d_rank_kept,
                               h->stream);
-  if (tiled) launch_scan_down_code_bit0(h->d_codes, h->d_match_prefix, h->d_counters + CNT_MATCHES, h->d_scan_tmp, n, h->d_pt_flags, h->stream);
-  else launch_exclusive_scan_code_bit0(h->d_codes, h->d_match_prefix, h->d_counters + CNT_MATCHES, h->d_scan_tmp, n, h->d_pt_flags, h->stream);
-  launch_shard_keep_flags(h->d_codes, h->d_match_prefix, h->d_counters + CNT_MATCHES, n, T, h->d_pt_flags, h->d_pts_send, h->stream);
-  launch_exclusive_scan_u32(h->d_pt_flags, h->d_pt_prefix, h->d_counters + CNT_POINTS, h->d_scan_tmp, n, h->stream);
-  launch_shard_pack(h->d_own_w, h->d_lkeep, h->d_pt_slots, h->d_counters + CNT_OWN_MATCHES, own, h->d_match_prefix, h->d_counters + CNT_MATCHES,
-                    h->d_pt_prefix, T, h->d_pts_send, own, n, h->d_rank_kept, N, h->d_counters + CNT_MAX_KEPT, h->stream,
-                    h->routed ? h->d_counters + CNT_SCRATCH : nullptr);
-  if (tk.timed) hipEventRecord(h->evt[EV_S2 + h->fpar * EV_FRONT_STRIDE], h->stream);
+  if (tiled) launch_scan_down_code_bit0(h->d_codes, h->d_match_prefix, F.d_counters + CNT_MATCHES, h->d_scan_tmp, n, F.d_pt_flags, h->stream);
+  else launch_exclusive_scan_code_bit0(h->d_codes, h->d_match_prefix, F.d_counters + CNT_MATCHES, h->d_scan_tmp, n, F.d_pt_flags, h->stream);
+  launch_shard_keep_flags(h->d_codes, h->d_match_prefix, F.d_counters + CNT_MATCHES, n, T, F.d_pt_flags, h->d_pts_send, h->stream);
+  launch_exclusive_scan_u32(F.d_pt_flags, F.d_pt_prefix, F.d_counters + CNT_POINTS, h->d_scan_tmp, n, h->stream);
+  launch_shard_pack(h->d_own_w, h->d_lkeep, F.d_pt_slots, F.d_counters + CNT_OWN_MATCHES, own, h->d_match_prefix, F.d_counters + CNT_MATCHES,
+                    F.d_pt_prefix, T, h->d_pts_send, own, n, h->d_rank_kept, N, F.d_counters + CNT_MAX_KEPT, h->stream,
+                    h->routed ? F.d_counters + CNT_SCRATCH : nullptr);
+  if (tk.timed) hipEventRecord(F.ev->e[FE_S2], h->stream);
   HIPCHK(hipGetLastError());
   return ESVO_OK;
 }
 // what opens phase 2 of a sharded tick (tick_phase2)
-int shard_scatter_frame(esvo_context* h, esvo_context::TickState& tk) {
+int shard_scatter_frame(esvo_context* h, TickState& tk) {
   const u32 N = (u32)h->dp.ev_nshards;
   launch_shard_scatter(N > 1 ? h->d_pts_all : h->d_pts_send, 1 + (size_t)tk.max_kept * (sizeof(DevPoint) / 8), N, tk.max_kept,
                        h->d_win + tk.off, tk.n, h->stream, h->routed ? h->d_halo_viol : nullptr);
@@ -222,7 +224,7 @@ extern "C" int esvo_shard_tick_phase(esvo_handle h, int phase, uint64_t t_ns, co
   if (!h->sharded) FAIL(ESVO_ERR_STATE, "call esvo_shard_set_band first");
   HIPCHK(hipSetDevice(h->device));
   // (stage-timing events are sampled, context.hpp lat_ticks: phase 0 decides for the tick; switched back on when the call returns)
-  StageEventsScope timed_scope(h, phase == 0 ? true : h->tk[h->fpar].timed);
+  StageEventsScope timed_scope(h, phase == 0 ? true : h->front_cur().tk.timed);
   switch (phase) {
     case 0:
       if (!h->dn_pending && (!pose_t_ns || !pose_T)) return ESVO_ERR_INVALID_ARG;

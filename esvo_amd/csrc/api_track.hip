@@ -25,13 +25,13 @@ int esvo_track_set_current(esvo_handle h, const uint8_t* ts_left, int kernel_siz
     else HIPCHK(hipMemcpyAsync(h->d_trk_blur, src, npx, hipMemcpyDeviceToDevice, h->stream_t));
   } else {
     // The resident left surface belongs to the mapper group, whose thread may render the next one at any moment: the read
-    // is enqueued behind the newest render (EV_R1) and marked, under mu_ts, so that the next render queues behind it.
+    // is enqueued behind the newest render (TE_R1) and marked, under mu_ts, so that the next render queues behind it.
     std::lock_guard<std::mutex> lt(h->mu_ts);
     if (!h->ts_valid[0]) FAIL(ESVO_ERR_STATE, "no device-resident left Time Surface: call esvo_ts_render(h, 0, ...) first");
-    // (a render that runs alone records EV_R1 only once the tracker has shown up -- context.hpp, trk_used; renders are enqueued
+    // (a render that runs alone records TE_R1 only once the tracker has shown up -- context.hpp, trk_used; renders are enqueued
     //  under mu_ts, held here: the first call drains the front stream instead, every later render has recorded the event)
     if (!h->trk_used.exchange(true)) HIPCHK(hipStreamSynchronize(h->stream));
-    HIPCHK(hipStreamWaitEvent(h->stream_t, h->evt[EV_R1], 0));  // the render of camera 0 on the front stream
+    HIPCHK(hipStreamWaitEvent(h->stream_t, h->ts_ev[0].e[TE_R1], 0));  // the render of camera 0 on the front stream
     if (kernel_size == 5) launch_gaussian5(src, h->d_trk_blur, h->W, h->H, h->stream_t);
     else HIPCHK(hipMemcpyAsync(h->d_trk_blur, src, npx, hipMemcpyDeviceToDevice, h->stream_t));
     HIPCHK(hipEventRecord(h->evt_trk_read, h->stream_t));

@@ -8,10 +8,10 @@ void collect_ts_timing(esvo_context* h, int only) {
   for (int cam = 0; cam < 2; ++cam) {
     if (!h->ts_timing_pending[cam] || (only >= 0 && cam != only)) continue;
     h->ts_timing_pending[cam] = false;
-    const int o = cam * EV_TS_STRIDE;
+    const TsEvents& T = h->ts_ev[cam];
     float sc = 0, rd = 0;
-    if (hipEventElapsedTime(&sc, h->evt[EV_SC0 + o], h->evt[EV_SC1 + o]) == hipSuccess &&
-        hipEventElapsedTime(&rd, h->evt[EV_SC1 + o], h->evt[EV_R1 + o]) == hipSuccess) {
+    if (hipEventElapsedTime(&sc, T.e[TE_SC0], T.e[TE_SC1]) == hipSuccess &&
+        hipEventElapsedTime(&rd, T.e[TE_SC1], T.e[TE_R1]) == hipSuccess) {
       h->stats.ms_ts_scatter = h->stats.ms_kernel[0] = sc;
       h->stats.ms_ts_render = h->stats.ms_kernel[1] = rd;
       h->stats.sum_ms_kernel[0] += sc;
@@ -144,8 +144,8 @@ int ts_render_pair(esvo_context* h, uint64_t t_ns, uint8_t* const obs_out[2]) {
         FAIL(ESVO_ERR_STATE, "esvo_ts_render: t_ns precedes events of an earlier render (render times must not decrease; esvo_reset to replay)");
     }
     for (int cam = 0; cam < 2; ++cam)
-      if (h->ts_timing_pending[cam] && hipEventQuery(h->evt[EV_R1 + cam * EV_TS_STRIDE]) == hipSuccess) collect_ts_timing(h, cam);
-    if (timed) hipEventRecord(h->evt[EV_SC0], h->stream);
+      if (h->ts_timing_pending[cam] && hipEventQuery(h->ts_ev[cam].e[TE_R1]) == hipSuccess) collect_ts_timing(h, cam);
+    if (timed) hipEventRecord(h->ts_ev[0].e[TE_SC0], h->stream);
     TsScatterSegs g;
     int n_seg = 0;
     if (h->tsq_len) { queue_prepare(h, 0, (u64)t_ns); queue_prepare(h, 1, (u64)t_ns); }
@@ -169,7 +169,7 @@ int ts_render_pair(esvo_context* h, uint64_t t_ns, uint8_t* const obs_out[2]) {
       h->scattered[cam] = upto[cam];
     }
     launch_ts_scatter_segs(g, n_seg, h->W, h->H, h->stream);
-    if (timed) hipEventRecord(h->evt[EV_SC1], h->stream);
+    if (timed) hipEventRecord(h->ts_ev[0].e[TE_SC1], h->stream);
   }
   TsPair c;
   for (int cam = 0; cam < 2; ++cam) {
@@ -183,7 +183,7 @@ int ts_render_pair(esvo_context* h, uint64_t t_ns, uint8_t* const obs_out[2]) {
     // (a routed band handle renders the rows of its band + halo only: h->rband_*, whole tiles)
     launch_ts_render_pair(c, h->W, h->H, (u64)t_ns, h->prm.decay_ms / 1000.0, h->prm.ignore_polarity, h->prm.median_blur_kernel_size,
                           h->stream, h->routed ? h->rband_y0 : 0, h->routed ? h->rband_y1 : -1);
-    if (timed || h->trk_used.load()) hipEventRecord(h->evt[EV_R1], h->stream);  // (also what esvo_track_set_current waits for)
+    if (timed || h->trk_used.load()) hipEventRecord(h->ts_ev[0].e[TE_R1], h->stream);  // (also what esvo_track_set_current waits for)
     HIPCHK(hipGetLastError());
     h->ts_valid[0] = h->ts_valid[1] = true;
     for (int cam = 0; cam < 2; ++cam) { int rch = hist_store(h, cam, t_ns, h->d_ts[cam], false); if (rch) return rch; }  // (history off: nothing)
@@ -705,12 +705,12 @@ int esvo_ts_render_forward(esvo_handle h, int cam, uint64_t t_ns, uint8_t* out_m
     launch_ts_render_forward(h->d_sae[cam], h->d_fwd_off[cam], h->d_fwd_src[cam], h->d_fwd_lut[cam], h->d_fwd_val, cam ? h->d_raw1 : h->d_raw,
                              h->d_ts[cam], h->W, h->H, (u64)t_ns, h->prm.decay_ms / 1000.0, h->prm.ignore_polarity,
                              h->prm.median_blur_kernel_size, h->stream);
-    if (cam == 0) hipEventRecord(h->evt[EV_R1], h->stream);  // what esvo_track_set_current waits for
+    if (cam == 0) hipEventRecord(h->ts_ev[0].e[TE_R1], h->stream);  // what esvo_track_set_current waits for
     HIPCHK(hipGetLastError());
     h->ts_valid[cam] = true;
     { int rch = hist_store(h, cam, t_ns, h->d_ts[cam], false); if (rch) return rch; }  // the Time-Surface history (off: nothing)
   }
-  if (cam == 0) h->ts_timing_pending[0] = false;  // EV_R1 no longer belongs to a timed scatter / render pair
+  if (cam == 0) h->ts_timing_pending[0] = false;  // TE_R1 no longer belongs to a timed scatter / render pair
   h->stats.ts_frames[cam]++;
   if (out_mono8) {
     HIPCHK(hipMemcpyAsync(out_mono8, h->d_ts[cam], (size_t)h->W * h->H, hipMemcpyDeviceToHost, h->stream));
@@ -723,7 +723,7 @@ int esvo_ts_render(esvo_handle h, int cam, uint64_t t_ns, uint8_t* out_mono8) {
   if (!h || cam < 0 || cam > 1) return ESVO_ERR_INVALID_ARG;
   API_LOCK(h);
   HIPCHK(hipSetDevice(h->device));
-  const int evo = cam * EV_TS_STRIDE;
+  const TsEvents& T = h->ts_ev[cam];
   const bool timed = esvo_stage_timed(h);  // sampled for renders that run alone (context.hpp, lat_ticks)
   {
     std::lock_guard<std::mutex> lr(h->mu_ring);
@@ -736,8 +736,8 @@ int esvo_ts_render(esvo_handle h, int cam, uint64_t t_ns, uint8_t* out_mono8) {
     // events already scattered would read pixels as empty where getMostRecentEventBeforeT finds the older event.
     if (!h->tsq_len && upto < h->scattered[cam])
       FAIL(ESVO_ERR_STATE, "esvo_ts_render: t_ns precedes events of an earlier render (render times must not decrease; esvo_reset to replay)");
-    if (h->ts_timing_pending[cam] && hipEventQuery(h->evt[EV_R1 + evo]) == hipSuccess) collect_ts_timing(h, cam);
-    if (timed) hipEventRecord(h->evt[EV_SC0 + evo], h->stream);
+    if (h->ts_timing_pending[cam] && hipEventQuery(T.e[TE_R1]) == hipSuccess) collect_ts_timing(h, cam);
+    if (timed) hipEventRecord(T.e[TE_SC0], h->stream);
     if (h->tsq_len) queue_prepare(h, cam, (u64)t_ns);
     else if (upto > h->scattered[cam]) {
       u64 a = h->scattered[cam];
@@ -753,7 +753,7 @@ int esvo_ts_render(esvo_handle h, int cam, uint64_t t_ns, uint8_t* out_mono8) {
       h->scattered[cam] = upto;
       h->stats.events_scattered[cam] += total;
     }
-    if (timed) hipEventRecord(h->evt[EV_SC1 + evo], h->stream);
+    if (timed) hipEventRecord(T.e[TE_SC1], h->stream);
   }
   {
     std::lock_guard<std::mutex> lt(h->mu_ts);
@@ -761,7 +761,7 @@ int esvo_ts_render(esvo_handle h, int cam, uint64_t t_ns, uint8_t* out_mono8) {
     launch_ts_render(h->d_sae[cam], h->d_fixmap[cam], h->d_raw, h->d_ts[cam], h->W, h->H, (u64)t_ns, h->prm.decay_ms / 1000.0,
                      h->prm.ignore_polarity, h->prm.median_blur_kernel_size, h->stream, h->routed ? h->rband_y0 : 0,
                      h->routed ? h->rband_y1 : -1);
-    if (timed || (cam == 0 && h->trk_used.load())) hipEventRecord(h->evt[EV_R1 + evo], h->stream);
+    if (timed || (cam == 0 && h->trk_used.load())) hipEventRecord(T.e[TE_R1], h->stream);
     HIPCHK(hipGetLastError());
     h->ts_valid[cam] = true;
     { int rch = hist_store(h, cam, t_ns, h->d_ts[cam], false); if (rch) return rch; }  // the Time-Surface history (off: nothing)

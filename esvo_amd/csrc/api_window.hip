@@ -12,36 +12,35 @@ static int read_counters_b(esvo_context* h, int row, bool sync) {
 }
 // the back stage starts when everything enqueued on the front stream so far is done
 int back_after_front(esvo_context* h) {
-  HIPCHK(hipEventRecord(h->evt[EV_FRAME], h->stream));
-  HIPCHK(hipStreamWaitEvent(h->stream_b, h->evt[EV_FRAME], 0));
+  HIPCHK(hipEventRecord(h->ev_frame, h->stream));
+  HIPCHK(hipStreamWaitEvent(h->stream_b, h->ev_frame, 0));
   return ESVO_OK;
 }
 // timings and counters of a finished back stage
 void collect_back(esvo_context* h, int par) {
   if (!h->back_pending[par]) return;
   h->back_pending[par] = false;
-  const int o = par * EV_BACK_STRIDE;
+  const BackSlot& B = h->back[par];
   esvo_stats_t& s = h->stats;
-  s.last_fusions = h->h_cnt_b[CNTB_ROW * par + CNTB_FUSIONS];
+  s.last_fusions = B.h_cnt[CNTB_FUSIONS];
   if (h->routed && h->h_cnt_b[CNTB_ROW * CNTB_ROW_HALO + par]) {  // (the running total over all ranks: identical on every rank at this point of the call sequence)
     s.halo_violations = h->h_cnt_b[CNTB_ROW * CNTB_ROW_HALO + par];
     h->halo_error = true;
   }
-  if (h->prm.regularization) s.last_map_size = h->h_cnt_b[CNTB_ROW * par + CNTB_REG_ELEMS];  // alive cells of the band (exports refresh it)
-  if (!h->back_timed[par]) return;  // latency mode: this back stage's timings were not sampled (context.hpp, lat_ticks)
+  if (h->prm.regularization) s.last_map_size = B.h_cnt[CNTB_REG_ELEMS];  // alive cells of the band (exports refresh it)
+  if (!B.timed) return;  // latency mode: this back stage's timings were not sampled (context.hpp, lat_ticks)
   float fu = 0, cl = 0, rg = 0;
-  hipEventElapsedTime(&fu, h->evt[EV_FU0 + o], h->evt[EV_FU1 + o]);
-  hipEventElapsedTime(&cl, h->evt[EV_FU1 + o], h->evt[EV_CL1 + o]);
-  hipEventElapsedTime(&rg, h->evt[EV_CL1 + o], h->evt[EV_RG1 + o]);
+  hipEventElapsedTime(&fu, B.ev.e[BE_FU0], B.ev.e[BE_FU1]);
+  hipEventElapsedTime(&cl, B.ev.e[BE_FU1], B.ev.e[BE_CL1]);
+  hipEventElapsedTime(&rg, B.ev.e[BE_CL1], B.ev.e[BE_RG1]);
   s.ms_fusion = fu + cl;
   s.ms_regularization = rg;
   s.ms_kernel[4] = fu; s.ms_kernel[5] = cl; s.ms_kernel[6] = rg;
   s.sum_ms_kernel[4] += fu; s.sum_ms_kernel[5] += cl; s.sum_ms_kernel[6] += rg;
   h->ema_back_ms = h->ema_back_ms > 0.f ? 0.75f * h->ema_back_ms + 0.25f * (fu + cl + rg) : fu + cl + rg;
   if (h->tl_on && h->tl_ref) {
-    const int bk[4] = {EV_FU0, EV_FU1, EV_CL1, EV_RG1};
-    std::array<float, 4> row;
-    for (int i = 0; i < 4; ++i) { row[i] = -1.f; if (hipEventElapsedTime(&row[i], h->tl_ref, h->evt[bk[i] + o]) != hipSuccess) (void)hipGetLastError(); }
+    std::array<float, 4> row;  // BE_FU0 .. BE_RG1
+    for (int i = 0; i < 4; ++i) { row[i] = -1.f; if (hipEventElapsedTime(&row[i], h->tl_ref, B.ev.e[i]) != hipSuccess) (void)hipGetLastError(); }
     h->tl_back.push_back(row);
   }
 }
@@ -140,9 +139,9 @@ int flush_deferred_copies(esvo_context* h) {
   if (!d.active) return ESVO_OK;
   if (d.a_flags) launch_back_prologue(nullptr, nullptr, 0, d.a_src, d.a_dst, d.a_bytes, nullptr, nullptr, 0, h->stream_b, d.a_flags, d.a_prefix, d.a_slots);
   else if (d.a_bytes) HIPCHK(hipMemcpyAsync(d.a_dst, d.a_src, d.a_bytes, hipMemcpyDeviceToDevice, h->stream_b));
-  if (d.ev_a >= 0) HIPCHK(hipEventRecord(h->evt[d.ev_a], h->stream_b));
+  if (d.ev_a) HIPCHK(hipEventRecord(d.ev_a, h->stream_b));
   if (d.b_bytes) HIPCHK(hipMemcpyAsync(d.b_dst, d.b_src, d.b_bytes, hipMemcpyDeviceToDevice, h->stream_b));
-  if (d.ev_b >= 0) HIPCHK(hipEventRecord(h->evt[d.ev_b], h->stream_b));
+  if (d.ev_b) HIPCHK(hipEventRecord(d.ev_b, h->stream_b));
   return ESVO_OK;
 }
 // pose table of the frame: from the host (stage-wise API) or, in a tick, the front stage's device table
@@ -168,11 +167,11 @@ int commit_frame(esvo_context* h, u32 off, u32 count, const double* pose_T_host,
       HIPCHK(hipMemcpyAsync(dst, pin, sizeof(double) * 16 * m, hipMemcpyHostToDevice, h->stream_b));
       HIPCHK(hipEventRecord(h->pool_evt[ps], h->stream_b));
     } else if (h->pro.active) {  // latency mode: carried by run_fuse's first launch
-      h->pro.b_src = h->d_pose_T2[pose_buf]; h->pro.b_dst = dst; h->pro.b_bytes = sizeof(double) * 16 * m;
-      h->pro.ev_b = EV_POSE + pose_buf * EV_BACK_STRIDE;
+      h->pro.b_src = h->pose[pose_buf].d_T; h->pro.b_dst = dst; h->pro.b_bytes = sizeof(double) * 16 * m;
+      h->pro.ev_b = h->pose[pose_buf].released;
     } else {
-      HIPCHK(hipMemcpyAsync(dst, h->d_pose_T2[pose_buf], sizeof(double) * 16 * m, hipMemcpyDeviceToDevice, h->stream_b));
-      HIPCHK(hipEventRecord(h->evt[EV_POSE + pose_buf * EV_BACK_STRIDE], h->stream_b));
+      HIPCHK(hipMemcpyAsync(dst, h->pose[pose_buf].d_T, sizeof(double) * 16 * m, hipMemcpyDeviceToDevice, h->stream_b));
+      HIPCHK(hipEventRecord(h->pose[pose_buf].released, h->stream_b));
     }
   }
   h->frames.push_back(FrameRec{off, count, slot, 1});
@@ -187,8 +186,8 @@ int run_fuse(esvo_context* h, int par, const double* T_world_obs, bool naive) {
   // frames newest -> oldest (esvo_Mapping.cpp:372-377)
   // The table is laid out COMPACTLY for the frames in use -- [cum (nf + 1) | off (nf) | slot (nf)] -- so that one small
   // upload carries it (max_frames is sized for the worst case of CONST_POINTS, one point per frame; a tick uses a handful).
-  const size_t tab = 3 * (size_t)h->max_frames + 1;
-  u32* host = h->h_fr_table + (size_t)par * tab;
+  BackSlot& B = h->back[par];
+  u32* host = B.h_fr_table;
   u32 nf = 0;
   for (size_t q = h->frames.size(); q-- > 0;)
     if (h->frames[q].count) ++nf;  // empty frames contribute no point (DepthFusion::update loops over none)
@@ -206,8 +205,8 @@ int run_fuse(esvo_context* h, int par, const double* T_world_obs, bool naive) {
   }
   cum[nf] = total;
   hipStream_t sb = h->stream_b;
-  int tail_ev[2] = {-1, -1};
-  u32* dtab = h->d_fr_table + (size_t)par * tab;
+  hipEvent_t tail_ev[2] = {nullptr, nullptr};
+  u32* dtab = B.d_fr_table;
   if (h->pro.active) {  // latency mode: the frame's points and its pose table travel with the table (one launch, not three operations)
     const esvo_context::DeferredCopies d = h->pro;
     h->pro = esvo_context::DeferredCopies();
@@ -215,8 +214,7 @@ int run_fuse(esvo_context* h, int par, const double* T_world_obs, bool naive) {
                          d.a_flags, d.a_prefix, d.a_slots);
     // "staging buffer / pose table free again": recorded at the END of this back stage, not here between two dependent launches
     // (~5 us each); who waits for them -- the front stage two ticks on -- comes long after either point
-    tail_ev[0] = d.ev_a;
-    tail_ev[1] = d.ev_b;
+    tail_ev[0] = d.ev_a; tail_ev[1] = d.ev_b;
   } else {
     launch_upload_words(host, dtab, sizeof(u32) * (3 * (size_t)nf + 1), sb);
   }
@@ -240,22 +238,21 @@ int run_fuse(esvo_context* h, int par, const double* T_world_obs, bool naive) {
   a.owner_max = h->prm.regularization ? h->d_owner_max : nullptr;
   a.owner_min = h->d_owner_min; a.n_reg_elems = h->prm.regularization ? h->d_cnt_b + CNTB_REG_ELEMS : nullptr;
   if (total > h->win_cap) {
-    for (int e : tail_ev) if (e >= 0) hipEventRecord(h->evt[e], sb);
+    for (hipEvent_t e : tail_ev) if (e) hipEventRecord(e, sb);
     FAIL(ESVO_ERR_CAPACITY, "window points exceed capacity");
   }
-  const int o = par * EV_BACK_STRIDE;
   const bool timed = h->stage_events_on;
-  h->back_timed[par] = timed;
-  if (timed) hipEventRecord(h->evt[EV_FU0 + o], sb);
+  B.timed = timed;
+  if (timed) hipEventRecord(B.ev.e[BE_FU0], sb);
   launch_fuse(a, h->dp, sb);
-  if (timed) hipEventRecord(h->evt[EV_FU1 + o], sb);
+  if (timed) hipEventRecord(B.ev.e[BE_FU1], sb);
   h->d_map_cur = h->d_map;
   // the ids this fusion numbered (kernels_fuse.hip: record id q K + k, launch_fuse's K): what esvo_map_cloud_build scans over
   h->map_id_bound = total * ((naive || h->dp.fusion_radius == 0) ? 4u : 9u);
   // (naive propagation, esvo_MVStereo.cpp:416-428: the map is published as it is, neither cleaned nor regularised)
   const bool do_clean = naive ? false : (h->prm.clean_requires_full_window ? (h->n_window_frames >= (size_t)h->prm.max_fusion_frames) : true);
   if (do_clean) launch_clean(h->d_map, h->dp, sb);
-  if (timed) hipEventRecord(h->evt[EV_CL1 + o], sb);
+  if (timed) hipEventRecord(B.ev.e[BE_CL1], sb);
   if (h->prm.regularization && !naive) {
     launch_reg_view(h->d_map, h->d_map2, h->d_owner_max, h->d_owner_min, h->d_reg_ab, h->d_reg_cd, h->d_cnt_b + CNTB_REG_ELEMS, h->dp, sb);
     // (the tile kernel's layout for sparse maps when the newest known element count -- the previous tick's -- is below a tenth of
@@ -265,10 +262,10 @@ int run_fuse(esvo_context* h, int par, const double* T_world_obs, bool naive) {
     launch_reg_apply(h->d_map, h->d_map2, h->d_owner_max, h->d_owner_min, h->d_reg_ab, h->d_reg_cd, h->d_cnt_b + CNTB_REG_ELEMS, h->dp, sb, sparse);
     h->d_map_cur = h->d_map2;
   }
-  HIPCHK(hipMemcpyAsync(h->h_cnt_b + CNTB_ROW * par, h->d_cnt_b, sizeof(u32) * CNTB_ROW, hipMemcpyDeviceToHost, sb));
+  HIPCHK(hipMemcpyAsync(B.h_cnt, h->d_cnt_b, sizeof(u32) * CNTB_ROW, hipMemcpyDeviceToHost, sb));
   if (h->routed) HIPCHK(hipMemcpyAsync(h->h_cnt_b + CNTB_ROW * CNTB_ROW_HALO + par, h->d_halo_viol, sizeof(u32), hipMemcpyDeviceToHost, sb));
-  hipEventRecord(h->evt[EV_RG1 + o], sb);  // also "back stage of this parity done"
-  for (int e : tail_ev) if (e >= 0) hipEventRecord(h->evt[e], sb);
+  hipEventRecord(B.ev.e[BE_RG1], sb);  // also "back stage of this parity done"
+  for (hipEvent_t e : tail_ev) if (e) hipEventRecord(e, sb);
   HIPCHK(hipGetLastError());
   h->back_pending[par] = true;
   return ESVO_OK;
@@ -319,7 +316,7 @@ int fuse_window_now(esvo_context* h, const double* T_world_obs, bool naive, int*
   const int par = h->par;
   h->par ^= 1;
   if (par_out) *par_out = par;
-  HIPCHK(hipEventSynchronize(h->evt[EV_RG1 + par * EV_BACK_STRIDE]));
+  HIPCHK(hipEventSynchronize(h->back[par].ev.e[BE_RG1]));
   collect_back(h, par);
   return run_fuse(h, par, T_world_obs, naive);
 }

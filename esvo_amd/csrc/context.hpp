@@ -3,8 +3,9 @@
 // One esvo_context owns every device buffer of one GPU: SAE + staged event rings (Time Surface), the observation pair,
 // per-tick BM/LM scratch, the fusion window ring and the dense DepthMap.  It owns them through DevBuf / PinBuf members
 // (devmem.hpp): a member that is a buffer is freed with the handle, a raw pointer member owns nothing (the views are listed
-// together below) -- esvo_destroy has no list to keep.  Single-owner events are DevEvent members in the same way; the evt[]
-// table and the streams stay raw handles, created and destroyed by esvo_create / esvo_destroy.  Each entry point replays, on
+// together below) -- esvo_destroy has no list to keep.  Events are DevEvent members in the same way; only the streams stay raw
+// handles, created and destroyed by esvo_create / esvo_destroy.  Two ticks are in flight: what one index of that machinery selects
+// -- buffers, flags, stage events -- sits in one slot struct (front[fpar], back[par], pose[pose_buf]).  Each entry point replays, on
 // the handle's HIP streams, the call sequence of the reference seam it replaces (cited in include/esvo_hip.h); nothing
 // computes on the CPU except bookkeeping (time-stamp binary searches, window policy, output ordering).
 //   api_core.hip   lifecycle, parameters, self-tests           api_ts.hip     event ingest, Time-Surface render
@@ -32,14 +33,6 @@
 #include "devmem.hpp"
 
 using namespace esvo;
-
-// front-stage events live on the front stream; the back-stage set exists once per tick parity (two ticks in flight)
-enum { EV_SC0 = 0, EV_SC1, EV_R1, EV_SC0b, EV_SC1b, EV_R1b, EV_FRAME,
-       EV_T0, EV_BM0, EV_BM1, EV_S1, EV_LM0, EV_LM1, EV_S2, EV_CNT, EV_STG, EV_A1, EV_T0b, EV_BM0b, EV_BM1b, EV_S1b, EV_LM0b, EV_LM1b, EV_S2b, EV_CNTb, EV_STGb, EV_A1b,
-       EV_FU0, EV_FU1, EV_CL1, EV_RG1, EV_POSE, EV_FU0b, EV_FU1b, EV_CL1b, EV_RG1b, EV_POSEb, EV_N };
-constexpr int EV_BACK_STRIDE = EV_FU0b - EV_FU0;  // evt[EV_x + par * EV_BACK_STRIDE]
-constexpr int EV_FRONT_STRIDE = EV_T0b - EV_T0;   // evt[EV_x + fpar * EV_FRONT_STRIDE]
-constexpr int EV_TS_STRIDE = EV_SC0b - EV_SC0;    // evt[EV_x + cam * EV_TS_STRIDE]
 
 struct FrameRec {
   u32 off;    // offset in the window ring
@@ -118,6 +111,52 @@ struct CloudSession {  // under mu_cloud: the device-resident point cloud (esvo_
   bool cloud_read_pending[2] = {false, false};
 };
 
+// A tick's state between its phases.  Unsharded ticks are finished lazily: esvo_map_tick(k) enqueues the front
+// stage of tick k and only then completes tick k-1 (point count -> window policy -> back stage), so the host
+// never waits on the front stream while it still has work to enqueue there.
+struct TickState {
+  u32 n = 0, off = 0, points = 0, n_pose = 0;
+  u32 n_loc = 0;                    // routed band mode: events of the selection in this rank's ring (n stays the global count)
+  u32 n_own = 0;                    //   ... of which the rank owns (block-matches and refines) this many
+  u32 g_first = 0;                  //   global index (low 32 bits) of the selection's newest event
+  u32 max_kept = 0;                 // sharded: largest kept count among the ranks (block length of exchange 2)
+  int pose_buf = 0;
+  u64 t_ns = 0;
+  double T_world_obs[16];
+  hipStream_t lm_stream = nullptr;  // where the tick's LM launch was enqueued
+  hipStream_t cnt_stream = nullptr; // where its frame (point compaction) and counters follow: the same, or the idle second LM queue
+  int obs_par = 0;                  // which observation pair it reads
+  int lm_pair = -1;                 // LM layout of the tick: 1 pair, 0 wide, -1 not a candidate (policy feedback)
+  bool lat = false;                 // enqueued in latency mode: LM in the front queue, polled waits
+  bool timed = true;                // its stage-timing events were recorded
+  bool lm_two = false;              // its LM launch alternates between the two LM queues
+  bool host_row_sent = false;        // latency mode: its point compaction left the counter row in the pinned host row (no copy follows)
+  bool gather = false;              // latency mode: its frame is still in the solver slots (flags + prefix): the back stage's first launch compacts it
+  bool timed_lm = true;             // ... at least the two around the LM launch (the layout policy's feedback)
+};
+
+// ---- THE SLOTS: what one index of the two-ticks-in-flight machinery selects.  They sit outside the *Session structs, so all of it
+// survives esvo_reset (whose drains complete every event): the halves are symmetric, work resumes on whichever is current.
+// The observation pair, the map pair, the cloud pair and the streams are other domains with swap points of their own: handle members.
+struct FrontSlot {  // front[fpar]: what a front stage (block matching, LM, frame assembly) writes while the other parity's LM stage may still run
+  DevBuf<esvo_match_t> d_matches;
+  DevBuf<u32> d_counters;         // the front stage's counter row (common.hpp: CNT_*)
+  DevBuf<DevPoint> d_pt_slots, d_stage;  // LM output by slot (+ keep flags, their scan, its scratch); a lazily completed tick's frame until its count is known
+  DevBuf<u32> d_pt_flags, d_pt_prefix, d_scan_tmp_l;
+  DevBuf<u32> d_lm_pix_order;     // the narrow LM launch's processing order (esvo_context::d_lm_sort_rows); allocated when the handle can see such launches
+  TickState tk;                   // read only while tick_pending, which flush_pending_tick clears
+  bool gather_guard = false;      // a back stage's first launch reads the solver slots until FE_STG: complete after a reset's drains
+  FrontEvents own_ev, *ev = &own_ev;  // ev: the set in use: its own, or one the communicator lends per own tick (api_comm.hip, OwnTick)
+  u32* h_counters = nullptr; u64* d_clk = nullptr;  // views: this parity's row / block of the handle's h_counters / d_clk
+};
+struct BackSlot {  // back[par]: a back stage (fusion, clean, regulariser) and what the host reads of it two ticks later
+  BackEvents ev;                  // BE_RG1 is also "back stage of this parity done"
+  bool timed = true;              // the stage recorded its stage events: describes ev, which survives a reset
+  u32 *h_cnt = nullptr, *h_fr_table = nullptr, *d_fr_table = nullptr;  // views: its row of h_cnt_b, its halves of the frame tables
+};
+// pose[pose_buf]: a tick's pose table, [T | toSec]; released: the back stage has copied it into its frame's slot (the next upload waits)
+struct PoseBuf { DevBuf<double> d_T; DevEvent released; };
+
 struct esvo_context : IngestSession, TsSession, SchedSession, MapSession, CloudSession {
   esvo_params_t prm;
   DevParams dp;
@@ -128,13 +167,11 @@ struct esvo_context : IngestSession, TsSession, SchedSession, MapSession, CloudS
   hipStream_t stream = nullptr;
   hipStream_t stream_b = nullptr;
   // LM stage of a lazy tick (refinement, frame assembly, counters): block matching and the Time Surfaces of the NEXT tick run
-  // beside it on `stream`.  What the two stages share is double-buffered by POINTER SWAP: d_obs / d_matches / d_counters
-  // below alias one of two buffers each (kernels capture the pointer at launch, so work in flight keeps its own).
+  // beside it on `stream`.  What the two stages share exists twice: d_obs2 and the FrontSlot buffers (work in flight keeps its own).
   hipStream_t stream_l = nullptr;
   // A SECOND queue for the LM stage (round 3): the LM stages of consecutive lazy ticks alternate between stream_l and
   // stream_l1 by the tick's parity, so the head of tick k+1's launch fills the chip while the tail of tick k's -- a few
-  // long dependent chains -- drains.  Used for launches in the latency-bound (wide) layout; everything the stage writes
-  // (d_pt_slots / d_pt_flags / d_pt_prefix / the scan scratch, besides the buffers listed above) exists once per parity.
+  // long dependent chains -- drains.  Used for launches in the latency-bound (wide) layout; what the stage writes is in FrontSlot.
   hipStream_t stream_l1 = nullptr;
   // Whether the second queue pays depends on what else the tick holds: where the LM launch is much longer than the fusion
   // stage (346x260, no regulariser: 0.37 ms against 0.12) two launches in flight raise the rate by 18 %; where the two are
@@ -173,19 +210,17 @@ struct esvo_context : IngestSession, TsSession, SchedSession, MapSession, CloudS
   u32 lat_timed_every = 31;       // ESVO_LOWLAT_TIMED_EVERY (A/B; 1 = every tick)
   int reg_sparse_forced = -1;     // ESVO_REG_SPARSE (A/B): the regulariser's sparse-map layout never (0) / always (1); -1: by the element count
   bool stage_events_on = true;    // false while a tick whose stage timings are not sampled is being enqueued (api_map.hip)
-  std::atomic<bool> trk_used{false};  // esvo_track_set_current has read the resident surface: renders record EV_R1 for it
+  std::atomic<bool> trk_used{false};  // esvo_track_set_current has read the resident surface: renders record TE_R1 for it
   // ... and the copies that open its back stage (frame into the ring, pose table into the frame's slot) are not enqueued one by one
   // but handed to run_fuse, whose frame-table upload carries them in the same launch (scan.hip, back_prologue_kernel)
   struct DeferredCopies {
     bool active = false;
-    const void* a_src = nullptr; void* a_dst = nullptr; size_t a_bytes = 0; int ev_a = -1;  // frame points; event recorded behind it
+    const void* a_src = nullptr; void* a_dst = nullptr; size_t a_bytes = 0; hipEvent_t ev_a = nullptr;  // frame points; event recorded behind it (null: none)
     const u32* a_flags = nullptr; const u32* a_prefix = nullptr; u32 a_slots = 0;          // gather mode: a_src = the solver slots
-    const void* b_src = nullptr; void* b_dst = nullptr; size_t b_bytes = 0; int ev_b = -1;  // pose table
+    const void* b_src = nullptr; void* b_dst = nullptr; size_t b_bytes = 0; hipEvent_t ev_b = nullptr;  // pose table
   } pro;
   DevBuf<uint8_t> d_obs2[2][2];
   int obs_par = 0;
-  DevBuf<esvo_match_t> d_matches2[2];
-  DevBuf<u32> d_counters2[2], d_scan_tmp_l2[2];
   hipStream_t stream_i = nullptr;  // event ingest (H2D into the ring): staging new events never waits for a running tick
   bool own_stream = false;
   int par = 0;                    // parity of the tick being assembled
@@ -200,7 +235,7 @@ struct esvo_context : IngestSession, TsSession, SchedSession, MapSession, CloudS
   std::mutex mu_ring;           // IngestSession, scatter_seq, stats.events_staged / _scattered.  Never held across a host wait.
   std::mutex mu_push[2];        // one pusher per camera at a time (held across its host-to-device copy)
   std::mutex mu_track;          // tracker-group calls
-  std::mutex mu_ts;             // the resident left Time Surface (d_ts[0], ts_valid[0], EV_R1) between a render and a
+  std::mutex mu_ts;             // the resident left Time Surface (d_ts[0], ts_valid[0], TE_R1) between a render and a
                                 // tracker read (esvo_track_set_current without a host image); the Time-Surface history's table
   std::mutex mu_cloud;          // the device-resident point cloud between a build (mapper group) and a tracker gather
                                 // (esvo_track_set_reference_from_cloud): CloudSession, evt_cloud_built, evt_cloud_read.  Held only while those change or while work that reads
@@ -213,13 +248,7 @@ struct esvo_context : IngestSession, TsSession, SchedSession, MapSession, CloudS
   // ---- VIEWS: raw pointers that own nothing and are never freed.  Each aliases one buffer of a double-buffered set (or a
   // part of one) and is re-pointed by a swap; kernels capture the pointer at launch, so work in flight keeps its own.
   uint8_t* d_obs[2] = {nullptr, nullptr};  // d_obs2[obs_par][cam]: the observation pair of the current parity
-  esvo_match_t* d_matches = nullptr;       // d_matches2[fpar]
-  u32* d_counters = nullptr;               // d_counters2[fpar]: the front stage's counter row (common.hpp: CNT_*)
-  DevPoint* d_pt_slots = nullptr;          // d_pt_slots2 / d_pt_flags2 / d_pt_prefix2 [fpar]: LM output by slot + keep flags + their scan
-  u32* d_pt_flags = nullptr;
-  u32* d_pt_prefix = nullptr;
-  u32* d_scan_tmp_l = nullptr;             // d_scan_tmp_l2[fpar]: scan scratch of the LM stage
-  double* d_pose_T = nullptr;              // d_pose_T2[pose_buf]: the tick's pose table
+  double* d_pose_T = nullptr;              // pose[pose_buf].d_T: the tick's pose table (re-pointed by upload_poses alone)
   double* d_pose_sec = nullptr;            // its tail (d_pose_T + 16 m): toSec() of the stamps
   MapCell* d_map = nullptr;                // the cells of d_map_mem[0]
   MapCell* d_map2 = nullptr;               // the cells of d_map_mem[1]
@@ -263,7 +292,7 @@ struct esvo_context : IngestSession, TsSession, SchedSession, MapSession, CloudS
   DevBuf<uint8_t> d_obs_tmp;
 
   // pose table of the tick
-  DevBuf<double> d_pose_T2[2];
+  PoseBuf pose[2];
   int pose_buf = 0;
   std::vector<double> h_pose_T;
   PinBuf<double> h_pin;        // pinned staging: 2 slots x (max_poses x 17 + 16) doubles
@@ -278,9 +307,8 @@ struct esvo_context : IngestSession, TsSession, SchedSession, MapSession, CloudS
   DevBuf<double> d_lm_fvec0, d_lm_fnorm0;
   DevBuf<u32> d_lm_meta, d_lm_order, d_lm_hist;
   // the processing order of the narrow LM launch (kernels_lm.hip): built on the front queue behind the match compaction, read by
-  // the LM launch on its own queue while the next tick's front stage runs -- so the order exists per front parity (as d_matches2
-  // does); the sort's rows and histogram are the front queue's alone.  Allocated when the handle can see narrow launches.
-  DevBuf<u32> d_lm_pix_order2[2];
+  // the LM launch on its own queue while the next tick's front stage runs -- so the order exists per front parity
+  // (FrontSlot::d_lm_pix_order); the sort's rows and histogram are the front queue's alone.
   DevBuf<u64> d_lm_sort_rows[2];
   DevBuf<u32> d_lm_sort_hist;
   bool lm_order_on = true;        // ESVO_LM_ORDER=0 (test / A/B only): the launch takes its slots in grid order
@@ -293,11 +321,8 @@ struct esvo_context : IngestSession, TsSession, SchedSession, MapSession, CloudS
   u32 bm_dedupe_min = esvo::BM_DEDUPE_MIN_EVENTS;  // ESVO_BM_DEDUPE_MIN=<n> (tests): the smallest launch bound that shares
   DevBuf<u64> d_clk;           // in-run shader-clock probe of the LM kernel (LmArgs::clk, common.hpp); read by esvo_get_stats
   bool clk_probe = true;          // ESVO_CLK_PROBE=0 (A/B only) launches the LM kernel without it
-  DevBuf<DevPoint> d_pt_slots2[2];
-  DevBuf<u32> d_pt_flags2[2], d_pt_prefix2[2];
   DevBuf<DevPoint> d_pts_tmp;  // stage-wise refine output
-  DevBuf<DevPoint> d_stage[2];  // a lazily completed tick's frame (by parity) until its count is known
-  PinBuf<u32> h_counters;      // pinned
+  PinBuf<u32> h_counters;      // pinned, a row per front parity (FrontSlot::h_counters)
   DevBuf<u32> d_scan_tmp;
   DevBuf<u32> d_cnt_b;         // the back stage's counter row (common.hpp: CNTB_*)
   PinBuf<u32> h_cnt_b;         // pinned, CNTB_ROWS rows of it (CNTB_ROW_*)
@@ -365,37 +390,19 @@ struct esvo_context : IngestSession, TsSession, SchedSession, MapSession, CloudS
   DevBuf<esvo_event_t> d_tsq_dup;
   DevBuf<u32> d_halo_viol;            // [2] matches whose refinement read outside oband, all ranks, summed over the ticks | scratch
   DevBuf<u32> d_dn_flags;             // [2][max_ev] kept flag + exclusive prefix per walk position of the raw selection (lazily)
-  // A tick's state between its phases.  Unsharded ticks are finished lazily: esvo_map_tick(k) enqueues the front
-  // stage of tick k and only then completes tick k-1 (point count -> window policy -> back stage), so the host
-  // never waits on the front stream while it still has work to enqueue there.
-  struct TickState {
-    u32 n = 0, off = 0, points = 0, n_pose = 0;
-    u32 n_loc = 0;                    // routed band mode: events of the selection in this rank's ring (n stays the global count)
-    u32 n_own = 0;                    //   ... of which the rank owns (block-matches and refines) this many
-    u32 g_first = 0;                  //   global index (low 32 bits) of the selection's newest event
-    u32 max_kept = 0;                 // sharded: largest kept count among the ranks (block length of exchange 2)
-    int pose_buf = 0;
-    u64 t_ns = 0;
-    double T_world_obs[16];
-    hipStream_t lm_stream = nullptr;  // where the tick's LM launch was enqueued
-    hipStream_t cnt_stream = nullptr; // where its frame (point compaction) and counters follow: the same, or the idle second LM queue
-    int obs_par = 0;                  // which observation pair it reads
-    int lm_pair = -1;                 // LM layout of the tick: 1 pair, 0 wide, -1 not a candidate (policy feedback)
-    bool lat = false;                 // enqueued in latency mode: LM in the front queue, polled waits
-    bool timed = true;                // its stage-timing events were recorded
-    bool lm_two = false;              // its LM launch alternates between the two LM queues
-    bool host_row_sent = false;        // latency mode: its point compaction left the counter row in the pinned host row (no copy follows)
-    bool gather = false;              // latency mode: its frame is still in the solver slots (flags + prefix): the back stage's first launch compacts it
-    bool timed_lm = true;             // ... at least the two around the LM launch (the layout policy's feedback)
-  } tk[2];
   // pair layout of the LM kernel (kernels_lm.hip): chosen per tick from the LM launch times the handle measures anyway
   // (HIP events).  The first eight candidate ticks alternate between the layouts, then the faster one is used, with one tick
   // of the other every 64 so that a change of scene is noticed; a layout's figure is the MINIMUM of its last four launches
   // (the first ticks of a handle are slow whatever the layout).  ESVO_LM_PAIR = 0 / 1 forces never / always.  Scheduling
   // only: same bits either way.
   int lm_pair_forced = -1;
+  FrontSlot front[2];
   int fpar = 0;                   // parity of the newest front stage
-  bool tick_pending = false;      // tk[fpar] has its front stage enqueued but is not committed yet
+  FrontSlot& front_cur() { return front[fpar]; }
+  bool tick_pending = false;      // front_cur().tk has its front stage enqueued but is not committed yet
+  BackSlot back[2];
+  TsEvents ts_ev[2];              // per camera; TE_R1 of camera 0 is also what esvo_track_set_current waits for (mu_ts)
+  DevEvent ev_frame;              // back_after_front: everything enqueued on the front stream so far, for the back stream
   // per-pixel event queues (max_event_queue_len > 0; kernels_ts.hip): key sets of both cameras + the batch's tile lists
   int tsq_len = 0;
   DevBuf<u64> d_tsq[2];
@@ -467,20 +474,14 @@ struct esvo_context : IngestSession, TsSession, SchedSession, MapSession, CloudS
 
   struct esvo_comm* comm = nullptr;  // multi-GPU exchange (api_comm.hip), null on single-GPU handles
 
-  hipEvent_t evt[EV_N];
-  bool evt_ok = false;
   esvo_stats_t stats;
 
   // ---- SURVIVES A RESET although it belongs to the session (everything outside the *Session structs survives; what is fixed at
-  // esvo_create, configuration, buffers and events do so by nature).  Left in place above: par / fpar / obs_par / pose_buf and the
-  // views that follow them (the double-buffered sets are symmetric: work resumes on whichever half is current); tk[] (read only
-  // while tick_pending, which flush_pending_tick clears); pro (active inside one tick_phase2); the tools' timeline; (?) em, which
-  // has no reset hook.  (?): the code shows no reason -- a reset handle keeps it as it always has, a later change decides.
+  // esvo_create, configuration, buffers and events do so by nature).  Left in place above: par / fpar / obs_par / pose_buf, the slots
+  // and views they select; pro (active inside one tick_phase2); the tools' timeline; (?) em, which has no reset hook.
+  // (?): the code shows no reason -- a reset handle keeps it as it always has, a later change decides.
   u32 lat_ticks = 0;            // ticks enqueued with nothing pending before them (band-sharded ticks: all of them -- every phase of such a
   u32 pipe_seq = 0;             // tick is waited for by an exchange) / overlapping small ticks: they pace the SAMPLING of stage timings, no result
-  bool gather_guard[2] = {false, false};  // a back stage's first launch reads that parity's solver slots until EV_STG: complete after a reset's drains
-  bool back_timed[2] = {true, true};  // the back stage of that parity recorded its stage events: describes evt[], which survives
-  u32 back_frames[2] = {0, 0};  // (written and read by nobody)
   u64 scatter_seq = 0;          // scatter launches so far, under mu_ring (a pusher that drained the front stream resets scatter_pending_lo
                                 // only if no scatter was enqueued meanwhile): compared for equality only
   u64 em_guard_lo[2] = {~0ull, ~0ull};  // oldest ring event an esvo_map_tick_em gather may still read (api_em.hip): lifted before that call returns
@@ -524,7 +525,7 @@ u64 ros_time_from_sec(double t);
 int upload_poses(esvo_context* h, const uint64_t* pose_t_ns, const double* pose_T, size_t m, u32* d_zero_row = nullptr);
 int select_events(esvo_context* h, uint64_t t_ns, u64* first_out, u32* n_out);
 int denoise_select(esvo_context* h, u32 n, u32* n_kept);
-void switch_front_parity(esvo_context* h);
+inline void switch_front_parity(esvo_context* h) { h->fpar ^= 1; }  // a new front stage takes the other FrontSlot: the previous tick's LM stage may still run on its own
 int run_bm(esvo_context* h, const esvo_event_t* d_ev, u64 first, u64 cap, int reverse, u32 n, const u32* sel = nullptr);
 int run_order_matches(esvo_context* h, u32 n, bool local, bool by_index = false);
 int run_lm(esvo_context* h, u32 max_matches, int cull, bool dense, hipStream_t st = nullptr, int pair = -1, const u32* order = nullptr, bool by_index = false);
@@ -534,9 +535,9 @@ int read_counters(esvo_context* h);
 int tick_phase0(esvo_context* h, uint64_t t_ns, const uint64_t* pose_t_ns, const double* pose_T, size_t m, FrontOpts opt = FrontOpts());
 int tick_phase1_enqueue(esvo_context* h);
 int tick_phase1_collect(esvo_context* h, int fp);
-int collect_front_stats(esvo_context* h, esvo_context::TickState& tk, const u32* cnt, const hipEvent_t* ev);
+int collect_front_stats(esvo_context* h, TickState& tk, const u32* cnt, const FrontEvents& ev);
 int tick_phase2(esvo_context* h, int fp);
-int flush_pending_tick(esvo_context* h);  // completes a lazily finished tick (see esvo_context::TickState)
+int flush_pending_tick(esvo_context* h);  // completes a lazily finished tick (see TickState)
 int finalize_tick_stats(esvo_context* h);
 void begin_observation(esvo_context* h);
 void revert_observation(esvo_context* h);
@@ -556,9 +557,9 @@ int export_map(esvo_context* h, std::vector<esvo_depth_point_t>& out, std::vecto
 // api_shard.hip
 int select_events_routed(esvo_context* h, uint64_t t_ns, u32* n_out, u32* g_first_out, u64* loc_first_out, u32* n_loc_out, u32* n_own_out);
 int routed_denoise_resume(esvo_context* h);
-int shard_front(esvo_context* h, esvo_context::TickState& tk, u32 n, const u32* sel);
-int shard_order_points(esvo_context* h, esvo_context::TickState& tk);
-int shard_scatter_frame(esvo_context* h, esvo_context::TickState& tk);
+int shard_front(esvo_context* h, TickState& tk, u32 n, const u32* sel);
+int shard_order_points(esvo_context* h, TickState& tk);
+int shard_scatter_frame(esvo_context* h, TickState& tk);
 // api_comm.hip
 void comm_release(esvo_context* h);
 void comm_reset(esvo_context* h);
@@ -606,7 +607,7 @@ struct StageEventsScope {  // stage-timing events off (or on) for the calls of o
 inline bool esvo_stage_timed(const esvo_context* h) {
   if (!h->lat_mode || h->tl_on || (h->comm && !h->sharded)) return true;  // (tick-interleaved ranks: every tick)
   if (h->tick_pending) {  // overlapping ticks: the small ones are paced by the HOST's enqueueing (pipe_seq); the large ones: every tick
-    if (h->tk[h->fpar].n && h->tk[h->fpar].n <= h->lat_max_events) return h->pipe_seq % h->pipe_timed_every == 0u;
+    if (h->front[h->fpar].tk.n && h->front[h->fpar].tk.n <= h->lat_max_events) return h->pipe_seq % h->pipe_timed_every == 0u;
     return true;
   }
   return h->lat_ticks < 8u || h->lat_ticks % h->lat_timed_every == 0u;

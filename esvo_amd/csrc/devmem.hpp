@@ -59,7 +59,7 @@ class Buf {
 template <typename T> using DevBuf = Buf<T, false>;
 template <typename T> using PinBuf = Buf<T, true>;
 
-// an event with one owner (the evt[] table of the handle is not one: the communicator lends events into it)
+// an event with one owner; one that was never created destroys to nothing
 class DevEvent {
   hipEvent_t e_ = nullptr;
 
@@ -71,5 +71,16 @@ class DevEvent {
   operator hipEvent_t() const { return e_; }
   hipError_t create(unsigned flags = hipEventDefault) { return e_ ? hipSuccess : hipEventCreateWithFlags(&e_, flags); }
 };
+
+// The stage events of one tick half, owned as a set and indexed by the set's own enum.  A set whose create() failed midway
+// frees what it got with its owner, like any DevEvent.
+template <int N> struct EventSet {
+  DevEvent e[N];
+  hipError_t create() { hipError_t r = hipSuccess; for (DevEvent& x : e) if (r == hipSuccess) r = x.create(); return r; }
+};
+enum { FE_T0, FE_BM0, FE_BM1, FE_S1, FE_LM0, FE_LM1, FE_S2, FE_CNT, FE_STG, FE_A1, FE_N };  // a front stage, in stream order up to FE_CNT
+enum { BE_FU0, BE_FU1, BE_CL1, BE_RG1, BE_N };                                             // a back stage
+enum { TE_SC0, TE_SC1, TE_R1, TE_N };                                                      // a camera's scatter and render
+using FrontEvents = EventSet<FE_N>; using BackEvents = EventSet<BE_N>; using TsEvents = EventSet<TE_N>;
 
 }  // namespace esvo

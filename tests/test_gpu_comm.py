@@ -98,6 +98,43 @@ def test_rccl_one_rank_communicator(upenn_rig, upenn_stream):
     dev.comm_destroy()
 
 
+def test_plain_ticks_after_comm_destroy(upenn_rig, upenn_stream):
+    """A handle that ran tick-interleaved ticks (four: both front parities and every own-tick slot have lent their front-stage
+    events) ticks on its own events again after esvo_comm_destroy: the maps of ordinary ticks equal the single-handle ones bit
+    for bit, and the first of them -- a lone tick, whose stage events are recorded -- reports stage timings read from them."""
+    from esvo_amd import lib
+    p, _ = params.make_params(params.PRESETS["mapping_upenn"], upenn_rig)
+    ticks = _ticks(upenn_stream, p, 5)
+    ref = _single(p, upenn_rig, upenn_stream, ticks)
+    tr = LocalTransport(1)
+    dev = lib.Esvo(p, upenn_rig)
+    dev.comm_init_callbacks(0, 1, lambda s, d, n, st: tr.all_gather(0, s, d, n))
+    dev.ts_push_events(0, upenn_stream.ev_left)
+    dev.ts_push_events(1, upenn_stream.ev_right)
+    for t, stamps, poses, T in ticks[:4]:
+        assert dev.comm_owns_next_tick()
+        dev.ts_render(0, t, download=False)
+        dev.ts_render(1, t, download=False)
+        dev.comm_tick(t, T, stamps, poses)
+    dev.comm_flush()
+    dev.comm_destroy()
+    dev.reset()
+    dev.ts_push_events(0, upenn_stream.ev_left)
+    dev.ts_push_events(1, upenn_stream.ev_right)
+    samples0 = int(dev.stats().stage_timing_samples)
+    for k, (t, stamps, poses, T) in enumerate(ticks):
+        dev.ts_render(0, t, download=False)
+        dev.ts_render(1, t, download=False)
+        dev.set_observation(t, None, None, T)
+        dev.tick(t, stamps, poses)
+        _same(dev.get_map(), ref[k])
+        if k == 0:
+            s = dev.stats()
+            print("first plain tick: ms_bm", s.ms_bm, "ms_refine", s.ms_refine, "samples", samples0, "->", int(s.stage_timing_samples))
+            assert s.ms_bm > 0 and s.ms_refine > 0
+            assert int(s.stage_timing_samples) > samples0
+
+
 @pytest.mark.parametrize("world,preset,rig_fix,stream_fix,n_ticks", [
     (2, "mapping_upenn", "upenn_rig", "upenn_stream", 7),      # CONST_POINTS window, a partial last round
     (3, "mapping_dsec", "dsec_rig", "dsec_stream", 7),         # CONST_FRAMES 5, 3x3 fusion, regulariser
