@@ -82,7 +82,7 @@ class ParamsStruct(C.Structure):
         ("max_poses_per_tick", C.c_int32),
         ("event_ring_capacity", C.c_int64),
         ("max_event_queue_len", C.c_int32),   # ABI 5: 0 = one stamp per pixel (fast path), 1..32 = EventQueueMat semantics
-        ("pad_params_", C.c_int32),
+        ("lm_scale_pass_limit", C.c_int32),   # 0: off; > 0: pass limit per evaluation; LM_SCALE_COUNT_ONLY: count only
     ]
 
 
@@ -222,6 +222,18 @@ class EmStatsStruct(C.Structure):
     _fields_ = [
         ("events", C.c_uint64), ("right_events", C.c_uint64), ("time_polarity", C.c_uint64), ("epipolar", C.c_uint64),
         ("patch_ok", C.c_uint64), ("matches", C.c_uint64), ("slices", C.c_uint64), ("ms_match", C.c_float), ("pad_", C.c_float),
+    ]
+
+
+# ---- the scale-loop guard of the LM refinement (esvo_lm_stats_t of include/esvo_hip.h)
+LM_SCALE_COUNT_ONLY = 2 ** 31 - 1   # ESVO_LM_SCALE_COUNT_ONLY: ParamsStruct.lm_scale_pass_limit that counts and never abandons
+
+
+class LmStatsStruct(C.Structure):
+    _fields_ = [
+        ("enabled", C.c_uint32), ("last_max_passes_eval", C.c_uint32), ("last_max_passes_match", C.c_uint32), ("last_abandoned", C.c_uint32),
+        ("last_passes", C.c_uint64), ("last_evals", C.c_uint64), ("last_shortcut_evals", C.c_uint64),
+        ("total_passes", C.c_uint64), ("total_evals", C.c_uint64), ("total_shortcut_evals", C.c_uint64), ("total_abandoned", C.c_uint64),
     ]
 
 

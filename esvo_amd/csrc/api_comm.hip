@@ -551,6 +551,8 @@ int esvo_comm_init(esvo_handle h, const uint8_t id[ESVO_COMM_ID_BYTES], int rank
   API_LOCK(h);
   if (h->comm) FAIL(ESVO_ERR_STATE, "the handle already has a communicator");
   if (h->hist_len) FAIL(ESVO_ERR_UNSUPPORTED, "the handle keeps a Time-Surface history: esvo_ts_history_configure(h, 0) before giving it a communicator");
+  if (h->prm.lm_scale_pass_limit != 0)
+    FAIL(ESVO_ERR_STATE, "the handle runs the LM scale-loop guard (lm_scale_pass_limit != 0), a single-GPU feature: set the limit to 0 before giving it a communicator");
   if (const char* e = load_rccl()) FAIL(ESVO_ERR_UNSUPPORTED, e);
   HIPCHK(hipSetDevice(h->device));
   { int rcp = flush_pending_tick(h); if (rcp) return rcp; }
@@ -574,6 +576,8 @@ int esvo_comm_init_callbacks(esvo_handle h, int rank, int world, esvo_all_gather
   API_LOCK(h);
   if (h->comm) FAIL(ESVO_ERR_STATE, "the handle already has a communicator");
   if (h->hist_len) FAIL(ESVO_ERR_UNSUPPORTED, "the handle keeps a Time-Surface history: esvo_ts_history_configure(h, 0) before giving it a communicator");
+  if (h->prm.lm_scale_pass_limit != 0)
+    FAIL(ESVO_ERR_STATE, "the handle runs the LM scale-loop guard (lm_scale_pass_limit != 0), a single-GPU feature: set the limit to 0 before giving it a communicator");
   HIPCHK(hipSetDevice(h->device));
   { int rcp = flush_pending_tick(h); if (rcp) return rcp; }
   h->comm = new esvo_comm();

@@ -37,6 +37,7 @@ int validate_params(const esvo_params_t* p, std::string& why) {
   if (p->td_nu <= 2.0 || p->td_scale <= 0) { why = "Tdist_nu must be > 2 and Tdist_scale > 0"; return ESVO_ERR_INVALID_ARG; }
   if (p->num_threads < 1 || p->num_threads > 64) { why = "num_threads out of range"; return ESVO_ERR_INVALID_ARG; }
   if (p->lm_max_iteration < 1) { why = "lm_max_iteration must be >= 1"; return ESVO_ERR_INVALID_ARG; }
+  if (p->lm_scale_pass_limit < 0) { why = "lm_scale_pass_limit must be 0 (off), a positive pass limit or ESVO_LM_SCALE_COUNT_ONLY"; return ESVO_ERR_INVALID_ARG; }
   if (p->reg_radius < 0 || p->reg_radius > 31) { why = "RegularizationRadius out of range [0,31] (one 64-bit mask per tap row)"; return ESVO_ERR_INVALID_ARG; }
   return ESVO_OK;
 }
@@ -453,6 +454,8 @@ int esvo_reset(esvo_handle h) {
   std::memset(&h->stats, 0, sizeof(h->stats));
   h->stats.clk_ref_khz = khz;
   for (const FrontSlot& F : h->front) HIPCHK(hipMemset(F.d_clk, 0, sizeof(u64) * CLK_SCRATCH));  // the probe's sums (alloc_tick_scratch)
+  for (const FrontSlot& F : h->front)  // the scale-loop guard's stripes, where a guarded launch has allocated them
+    if (F.d_lm_guard) HIPCHK(hipMemset(F.d_lm_guard, 0, sizeof(u32) * LM_GUARD_STRIPES * LM_GUARD_WORDS));
   return ESVO_OK;
 }
 
@@ -465,6 +468,8 @@ int esvo_set_params(esvo_handle h, const esvo_params_t* params) {
   if (rc) FAIL(rc, why);
   if ((u32)std::max(params->max_events_per_tick, params->process_event_num) > h->max_ev)
     FAIL(ESVO_ERR_CAPACITY, "process_event_num exceeds the capacity fixed at esvo_create");
+  if (params->lm_scale_pass_limit != 0 && (h->sharded || h->comm))
+    FAIL(ESVO_ERR_STATE, "handle is band-sharded or tick-interleaved: the LM scale-loop guard (lm_scale_pass_limit) is a single-GPU feature");
   {
     const u32 need = params->fusion_strategy == ESVO_FUSION_CONST_POINTS ? (u32)(1.5 * params->max_fusion_points) + 4u
                                                                          : (u32)params->max_fusion_frames + 2u;

@@ -97,6 +97,7 @@ int run_match(esvo_context* h, const esvo_event_t* d_ev, u64 first, u64 cap, int
 
 // which LM layout the next lazy tick uses (context.hpp: lm_pair_*): -1 not a candidate, else 0 wide / 1 pair
 static int lm_pair_policy(esvo_context* h, u32 n_events) {
+  if (lm_guard_wanted(h)) return -1;  // the guard has no pair layout (kernels_lm.hip)
   if (n_events == 0 || n_events > esvo::LM_PAIR_MAX_EVENTS || h->prm.ls_norm == ESVO_LSNORM_L2) return -1;
   if (h->lm_pair_forced >= 0) return h->lm_pair_forced;
   const u32 k = h->lm_pair_decisions++;
@@ -117,7 +118,7 @@ static int lm_pair_policy(esvo_context* h, u32 n_events) {
 // tick -- the count stays on the device.  Launches that do not read an order (wide, pair, dense, band, split) get none (nullptr).
 static const u32* run_lm_order(esvo_context* h, u32 max_matches) {
   FrontSlot& F = h->front_cur();
-  const bool split = h->d_lm_fvec0 != nullptr && max_matches >= esvo::LM_SPLIT_MIN_EVENTS;
+  const bool split = h->d_lm_fvec0 != nullptr && max_matches >= esvo::LM_SPLIT_MIN_EVENTS && !lm_guard_wanted(h);  // (guarded: the ordered launch)
   if (!h->lm_order_on || !h->front[0].d_lm_pix_order || !lm_launch_is_ordered(max_matches, false, false, split, h->dp)) return nullptr;
   u32* order = F.d_lm_pix_order;
   u64* const rows[2] = {h->d_lm_sort_rows[0], h->d_lm_sort_rows[1]};
@@ -142,15 +143,27 @@ int run_lm(esvo_context* h, u32 max_matches, int cull, bool dense, hipStream_t s
   a.tsL = h->d_obs[0]; a.tsR = h->d_obs[1];
   a.pose_T = h->d_pose_T; std::memcpy(a.T_world_obs, h->T_world_obs, sizeof(double) * 16);
   a.out_slots = F.d_pt_slots; a.out_flags = flags; a.cull = cull; a.dense = dense ? 1 : 0;
-  const bool split = h->d_lm_fvec0 != nullptr && max_matches >= esvo::LM_SPLIT_MIN_EVENTS;
+  // the scale-loop guard: a plain handle's launches only (a dense launch is a rank's share); its stripes exist from the first such launch on
+  LmGuard guard;
+  if (!dense && lm_guard_wanted(h)) {
+    if (!F.d_lm_guard) {
+      HIPCHK(F.d_lm_guard.alloc((size_t)esvo::LM_GUARD_STRIPES * esvo::LM_GUARD_WORDS));
+      HIPCHK(hipMemsetAsync(F.d_lm_guard, 0, sizeof(u32) * esvo::LM_GUARD_STRIPES * esvo::LM_GUARD_WORDS, st));
+    }
+    guard.stripes = F.d_lm_guard;
+    guard.limit = h->prm.lm_scale_pass_limit;
+  }
+  F.tk.lm_guard = guard.limit != 0;
+  const bool split = h->d_lm_fvec0 != nullptr && max_matches >= esvo::LM_SPLIT_MIN_EVENTS && !F.tk.lm_guard;
   a.split_fvec0 = split ? h->d_lm_fvec0 : nullptr; a.split_fnorm0 = h->d_lm_fnorm0; a.split_meta = h->d_lm_meta;
   a.split_order = h->d_lm_order; a.split_hist = h->d_lm_hist;
   a.pair = pair >= 0 ? pair : (h->lm_pair_forced == 1 && max_matches <= esvo::LM_PAIR_MAX_EVENTS ? 1 : 0);
+  if (F.tk.lm_guard) a.pair = 0;  // (a forced ESVO_LM_PAIR loses to the guard)
   a.clk = h->clk_probe ? F.d_clk : nullptr;  // (a block per front parity: api_core.hip)
   if (h->routed && dense) { a.halo_viol = F.d_counters + CNT_SCRATCH; a.vy0 = h->oband_y0; a.vy1 = h->oband_y1; }
   const bool timed_lm = h->stage_events_on || F.tk.timed_lm;
   if (timed_lm) hipEventRecord(F.ev->e[FE_LM0], st);
-  launch_lm_refine(a, h->dp, F.d_counters + CNT_SOLVED, st);
+  launch_lm_refine(a, h->dp, F.d_counters + CNT_SOLVED, st, guard);
   // (FE_LM1 is also what the point compaction waits for when it runs on the other LM queue: tick_phase0)
   if (timed_lm || F.tk.cnt_stream != st) hipEventRecord(F.ev->e[FE_LM1], st);
   HIPCHK(hipGetLastError());
@@ -162,6 +175,7 @@ int run_order_points(esvo_context* h, u32 max_matches, DevPoint* dst, hipStream_
   FrontSlot& F = h->front_cur();
   u32* scratch = (st && st != h->stream) ? F.d_scan_tmp_l : h->d_scan_tmp;  // the LM stage scans beside the next tick's BM
   if (!st) st = h->stream;
+  if (F.tk.lm_guard) launch_lm_guard_fold(F.d_lm_guard, F.d_counters, st);  // (before the small compaction copies the row to the host)
   if (scan_compact_is_small(max_matches)) {
     // (the refinement kernel writes a flag for every slot of its launch, 0 beyond the match count: no count to clip to)
     launch_scan_compact_points_small(F.d_pt_flags, F.d_pt_prefix, F.d_counters + CNT_POINTS, max_matches, F.d_pt_slots, dst, st,
@@ -191,6 +205,20 @@ void collect_bm_failures(esvo_context* h, const u32* row, bool accumulate) {
   esvo_stats_t& s = h->stats;
   s.last_bm_info_noise_low = r[0]; s.last_bm_coarse_fail = r[1]; s.last_bm_fine_fail = r[2];
   if (accumulate) { s.total_bm_info_noise_low += r[0]; s.total_bm_coarse_fail += r[1]; s.total_bm_fine_fail += r[2]; }
+}
+bool lm_guard_wanted(const esvo_context* h) {
+  return h->prm.lm_scale_pass_limit != 0 && h->prm.ls_norm != ESVO_LSNORM_L2 && !h->sharded && !h->comm;
+}
+void collect_lm_guard(esvo_context* h, const u32* row, bool guarded) {
+  esvo_lm_stats_t& s = h->lm_stats;
+  s.last_max_passes_eval = guarded ? row[CNT_LM_MAX_EVAL] : 0;
+  s.last_max_passes_match = guarded ? row[CNT_LM_MAX_MATCH] : 0;
+  s.last_abandoned = guarded ? row[CNT_LM_ABANDONED] : 0;
+  s.last_passes = guarded ? row[CNT_LM_PASSES] : 0;
+  s.last_evals = guarded ? row[CNT_LM_EVALS] : 0;
+  s.last_shortcut_evals = guarded ? row[CNT_LM_SHORTCUT] : 0;
+  s.total_passes += s.last_passes; s.total_evals += s.last_evals; s.total_shortcut_evals += s.last_shortcut_evals;
+  s.total_abandoned += s.last_abandoned;
 }
 int read_counters(esvo_context* h) {
   HIPCHK(hipMemcpyAsync(h->h_counters, h->front_cur().d_counters, sizeof(u32) * CNT_ROW, hipMemcpyDeviceToHost, h->stream));  // (row 0, whatever the parity)
@@ -308,6 +336,7 @@ int esvo_map_refine(esvo_handle h, const esvo_match_t* matches, size_t n, int cu
   *n_out = np;
   h->stats.last_solved = h->h_counters[CNT_SOLVED];
   h->stats.last_points = np;
+  collect_lm_guard(h, h->h_counters, h->front_cur().tk.lm_guard);
   if (out && np) {
     if (np > cap) FAIL(ESVO_ERR_CAPACITY, "output array too small for the depth points");
     HIPCHK(hipMemcpy(out, h->d_pts_tmp, sizeof(esvo_depth_point_t) * np, hipMemcpyDeviceToHost));
@@ -385,6 +414,7 @@ int tick_phase0(esvo_context* h, uint64_t t_ns, const uint64_t* pose_t_ns, const
   tk.n_loc = n_loc; tk.n_own = n_own; tk.g_first = g_first;
   tk.lm_stream = tk.cnt_stream = h->stream;
   tk.lm_pair = -1;
+  tk.lm_guard = false;
   // latency mode: nothing of an earlier tick is pending, so this tick has nothing to run beside -- its LM launch stays in the front
   // queue (one cross-queue hand-off less on the path the caller waits for), the host polls for its counters and its end, and its
   // stage timings are sampled, not recorded tick by tick (context.hpp)
@@ -521,6 +551,7 @@ int collect_front_stats(esvo_context* h, TickState& tk, const u32* cnt, const Fr
   s.total_matches += cnt[CNT_MATCHES];
   s.total_points += n_points;
   collect_bm_failures(h, cnt, true);
+  collect_lm_guard(h, cnt, n && tk.lm_guard);
   tk.points = n_points;
   if (tk.timed) {
     s.ms_bm = s.ms_refine = 0;

@@ -315,4 +315,22 @@ int esvo_get_stats(esvo_handle h, esvo_stats_t* out) {
   return ESVO_OK;
 }
 
+int esvo_map_lm_stats(esvo_handle h, esvo_lm_stats_t* out) {
+  if (!h || !out) return ESVO_ERR_INVALID_ARG;
+  API_LOCK(h);
+  HIPCHK(hipSetDevice(h->device));
+  int rc = finalize_tick_stats(h);  // (completes a pending tick: its counter row is collected there)
+  if (rc) return rc;
+  *out = esvo_lm_stats_t{};
+  if (!lm_guard_wanted(h)) return ESVO_OK;  // limit 0, or no scale loop (l2): every field reads 0
+  *out = h->lm_stats;
+  out->enabled = 1;
+  return ESVO_OK;
+}
+
+void esvo_lm_sizes(size_t out[4]) {
+  out[0] = sizeof(esvo_lm_stats_t); out[1] = (size_t)ESVO_LM_SCALE_COUNT_ONLY;
+  out[2] = 0; out[3] = 0;
+}
+
 }  // extern "C"

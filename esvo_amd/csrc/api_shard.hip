@@ -254,6 +254,8 @@ int esvo_shard_set_band(esvo_handle h, int row_begin, int row_end, int shard, in
     return ESVO_ERR_INVALID_ARG;
   API_LOCK(h);
   if (h->hist_len) FAIL(ESVO_ERR_UNSUPPORTED, "the handle keeps a Time-Surface history: esvo_ts_history_configure(h, 0) before sharding it");
+  if (h->prm.lm_scale_pass_limit != 0)
+    FAIL(ESVO_ERR_STATE, "the handle runs the LM scale-loop guard (lm_scale_pass_limit != 0), a single-GPU feature: set the limit to 0 before sharding it");
   { int rcp = flush_pending_tick(h); if (rcp) return rcp; }
   if (h->routed && !rings_empty(h))
     FAIL(ESVO_ERR_STATE, "the handle routes events by row and holds staged events: esvo_reset before changing its band");

@@ -44,11 +44,17 @@ enum : int {
   CNT_MATCHES = 0,        // matches of the tick (sharded: of all ranks, after exchange 1)
   CNT_POINTS = 1,         // points of its frame
   CNT_SOLVED = 2,         // refinements that ran (sharded: this rank's share)
+  CNT_LM_PASSES = 3,      // the LM scale-loop guard (LmGuard below; written by its fold kernel, only while the guard is on):
+  CNT_LM_EVALS = 4,       //   passes and evaluations of the launch,
   CNT_DENOISE_KEPT = 5,   // Denoising: events kept by the mask (read back before block matching sizes its launch)
+  CNT_LM_SHORTCUT = 6,    //   evaluations whose collapse was taken for granted, matches abandoned,
+  CNT_LM_ABANDONED = 7,
   CNT_OWN_MATCHES = 8,    // sharded: length of the rank's dense local match list
   CNT_MAX_KEPT = 9,       // sharded: largest kept count among the ranks (block length of exchange 2)
   CNT_SCRATCH = 10,       // four words, per mode: [0] this rank's halo violations in a routed tick (LM kernel, carried by exchange 2);
                           // esvo_MVStereo mode 4: [0..3] on-image / matched-column / disparity-ok / zero-disparity events (SGM statistics)
+  CNT_LM_MAX_EVAL = 14,   //   most passes of one evaluation, of one match
+  CNT_LM_MAX_MATCH = 15,
 };
 constexpr int CNT_STRIPES = 16;
 constexpr int CNT_BM_FAIL = 16;
@@ -415,6 +421,16 @@ struct LmArgs {
   u32* halo_viol = nullptr;
   int vy0 = 0, vy1 = 0;
 };
+// The scale-loop guard (esvo_params_t::lm_scale_pass_limit, include/esvo_hip.h): limit != 0 selects the guarded instantiations,
+// which count the passes of the Student-t scale loop per evaluation and abandon a match at its first evaluation over the limit.
+// A wave leaves its counts with one atomic per word in stripe (block index % LM_GUARD_STRIPES) of `stripes`; launch_lm_guard_fold
+// sums the stripes into the front stage's counter row (CNT_LM_*) and clears them for the next launch.
+constexpr u32 LM_GUARD_STRIPES = 32, LM_GUARD_WORDS = 8;  // per stripe: passes, evals, shortcut evals, abandoned, max per eval, max per match, 2 unused
+struct LmGuard {
+  u32* stripes = nullptr;  // [LM_GUARD_STRIPES][LM_GUARD_WORDS], zero between launches
+  int limit = 0;
+};
+void launch_lm_guard_fold(u32* stripes, u32* counter_row, hipStream_t s);
 constexpr u32 CLK_XCDS = 8, CLK_SAMPLES = 16, CLK_SCRATCH = 32, CLK_STRIDE = 65;
 inline size_t clk_words(u32 max_ev) { return CLK_SCRATCH + 2 * ((size_t)max_ev / 64 + 2); }
 constexpr u32 LM_PAIR_MAX_EVENTS = 10000u;       // launches bounded by more events never use the pair layout (2 waves per match)
@@ -423,7 +439,8 @@ constexpr u32 LM_TWO_QUEUES_MAX_EVENTS = 40000u;  // = LM_WIDE_MAX (kernels_lm.h
 #define LM_SPLIT_MIN 400000u
 #endif
 constexpr u32 LM_SPLIT_MIN_EVENTS = LM_SPLIT_MIN;  // launches bounded by at least this many events use the split launch (kernels_lm.hip, LmSplit)
-void launch_lm_refine(const LmArgs& a, const DevParams& p, u32* n_solved, hipStream_t s);
+// g.limit != 0: the guarded kernels; never the pair layout, never the split launch (the ordered narrow launch stands in)
+void launch_lm_refine(const LmArgs& a, const DevParams& p, u32* n_solved, hipStream_t s, const LmGuard& g = LmGuard());
 // The processing order of a narrow launch (kernels_lm.hip): the solver slots sorted by their match's pixel, tile-major, stable.
 // rows[0] / rows[1]: max_matches words of 64 bits; hist: voxel_hist_words(max_matches); scan_tmp: scan_scratch_elems of that;
 // order: max_matches words.  dense: slot s holds match s (else match stride_item(s, *n_matches, num_threads)).

@@ -103,6 +103,7 @@ struct MapSession {  // mapper group (mu_api): observation, window, DepthMap, wh
   bool dn_pending = false;      // Denoising on a routed handle: phase 0 returned ESVO_AGAIN, the mask bits are being exchanged
   bool sgm_disp_valid = false;  // the per-tick SGM mode (esvo_map_tick_sgm / esvo_map_push_disparity_frame): d_sgm_disp holds an image
   esvo_sgm_stats_t sgm_stats = {};
+  esvo_lm_stats_t lm_stats = {};  // the scale-loop guard (esvo_map_lm_stats): the last launch's counts and the running totals
 };
 struct CloudSession {  // under mu_cloud: the device-resident point cloud (esvo_context::d_cloud_xyz)
   int cloud_cur = -1;           // the buffer that holds the snapshot (-1: none -- before the first build, after a reset)
@@ -133,6 +134,7 @@ struct TickState {
   bool host_row_sent = false;        // latency mode: its point compaction left the counter row in the pinned host row (no copy follows)
   bool gather = false;              // latency mode: its frame is still in the solver slots (flags + prefix): the back stage's first launch compacts it
   bool timed_lm = true;             // ... at least the two around the LM launch (the layout policy's feedback)
+  bool lm_guard = false;            // its LM launch ran the scale-loop guard: the fold follows, the counter row holds CNT_LM_*
 };
 
 // ---- THE SLOTS: what one index of the two-ticks-in-flight machinery selects.  They sit outside the *Session structs, so all of it
@@ -144,6 +146,7 @@ struct FrontSlot {  // front[fpar]: what a front stage (block matching, LM, fram
   DevBuf<DevPoint> d_pt_slots, d_stage;  // LM output by slot (+ keep flags, their scan, its scratch); a lazily completed tick's frame until its count is known
   DevBuf<u32> d_pt_flags, d_pt_prefix, d_scan_tmp_l;
   DevBuf<u32> d_lm_pix_order;     // the narrow LM launch's processing order (esvo_context::d_lm_sort_rows); allocated when the handle can see such launches
+  DevBuf<u32> d_lm_guard;         // the scale-loop guard's striped counts (common.hpp: LmGuard); allocated by the first guarded launch
   TickState tk;                   // read only while tick_pending, which flush_pending_tick clears
   bool gather_guard = false;      // a back stage's first launch reads the solver slots until FE_STG: complete after a reset's drains
   FrontEvents own_ev, *ev = &own_ev;  // ev: the set in use: its own, or one the communicator lends per own tick (api_comm.hip, OwnTick)
@@ -532,6 +535,8 @@ int run_lm(esvo_context* h, u32 max_matches, int cull, bool dense, hipStream_t s
 int run_order_points(esvo_context* h, u32 max_matches, DevPoint* dst, hipStream_t st = nullptr, u32* host_row = nullptr);
 void collect_bm_failures(esvo_context* h, const u32* row, bool accumulate);
 int read_counters(esvo_context* h);
+bool lm_guard_wanted(const esvo_context* h);  // the scale-loop guard applies to the handle's next refinement launch
+void collect_lm_guard(esvo_context* h, const u32* row, bool guarded);  // the launch's CNT_LM_* words -> MapSession::lm_stats
 int tick_phase0(esvo_context* h, uint64_t t_ns, const uint64_t* pose_t_ns, const double* pose_T, size_t m, FrontOpts opt = FrontOpts());
 int tick_phase1_enqueue(esvo_context* h);
 int tick_phase1_collect(esvo_context* h, int fp);

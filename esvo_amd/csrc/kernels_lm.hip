@@ -243,9 +243,17 @@ __device__ inline void interp_column(__amdgpu_buffer_rsrc_t img, int W, const Pa
 // BAND (routed band mode: the rank's observation pair holds its band + halo rows only): an evaluation whose source blocks
 // leave those rows would read stale bytes -- it is recorded in `viol` (the tick is then refused with ESVO_ERR_HALO by every
 // rank, include/esvo_hip.h), never silently used.
-template <bool WIDE, bool L2, bool COUNT = false, bool BAND = false>
+// GUARD (the scale-loop guard, common.hpp: LmGuard): ge->passes = completed updates s2 = sum / N with a non-zero sum (0 on the
+// failure fill and on the shortcut), ge->shortcut, and ge->over = the loop had completed ge->limit passes when its test asked
+// for another -- it ends there, the caller abandons the match.  All three are uniform over the match's lanes, like the loop.
+// (ge is the one element of the pack GE, which is empty in the unguarded instantiations: their signature is what it was.)
+struct LmGuardEval { int limit, passes; bool shortcut, over; };
+template <bool WIDE, bool L2, bool COUNT = false, bool BAND = false, bool GUARD = false, typename... GE>
 __device__ bool lm_eval(const DevParams& p, const LmProblem& pr, LmCache<WIDE>& cc, double x, double* fv, int* n_iter = nullptr,
-                        bool* viol = nullptr) {
+                        bool* viol = nullptr, GE*... ge_pack) {
+  static_assert(sizeof...(GE) == (GUARD ? 1 : 0), "the guarded evaluator takes one LmGuardEval");
+  LmGuardEval* ge = nullptr;
+  if constexpr (GUARD) { ge = (ge_pack, ...); ge->passes = 0; ge->shortcut = false; ge->over = false; }
   int iters = 0;  // t-scale iterations of this evaluation (COUNT only: the split launch orders the matches by it)
   constexpr int RL = Lay<WIDE>::RL;
   // element (y, c) of the patch exists: column 15 only feeds its neighbour; row group 3 of the wide layout owns one row
@@ -363,6 +371,7 @@ __device__ bool lm_eval(const DevParams& p, const LmProblem& pr, LmCache<WIDE>& 
   if ((double)knz * (nu + 1) / (double)N <= 0.94 && minabs >= 1e-6) {
     s2 = scale2_0;  // provable outcome of the uncapped loop (header comment)
     DEV_LM_SHORTCUT(pr);
+    if constexpr (GUARD) ge->shortcut = true;
   } else {
     // DepthProblem.cpp:96-124: s1 <- s2 until |s2 - s1| / s1 <= 5 %.  Every quotient below is the IEEE quotient
     // (fdiv.hpp): r^2 / s1 and the convergence test share the divisor s1, sum / N has a constant divisor, and
@@ -393,8 +402,10 @@ __device__ bool lm_eval(const DevParams& p, const LmProblem& pr, LmCache<WIDE>& 
         const double sum = patch_sum<WIDE>(t, pr.rg);
         if (sum == 0) { s2 = scale2_0; done = true; break; }
         s2 = div_fast(sum, rN);
+        if constexpr (GUARD) ++ge->passes;
         const double rel = div_fast(fabs(s2 - s1), rs1);
         if (!(rel > 0.05)) { done = true; break; }
+        if constexpr (GUARD) { if (ge->passes >= ge->limit) { ge->over = true; done = true; break; } }
         s1 = s2;
       }
     }
@@ -415,8 +426,10 @@ __device__ bool lm_eval(const DevParams& p, const LmProblem& pr, LmCache<WIDE>& 
       const double sum = patch_sum<WIDE>(t, pr.rg);
       if (sum == 0) { s2 = scale2_0; break; }
       s2 = div_by(sum, rN);
+      if constexpr (GUARD) ++ge->passes;
       const double rel = div_by(fabs(s2 - s1), rs1);
       if (!(rel > 0.05)) break;
+      if constexpr (GUARD) { if (ge->passes >= ge->limit) { ge->over = true; break; } }
       s1 = s2;
     }
   }
@@ -494,6 +507,10 @@ struct LmSplit {
                    // the first stage's block index: 4 x 10^4 atomics on the five or six bins that occur in practice
                    // serialise on their L2 lines otherwise (measured: 0.18 ms for the sort alone)
 };
+// The kernel's last argument: LmSplit, and in the GUARD instantiations the scale-loop guard behind it.  The unguarded
+// instantiations' argument block is byte for byte what it was before the guard existed, and so is their code.
+template <bool GUARD> struct LmSplitArg : LmSplit {};
+template <> struct LmSplitArg<true> : LmSplit { LmGuard guard; };
 #define LM_SPLIT_BINS 64
 #define LM_SPLIT_STRIPES 32
 __device__ inline u32 lm_split_stripe(u32 slot) { return (slot >> 2) & (LM_SPLIT_STRIPES - 1); }  // 4 slots per first-stage wave
@@ -518,9 +535,19 @@ __device__ inline u32 lm_split_stripe(u32 slot) { return (slot >> 2) & (LM_SPLIT
 // sizes get 2-8 % SLOWER (short chains: the second wave, the exchange and the extra SGPR spills cost more than the few
 // reused evaluations save), and above ~2000 matches the doubled waves crowd the SIMDs.  The handle therefore measures
 // (api_map.hip, lm_pair_policy): both layouts give the same bits, so it may switch between ticks.
-template <bool WIDE, bool L2 = false, int STAGE = 0, bool PAIR = false, bool BAND = false>
-__global__ void __launch_bounds__(PAIR ? 128 : LM_BLOCK, WIDE ? LM_WIDE_WAVES : LM_WAVES) lm_refine_kernel(LmArgs a, DevParams p, u32* n_solved, LmSplit sp) {
+// ---- the scale-loop guard (GUARD; common.hpp: LmGuard) -----------------------------------------------------------------------
+// A match's counts (evaluations, passes, its largest evaluation, shortcut evaluations) are group-uniform integers in its lanes.
+// Its first evaluation over the limit takes the match's lanes out of the solver loop -- the exit every match takes sooner or
+// later, at its own time -- so an abandoned match costs its wave nothing more, and its neighbours run the instructions they
+// would have run beside a match that converged at that point.  Behind the loop the wave adds its matches' counts up and its
+// first lane leaves them in the launch's striped block.  Single launches only: the pair layout's second wave evaluates points
+// the solver may never ask for, and the split launch's first stage is not a whole solve.
+template <bool GUARD> struct LmGuardCounts {};
+template <> struct LmGuardCounts<true> { int evals = 0, passes = 0, max_eval = 0, shortcut = 0; bool abandoned = false; };
+template <bool WIDE, bool L2 = false, int STAGE = 0, bool PAIR = false, bool BAND = false, bool GUARD = false>
+__global__ void __launch_bounds__(PAIR ? 128 : LM_BLOCK, WIDE ? LM_WIDE_WAVES : LM_WAVES) lm_refine_kernel(LmArgs a, DevParams p, u32* n_solved, LmSplitArg<GUARD> sp) {
   static_assert(!PAIR || (WIDE && !L2 && STAGE == 0), "the pair layout is a variant of the wide one");
+  static_assert(!GUARD || (STAGE == 0 && !PAIR && !BAND && !L2 && LM_BLOCK == 64), "the guard: single launches of the Student-t model on a plain handle, one wave per workgroup");
   static_assert(!BAND || (STAGE == 0 && !PAIR), "routed band launches are single launches of the narrow or the wide layout");
   constexpr int RL = Lay<WIDE>::RL;
   // [exchange parity][wave][row][lane]: residuals of the two points evaluated side by side, + whether each was tight
@@ -631,6 +658,7 @@ __global__ void __launch_bounds__(PAIR ? 128 : LM_BLOCK, WIDE ? LM_WIDE_WAVES : 
   double xs = 0.;
   int xpar = 0;
   bool have_spec = false;
+  LmGuardCounts<GUARD> gc;
   if constexpr (STAGE == 1) {  // minimizeInit only: F(x0), |F(x0)|, what the evaluation cost
     int n_it = 0;
     const bool tgt = lm_eval<WIDE, L2, true>(p, pr, cc, x, out, &n_it);
@@ -706,6 +734,15 @@ __global__ void __launch_bounds__(PAIR ? 128 : LM_BLOCK, WIDE ? LM_WIDE_WAVES : 
           have_spec = true;
         }
       }
+    } else if constexpr (GUARD) {
+      LmGuardEval ge;
+      ge.limit = sp.guard.limit;
+      out_tight = lm_eval<WIDE, L2, false, BAND, true>(p, pr, cc, xe, out, nullptr, &viol, &ge);
+      ++gc.evals;
+      gc.passes += ge.passes;
+      gc.max_eval = max(gc.max_eval, ge.passes);
+      gc.shortcut += ge.shortcut ? 1 : 0;
+      if (ge.over) { gc.abandoned = true; break; }
     } else {
       out_tight = lm_eval<WIDE, L2, false, BAND>(p, pr, cc, xe, out, nullptr, &viol);
     }
@@ -832,7 +869,29 @@ __global__ void __launch_bounds__(PAIR ? 128 : LM_BLOCK, WIDE ? LM_WIDE_WAVES : 
     atomicAdd(&a.clk[2 * xcc + 1], r1 - sc[1]);
     atomicAdd(&a.clk[CLK_SAMPLES], 1ull);
   }
+  if constexpr (GUARD) {  // the wave's counts: its matches' lead lanes are lanes 0, 16, 32, 48 (wide: lane 0)
+    const bool mine = active && lead;
+    auto wave_sum = [](int v) {
+      return (__builtin_amdgcn_readlane(v, 0) + __builtin_amdgcn_readlane(v, 16)) + (__builtin_amdgcn_readlane(v, 32) + __builtin_amdgcn_readlane(v, 48));
+    };
+    auto wave_max = [](int v) {
+      return max(max(__builtin_amdgcn_readlane(v, 0), __builtin_amdgcn_readlane(v, 16)), max(__builtin_amdgcn_readlane(v, 32), __builtin_amdgcn_readlane(v, 48)));
+    };
+    const int w_passes = wave_sum(mine ? gc.passes : 0), w_evals = wave_sum(mine ? gc.evals : 0), w_shortcut = wave_sum(mine ? gc.shortcut : 0);
+    const int w_abandoned = wave_sum(mine && gc.abandoned ? 1 : 0);
+    const int w_max_eval = wave_max(mine ? gc.max_eval : 0), w_max_match = wave_max(mine ? gc.passes : 0);
+    if (threadIdx.x == 0) {
+      u32* g = sp.guard.stripes + (size_t)(blockIdx.x & (LM_GUARD_STRIPES - 1u)) * LM_GUARD_WORDS;
+      if (w_passes) atomicAdd(g + 0, (u32)w_passes);
+      if (w_evals) atomicAdd(g + 1, (u32)w_evals);
+      if (w_shortcut) atomicAdd(g + 2, (u32)w_shortcut);
+      if (w_abandoned) atomicAdd(g + 3, (u32)w_abandoned);
+      if (w_max_eval) atomicMax(g + 4, (u32)w_max_eval);
+      if (w_max_match) atomicMax(g + 5, (u32)w_max_match);
+    }
+  }
   if (!active || !lead) return;
+  if constexpr (GUARD) { if (gc.abandoned) { a.out_flags[s] = 0u; return; } }  // no point, not solved
   if constexpr (BAND) { if (viol) atomicAdd(a.halo_viol, 1u); }
   const bool solved = !(x <= 0.001);  // DepthProblemSolver.cpp:192
   bool keep = solved;
@@ -974,7 +1033,7 @@ void launch_lm_pixel_order(const esvo_match_t* matches, const u32* n_matches, u3
   launch_radix_sort_pairs(rows, max_matches, n_matches, key_bits, hist, scan_tmp, order, s);
 }
 
-void launch_lm_refine_any(const LmArgs& a, const DevParams& p, u32* n_solved, hipStream_t s);  // kernels_lm_any.hip
+void launch_lm_refine_any(const LmArgs& a, const DevParams& p, u32* n_solved, hipStream_t s, const LmGuard& g);  // kernels_lm_any.hip
 // whether a launch bounded by max_matches takes the one-wave-per-match layout -- the one that reads LmArgs::match_index
 bool lm_launch_is_wide(u32 max_matches, const DevParams& p) {
   return max_matches > 0 && p.wx == LM_COLS && p.wy == LM_ROWS && p.ls_norm != ESVO_LSNORM_L2 && max_matches <= LM_WIDE_MAX && LM_BLOCK == 64;
@@ -984,10 +1043,10 @@ bool lm_launch_is_wide(u32 max_matches, const DevParams& p) {
 bool lm_launch_is_ordered(u32 max_matches, bool dense, bool band, bool split, const DevParams& p) {
   return max_matches > LM_WIDE_MAX && p.wx == LM_COLS && p.wy == LM_ROWS && !dense && !band && !split;
 }
-void launch_lm_refine(const LmArgs& a, const DevParams& p, u32* n_solved, hipStream_t s) {
+void launch_lm_refine(const LmArgs& a, const DevParams& p, u32* n_solved, hipStream_t s, const LmGuard& g) {
   if (a.max_matches == 0) return;
-  if (p.wx != LM_COLS || p.wy != LM_ROWS) { launch_lm_refine_any(a, p, n_solved, s); return; }  // (no clock probe, no layouts)
-  LmSplit sp;
+  if (p.wx != LM_COLS || p.wy != LM_ROWS) { launch_lm_refine_any(a, p, n_solved, s, g); return; }  // (no clock probe, no layouts)
+  LmSplitArg<false> sp;
   sp.fvec0 = a.split_fvec0; sp.fnorm0 = a.split_fnorm0; sp.meta = a.split_meta; sp.order = a.split_order; sp.hist = a.split_hist;
   const u32 groups_per_block = LM_BLOCK / 16;
   const u32 blocks = (a.max_matches + groups_per_block - 1) / groups_per_block;
@@ -1002,6 +1061,18 @@ void launch_lm_refine(const LmArgs& a, const DevParams& p, u32* n_solved, hipStr
     else
       hipLaunchKernelGGL((lm_refine_kernel<false, false, 0, false, true>), dim3(blocks), dim3(LM_BLOCK), 0, s, a, p, n_solved, sp);
     return;
+  }
+  if constexpr (LM_BLOCK == 64) {
+    if (g.limit != 0 && g.stripes) {  // the scale-loop guard: one launch, wide or narrow (a.order: the caller's, as for any single narrow launch)
+      LmSplitArg<true> spg;
+      static_cast<LmSplit&>(spg) = sp;
+      spg.guard = g;
+      if (a.max_matches <= LM_WIDE_MAX)
+        hipLaunchKernelGGL((lm_refine_kernel<true, false, 0, false, false, true>), dim3(a.max_matches), dim3(64), 0, s, a, p, n_solved, spg);
+      else
+        hipLaunchKernelGGL((lm_refine_kernel<false, false, 0, false, false, true>), dim3(blocks), dim3(LM_BLOCK), 0, s, a, p, n_solved, spg);
+      return;
+    }
   }
   // the match count lives on the device; the layout is chosen by the launch's bound (the events handed to block matching)
   if (a.max_matches <= LM_WIDE_MAX && LM_BLOCK == 64) {
@@ -1018,6 +1089,24 @@ void launch_lm_refine(const LmArgs& a, const DevParams& p, u32* n_solved, hipStr
     return;
   }
   hipLaunchKernelGGL((lm_refine_kernel<false, false, 0>), dim3(blocks), dim3(LM_BLOCK), 0, s, a, p, n_solved, sp);
+}
+
+// The guard's fold, beside the compaction of the launch's points: the stripes' sums and maxima go into the front stage's counter
+// row, which the host reads anyway, and the stripes are zero again for the next launch.
+__global__ void __launch_bounds__(64) lm_guard_fold_kernel(u32* __restrict__ stripes, u32* __restrict__ row) {
+  const u32 k = threadIdx.x;
+  if (k >= 6u) return;
+  u32 acc = 0;
+  for (u32 st = 0; st < LM_GUARD_STRIPES; ++st) {
+    const u32 v = stripes[st * LM_GUARD_WORDS + k];
+    stripes[st * LM_GUARD_WORDS + k] = 0u;
+    acc = k < 4u ? acc + v : max(acc, v);
+  }
+  // stripe words 0..5 -> CNT_LM_PASSES, _EVALS, _SHORTCUT, _ABANDONED, _MAX_EVAL, _MAX_MATCH
+  row[k < 2u ? CNT_LM_PASSES + k : (k < 4u ? CNT_LM_SHORTCUT + (k - 2u) : CNT_LM_MAX_EVAL + (k - 4u))] = acc;
+}
+void launch_lm_guard_fold(u32* stripes, u32* counter_row, hipStream_t s) {
+  hipLaunchKernelGGL(lm_guard_fold_kernel, dim3(1), dim3(64), 0, s, stripes, counter_row);
 }
 
 // stable compaction of the solver slots into a frame buffer

@@ -63,8 +63,12 @@ __device__ inline AnyGeom any_geom(const DevParams& p, int wx, int wy, double lx
 
 // DepthProblem::operator(): fv[y][c] = residual of patch element (y, c) (0 in the padding lanes); rr = scratch for the raw
 // residuals.  L2: LSnorm "l2" (the plain temporal residual, 255 on failure).
-template <bool L2>
-__device__ void any_eval(const DevParams& p, const AnyProblem& pr, double x, double* fv, double* rr, bool& viol) {
+// GUARD (the scale-loop guard, common.hpp: LmGuard; wave-uniform): ge.passes = completed updates s2 = sum / N with a non-zero
+// sum, ge.shortcut, ge.over = the loop had completed ge.limit passes when its test asked for another (it ends there).
+struct AnyGuardEval { int limit, passes; bool shortcut, over; };
+template <bool L2, bool GUARD = false>
+__device__ void any_eval(const DevParams& p, const AnyProblem& pr, double x, double* fv, double* rr, bool& viol, AnyGuardEval* ge = nullptr) {
+  if constexpr (GUARD) { ge->passes = 0; ge->shortcut = false; ge->over = false; }
   const int wx = pr.wx, wy = pr.wy, c = pr.c, P = pr.P;
   const bool el = c < wx;
   const double nu = p.td_nu;
@@ -137,6 +141,7 @@ __device__ void any_eval(const DevParams& p, const AnyProblem& pr, double x, dou
   double s2;
   if ((double)knz * (nu + 1) / (double)N <= 0.94 && minabs >= 1e-6) {
     s2 = scale2_0;  // provable outcome of the reference's uncapped loop (kernels_lm.hip header)
+    if constexpr (GUARD) ge->shortcut = true;
   } else {          // DepthProblem.cpp:96-124: s1 <- s2 until |s2 - s1| / s1 <= 5 %
     double s1 = scale2_0;
     while (true) {
@@ -150,7 +155,9 @@ __device__ void any_eval(const DevParams& p, const AnyProblem& pr, double x, dou
       const double sum = any_butterfly(a, P);
       if (sum == 0) { s2 = scale2_0; break; }
       s2 = sum / (double)N;
+      if constexpr (GUARD) ++ge->passes;
       if (!(fabs(s2 - s1) / s1 > 0.05)) break;
+      if constexpr (GUARD) { if (ge->passes >= ge->limit) { ge->over = true; break; } }
       s1 = s2;
     }
   }
@@ -160,8 +167,11 @@ __device__ void any_eval(const DevParams& p, const AnyProblem& pr, double x, dou
   }
 }
 
-template <bool L2>
-__global__ void __launch_bounds__(64) lm_refine_any_kernel(LmArgs a, DevParams p, u32* n_solved) {
+// GUARD: the match's counts are wave-uniform (one match per wave); its first evaluation over the limit ends the solve, lane 0
+// leaves the counts in the launch's striped block (g, behind the arguments the unguarded instantiations read).
+template <bool L2, bool GUARD = false>
+__global__ void __launch_bounds__(64) lm_refine_any_kernel(LmArgs a, DevParams p, u32* n_solved, LmGuard g) {
+  static_assert(!GUARD || !L2, "the Gaussian model has no scale loop");
   const int wx = p.wx, wy = p.wy;
   int P = 1;
   while (P < wx) P <<= 1;
@@ -209,6 +219,8 @@ __global__ void __launch_bounds__(64) lm_refine_any_kernel(LmArgs a, DevParams p
   int phase = 0;
   bool need_step = false;
   double xe = x;
+  int g_evals = 0, g_passes = 0, g_max_eval = 0, g_shortcut = 0;  // GUARD
+  bool g_abandoned = false;
   while (true) {
     if (need_step) {
       const double pstep = lm_lmpar2(r, diag, qtf, delta, par);
@@ -219,7 +231,18 @@ __global__ void __launch_bounds__(64) lm_refine_any_kernel(LmArgs a, DevParams p
       xe = xnew;
       need_step = false;
     }
-    any_eval<L2>(p, pr, xe, out, rr, viol);
+    if constexpr (GUARD) {
+      AnyGuardEval ge;
+      ge.limit = g.limit;
+      any_eval<L2, true>(p, pr, xe, out, rr, viol, &ge);
+      ++g_evals;
+      g_passes += ge.passes;
+      g_max_eval = max(g_max_eval, ge.passes);
+      g_shortcut += ge.shortcut ? 1 : 0;
+      if (ge.over) { g_abandoned = true; break; }
+    } else {
+      any_eval<L2>(p, pr, xe, out, rr, viol);
+    }
     __syncthreads();  // one wave per workgroup: orders the LDS writes of all lanes before the cross-lane read of element (0, 0)
     int status = -1;
     bool outer_tail = false;
@@ -322,6 +345,14 @@ __global__ void __launch_bounds__(64) lm_refine_any_kernel(LmArgs a, DevParams p
     }
   }
   if (c != 0) return;
+  if constexpr (GUARD) {
+    u32* gs = g.stripes + (size_t)(blockIdx.x & (LM_GUARD_STRIPES - 1u)) * LM_GUARD_WORDS;
+    if (g_passes) atomicAdd(gs + 0, (u32)g_passes);
+    atomicAdd(gs + 1, (u32)g_evals);
+    if (g_shortcut) atomicAdd(gs + 2, (u32)g_shortcut);
+    if (g_passes) { atomicMax(gs + 4, (u32)g_max_eval); atomicMax(gs + 5, (u32)g_passes); }
+    if (g_abandoned) { atomicAdd(gs + 3, 1u); a.out_flags[s] = 0u; return; }  // no point, not solved
+  }
   if (a.halo_viol && viol) atomicAdd(a.halo_viol, 1u);
   const bool solved = !(x <= 0.001);  // DepthProblemSolver.cpp:192
   bool keep = solved;
@@ -357,13 +388,15 @@ __global__ void __launch_bounds__(64) lm_refine_any_kernel(LmArgs a, DevParams p
   a.out_flags[s] = keep ? 1u : 0u;
 }
 
-void launch_lm_refine_any(const LmArgs& a, const DevParams& p, u32* n_solved, hipStream_t s) {
+void launch_lm_refine_any(const LmArgs& a, const DevParams& p, u32* n_solved, hipStream_t s, const LmGuard& g) {
   if (a.max_matches == 0) return;
   const size_t lds = (size_t)3 * p.wy * 64 * sizeof(double);
   if (p.ls_norm == ESVO_LSNORM_L2)
-    hipLaunchKernelGGL((lm_refine_any_kernel<true>), dim3(a.max_matches), dim3(64), lds, s, a, p, n_solved);
+    hipLaunchKernelGGL((lm_refine_any_kernel<true>), dim3(a.max_matches), dim3(64), lds, s, a, p, n_solved, g);
+  else if (g.limit != 0 && g.stripes && !a.halo_viol)
+    hipLaunchKernelGGL((lm_refine_any_kernel<false, true>), dim3(a.max_matches), dim3(64), lds, s, a, p, n_solved, g);
   else
-    hipLaunchKernelGGL((lm_refine_any_kernel<false>), dim3(a.max_matches), dim3(64), lds, s, a, p, n_solved);
+    hipLaunchKernelGGL((lm_refine_any_kernel<false>), dim3(a.max_matches), dim3(64), lds, s, a, p, n_solved, g);
 }
 
 }  // namespace esvo

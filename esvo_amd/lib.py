@@ -11,7 +11,7 @@ import subprocess
 import numpy as np
 
 from .abi import (DEPTH_POINT_DTYPE, EM_POSE_FN, ERR_CAPACITY, ERR_INVALID_ARG, ERR_STATE, EVENT_DTYPE, MATCH_DTYPE, CalibStruct, EmSelectionStruct,
-                  EmStatsStruct, GpcParamsStruct, GpcStatsStruct, ParamsStruct, SgmStatsStruct, StatsStruct, TRACK_ITER_DTYPE, TRACK_SOLVE_MAX_ITERATIONS,
+                  EmStatsStruct, GpcParamsStruct, GpcStatsStruct, LmStatsStruct, ParamsStruct, SgmStatsStruct, StatsStruct, TRACK_ITER_DTYPE, TRACK_SOLVE_MAX_ITERATIONS,
                   TrackSolveInfoStruct, TrackSolveParamsStruct)
 
 _CSRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc")
@@ -36,6 +36,7 @@ SYMBOLS = [
     "esvo_comm_unique_id", "esvo_comm_rccl_info", "esvo_comm_init", "esvo_comm_init_callbacks", "esvo_comm_destroy", "esvo_comm_owns_next_tick",
     "esvo_comm_tick", "esvo_comm_tick_resident", "esvo_comm_get_stats", "esvo_comm_flush", "esvo_comm_newest_map", "esvo_comm_shard_tick", "esvo_comm_gather_map", "esvo_comm_gather_pointcloud_xyz", "esvo_comm_gather_ts",
     "esvo_map_match_em", "esvo_map_tick_em", "esvo_map_em_get_selection", "esvo_map_em_stats", "esvo_em_sizes",
+    "esvo_map_lm_stats", "esvo_lm_sizes",
     "esvo_map_tick_sgm", "esvo_map_push_disparity_frame", "esvo_map_sgm_stats", "esvo_sgm_sizes",
     "esvo_map_cloud_build", "esvo_map_cloud_get", "esvo_map_cloud_device", "esvo_track_set_reference_from_cloud", "esvo_track_stochastic_order",
     "esvo_map_cloud_near", "esvo_map_voxel_filter", "esvo_map_gpc_configure", "esvo_map_gpc_update", "esvo_map_gpc_get", "esvo_map_gpc_device",
@@ -219,6 +220,9 @@ def load():
     lib.esvo_map_em_stats.argtypes = [vp, vp]
     lib.esvo_em_sizes.argtypes = [vp]
     lib.esvo_em_sizes.restype = None
+    lib.esvo_map_lm_stats.argtypes = [vp, vp]
+    lib.esvo_lm_sizes.argtypes = [vp]
+    lib.esvo_lm_sizes.restype = None
     lib.esvo_map_tick_sgm.argtypes = [vp, vp, vp, psz, vp]
     lib.esvo_map_push_disparity_frame.argtypes = [vp, vp, vp, sz, psz]
     lib.esvo_map_sgm_stats.argtypes = [vp, vp]
@@ -249,7 +253,7 @@ def load():
     lib.esvo_ts_history_select.argtypes = [vp, sz, i32, EM_POSE_FN, vp, psz, vp]
     lib.esvo_ts_history_select_observation.argtypes = [vp, i32, EM_POSE_FN, vp, C.POINTER(C.c_uint64), vp]
     for s in SYMBOLS:
-        if s not in ("esvo_default_params", "esvo_last_error", "esvo_abi_sizes", "esvo_bag_last_error", "esvo_em_sizes", "esvo_sgm_sizes",
+        if s not in ("esvo_default_params", "esvo_last_error", "esvo_abi_sizes", "esvo_bag_last_error", "esvo_em_sizes", "esvo_lm_sizes", "esvo_sgm_sizes",
                      "esvo_track_sizes", "esvo_gpc_sizes"):
             getattr(lib, s).restype = C.c_int
     lib.esvo_abi_sizes.argtypes = [vp]
@@ -669,6 +673,13 @@ def em_sizes():
     return list(out)
 
 
+def lm_sizes():
+    """sizeof(esvo_lm_stats_t), ESVO_LM_SCALE_COUNT_ONLY, 0, 0 (esvo_lm_sizes)"""
+    out = (C.c_size_t * 4)()
+    load().esvo_lm_sizes(out)
+    return list(out)
+
+
 def sgm_sizes():
     """sizeof(esvo_sgm_stats_t), numDisparities, 0, 0 (esvo_sgm_sizes)"""
     out = (C.c_size_t * 4)()
@@ -942,6 +953,12 @@ class Esvo:
     def em_stats(self):
         s = EmStatsStruct()
         self._ck(self.lib.esvo_map_em_stats(self.h, C.byref(s)))
+        return s
+
+    def lm_stats(self):
+        """the scale-loop guard's counts (esvo_map_lm_stats; ParamsStruct.lm_scale_pass_limit): all zero while the limit is 0"""
+        s = LmStatsStruct()
+        self._ck(self.lib.esvo_map_lm_stats(self.h, C.byref(s)))
         return s
 
     # ---- semi-global matching per tick: esvo_MVStereo mode 4

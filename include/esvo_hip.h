@@ -156,8 +156,13 @@ typedef struct esvo_params_t {
    * newer events of a pixel reads that pixel empty, TimeSurface.h:39-75) is not reproduced.  1..32: EventQueueMat semantics
    * exactly -- every staged event enters its pixel's queue at the next render, renders at any time in any order. */
   int32_t max_event_queue_len;
-  int32_t pad_params_;
+  /* Scale-loop guard of the LM refinement (esvo_map_lm_stats below).  The reference's Student-t scale loop
+   * (DepthProblem.cpp:96-124) has no iteration cap.  0 (default): off -- nothing is counted or bounded.  > 0: a match is abandoned
+   * by its first evaluation that has completed this many passes while the loop test asks for another; it yields no point.
+   * ESVO_LM_SCALE_COUNT_ONLY: passes are counted, no match is abandoned.  Negative: refused. */
+  int32_t lm_scale_pass_limit;
 } esvo_params_t;
+#define ESVO_LM_SCALE_COUNT_ONLY INT32_MAX
 
 /* What flows EventBM -> DepthProblemSolver.  The reference's EventMatchPair
  * (EventMatchPair.h:16-38) carries a full pose; consumers read only x_left_,
@@ -502,6 +507,39 @@ int esvo_map_em_get_selection(esvo_handle h, esvo_em_selection_t* sel, uint32_t*
 int esvo_map_em_stats(esvo_handle h, esvo_em_stats_t* out);
 /* sizeof() of {esvo_em_params_t, esvo_em_selection_t, esvo_em_stats_t}, 0. */
 void esvo_em_sizes(size_t out[4]);
+
+/* ---- Mapper: the scale loop of the LM refinement -------------------------------------------------------------------
+ *
+ * With esvo_params_t::lm_scale_pass_limit != 0 the refinement kernels count the passes of the Student-t scale loop and, with a
+ * limit below ESVO_LM_SCALE_COUNT_ONLY, abandon matches whose loop crawls.
+ *   pass        one completed update s2 = sum / N with a non-zero sum.  An evaluation that takes the failure fill, or whose
+ *               collapse is taken for granted (at most floor(0.94 N / (nu + 1)) non-zero residuals, none below 1e-6), has 0.
+ *   over        an evaluation that has completed `limit` passes and whose loop test (|s2 - s1| / s1 > 5 %) asks for another.
+ *   abandoned   the first evaluation the solver asks for that is over the limit abandons its match: no point, slot flag 0, not
+ *               counted in last_solved / last_points.  Every other match gives the bits it gives with the limit 0.
+ * Counted: every launch of the refinement on a plain handle (esvo_map_refine, esvo_map_tick, _tick_resident, esvo_map_front,
+ * esvo_map_tick_em mode 2).  The evaluations are those the device computes: F(x0), F(x + h) and F(x + p); NumericalDiff's second
+ * F(x) is the residual vector already held.  With the limit 0, and under LSnorm l2 (no scale loop), every field reads 0.
+ * A band-sharded or tick-interleaved handle refuses a non-zero limit (esvo_shard_set_band, esvo_comm_init*, esvo_set_params:
+ * ESVO_ERR_STATE).  The pair layout of small launches is not used while the guard is on (its second wave evaluates points the
+ * solver may never ask for). */
+typedef struct esvo_lm_stats_t {
+  uint32_t enabled;                /* 1: the last refinement launch ran with a non-zero limit under the Student-t model */
+  uint32_t last_max_passes_eval;   /* of the last completed launch: most passes of one evaluation */
+  uint32_t last_max_passes_match;  /*   ... most passes of one match, summed over its evaluations */
+  uint32_t last_abandoned;         /*   ... matches abandoned */
+  uint64_t last_passes;            /*   ... passes, evaluations, evaluations that took the collapse for granted */
+  uint64_t last_evals;
+  uint64_t last_shortcut_evals;
+  uint64_t total_passes;           /* since esvo_create / esvo_reset */
+  uint64_t total_evals;
+  uint64_t total_shortcut_evals;
+  uint64_t total_abandoned;
+} esvo_lm_stats_t;
+/* Waits for outstanding refinement launches as esvo_get_stats does. */
+int esvo_map_lm_stats(esvo_handle h, esvo_lm_stats_t* out);
+/* sizeof(esvo_lm_stats_t), ESVO_LM_SCALE_COUNT_ONLY, 0, 0. */
+void esvo_lm_sizes(size_t out[4]);
 
 /* ---- Mapper: semi-global matching per tick, esvo_MVStereo mode 4 -------------------------------------------------
  *

@@ -86,6 +86,13 @@ class Context {
   }
   void setParams(const esvo_params_t& p) { check(esvo_set_params(h_, &p), "esvo_set_params"); params_ = p; }
   void reset() { check(esvo_reset(h_), "esvo_reset"); }  // esvo_Mapping::reset, esvo_Mapping.cpp:764-804
+  // the scale-loop guard of the LM refinement: the limit travels in the parameters (setParams), the counts come back here
+  void setLmScalePassLimit(int32_t limit) { esvo_params_t p = params_; p.lm_scale_pass_limit = limit; setParams(p); }
+  esvo_lm_stats_t lmStats() const {
+    esvo_lm_stats_t st{};
+    check(esvo_map_lm_stats(h_, &st), "esvo_map_lm_stats");
+    return st;
+  }
 
  private:
   esvo_params_t params_;

@@ -20,7 +20,7 @@ import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SRC = os.path.join(ROOT, "esvo_amd", "csrc", "kernels_lm.hip")
-KERNEL = "lm_refine_kernelILb0ELb0ELi0ELb0ELb0EEE"   # narrow layout, Student-t, single launch, no band guard
+KERNEL = "lm_refine_kernelILb0ELb0ELi0ELb0ELb0ELb0EEE"   # narrow layout, Student-t, single launch, no band guard, no scale-loop guard
 
 MARKS = [  # (region, first line = the line holding this text); a region lasts until the next mark
     ("interpolation (geometry, loads, bilinear)", "__device__ inline PatchGeom interp_geom"),
@@ -33,14 +33,14 @@ MARKS = [  # (region, first line = the line holding this text); a region lasts u
     ("t-scale loop (general, rare)", "    while (!done) {"),
     ("weights sqrt((nu+1)/(nu+r^2/s2)) r (tight)", "// The weights sqrt((nu + 1) / (nu + r^2 / s2))"),
     ("weights (general, rare)", "  const Recip rs2 = make_recip(s2);"),
-    ("kernel prologue (match, pose, set-up)", "lm_refine_kernel(LmArgs a, DevParams p, u32* n_solved, LmSplit sp) {"),
+    ("kernel prologue (match, pose, set-up)", "lm_refine_kernel(LmArgs a, DevParams p, u32* n_solved, LmSplitArg<GUARD> sp) {"),
     ("solver: lmpar + trial point", "    if (need_step) {  // determine the LM parameter"),
     ("solver: evaluator call site / pair exchange", "    bool out_tight;"),
     ("solver: phase 0 (minimizeInit)", "    if (phase == 0) {  // minimizeInit"),
     ("solver: phase 1 (forward difference, J, qtf)", "    } else if (phase == 1) {"),
     ("solver: phase 2 (trust-region test)", "    } else {  // phase 2: trust-region trial at xnew"),
     ("solver: outer loop (DepthProblemSolver.cpp:161-188)", "    if (phase == 0) {\n"),
-    ("kernel epilogue (point, culling, store)", "  if (!active || !lead) return;\n  if constexpr (BAND) { if (viol) atomicAdd(a.halo_viol, 1u); }"),
+    ("kernel epilogue (point, culling, store)", "  if (!active || !lead) return;\n  if constexpr (GUARD) { if (gc.abandoned)"),
     ("(other kernels / host)", "// counting sort of the slots by the cost of F(x0)"),
 ]
 
