@@ -161,6 +161,88 @@ def make_events(x, y, t_ns, polarity=None):
     return ev
 
 
+# ---- event columns (esvo_event_columns_t of include/esvo_hip.h): x / y / t / p arrays in host or device memory
+T_NS_I64, T_US_I64, T_US_U32 = 0, 1, 2
+P_U8, P_I8 = 0, 1
+MEM_HOST, MEM_DEVICE = 0, 1
+STAMP_END_NS = 2 ** 32 * 10 ** 9   # a valid stamp is below this: what sec (u32) can hold
+
+
+class EventColumnsStruct(C.Structure):
+    _fields_ = [
+        ("x", C.c_void_p), ("y", C.c_void_p), ("t", C.c_void_p), ("p", C.c_void_p),
+        ("t_offset", C.c_int64),
+        ("t_type", C.c_int32), ("p_type", C.c_int32), ("memory", C.c_int32), ("reserved", C.c_int32),
+    ]
+
+
+class ColumnsError(ValueError):
+    """an element of the columns has no valid stamp; `first_bad` is its index"""
+
+    def __init__(self, first_bad):
+        super().__init__(f"event columns: element {first_bad} has no valid time stamp ((t + t_offset) * unit outside [0, 2^32 * 10^9))")
+        self.first_bad = int(first_bad)
+
+
+def column_t_type(dtype, unit):
+    """t_type of a stamp column from its dtype and unit ("ns" | "us"); ValueError for a combination the C-ABI does not take"""
+    dtype = np.dtype(dtype)
+    if unit == "ns" and dtype == np.int64:
+        return T_NS_I64
+    if unit == "us" and dtype == np.int64:
+        return T_US_I64
+    if unit == "us" and dtype == np.uint32:
+        return T_US_U32
+    raise ValueError(f"event columns: t must be int64 (unit 'ns' or 'us') or uint32 (unit 'us'), not {dtype} with unit {unit!r}")
+
+
+def column_p_type(dtype):
+    dtype = np.dtype(dtype)
+    if dtype in (np.dtype(np.uint8), np.dtype(np.bool_)):
+        return P_U8
+    if dtype == np.int8:
+        return P_I8
+    raise ValueError(f"event columns: p must be uint8 / bool (!= 0 is ON) or int8 (> 0 is ON), not {dtype}")
+
+
+def check_t_offset(t_offset):
+    t_offset = int(t_offset)
+    if not -2 ** 63 <= t_offset < 2 ** 63:
+        raise ValueError("event columns: t_offset must fit int64")
+    return t_offset
+
+
+def columns_to_events(x, y, t, p=None, unit="ns", t_offset=0):
+    """esvo_event_columns_to_events in numpy: the esvo_event_t records of the columns x, y (16-bit), t (int64 ns / us or uint32 us)
+    and p (uint8: != 0 is ON; int8: > 0 is ON; None: all ON), stamp = (t + t_offset) * unit.  Exact: no element is added or scaled
+    before it is known to stay inside int64.  Raises ColumnsError (first_bad) where a stamp is not in [0, 2^32 * 10^9)."""
+    t = np.asarray(t)
+    t_type = column_t_type(t.dtype, unit)
+    off, k = check_t_offset(t_offset), (1 if t_type == T_NS_I64 else 1000)
+    n = t.shape[0]
+    x, y = np.asarray(x), np.asarray(y)
+    if x.dtype.itemsize != 2 or y.dtype.itemsize != 2 or x.dtype.kind not in "iu" or y.dtype.kind not in "iu":
+        raise ValueError("event columns: x and y must be 16-bit integers")
+    if x.shape != (n,) or y.shape != (n,) or (p is not None and np.asarray(p).shape != (n,)):
+        raise ValueError("event columns: one-dimensional columns of one length are expected")
+    t64 = t.astype(np.int64)
+    lo, hi = max(-off, -2 ** 63), min((STAMP_END_NS - 1) // k - off, 2 ** 63 - 1)   # 0 <= t + off <= hi + off, as bounds on t
+    ok = (t64 >= np.int64(lo)) & (t64 <= np.int64(hi)) if lo <= hi else np.zeros(n, bool)
+    if not ok.all():
+        raise ColumnsError(int(np.argmin(ok)))
+    s = (t64 + np.int64(off)).astype(np.uint64) * np.uint64(k)
+    ev = np.zeros(n, dtype=EVENT_DTYPE)
+    ev["x"], ev["y"] = x.view(np.uint16), y.view(np.uint16)
+    ev["sec"] = (s // np.uint64(1_000_000_000)).astype(np.uint32)
+    ev["nsec"] = (s % np.uint64(1_000_000_000)).astype(np.uint32)
+    if p is None:
+        ev["polarity"] = 1
+    else:
+        p = np.asarray(p)
+        ev["polarity"] = (p > 0) if column_p_type(p.dtype) == P_I8 else (p != 0)
+    return ev
+
+
 def event_ns(ev):
     return ev["sec"].astype(np.uint64) * np.uint64(1_000_000_000) + ev["nsec"].astype(np.uint64)
 

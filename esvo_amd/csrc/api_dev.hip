@@ -11,7 +11,8 @@
 // Return value: a negative esvo_status_t, or the number of guard words that no longer hold the pattern (0 when all is well).
 // The exceptions are at the end, take a handle, launch nothing and copy something out: esvo_debug_fuse_cell_counts one buffer of the
 // last fusion (tests/test_gpu_fuse_cases.py), esvo_debug_bm_owner_count the owner count of the last shared block-matching launch
-// (tests/test_gpu_bm_dedupe.py); esvo_debug_live_allocations and esvo_debug_devmem_selftest take no handle and read / walk
+// (tests/test_gpu_bm_dedupe.py), esvo_debug_ts_ring a camera's event ring and the host's stamp mirror
+// (tests/test_gpu_event_columns.py); esvo_debug_live_allocations and esvo_debug_devmem_selftest take no handle and read / walk
 // the ledger of devmem.hpp (tests/test_gpu_lifecycle.py).
 #include <vector>
 
@@ -483,6 +484,33 @@ int esvo_debug_bm_owner_count(esvo_handle h, uint32_t* n_owners, int* shared) {
   if (!h->d_bm_dedupe) return ESVO_OK;
   HIPCHK(hipStreamSynchronize(h->stream));
   HIPCHK(hipMemcpy(n_owners, h->d_bm_dedupe + (size_t)h->W * h->H, sizeof(u32), hipMemcpyDeviceToHost));
+  return ESVO_OK;
+}
+
+// The event ring of a camera as the ingest calls left it: the records of the absolute indices [first_abs, first_abs + n) (out, n
+// records), the host's stamp mirror for them (stamps, n words) and ring_base / ring_next (bounds); each pointer may be NULL.  The
+// range must lie inside [ring_base, ring_next).  Launches nothing; waits for the camera's pusher and drains the ingest stream first.
+// (A render shows a staged stamp through a 30 ms decay rounded to u8: the nanoseconds are invisible there -- tests/test_gpu_event_columns.py.)
+int esvo_debug_ts_ring(esvo_handle h, int cam, uint64_t first_abs, size_t n, esvo_event_t* out, uint64_t* stamps, uint64_t bounds[2]) {
+  if (!h || cam < 0 || cam > 1) return ESVO_ERR_INVALID_ARG;
+  std::lock_guard<std::mutex> lp(h->mu_push[cam]);
+  HIPCHK(hipSetDevice(h->device));
+  HIPCHK(hipStreamSynchronize(h->stream_i));
+  {
+    std::lock_guard<std::mutex> lr(h->mu_ring);
+    const u64 base = h->ring_base[cam], next = h->ring_next[cam];
+    if (bounds) { bounds[0] = base; bounds[1] = next; }
+    if (n && (first_abs < base || first_abs > next || n > next - first_abs))
+      FAIL(ESVO_ERR_INVALID_ARG, "esvo_debug_ts_ring: the range must lie inside [ring_base, ring_next)");
+    if (stamps)
+      for (size_t i = 0; i < n; ++i) stamps[i] = h->ts_host[cam][(size_t)(first_abs - base) + i];
+  }
+  if (out && n) {
+    const u64 slot = first_abs % h->ring_cap;
+    const size_t first = (size_t)std::min<u64>(n, h->ring_cap - slot);
+    HIPCHK(hipMemcpy(out, h->d_ring[cam] + slot, sizeof(esvo_event_t) * first, hipMemcpyDeviceToHost));
+    if (first < n) HIPCHK(hipMemcpy(out + first, h->d_ring[cam], sizeof(esvo_event_t) * (n - first), hipMemcpyDeviceToHost));
+  }
   return ESVO_OK;
 }
 

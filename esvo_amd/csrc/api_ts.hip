@@ -628,6 +628,158 @@ int esvo_ts_push_event_array(esvo_handle h, int cam, const uint8_t* msg, size_t 
   return ESVO_OK;
 }
 
+// ---- column ingest: x / y / t / p arrays in host or device memory (include/esvo_hip.h, esvo_ts_push_event_columns) ----------------
+extern "C++" {
+namespace {
+size_t col_t_size(int t_type) { return t_type == ESVO_T_US_U32 ? 4 : 8; }
+const char* columns_arg_error(const esvo_event_columns_t* c, size_t n) {
+  if (c->t_type != ESVO_T_NS_I64 && c->t_type != ESVO_T_US_I64 && c->t_type != ESVO_T_US_U32) return "event columns: unknown t_type";
+  if (c->p_type != ESVO_P_U8 && c->p_type != ESVO_P_I8) return "event columns: unknown p_type";
+  if (c->memory != ESVO_MEM_HOST && c->memory != ESVO_MEM_DEVICE) return "event columns: unknown memory";
+  if (n && (!c->x || !c->y || !c->t)) return "event columns: x, y and t must not be NULL";
+  if ((uintptr_t)c->x % 2 || (uintptr_t)c->y % 2 || (uintptr_t)c->t % col_t_size(c->t_type))
+    return "event columns: a column base is not aligned for its element type";
+  return nullptr;
+}
+std::string columns_bad_element(size_t i) { return "event columns: element " + std::to_string(i) + " has no valid time stamp ((t + t_offset) * unit outside [0, 2^32 * 10^9))"; }
+// the records of host columns whose stamps are known and valid
+void columns_materialise(const uint16_t* x, const uint16_t* y, const void* p, int p_type, const u64* stamps, size_t n, esvo_event_t* out) {
+  for (size_t i = 0; i < n; ++i) {
+    const uint4 w = columns_record(x[i], y[i], stamps[i], columns_polarity(p, i, p_type));
+    std::memcpy(out + i, &w, sizeof(w));
+  }
+}
+// What the runtime knows of a pointer: 0 host memory (pageable, pinned or registered), 1 plain device memory of `device`,
+// 2 anything else (managed memory, another GPU's).  Launches nothing, copies nothing.
+int column_memory_kind(const void* p, int device) {
+  hipPointerAttribute_t a;
+  std::memset(&a, 0, sizeof(a));
+  if (hipPointerGetAttributes(&a, p) != hipSuccess) { (void)hipGetLastError(); return 0; }  // unknown to the runtime: pageable
+  if (a.isManaged || a.type == hipMemoryTypeManaged) return 2;
+  if (a.type == hipMemoryTypeUnregistered || a.type == hipMemoryTypeHost) return 0;
+  return a.type == hipMemoryTypeDevice && a.device == device ? 1 : 2;
+}
+}  // namespace
+}  // extern "C++"
+
+int esvo_event_columns_to_events(const esvo_event_columns_t* c, size_t n, esvo_event_t* out, size_t* first_bad) {
+  esvo_context* h = nullptr;
+  if (first_bad) *first_bad = n;
+  if (!c || (n && !out)) return ESVO_ERR_INVALID_ARG;
+  if (const char* msg = columns_arg_error(c, n)) FAIL(ESVO_ERR_INVALID_ARG, msg);
+  if (c->memory != ESVO_MEM_HOST) FAIL(ESVO_ERR_INVALID_ARG, "esvo_event_columns_to_events: host memory only");
+  const uint16_t* x = static_cast<const uint16_t*>(c->x);
+  const uint16_t* y = static_cast<const uint16_t*>(c->y);
+  for (size_t i = 0; i < n; ++i) {
+    const u64 s = columns_stamp_ns(c->t, i, c->t_type, c->t_offset);
+    if (s == COL_BAD_STAMP) {
+      if (first_bad) *first_bad = i;
+      FAIL(ESVO_ERR_INVALID_ARG, columns_bad_element(i));
+    }
+    const uint4 w = columns_record(x[i], y[i], s, columns_polarity(c->p, i, c->p_type));
+    std::memcpy(out + i, &w, sizeof(w));
+  }
+  return ESVO_OK;
+}
+void esvo_event_columns_sizes(size_t out[4]) {
+  out[0] = sizeof(esvo_event_columns_t);
+  out[1] = out[2] = out[3] = 0;
+}
+
+int esvo_ts_push_event_columns(esvo_handle h, int cam, const esvo_event_columns_t* c, size_t n) {
+  if (!h || cam < 0 || cam > 1 || !c) return ESVO_ERR_INVALID_ARG;
+  if (n == 0) return ESVO_OK;
+  if (const char* msg = columns_arg_error(c, n)) FAIL(ESVO_ERR_INVALID_ARG, msg);
+  if (n > h->ring_cap) FAIL(ESVO_ERR_CAPACITY, "event block larger than the event ring");
+  const bool on_device = c->memory == ESVO_MEM_DEVICE;
+  const uint16_t* x = static_cast<const uint16_t*>(c->x);
+  const uint16_t* y = static_cast<const uint16_t*>(c->y);
+  std::unique_lock<std::mutex> lp(h->mu_push[cam]);
+  HIPCHK(hipSetDevice(h->device));
+  {  // where the columns lie, first and last byte of each, before anything is launched or copied
+    const void* base[4] = {c->x, c->y, c->t, c->p};
+    const size_t bytes[4] = {2 * n, 2 * n, col_t_size(c->t_type) * n, n};
+    for (int k = 0; k < 4; ++k) {
+      if (!base[k]) continue;
+      const int want = on_device ? 1 : 0;
+      if (column_memory_kind(base[k], h->device) != want || column_memory_kind(static_cast<const uint8_t*>(base[k]) + bytes[k] - 1, h->device) != want)
+        FAIL(ESVO_ERR_INVALID_ARG, on_device ? "event columns labelled ESVO_MEM_DEVICE must be plain device memory of the handle's GPU (not host, managed or another GPU's)"
+                                             : "event columns labelled ESVO_MEM_HOST must be host memory (a device or managed pointer was given)");
+    }
+  }
+  if (n > h->col_cap[cam]) {  // (idle: every column push ends with a wait for the ingest stream)
+    const size_t cap = (std::max<size_t>(n + n / 2, 256) + 255) / 256 * 256;
+    h->col_cap[cam] = 0;
+    (void)h->d_col[cam].release(); (void)h->h_col_stamps[cam].release();
+    HIPCHK(h->d_col[cam].alloc(cap * 13));
+    HIPCHK(h->h_col_stamps[cam].alloc(cap));
+    h->col_cap[cam] = cap;
+  }
+  const size_t cap = h->col_cap[cam];
+  u64* const d_stamps = reinterpret_cast<u64*>(h->d_col[cam].get());
+  u64* const stamps = h->h_col_stamps[cam];
+  if (on_device) {  // t -> stamps on the device, down once
+    launch_ts_columns_stamps(c->t, c->t_type, c->t_offset, n, d_stamps, h->stream_i);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(stamps, d_stamps, sizeof(u64) * n, hipMemcpyDeviceToHost, h->stream_i));
+    HIPCHK(hipStreamSynchronize(h->stream_i));
+  }
+  // the walk: the stamps (host columns: computed here), their validity, their order
+  bool in_order = true;
+  u64 last = 0;
+  for (size_t i = 0; i < n; ++i) {
+    const u64 s = on_device ? stamps[i] : columns_stamp_ns(c->t, i, c->t_type, c->t_offset);
+    if (s == COL_BAD_STAMP) FAIL(ESVO_ERR_INVALID_ARG, columns_bad_element(i));
+    stamps[i] = s;
+    in_order = in_order && s >= last;
+    last = s;
+  }
+  if (in_order) {
+    std::lock_guard<std::mutex> lr(h->mu_ring);
+    const u64 newest = h->routed ? h->last_stamp[cam] : (h->ts_host[cam].empty() ? 0 : h->ts_host[cam].back());
+    in_order = stamps[0] >= newest;
+  }
+  if (!in_order || h->routed) {  // the slow paths take records: what esvo_ts_push_events does with them, nothing of it twice
+    std::vector<esvo_event_t> E(n);
+    if (on_device) {
+      std::vector<uint16_t> hx(n), hy(n);
+      std::vector<uint8_t> hp(c->p ? n : 0);
+      HIPCHK(hipMemcpyAsync(hx.data(), c->x, 2 * n, hipMemcpyDeviceToHost, h->stream_i));
+      HIPCHK(hipMemcpyAsync(hy.data(), c->y, 2 * n, hipMemcpyDeviceToHost, h->stream_i));
+      if (c->p) HIPCHK(hipMemcpyAsync(hp.data(), c->p, n, hipMemcpyDeviceToHost, h->stream_i));
+      HIPCHK(hipStreamSynchronize(h->stream_i));
+      columns_materialise(hx.data(), hy.data(), c->p ? hp.data() : nullptr, c->p_type, stamps, n, E.data());
+    } else {
+      columns_materialise(x, y, c->p, c->p_type, stamps, n, E.data());
+    }
+    const auto get = [&](size_t i) { return E[i]; };
+    if (in_order) return push_routed(h, cam, n, get);
+    lp.unlock();  // (push_unsorted takes mu_api before mu_push: the order esvo_reset takes them in)
+    return push_unsorted(h, cam, n, get);
+  }
+  PushTicket tk;
+  { int rc = push_begin(h, cam, n, stamps[0], tk); if (rc) return rc; }
+  { int rc = push_drain(h, cam, tk); if (rc) return rc; }
+  const uint16_t* kx = x;
+  const uint16_t* ky = y;
+  const void* kp = c->p;
+  if (!on_device) {  // the columns as they are, beside their stamps
+    uint8_t* const d = h->d_col[cam];
+    PUSH_HIPCHK(hipMemcpyAsync(d_stamps, stamps, sizeof(u64) * n, hipMemcpyHostToDevice, h->stream_i));
+    PUSH_HIPCHK(hipMemcpyAsync(d + 8 * cap, x, 2 * n, hipMemcpyHostToDevice, h->stream_i));
+    PUSH_HIPCHK(hipMemcpyAsync(d + 10 * cap, y, 2 * n, hipMemcpyHostToDevice, h->stream_i));
+    if (c->p) PUSH_HIPCHK(hipMemcpyAsync(d + 12 * cap, c->p, n, hipMemcpyHostToDevice, h->stream_i));
+    kx = reinterpret_cast<const uint16_t*>(d + 8 * cap);
+    ky = reinterpret_cast<const uint16_t*>(d + 10 * cap);
+    if (c->p) kp = d + 12 * cap;
+  }
+  launch_ts_pack_columns(kx, ky, d_stamps, kp, c->p_type, n, h->d_ring[cam], tk.slot, h->ring_cap, h->stream_i);
+  PUSH_HIPCHK(hipGetLastError());
+  PUSH_HIPCHK(hipStreamSynchronize(h->stream_i));  // the columns are borrowed for the duration of the call only
+  push_commit(h, cam, n, [&](size_t i) { return stamps[i]; });
+  return ESVO_OK;
+}
+
 namespace {
 // FORWARD mode, first use for a camera: the contribution lists of TimeSurface.cpp:85-116.  A source pixel s with rectified
 // position (u, v), u, v >= 0, u_i + 1 < W, v_i + 1 < H adds to the four pixels around (u, v); every destination pixel gets the

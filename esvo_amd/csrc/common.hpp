@@ -230,6 +230,31 @@ __host__ __device__ inline bool ev_is_late(unsigned w) { return (w & 0xfffffffeu
 void launch_ts_merge(const esvo_event_t* staged, const esvo_event_t* packet, const u32* plan, size_t n, esvo_event_t* ring, u64 first_slot,
                      u64 ring_cap, hipStream_t s);
 void launch_ts_unpack_wire(const uint8_t* wire, size_t n, esvo_event_t* ring, u64 first_slot, u64 ring_cap, hipStream_t s);
+// Column ingest (esvo_ts_push_event_columns): the ONE conversion of a column element, shared by the host walk, the stamp kernel
+// and esvo_event_columns_to_events.  stamp_ns = (t[i] + t_offset) * unit, or COL_BAD_STAMP where an intermediate does not fit or
+// the result is not below 2^32 * 10^9 (no valid stamp equals the marker: it is above that bound).
+constexpr u64 COL_BAD_STAMP = ~0ull;
+constexpr u64 COL_STAMP_END = 4294967296ull * 1000000000ull;
+__host__ __device__ inline u64 columns_stamp_ns(const void* t, size_t i, int t_type, int64_t t_offset) {
+  const int64_t v = t_type == ESVO_T_US_U32 ? (int64_t)static_cast<const uint32_t*>(t)[i] : static_cast<const int64_t*>(t)[i];
+  int64_t s;
+  if (__builtin_add_overflow(v, t_offset, &s) || s < 0) return COL_BAD_STAMP;
+  const u64 unit = t_type == ESVO_T_NS_I64 ? 1ull : 1000ull;
+  if ((u64)s > (COL_STAMP_END - 1) / unit) return COL_BAD_STAMP;
+  return (u64)s * unit;
+}
+__host__ __device__ inline u32 columns_polarity(const void* p, size_t i, int p_type) {
+  if (!p) return 1u;
+  const uint8_t b = static_cast<const uint8_t*>(p)[i];
+  return p_type == ESVO_P_I8 ? ((int8_t)b > 0 ? 1u : 0u) : (b ? 1u : 0u);
+}
+// the four words of the record of one column element with a valid stamp: x | y << 16, sec, nsec, polarity (padding 0)
+__host__ __device__ inline uint4 columns_record(uint16_t x, uint16_t y, u64 stamp, u32 polarity) {
+  return make_uint4((u32)x | ((u32)y << 16), (u32)(stamp / 1000000000ull), (u32)(stamp % 1000000000ull), polarity);
+}
+void launch_ts_columns_stamps(const void* t, int t_type, int64_t t_offset, size_t n, u64* stamps, hipStream_t s);
+void launch_ts_pack_columns(const uint16_t* x, const uint16_t* y, const u64* stamps, const void* p, int p_type, size_t n,
+                            esvo_event_t* ring, u64 first_slot, u64 ring_cap, hipStream_t s);
 void launch_ts_scatter(const esvo_event_t* d_ev, size_t n, u64* d_sae, int W, int H, hipStream_t s);
 // (row0, row1: the rectified rows to render -- whole tiles of TS_TILE_ROWS; a routed band handle renders its band + halo only)
 #define TS_TILE_ROWS 16

@@ -286,6 +286,13 @@ struct esvo_context : IngestSession, TsSession, SchedSession, MapSession, CloudS
   DevEvent evt_hist;            // the front stream behind the newest store (a later record implies the earlier stores)
   DevBuf<esvo_event_t> d_ring[2];
   DevBuf<uint8_t> d_wire[2];  // staging of serialised 13-byte event records (esvo_ts_push_event_array), per camera
+  // staging of column packets (esvo_ts_push_event_columns), per camera and under its mu_push: col_cap events (a multiple of 256),
+  // grown on demand.  d_col: [col_cap u64 stamps | col_cap u16 x | col_cap u16 y | col_cap u8 p] -- the last three hold host
+  // columns only, device columns are read where they lie.  h_col_stamps: the pinned stamps, computed by the host's walk (host
+  // columns) or brought down from d_col (device columns); what push_commit publishes.
+  DevBuf<uint8_t> d_col[2];
+  PinBuf<u64> h_col_stamps[2];
+  size_t col_cap[2] = {0, 0};
   u64 ring_cap = 0;
   // esvo_ts_push_events_async: the newest enqueued (not awaited) copy of a camera; consumers of the ring on the front stream
   // queue behind it (ingest_fence, api_ts.hip) -- under mu_ring, with IngestSession::ingest_pending

@@ -709,4 +709,34 @@ void launch_ts_unpack_wire(const uint8_t* wire, size_t n, esvo_event_t* ring, u6
   hipLaunchKernelGGL(ts_unpack_wire_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, wire, n, ring, first_slot, ring_cap);
 }
 
+// ---- column ingest (esvo_ts_push_event_columns): x / y / t / p arrays -> esvo_event_t records in the event ring ---------------
+// Device-resident columns: t -> u64 nanosecond stamps (COL_BAD_STAMP for an invalid element) in the camera's staging buffer, which
+// comes down once for the host's walk (order, validity, stamp index).  One element per thread: consecutive lanes read consecutive
+// elements, a base needs only its element's alignment.
+__global__ void __launch_bounds__(256) ts_columns_stamps_kernel(const void* __restrict__ t, int t_type, int64_t t_offset, size_t n,
+                                                                u64* __restrict__ stamps) {
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  stamps[i] = columns_stamp_ns(t, i, t_type, t_offset);
+}
+void launch_ts_columns_stamps(const void* t, int t_type, int64_t t_offset, size_t n, u64* stamps, hipStream_t s) {
+  if (n == 0) return;
+  hipLaunchKernelGGL(ts_columns_stamps_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, t, t_type, t_offset, n, stamps);
+}
+// Both sources: x, y, the stamp (validated by the host before this launch) and p -> one whole record, one 16-byte store into the
+// ring (whose base is an allocation's: aligned).  Element loads only, so a column may start anywhere its element type allows.
+__global__ void __launch_bounds__(256) ts_pack_columns_kernel(const uint16_t* __restrict__ x, const uint16_t* __restrict__ y,
+                                                              const u64* __restrict__ stamps, const void* __restrict__ p, int p_type,
+                                                              size_t n, uint4* __restrict__ ring, u64 first_slot, u64 ring_cap) {
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  ring[(first_slot + i) % ring_cap] = columns_record(x[i], y[i], stamps[i], columns_polarity(p, i, p_type));
+}
+void launch_ts_pack_columns(const uint16_t* x, const uint16_t* y, const u64* stamps, const void* p, int p_type, size_t n,
+                            esvo_event_t* ring, u64 first_slot, u64 ring_cap, hipStream_t s) {
+  if (n == 0) return;
+  hipLaunchKernelGGL(ts_pack_columns_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, x, y, stamps, p, p_type, n,
+                     reinterpret_cast<uint4*>(ring), first_slot, ring_cap);
+}
+
 }  // namespace esvo

@@ -151,6 +151,9 @@ class ShardedEsvo:
     def ts_push_events(self, cam, ev):
         self.dev.ts_push_events(cam, ev)
 
+    def ts_push_columns(self, cam, x, y, t, p=None, unit="ns", t_offset=0):
+        self.dev.ts_push_columns(cam, x, y, t, p, unit, t_offset)
+
     def ts_render(self, cam, t_ns, download=True):
         return self.dev.ts_render(cam, t_ns, download)
 
@@ -258,6 +261,9 @@ class TickShardedEsvo:
     def ts_push_events(self, cam, ev):
         self.dev.ts_push_events(cam, ev)
 
+    def ts_push_columns(self, cam, x, y, t, p=None, unit="ns", t_offset=0):
+        self.dev.ts_push_columns(cam, x, y, t, p, unit, t_offset)
+
     def ts_render(self, cam, t_ns, download=True):
         if self._is_mine():  # the SAE only has to be current at this rank's own ticks
             return self.dev.ts_render(cam, t_ns, download)
@@ -361,6 +367,9 @@ class NativeTickSharded:
     def ts_push_events(self, cam, ev):
         self.dev.ts_push_events(cam, ev)
 
+    def ts_push_columns(self, cam, x, y, t, p=None, unit="ns", t_offset=0):
+        self.dev.ts_push_columns(cam, x, y, t, p, unit, t_offset)
+
     def ts_render(self, cam, t_ns, download=True):
         if self.dev.comm_owns_next_tick():  # the SAE only has to be current at this rank's own ticks
             return self.dev.ts_render(cam, t_ns, download)
@@ -434,6 +443,9 @@ class NativeBandSharded:
 
     def ts_push_events(self, cam, ev):
         self.dev.ts_push_events(cam, ev)
+
+    def ts_push_columns(self, cam, x, y, t, p=None, unit="ns", t_offset=0):
+        self.dev.ts_push_columns(cam, x, y, t, p, unit, t_offset)
 
     def ts_render(self, cam, t_ns, download=True):
         return self.dev.ts_render(cam, t_ns, download)

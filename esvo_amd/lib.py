@@ -10,7 +10,8 @@ import subprocess
 
 import numpy as np
 
-from .abi import (DEPTH_POINT_DTYPE, EM_POSE_FN, ERR_CAPACITY, ERR_INVALID_ARG, ERR_STATE, EVENT_DTYPE, MATCH_DTYPE, CalibStruct, EmSelectionStruct,
+from .abi import (MEM_DEVICE, MEM_HOST, P_U8, ColumnsError, EventColumnsStruct, check_t_offset, column_p_type, column_t_type,
+                  DEPTH_POINT_DTYPE, EM_POSE_FN, ERR_CAPACITY, ERR_INVALID_ARG, ERR_STATE, EVENT_DTYPE, MATCH_DTYPE, CalibStruct, EmSelectionStruct,
                   EmStatsStruct, GpcParamsStruct, GpcStatsStruct, LmStatsStruct, ParamsStruct, SgmStatsStruct, StatsStruct, TRACK_ITER_DTYPE, TRACK_SOLVE_MAX_ITERATIONS,
                   TrackSolveInfoStruct, TrackSolveParamsStruct)
 
@@ -23,7 +24,7 @@ HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off"
 
 SYMBOLS = [
     "esvo_default_params", "esvo_create", "esvo_destroy", "esvo_reset", "esvo_set_params", "esvo_last_error",
-    "esvo_set_stream", "esvo_synchronize", "esvo_ts_push_events", "esvo_ts_push_events_async", "esvo_ts_push_wait", "esvo_host_alloc", "esvo_host_free", "esvo_ts_push_event_array", "esvo_ts_render", "esvo_ts_render_forward", "esvo_map_set_observation",
+    "esvo_set_stream", "esvo_synchronize", "esvo_ts_push_events", "esvo_ts_push_events_async", "esvo_ts_push_wait", "esvo_host_alloc", "esvo_host_free", "esvo_ts_push_event_array", "esvo_ts_push_event_columns", "esvo_event_columns_to_events", "esvo_event_columns_sizes", "esvo_ts_render", "esvo_ts_render_forward", "esvo_map_set_observation",
     "esvo_map_match", "esvo_map_set_poses", "esvo_map_refine", "esvo_map_push_frame", "esvo_map_fuse",
     "esvo_map_tick", "esvo_map_tick_bm_only", "esvo_map_fuse_matches_naive", "esvo_map_tick_resident", "esvo_map_get_depth_points", "esvo_map_get_committed", "esvo_map_get_pointcloud_xyz", "esvo_map_get_last_frame",
     "esvo_get_stats", "esvo_shard_set_band", "esvo_shard_set_routing", "esvo_shard_get_rows", "esvo_shard_exchange", "esvo_shard_tick_phase", "esvo_abi_sizes",
@@ -152,6 +153,10 @@ def load():
     lib.esvo_host_alloc.argtypes = [sz, C.POINTER(vp)]
     lib.esvo_host_free.argtypes = [vp]
     lib.esvo_ts_push_event_array.argtypes = [vp, i32, vp, sz, psz]
+    lib.esvo_ts_push_event_columns.argtypes = [vp, i32, vp, sz]
+    lib.esvo_event_columns_to_events.argtypes = [vp, sz, vp, psz]
+    lib.esvo_event_columns_sizes.argtypes = [vp]
+    lib.esvo_event_columns_sizes.restype = None
     lib.esvo_ts_render.argtypes = [vp, i32, u64, vp]
     lib.esvo_ts_render_forward.argtypes = [vp, i32, u64, vp]
     lib.esvo_map_set_observation.argtypes = [vp, u64, vp, vp, vp]
@@ -254,7 +259,7 @@ def load():
     lib.esvo_ts_history_select_observation.argtypes = [vp, i32, EM_POSE_FN, vp, C.POINTER(C.c_uint64), vp]
     for s in SYMBOLS:
         if s not in ("esvo_default_params", "esvo_last_error", "esvo_abi_sizes", "esvo_bag_last_error", "esvo_em_sizes", "esvo_lm_sizes", "esvo_sgm_sizes",
-                     "esvo_track_sizes", "esvo_gpc_sizes"):
+                     "esvo_track_sizes", "esvo_gpc_sizes", "esvo_event_columns_sizes"):
             getattr(lib, s).restype = C.c_int
     lib.esvo_abi_sizes.argtypes = [vp]
     lib.esvo_abi_sizes.restype = None
@@ -660,6 +665,68 @@ class PinnedEvents:
             self.ptr = None
 
 
+def _column(a, name):
+    """(address, numpy dtype, length, on_device, what to keep alive) of one column: a numpy array (or anything numpy takes as one),
+    or device / host memory behind data_ptr() + is_cuda (torch) or __cuda_array_interface__; one-dimensional and contiguous"""
+    if hasattr(a, "data_ptr") and hasattr(a, "is_cuda"):
+        if a.dim() != 1 or not a.is_contiguous():
+            raise ValueError(f"event columns: {name} must be one-dimensional and contiguous")
+        return int(a.data_ptr()), np.dtype(str(a.dtype).replace("torch.", "")), int(a.numel()), bool(a.is_cuda), a
+    cai = getattr(a, "__cuda_array_interface__", None)
+    if cai is not None:
+        shape, dt = tuple(cai["shape"]), np.dtype(cai["typestr"])
+        if len(shape) != 1 or cai.get("strides") not in (None, (dt.itemsize,)):
+            raise ValueError(f"event columns: {name} must be one-dimensional and contiguous")
+        return int(cai["data"][0]), dt, int(shape[0]), True, a
+    arr = np.asarray(a)
+    if arr.ndim != 1:
+        raise ValueError(f"event columns: {name} must be one-dimensional")
+    arr = np.ascontiguousarray(arr)
+    return arr.ctypes.data, arr.dtype, len(arr), False, arr
+
+
+def event_columns_struct(x, y, t, p=None, unit="ns", t_offset=0):
+    """an esvo_event_columns_t over the given columns -> (struct, (n, what the struct's pointers need alive)); the types come from
+    the dtypes (abi.column_t_type / column_p_type), anything else is refused with a ValueError"""
+    cols = {"x": _column(x, "x"), "y": _column(y, "y"), "t": _column(t, "t")}
+    if p is not None:
+        cols["p"] = _column(p, "p")
+    n = cols["t"][2]
+    if any(c[2] != n for c in cols.values()):
+        raise ValueError("event columns: the columns differ in length: " + ", ".join(f"{k} {c[2]}" for k, c in cols.items()))
+    if len({c[3] for c in cols.values()}) != 1:
+        raise ValueError("event columns: all columns must be in host memory or all in device memory")
+    for k in ("x", "y"):
+        if cols[k][1].itemsize != 2 or cols[k][1].kind not in "iu":
+            raise ValueError(f"event columns: {k} must be uint16 or int16, not {cols[k][1]}")
+    s = EventColumnsStruct()
+    s.x, s.y, s.t, s.p = cols["x"][0] or None, cols["y"][0] or None, cols["t"][0] or None, (cols["p"][0] or None) if p is not None else None
+    s.t_type = column_t_type(cols["t"][1], unit)
+    s.p_type = column_p_type(cols["p"][1]) if p is not None else P_U8
+    s.t_offset = check_t_offset(t_offset)
+    s.memory = MEM_DEVICE if cols["t"][3] else MEM_HOST
+    return s, (n, [c[4] for c in cols.values()])
+
+
+def columns_to_events_c(x, y, t, p=None, unit="ns", t_offset=0):
+    """esvo_event_columns_to_events on host columns -> the esvo_event_t records; abi.ColumnsError (first_bad) for an invalid element"""
+    s, (n, _keep) = event_columns_struct(x, y, t, p, unit, t_offset)
+    out, bad = np.zeros(n, EVENT_DTYPE), C.c_size_t(0)
+    rc = load().esvo_event_columns_to_events(C.addressof(s), n, out.ctypes.data if n else None, C.byref(bad))
+    if rc == ERR_INVALID_ARG and bad.value < n:
+        raise ColumnsError(bad.value)
+    if rc != 0:
+        raise EsvoError(f"esvo_event_columns_to_events failed ({rc}): {load().esvo_last_error(None).decode(errors='replace')}", code=rc)
+    return out
+
+
+def event_columns_sizes():
+    """sizeof(esvo_event_columns_t), 0, 0, 0 (esvo_event_columns_sizes)"""
+    out = (C.c_size_t * 4)()
+    load().esvo_event_columns_sizes(out)
+    return list(out)
+
+
 def abi_sizes():
     out = (C.c_size_t * 8)()
     load().esvo_abi_sizes(out)
@@ -769,6 +836,33 @@ class Esvo:
         n = C.c_size_t()
         self._ck(self.lib.esvo_ts_push_event_array(self.h, int(cam), buf.ctypes.data, buf.size, C.byref(n)))
         return int(n.value)
+
+    def ts_push_columns(self, cam, x, y, t, p=None, unit="ns", t_offset=0):
+        """stage events from columns (esvo_ts_push_event_columns): x, y 16-bit; t int64 with unit "ns" / "us" or uint32 with unit
+        "us", stamp = (t + t_offset) * unit; p uint8 / bool (!= 0 is ON), int8 (> 0 is ON) or None (all ON).  The columns are numpy
+        arrays, or anything with data_ptr() / is_cuda (torch tensors) or __cuda_array_interface__: all in host memory or all in
+        device memory of the handle's GPU.  Device columns must be complete: torch's current stream is synchronised here, a producer
+        on any other stream is the caller's to wait for.  Synchronous: the columns may be reused when the call returns."""
+        s, keep = event_columns_struct(x, y, t, p, unit, t_offset)
+        if s.memory == MEM_DEVICE:
+            import sys
+            torch = sys.modules.get("torch")
+            if torch is not None and torch.cuda.is_available():
+                torch.cuda.current_stream().synchronize()
+        self._ck(self.lib.esvo_ts_push_event_columns(self.h, int(cam), C.addressof(s), keep[0]))
+
+    def debug_ts_ring(self, cam, first_abs=None, n=None):
+        """(records, stamps, ring_base, ring_next) of a camera's event ring (esvo_debug_ts_ring; not part of the ABI): the records and
+        the host's stamp mirror of the absolute indices [first_abs, first_abs + n), by default everything the ring still holds"""
+        fn = _dbg_fn("esvo_debug_ts_ring", [C.c_void_p, C.c_int, C.c_uint64, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p])
+        bounds = np.zeros(2, np.uint64)
+        self._ck(fn(self.h, int(cam), 0, 0, None, None, bounds.ctypes.data))
+        first_abs = int(bounds[0]) if first_abs is None else int(first_abs)
+        n = int(bounds[1]) - first_abs if n is None else int(n)
+        ev, stamps = np.zeros(max(n, 0), EVENT_DTYPE), np.zeros(max(n, 0), np.uint64)
+        self._ck(fn(self.h, int(cam), first_abs, max(n, 0), ev.ctypes.data if n > 0 else None, stamps.ctypes.data if n > 0 else None,
+                    bounds.ctypes.data))
+        return ev, stamps, int(bounds[0]), int(bounds[1])
 
     def ts_push_bag(self, cam, bag, topic, until_ns=0):
         """stage the dvs_msgs/EventArray messages of `topic` (bag time < until_ns; 0: all) from a BagReader; returns the event count"""

@@ -18,7 +18,7 @@
  *     concurrently, one thread per group -- the threading of the reference's nodes (esvo_Mapping.cpp:160,179-247: the
  *     MappingLoop worker thread; :669-703 and TimeSurface.cpp:403-425: eventsCallback on the ROS spinner under
  *     data_mutex_; esvo_Tracking's own loop):
- *       INGEST   esvo_ts_push_events(_async), esvo_ts_push_wait, esvo_ts_push_event_array, esvo_ts_push_bag (one thread per camera is fine)
+ *       INGEST   esvo_ts_push_events(_async), esvo_ts_push_wait, esvo_ts_push_event_array, esvo_ts_push_event_columns, esvo_ts_push_bag (one thread per camera is fine)
  *       TRACKER  esvo_track_*
  *       MAPPER   every other call that takes the handle (renders, observation, ticks, stage-wise calls, outputs,
  *                parameters, esvo_comm_*, esvo_reset -- which excludes the other two groups while it runs)
@@ -304,6 +304,43 @@ int esvo_host_free(void* p);
  * std::vector<dvs_msgs::Event> is materialised (rosbag::MessageInstance::instantiate does that at
  * events_repacking_helper/src/EventMessageEditor.cpp:111).  *n_events (nullable) receives the message's event count. */
 int esvo_ts_push_event_array(esvo_handle h, int cam, const uint8_t* msg, size_t n_bytes, size_t* n_events);
+/* The same from COLUMNS: four arrays x / y / t / p of n elements each, in host or in device memory -- what DSEC's files hold
+ * (x u16, y u16, p u8, t u32 microseconds + t_offset), what MVSEC-derived and simulator streams are, and what a GPU producer (a torch
+ * loader, a simulator) has in device memory already.  No esvo_event_t is interleaved on the host and no stamp is split there.
+ *   Conversion (exact, the same on every path): stamp_ns = (t[i] + t_offset) * (1 for ESVO_T_NS_I64, 1000 for the two US types), in
+ *   integers without wrap-around.  An element is INVALID if an intermediate does not fit or the result lies outside
+ *   0 <= stamp_ns < 2^32 * 10^9 (what sec can hold).  sec = stamp_ns / 10^9, nsec = stamp_ns % 10^9; the bits of x and y are copied;
+ *   polarity is 1 where p[i] != 0 (ESVO_P_U8) or (int8_t)p[i] > 0 (ESVO_P_I8, the +-1 convention), else 0; p == NULL: every event
+ *   ON; _pad is 0.  Any invalid element: ESVO_ERR_INVALID_ARG, esvo_last_error names the first bad index, nothing is staged and no
+ *   handle state changes.
+ *   Behaviour: exactly that of esvo_ts_push_events handed those records, in everything a later call can observe -- the in-order fast
+ *   path; the out-of-order merge with its late marks, stats.late_events and the queue mode's second copies; the routed band path;
+ *   the same capacity and state errors (out-of-order on a routed handle included); n == 0 is a no-op.  Synchronous: when the call
+ *   returns it has finished reading the columns, they may be reused at once.
+ *   memory = ESVO_MEM_DEVICE: the columns must be COMPLETE before the call (the caller synchronises its producing stream) and plain
+ *   device memory of the handle's GPU; the library checks that with hipPointerGetAttributes before any launch or copy: host, managed
+ *   or foreign-device pointers labelled DEVICE return ESVO_ERR_INVALID_ARG, and so does a device pointer labelled HOST.  Column
+ *   bases need only the alignment of their element type (a caller passes slices).
+ *   In-order packets on an unrouted handle are packed into the ring by a kernel: host columns go up as they are beside their u64
+ *   stamps (13 B/event), device columns are read where they lie (8 B/event of stamps come down for the order check and the host's
+ *   stamp index).  The other packets -- out of order inside themselves, reaching back behind the newest staged stamp, or any packet
+ *   on a routed handle -- are materialised as esvo_event_t on the host and take the paths of esvo_ts_push_events. */
+enum { ESVO_T_NS_I64 = 0, ESVO_T_US_I64 = 1, ESVO_T_US_U32 = 2 };   /* element type and unit of t */
+enum { ESVO_P_U8 = 0 /* != 0 is ON */, ESVO_P_I8 = 1 /* > 0 is ON: the +-1 convention */ };
+enum { ESVO_MEM_HOST = 0, ESVO_MEM_DEVICE = 1 };
+typedef struct esvo_event_columns_t {
+  const void* x; const void* y;   /* 16-bit each, read as unsigned (an int16 tensor's bits are fine) */
+  const void* t;                  /* t_type */
+  const void* p;                  /* p_type; NULL: every event ON */
+  int64_t t_offset;               /* in t's unit, added BEFORE the unit is scaled (DSEC's t_offset) */
+  int32_t t_type, p_type, memory, reserved;
+} esvo_event_columns_t;
+int esvo_ts_push_event_columns(esvo_handle h, int cam, const esvo_event_columns_t* c, size_t n);
+/* The conversion alone: host memory only (memory must be ESVO_MEM_HOST), no handle, no GPU.  *first_bad (nullable) receives the
+ * index of the first invalid element (then ESVO_ERR_INVALID_ARG is returned and `out` holds the records before it), else n. */
+int esvo_event_columns_to_events(const esvo_event_columns_t* c, size_t n, esvo_event_t* out, size_t* first_bad);
+/* sizeof(esvo_event_columns_t), 0, 0, 0 */
+void esvo_event_columns_sizes(size_t out[4]);
 /* rosbag (format 2.0) ingest, SURVEY.md §8(f).2: the reading side of events_repacking_helper
  * (events_repacking_helper/src/EventMessageEditor.cpp:66-119: rosbag::Bag::open, rosbag::View over an event topic,
  * MessageInstance::instantiate<dvs_msgs::EventArray>).  Chunks (compression none / bz2 / lz4) are walked in file order;

@@ -109,6 +109,10 @@ class TimeSurface {
   void eventsCallback(const Event* events, size_t n) {
     ctx_->check(esvo_ts_push_events(ctx_->handle(), cam_, events, n), "esvo_ts_push_events");
   }
+  // the same from x / y / t / p columns in host or device memory (DSEC's layout, a GPU producer's tensors): esvo_ts_push_event_columns
+  void eventColumns(const esvo_event_columns_t& columns, size_t n) {
+    ctx_->check(esvo_ts_push_event_columns(ctx_->handle(), cam_, &columns, n), "esvo_ts_push_event_columns");
+  }
   // TimeSurface::createTimeSurfaceAtTime: the rectified mono8 Time Surface at the sync time
   void createTimeSurfaceAtTime(uint64_t external_sync_time_ns, uint8_t* out_mono8 /*nullable*/) {
     ctx_->check(esvo_ts_render(ctx_->handle(), cam_, external_sync_time_ns, out_mono8), "esvo_ts_render");
