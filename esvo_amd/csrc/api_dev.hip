@@ -505,12 +505,9 @@ int esvo_debug_ts_ring(esvo_handle h, int cam, uint64_t first_abs, size_t n, esv
     if (stamps)
       for (size_t i = 0; i < n; ++i) stamps[i] = h->ts_host[cam][(size_t)(first_abs - base) + i];
   }
-  if (out && n) {
-    const u64 slot = first_abs % h->ring_cap;
-    const size_t first = (size_t)std::min<u64>(n, h->ring_cap - slot);
-    HIPCHK(hipMemcpy(out, h->d_ring[cam] + slot, sizeof(esvo_event_t) * first, hipMemcpyDeviceToHost));
-    if (first < n) HIPCHK(hipMemcpy(out + first, h->d_ring[cam], sizeof(esvo_event_t) * (n - first), hipMemcpyDeviceToHost));
-  }
+  if (out)
+    for (const RingSpan& s : ring_spans(h->ring_cap, first_abs, n))
+      HIPCHK(hipMemcpy(out + s.at, h->d_ring[cam] + s.slot, sizeof(esvo_event_t) * s.count, hipMemcpyDeviceToHost));
   return ESVO_OK;
 }
 

@@ -192,13 +192,8 @@ static size_t em_lower_bound_ns(const std::vector<u64>& ts, double t) {
 
 // copy [first, first + n) of camera cam's ring into dst (two pieces where the ring wraps)
 static int em_gather_ring(esvo_context* h, int cam, u64 first, u32 n, esvo_event_t* dst) {
-  u64 done = 0;
-  while (done < n) {
-    const u64 slot = (first + done) % h->ring_cap;
-    const u64 piece = std::min<u64>(n - done, h->ring_cap - slot);
-    HIPCHK(hipMemcpyAsync(dst + done, h->d_ring[cam] + slot, sizeof(esvo_event_t) * piece, hipMemcpyDeviceToDevice, h->stream));
-    done += piece;
-  }
+  for (const RingSpan& s : ring_spans(h->ring_cap, first, n))
+    HIPCHK(hipMemcpyAsync(dst + s.at, h->d_ring[cam] + s.slot, sizeof(esvo_event_t) * s.count, hipMemcpyDeviceToDevice, h->stream));
   return ESVO_OK;
 }
 

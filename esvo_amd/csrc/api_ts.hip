@@ -30,6 +30,50 @@ void ingest_fence(esvo_context* h, int cam) {
   h->ingest_pending[cam] = false;
 }
 
+// ---- the scatter step (caller holds mu_ring) ---------------------------------------------------------------------------------------
+// absolute index of the first staged event of `cam` with stamp >= t_ns: a render at t_ns takes the events below it (strict, TimeSurface.h:68)
+static u64 first_staged_at(const esvo_context* h, int cam, u64 t_ns) {
+  const auto& tsq = h->ts_host[cam];
+  return h->ring_base[cam] + (u64)(std::lower_bound(tsq.begin(), tsq.end(), t_ns) - tsq.begin());
+}
+// The SAE keeps ONE stamp per pixel, the reference a queue of 20 (TimeSurface.h:28-96): rendering at a T that precedes events
+// already scattered would read pixels as empty where getMostRecentEventBeforeT finds the older event.
+static int refuse_decreasing_render(esvo_context* h, int cam, u64 upto, const char* who) {
+  if (upto < h->scattered[cam])
+    FAIL(ESVO_ERR_STATE, std::string(who) + ": t_ns precedes events of an earlier render (render times must not decrease; esvo_reset to replay)");
+  return ESVO_OK;
+}
+// Kernels on the front stream are about to read the events [scattered, upto) of `cam`: what the pusher's eviction guard (push_begin)
+// and the counters need to know of that.  Returns the range's first index (upto: there is nothing to do).
+static u64 scatter_claim(esvo_context* h, int cam, u64 upto) {
+  const u64 a = h->scattered[cam];
+  if (upto <= a) return upto;
+  h->scatter_pending_lo[cam] = std::min(h->scatter_pending_lo[cam], a);
+  h->scatter_seq++;
+  h->stats.events_scattered[cam] += upto - a;
+  h->scattered[cam] = upto;
+  return a;
+}
+// ... and each contiguous piece of the ring goes to sink(events, count).  (upto - scattered <= ring_cap: staging refuses more.)
+template <typename Sink>
+static void scatter_upto(esvo_context* h, int cam, u64 upto, Sink sink) {
+  const u64 a = scatter_claim(h, cam, upto);
+  for (const RingSpan& s : ring_spans(h->ring_cap, a, upto - a)) sink(h->d_ring[cam] + s.slot, (size_t)s.count);
+}
+// the sink of the renders that scatter both cameras with one launch: at most two pieces per camera, four segments per launch
+struct ScatterSegs {
+  esvo_context* h;
+  TsScatterSegs g;
+  int n_seg = 0;
+  void flush() { launch_ts_scatter_segs(g, n_seg, h->W, h->H, h->stream); n_seg = 0; }  // (no segments: a no-op inside the launcher)
+  void add(int cam, u64 upto) {
+    scatter_upto(h, cam, upto, [&](const esvo_event_t* ev, size_t n) {
+      g.ev[n_seg] = ev; g.n[n_seg] = n; g.sae[n_seg] = h->d_sae[cam];
+      ++n_seg;
+    });
+  }
+};
+
 // Tick-interleaved multi-GPU operation (esvo_comm_tick on a tick another rank maps): every staged event with ts < t_ns that is
 // not in the SAE yet is scattered NOW -- on the front stream, which is idle between this rank's block matching and its next
 // own render, i.e. beside the own tick's LM launch -- so that the next own render finds only its own tick's events left to
@@ -39,30 +83,15 @@ void ingest_fence(esvo_context* h, int cam) {
 int ts_scatter_ahead(esvo_context* h, uint64_t t_ns) {
   if (h->tsq_len || h->routed) return ESVO_OK;  // (queue mode inserts and derives the SAE at render time)
   std::lock_guard<std::mutex> lr(h->mu_ring);
-  TsScatterSegs g;
-  int n_seg = 0;
+  ScatterSegs segs{h};
   for (int cam = 0; cam < 2; ++cam) {
-    const auto& tsq = h->ts_host[cam];
-    const size_t k = std::lower_bound(tsq.begin(), tsq.end(), (u64)t_ns) - tsq.begin();
-    const u64 upto = h->ring_base[cam] + k;
-    u64 a = h->scattered[cam];
-    if (upto <= a) continue;
+    const u64 upto = first_staged_at(h, cam, (u64)t_ns);
+    if (upto <= h->scattered[cam]) continue;
     ingest_fence(h, cam);
-    h->scatter_pending_lo[cam] = std::min(h->scatter_pending_lo[cam], a);
-    h->scatter_seq++;
-    h->stats.events_scattered[cam] += upto - a;
-    while (a < upto) {
-      const u64 slot = a % h->ring_cap;
-      const u64 cnt = std::min<u64>(upto - a, h->ring_cap - slot);
-      if (n_seg == 4) { launch_ts_scatter_segs(g, n_seg, h->W, h->H, h->stream); n_seg = 0; }
-      g.ev[n_seg] = h->d_ring[cam] + slot; g.n[n_seg] = (size_t)cnt; g.sae[n_seg] = h->d_sae[cam];
-      ++n_seg;
-      a += cnt;
-    }
-    h->scattered[cam] = upto;
+    segs.add(cam, upto);
   }
-  if (!n_seg) return ESVO_OK;
-  launch_ts_scatter_segs(g, n_seg, h->W, h->H, h->stream);
+  if (!segs.n_seg) return ESVO_OK;
+  segs.flush();
   HIPCHK(hipGetLastError());
   return ESVO_OK;
 }
@@ -79,28 +108,23 @@ void resident_write_begin(esvo_context* h, int cam) {
 // Queue mode (max_event_queue_len > 0; caller holds mu_ring): every staged event of `cam` that is not in its pixel's queue yet
 // goes in -- future ones included, as eventsCallback inserts them on arrival (TimeSurface.cpp:403-425) -- and the SAE word
 // of every pixel is derived for THIS render time (getMostRecentEventBeforeT); the render kernels read the SAE as ever.
+static TsQueueArgs queue_args(esvo_context* h, int cam) {
+  TsQueueArgs g{};
+  g.q = h->d_tsq[cam]; g.L = h->tsq_len;
+  g.tcount = h->d_tsq_tcount; g.tlist = h->d_tsq_tlist; g.tcap = h->tsq_tcap;
+  g.over = h->d_tsq_over; g.over_count = h->d_tsq_over_count; g.over_cap = (u32)esvo_context::TSQ_ROUND;
+  return g;
+}
 void queue_prepare(esvo_context* h, int cam, u64 t_ns) {
-  u64 a = h->scattered[cam];
   const u64 upto = h->ring_next[cam];
-  if (upto > a) {
-    h->scatter_pending_lo[cam] = std::min(h->scatter_pending_lo[cam], a);
-    h->scatter_seq++;
-    h->stats.events_scattered[cam] += upto - a;
-    while (a < upto) {  // rounds of at most TSQ_ROUND events: the overflow list can hold a whole round
-      TsQueueArgs g{};
-      g.q = h->d_tsq[cam]; g.L = h->tsq_len;
-      g.tcount = h->d_tsq_tcount; g.tlist = h->d_tsq_tlist; g.tcap = h->tsq_tcap;
-      g.over = h->d_tsq_over; g.over_count = h->d_tsq_over_count; g.over_cap = (u32)esvo_context::TSQ_ROUND;
-      u64 left = std::min<u64>(upto - a, esvo_context::TSQ_ROUND);
-      for (int k = 0; k < 2 && left; ++k) {
-        const u64 slot = a % h->ring_cap;
-        const u64 cnt = std::min<u64>(left, h->ring_cap - slot);
-        g.ev[k] = h->d_ring[cam] + slot; g.n[k] = (size_t)cnt;
-        a += cnt; left -= cnt;
-      }
-      launch_tsq_insert(g, h->W, h->H, h->stream);
+  for (u64 a = scatter_claim(h, cam, upto); a < upto; a += esvo_context::TSQ_ROUND) {  // rounds: the overflow list can hold a whole one
+    TsQueueArgs g = queue_args(h, cam);
+    int k = 0;
+    for (const RingSpan& s : ring_spans(h->ring_cap, a, std::min<u64>(upto - a, esvo_context::TSQ_ROUND))) {
+      g.ev[k] = h->d_ring[cam] + s.slot; g.n[k] = (size_t)s.count;
+      ++k;
     }
-    h->scattered[cam] = upto;
+    launch_tsq_insert(g, h->W, h->H, h->stream);
   }
   if (!h->tsq_dup[cam].empty()) {  // what eventsCallback inserted in place of late events: copies of the then-newest event (push_unsorted)
     auto& dup = h->tsq_dup[cam];
@@ -113,10 +137,7 @@ void queue_prepare(esvo_context* h, int cam, u64 t_ns) {
         const size_t cnt = std::min<size_t>(dup.size() - a0, esvo_context::TSQ_ROUND);
         hipMemcpyAsync(h->d_tsq_dup, dup.data() + a0, sizeof(esvo_event_t) * cnt, hipMemcpyHostToDevice, h->stream);
         hipStreamSynchronize(h->stream);  // (pageable source; the rare path)
-        TsQueueArgs g{};
-        g.q = h->d_tsq[cam]; g.L = h->tsq_len;
-        g.tcount = h->d_tsq_tcount; g.tlist = h->d_tsq_tlist; g.tcap = h->tsq_tcap;
-        g.over = h->d_tsq_over; g.over_count = h->d_tsq_over_count; g.over_cap = (u32)esvo_context::TSQ_ROUND;
+        TsQueueArgs g = queue_args(h, cam);
         g.ev[0] = h->d_tsq_dup; g.n[0] = cnt;
         launch_tsq_insert(g, h->W, h->H, h->stream);
       }
@@ -135,40 +156,18 @@ int ts_render_pair(esvo_context* h, uint64_t t_ns, uint8_t* const obs_out[2]) {
     std::lock_guard<std::mutex> lr(h->mu_ring);  // what a pusher on another thread reads and writes (context.hpp)
     ingest_fence(h, 0);
     ingest_fence(h, 1);
-    u64 upto[2];
+    u64 upto[2] = {0, 0};
     for (int cam = 0; cam < 2 && !h->tsq_len; ++cam) {
-      const auto& tsq = h->ts_host[cam];
-      const size_t k = std::lower_bound(tsq.begin(), tsq.end(), (u64)t_ns) - tsq.begin();
-      upto[cam] = h->ring_base[cam] + k;
-      if (upto[cam] < h->scattered[cam])
-        FAIL(ESVO_ERR_STATE, "esvo_ts_render: t_ns precedes events of an earlier render (render times must not decrease; esvo_reset to replay)");
+      upto[cam] = first_staged_at(h, cam, (u64)t_ns);
+      { int rc = refuse_decreasing_render(h, cam, upto[cam], "esvo_ts_render"); if (rc) return rc; }
     }
     for (int cam = 0; cam < 2; ++cam)
       if (h->ts_timing_pending[cam] && hipEventQuery(h->ts_ev[cam].e[TE_R1]) == hipSuccess) collect_ts_timing(h, cam);
     if (timed) hipEventRecord(h->ts_ev[0].e[TE_SC0], h->stream);
-    TsScatterSegs g;
-    int n_seg = 0;
+    ScatterSegs segs{h};
     if (h->tsq_len) { queue_prepare(h, 0, (u64)t_ns); queue_prepare(h, 1, (u64)t_ns); }
-    for (int cam = 0; cam < 2 && !h->tsq_len; ++cam) {
-      u64 a = h->scattered[cam];
-      if (upto[cam] <= a) continue;
-      h->scatter_pending_lo[cam] = std::min(h->scatter_pending_lo[cam], a);
-      h->scatter_seq++;
-      h->stats.events_scattered[cam] += upto[cam] - a;
-      while (a < upto[cam]) {
-        const u64 slot = a % h->ring_cap;
-        const u64 cnt = std::min<u64>(upto[cam] - a, h->ring_cap - slot);
-        if (n_seg == 4) {  // a range longer than the ring (cannot happen: staging refuses it) -- flush and go on
-          launch_ts_scatter_segs(g, n_seg, h->W, h->H, h->stream);
-          n_seg = 0;
-        }
-        g.ev[n_seg] = h->d_ring[cam] + slot; g.n[n_seg] = (size_t)cnt; g.sae[n_seg] = h->d_sae[cam];
-        ++n_seg;
-        a += cnt;
-      }
-      h->scattered[cam] = upto[cam];
-    }
-    launch_ts_scatter_segs(g, n_seg, h->W, h->H, h->stream);
+    else { segs.add(0, upto[0]); segs.add(1, upto[1]); }
+    segs.flush();  // (always: the timing events stand around it)
     if (timed) hipEventRecord(h->ts_ev[0].e[TE_SC1], h->stream);
   }
   TsPair c;
@@ -199,6 +198,14 @@ int ts_render_pair(esvo_context* h, uint64_t t_ns, uint8_t* const obs_out[2]) {
 
 // ---- Time Surface ---------------------------------------------------------------------------------
 namespace {
+u64 event_stamp(u32 sec, u32 nsec) { return (u64)sec * 1000000000ull + nsec; }
+u64 event_stamp(const esvo_event_t& e) { return event_stamp(e.sec, e.nsec); }
+// a record as the ring holds it: polarity 0 / 1 (bit 7 of the byte is the library's: EV_LATE, common.hpp), the padding zero
+esvo_event_t event_normalised(esvo_event_t e) {
+  e.polarity = e.polarity ? 1 : 0;
+  e._pad[0] = e._pad[1] = e._pad[2] = 0;
+  return e;
+}
 // ---- ingest protocol (INGEST group: may run on another thread than the renders and ticks of the same handle) ----------
 // Staging runs on its own stream.  A pusher (one per camera at a time, mu_push) works in three steps:
 //   begin   (mu_ring) order + capacity checks, then it RESERVES [ring_next, ring_next + n): from here on selections are
@@ -207,11 +214,7 @@ namespace {
 //           last selection point and the not yet completed scatter ranges, so only a (nearly) full ring needs the front
 //           stream drained -- done WITHOUT holding mu_ring;
 //   copy + commit  host-to-device on the ingest stream (no lock), then (mu_ring) the stamps and ring_next are published.
-struct PushTicket {
-  u64 slot = 0;
-  bool drain = false;
-  u64 seq = 0;
-};
+struct PushTicket { u64 slot = 0, seq = 0; bool drain = false; };
 int push_begin(esvo_context* h, int cam, size_t n, u64 t_first, PushTicket& tk) {
   std::lock_guard<std::mutex> lr(h->mu_ring);
   const auto& tsq = h->ts_host[cam];
@@ -241,21 +244,53 @@ void push_abort(esvo_context* h, int cam) {
 }
 int push_drain(esvo_context* h, int cam, const PushTicket& tk) {
   if (!tk.drain) return ESVO_OK;
-  if (hipStreamSynchronize(h->stream) != hipSuccess) { push_abort(h, cam); FAIL(ESVO_ERR_HIP, "draining the front stream failed"); }
+  if (hipStreamSynchronize(h->stream) != hipSuccess) FAIL(ESVO_ERR_HIP, "draining the front stream failed");
   std::lock_guard<std::mutex> lr(h->mu_ring);
   if (h->scatter_seq == tk.seq) h->scatter_pending_lo[0] = h->scatter_pending_lo[1] = ~0ull;  // nothing enqueued meanwhile
   return ESVO_OK;
 }
-template <typename StampFn>
-void push_commit(esvo_context* h, int cam, size_t n, StampFn stamp, bool copy_in_flight = false) {
+// also_locked(evicted): what else has to change in the same critical section (routed band mode); evicted: stamps dropped from the mirror
+struct StampArray { const u64* p; u64 operator()(size_t i) const { return p[i]; } };  // stamps that lie in an array: one insert into the mirror
+inline void append_stamps(std::deque<u64>& q, size_t n, StampArray a) { q.insert(q.end(), a.p, a.p + n); }
+template <typename StampFn> void append_stamps(std::deque<u64>& q, size_t n, StampFn stamp) { for (size_t i = 0; i < n; ++i) q.push_back(stamp(i)); }
+// (n and the stamp functor BY VALUE, the functor holding one pointer: read through a reference to the source this loop cost records a sixth of the call)
+template <typename StampFn, typename Also>
+void push_commit(esvo_context* h, int cam, size_t n, StampFn stamp, bool copy_in_flight, Also also_locked) {
   std::lock_guard<std::mutex> lr(h->mu_ring);
   if (copy_in_flight) h->ingest_pending[cam] = true;
   auto& tsq = h->ts_host[cam];
-  for (size_t i = 0; i < n; ++i) tsq.push_back(stamp(i));
+  append_stamps(tsq, n, stamp);
   h->ring_next[cam] += n;
   h->ring_reserved[cam] = h->ring_next[cam];
-  while (tsq.size() > h->ring_cap) { tsq.pop_front(); h->ring_base[cam]++; }
+  size_t evicted = 0;
+  for (; tsq.size() > h->ring_cap; ++evicted) { tsq.pop_front(); h->ring_base[cam]++; }
   h->stats.events_staged[cam] += n;
+  also_locked(evicted);
+}
+// a linear host array into the ring slots from `slot` on (ring: d_ring[cam] or the array beside it), on the ingest stream
+template <typename T>
+hipError_t copy_into_ring(esvo_context* h, T* ring, u64 slot, const T* src, size_t n) {
+  for (const RingSpan& s : ring_spans(h->ring_cap, slot, n)) {
+    const hipError_t e = hipMemcpyAsync(ring + s.slot, src + s.at, sizeof(T) * s.count, hipMemcpyHostToDevice, h->stream_i);
+    if (e != hipSuccess) return e;
+  }
+  return hipSuccess;
+}
+// The sequence itself (caller holds mu_push[cam]) for src.n events in order: src.stamp_fn(), a small functor i -> stamp; src.enqueue(ticket)
+// puts the records into the reserved ring slots, on the ingest stream; src.in_flight: the copy stays in flight behind evt_ingest (the async
+// call: the caller keeps the source alive until esvo_ts_push_wait, front-stream readers queue behind it, ingest_fence), else it is awaited.
+template <typename Src, typename Also>
+int push_staged(esvo_context* h, int cam, Src& src, Also also_locked) {
+  if (src.n) {
+    PushTicket tk;
+    { int rc = push_begin(h, cam, src.n, src.stamp_fn()(0), tk); if (rc) return rc; }
+    int rc = push_drain(h, cam, tk);
+    if (!rc) rc = src.enqueue(tk);
+    if (!rc) rc = [&]() -> int { HIPCHK(src.in_flight ? hipEventRecord(h->evt_ingest[cam], h->stream_i) : hipStreamSynchronize(h->stream_i)); return ESVO_OK; }();
+    if (rc) { push_abort(h, cam); return rc; }  // (every failure behind begin gives the reservation back)
+  }
+  push_commit(h, cam, src.n, src.stamp_fn(), src.in_flight, also_locked);
+  return ESVO_OK;
 }
 // ---- routed band mode (esvo_shard_set_routing): the packet is filtered on the host -----------------------------------------------
 // Of the n events of a packet the rank keeps those its Time Surfaces need (raw row inside the camera's source rows) and, for the
@@ -263,14 +298,13 @@ void push_commit(esvo_context* h, int cam, size_t n, StampFn stamp, bool copy_in
 // ring; each kept left event carries its index in the GLOBAL left sequence (d_ring_gidx), because the reference's event selection
 // (esvo_Mapping.cpp:562-574) and its thread-stride order are defined on the whole stream -- whose stamps stay on the host
 // (glob_ts).  Synchronous (the staging buffer is the library's): esvo_ts_push_events_async behaves like esvo_ts_push_events.
-// Caller holds mu_push[cam]; the packet is sorted.
+// Caller holds mu_push[cam]; the packet is sorted; get(i): its normalised records.
 template <typename GetEv>
 int push_routed(esvo_context* h, int cam, size_t n, GetEv get) {
-  auto stamp_of = [](const esvo_event_t& e) { return (u64)e.sec * 1000000000ull + e.nsec; };
   u64 g0 = 0;
   {
     std::lock_guard<std::mutex> lr(h->mu_ring);
-    if (h->last_stamp[cam] && stamp_of(get(0)) < h->last_stamp[cam])
+    if (h->last_stamp[cam] && event_stamp(get(0)) < h->last_stamp[cam])
       FAIL(ESVO_ERR_INVALID_ARG, "events must be sorted by time stamp (SURVEY Appendix A-1)");
     g0 = h->glob_base + h->glob_ts.size();
   }
@@ -293,57 +327,38 @@ int push_routed(esvo_context* h, int cam, size_t n, GetEv get) {
   u64 last = 0;
   for (size_t i = 0; i < n; ++i) {
     const esvo_event_t e = get(i);
-    const u64 t = stamp_of(e);
+    const u64 t = event_stamp(e);
     last = t;
     if (cam == 0) all_ts[i] = t;
     bool keep = false;
     if ((int)e.x < W && (int)e.y < H) keep = cam == 0 ? keep_px[(size_t)e.y * W + e.x] != 0 : ((int)e.y >= sy0 && (int)e.y < sy1);
     if (!keep) continue;
     kept[m] = e;
-    kept[m].polarity = e.polarity ? 1 : 0;   // (bit 7 of the byte is the library's: EV_LATE)
-    kept[m]._pad[0] = kept[m]._pad[1] = kept[m]._pad[2] = 0;
     if (cam == 0) { h->h_route_gidx[m] = (u32)(g0 + i); kept_gl.push_back(g0 + i); kept_own.push_back((keep_px[(size_t)e.y * W + e.x] >> 1) & 1); }
     kept_ts.push_back(t);
     ++m;
   }
-  if (m) {
-    PushTicket tk;
-    { int rc = push_begin(h, cam, m, kept_ts[0], tk); if (rc) return rc; }
-    { int rc = push_drain(h, cam, tk); if (rc) return rc; }
-    const size_t first = (size_t)std::min<u64>(m, h->ring_cap - tk.slot);
-    hipError_t e = hipMemcpyAsync(h->d_ring[cam] + tk.slot, kept, sizeof(esvo_event_t) * first, hipMemcpyHostToDevice, h->stream_i);
-    if (e == hipSuccess && first < m)
-      e = hipMemcpyAsync(h->d_ring[cam], kept + first, sizeof(esvo_event_t) * (m - first), hipMemcpyHostToDevice, h->stream_i);
-    if (e == hipSuccess && cam == 0) {
-      e = hipMemcpyAsync(h->d_ring_gidx + tk.slot, h->h_route_gidx, sizeof(u32) * first, hipMemcpyHostToDevice, h->stream_i);
-      if (e == hipSuccess && first < m)
-        e = hipMemcpyAsync(h->d_ring_gidx, h->h_route_gidx + first, sizeof(u32) * (m - first), hipMemcpyHostToDevice, h->stream_i);
+  struct Kept {
+    esvo_context* h; int cam; const esvo_event_t* ev; const u64* ts; size_t n; bool in_flight;
+    StampArray stamp_fn() const { return {ts}; }
+    int enqueue(const PushTicket& tk) {
+      HIPCHK(copy_into_ring(h, h->d_ring[cam].get(), tk.slot, ev, n));
+      if (cam == 0) HIPCHK(copy_into_ring(h, h->d_ring_gidx.get(), tk.slot, h->h_route_gidx.get(), n));
+      return ESVO_OK;
     }
-    if (e == hipSuccess) e = hipStreamSynchronize(h->stream_i);
-    if (e != hipSuccess) { push_abort(h, cam); FAIL(ESVO_ERR_HIP, std::string("staging the routed events failed: ") + hipGetErrorString(e)); }
-  }
-  std::lock_guard<std::mutex> lr(h->mu_ring);
-  auto& tsq = h->ts_host[cam];
-  for (size_t i = 0; i < m; ++i) tsq.push_back(kept_ts[i]);
-  h->ring_next[cam] += m;
-  h->ring_reserved[cam] = h->ring_next[cam];
-  if (cam == 0) {
+  } src{h, cam, kept, kept_ts.data(), m, false};
+  return push_staged(h, cam, src, [&](size_t evicted) {
+    h->last_stamp[cam] = last;
+    if (cam != 0) return;
     for (size_t i = 0; i < m; ++i) { h->kept_g.push_back(kept_gl[i]); h->own_before.push_back(h->own_total); h->own_total += kept_own[i]; }
+    for (size_t i = 0; i < evicted; ++i) { h->kept_g.pop_front(); h->own_before.pop_front(); }
     h->glob_ts.insert(h->glob_ts.end(), all_ts.begin(), all_ts.end());   // (one splice: the tick thread's selection takes this lock too)
     if (h->glob_ts.size() > h->ring_cap) {
       const size_t drop = h->glob_ts.size() - h->ring_cap;
       h->glob_ts.erase(h->glob_ts.begin(), h->glob_ts.begin() + (std::ptrdiff_t)drop);
       h->glob_base += drop;
     }
-  }
-  while (tsq.size() > h->ring_cap) {
-    tsq.pop_front();
-    h->ring_base[cam]++;
-    if (cam == 0) { h->kept_g.pop_front(); h->own_before.pop_front(); }
-  }
-  h->last_stamp[cam] = last;
-  h->stats.events_staged[cam] += m;
-  return ESVO_OK;
+  });
 }
 
 // ---- out-of-order input ---------------------------------------------------------------------------------------------------
@@ -365,38 +380,31 @@ int push_unsorted(esvo_context* h, int cam, size_t n, GetEv get) {
   std::lock_guard<std::mutex> lp(h->mu_push[cam]);
   HIPCHK(hipSetDevice(h->device));
   if (h->routed) FAIL(ESVO_ERR_UNSUPPORTED, "out-of-order packets on a row-routed band handle: sort them first (or use ESVO_ROUTE_BROADCAST)");
-  auto stamp_of = [](const esvo_event_t& e) { return (u64)e.sec * 1000000000ull + e.nsec; };
   std::vector<esvo_event_t> S(n);
   std::vector<u64> t(n);
   std::vector<u32> order(n);
   u64 newest = 0;
-  esvo_event_t newest_ev;
-  std::memset(&newest_ev, 0, sizeof(newest_ev));
+  esvo_event_t newest_ev{};
   size_t K = 0, pos_rel = 0;
   // nothing enqueued may still read the ring's tail (block matching of a pending tick, a scatter) while it moves
   if (hipStreamSynchronize(h->stream) != hipSuccess || hipStreamSynchronize(h->stream_i) != hipSuccess) FAIL(ESVO_ERR_HIP, "draining the streams failed");
-  bool have_newest_ev = false;
+  u64 last_idx = 0;
+  bool any = false, have_newest_ev = false;
   {
-    u64 last_idx = 0;
-    bool any = false;
-    {
-      std::lock_guard<std::mutex> lr(h->mu_ring);
-      if (!h->ts_host[cam].empty()) { newest = h->ts_host[cam].back(); last_idx = h->ring_next[cam] - 1; any = true; }
-    }
-    if (any && h->tsq_len) {  // queue mode: the record of the newest staged event (the ring's last: sorted), whose copies stand in for late events
-      HIPCHK(hipMemcpy(&newest_ev, h->d_ring[cam] + last_idx % h->ring_cap, sizeof(esvo_event_t), hipMemcpyDeviceToHost));
-      have_newest_ev = true;
-    }
+    std::lock_guard<std::mutex> lr(h->mu_ring);
+    if (!h->ts_host[cam].empty()) { newest = h->ts_host[cam].back(); last_idx = h->ring_next[cam] - 1; any = true; }
+  }
+  if (any && h->tsq_len) {  // queue mode: the record of the newest staged event (the ring's last: sorted), whose copies stand in for late events
+    HIPCHK(hipMemcpy(&newest_ev, h->d_ring[cam] + last_idx % h->ring_cap, sizeof(esvo_event_t), hipMemcpyDeviceToHost));
+    have_newest_ev = true;
   }
   // late on arrival: below the running maximum of everything that arrived before (a tie is NOT late: it becomes back())
   size_t n_late = 0;
   std::vector<esvo_event_t> dups;
   for (size_t i = 0; i < n; ++i) {
     esvo_event_t e = get(i);
-    t[i] = stamp_of(e);
+    t[i] = event_stamp(e);
     order[i] = (u32)i;
-    e.polarity = e.polarity ? 1 : 0;
-    e._pad[0] = e._pad[1] = e._pad[2] = 0;
     if (t[i] < newest) {
       e.polarity |= (uint8_t)EV_LATE;   // the library's mark: the byte and the padding magic together (common.hpp, ev_is_late)
       e._pad[0] = (uint8_t)(EV_LATE_PAD & 0xffu); e._pad[1] = (uint8_t)((EV_LATE_PAD >> 8) & 0xffu); e._pad[2] = (uint8_t)((EV_LATE_PAD >> 16) & 0xffu);
@@ -459,12 +467,8 @@ int push_unsorted(esvo_context* h, int cam, size_t n, GetEv get) {
   }
   hipError_t e = hipSuccess;
   const u64 slot0 = pos_abs % h->ring_cap;
-  if (K) {  // a copy of the tail (it may wrap)
-    const size_t first = (size_t)std::min<u64>(K, h->ring_cap - slot0);
-    e = hipMemcpyAsync(h->d_merge_a, h->d_ring[cam] + slot0, sizeof(esvo_event_t) * first, hipMemcpyDeviceToDevice, h->stream_i);
-    if (e == hipSuccess && first < K)
-      e = hipMemcpyAsync(h->d_merge_a + first, h->d_ring[cam], sizeof(esvo_event_t) * (K - first), hipMemcpyDeviceToDevice, h->stream_i);
-  }
+  for (const RingSpan& s : ring_spans(h->ring_cap, pos_abs, K))  // a copy of the tail (it may wrap)
+    if (e == hipSuccess) e = hipMemcpyAsync(h->d_merge_a + s.at, h->d_ring[cam] + s.slot, sizeof(esvo_event_t) * s.count, hipMemcpyDeviceToDevice, h->stream_i);
   if (e == hipSuccess) e = hipMemcpyAsync(h->d_merge_b, P.data(), sizeof(esvo_event_t) * n, hipMemcpyHostToDevice, h->stream_i);
   if (e == hipSuccess) e = hipMemcpyAsync(h->d_merge_plan, plan.data(), sizeof(u32) * (K + n), hipMemcpyHostToDevice, h->stream_i);
   if (e == hipSuccess) {
@@ -487,19 +491,106 @@ int push_unsorted(esvo_context* h, int cam, size_t n, GetEv get) {
   return ESVO_OK;
 }
 
-#define PUSH_HIPCHK(call)                                     \
-  do {                                                        \
-    hipError_t _pe = (call);                                  \
-    if (_pe != hipSuccess) {                                  \
-      push_abort(h, cam);                                     \
-      FAIL(ESVO_ERR_HIP, std::string(#call) + " failed: " + hipGetErrorString(_pe)); \
-    }                                                         \
-  } while (0)
+// ---- one staging driver for every packet format --------------------------------------------------------------------------------
+// A packet source supplies, beside what push_staged asks for,
+//   sorted()       the packet is in order in itself
+//   materialise()  makes record(i) valid: the normalised esvo_event_t, which only the paths that filter or sort on the host read
+//   prepare()      staging memory of its own, before anything is reserved
+// lp: mu_push[cam] where the source needed its staging for the stamps already; else it is taken here.
+template <typename Derived>
+struct PacketDefaults {
+  static constexpr bool in_flight = false;
+  bool sorted() const {  // (the column source answers from the walk that made its stamps: a second pass over a tick's stamps costs a tenth of the call)
+    const size_t n = static_cast<const Derived&>(*this).n;
+    const auto stamp = static_cast<const Derived&>(*this).stamp_fn();
+    bool in_order = true;
+    u64 last = stamp(0);
+    for (size_t i = 1; i < n && in_order; ++i) {
+      const u64 t = stamp(i);
+      in_order = t >= last;
+      last = t;
+    }
+    return in_order;
+  }
+  int materialise() { return ESVO_OK; }
+  int prepare() { return ESVO_OK; }
+};
+template <typename Src>
+int push_packet(esvo_context* h, int cam, Src& src, std::unique_lock<std::mutex> lp = {}) {
+  const auto record = [&](size_t i) { return src.record(i); };
+  // sorted, and not older than what is staged: the fast path; anything else is sorted in as the reference's callbacks do
+  bool in_order = src.sorted();
+  if (in_order) {
+    std::lock_guard<std::mutex> lr(h->mu_ring);
+    const u64 newest = h->routed ? h->last_stamp[cam] : (h->ts_host[cam].empty() ? 0 : h->ts_host[cam].back());
+    in_order = src.stamp_fn()(0) >= newest;
+  }
+  if (!in_order) {
+    { int rc = src.materialise(); if (rc) return rc; }
+    if (lp.owns_lock()) lp.unlock();  // (push_unsorted takes mu_api before mu_push: the order esvo_reset takes them in)
+    return push_unsorted(h, cam, src.n, record);
+  }
+  if (!lp.owns_lock()) {
+    lp = std::unique_lock<std::mutex>(h->mu_push[cam]);
+    HIPCHK(hipSetDevice(h->device));
+  }
+  if (h->routed) {
+    { int rc = src.materialise(); if (rc) return rc; }
+    return push_routed(h, cam, src.n, record);
+  }
+  { int rc = src.prepare(); if (rc) return rc; }
+  return push_staged(h, cam, src, [](size_t) {});
+}
+
+struct RecordPacket : PacketDefaults<RecordPacket> {  // esvo_event_t records in host memory, copied as they are
+  esvo_context* h; int cam; const esvo_event_t* ev; size_t n; bool in_flight;
+  auto stamp_fn() const { return [ev = ev](size_t i) { return event_stamp(ev[i]); }; }
+  esvo_event_t record(size_t i) const { return event_normalised(ev[i]); }
+  int enqueue(const PushTicket& tk) {
+    HIPCHK(copy_into_ring(h, h->d_ring[cam].get(), tk.slot, ev, n));
+    return ESVO_OK;
+  }
+};
+
+u32 rd32(const uint8_t* p) { return (u32)p[0] | ((u32)p[1] << 8) | ((u32)p[2] << 16) | ((u32)p[3] << 24); }
+// The 13-byte records of a dvs_msgs/EventArray {u16 x, u16 y, u32 sec, u32 nsec, u8 polarity}: they go to the device as they are and
+// are widened to esvo_event_t in the ring by a kernel; the host only walks the time stamps (order check + selection index).
+struct WirePacket : PacketDefaults<WirePacket> {
+  esvo_context* h; int cam; const uint8_t* rec; size_t n;
+  auto stamp_fn() const { return [rec = rec](size_t i) { return event_stamp(rd32(rec + i * 13 + 4), rd32(rec + i * 13 + 8)); }; }
+  esvo_event_t record(size_t i) const {  // widened on the host
+    const uint8_t* r = rec + i * 13;
+    esvo_event_t e{};
+    e.x = (uint16_t)(r[0] | (r[1] << 8));
+    e.y = (uint16_t)(r[2] | (r[3] << 8));
+    e.sec = rd32(r + 4);
+    e.nsec = rd32(r + 8);
+    e.polarity = r[12];
+    return event_normalised(e);
+  }
+  int prepare() {
+    if (n * 13 > h->d_wire[cam].cap())  // this camera's staging buffer: its pusher is the only user (mu_push)
+      HIPCHK(h->d_wire[cam].alloc(std::max<size_t>(n * 13, (size_t)1 << 20)));
+    return ESVO_OK;
+  }
+  int enqueue(const PushTicket& tk) {
+    HIPCHK(hipMemcpyAsync(h->d_wire[cam], rec, n * 13, hipMemcpyHostToDevice, h->stream_i));
+    launch_ts_unpack_wire(h->d_wire[cam], n, h->d_ring[cam], tk.slot, h->ring_cap, h->stream_i);
+    HIPCHK(hipGetLastError());
+    return ESVO_OK;
+  }
+};
 }  // namespace
 
 extern "C" {
 
-static int push_events_impl(esvo_handle h, int cam, const esvo_event_t* ev, size_t n, bool wait);
+static int push_events_impl(esvo_handle h, int cam, const esvo_event_t* ev, size_t n, bool wait) {
+  if (!h || cam < 0 || cam > 1 || (n && !ev)) return ESVO_ERR_INVALID_ARG;
+  if (n == 0) return ESVO_OK;
+  if (n > h->ring_cap) FAIL(ESVO_ERR_CAPACITY, "event block larger than the event ring");
+  RecordPacket src{{}, h, cam, ev, n, !wait};
+  return push_packet(h, cam, src);
+}
 int esvo_ts_push_events(esvo_handle h, int cam, const esvo_event_t* ev, size_t n) { return push_events_impl(h, cam, ev, n, true); }
 int esvo_ts_push_events_async(esvo_handle h, int cam, const esvo_event_t* ev, size_t n) { return push_events_impl(h, cam, ev, n, false); }
 int esvo_ts_push_wait(esvo_handle h, int cam) {
@@ -520,112 +611,24 @@ int esvo_host_free(void* p) {
   if (p) HIPCHK(hipHostFree(p));
   return ESVO_OK;
 }
-static int push_events_impl(esvo_handle h, int cam, const esvo_event_t* ev, size_t n, bool wait) {
-  if (!h || cam < 0 || cam > 1 || (n && !ev)) return ESVO_ERR_INVALID_ARG;
-  if (n == 0) return ESVO_OK;
-  if (n > h->ring_cap) FAIL(ESVO_ERR_CAPACITY, "event block larger than the event ring");
-  auto stamp = [&](size_t i) { return (u64)ev[i].sec * 1000000000ull + ev[i].nsec; };
-  {  // sorted, and not older than what is staged: the fast path; anything else is sorted in as the reference's callbacks do
-    bool in_order = true;
-    u64 last = stamp(0);
-    for (size_t i = 1; i < n && in_order; ++i) {
-      const u64 t = stamp(i);
-      in_order = t >= last;
-      last = t;
-    }
-    if (in_order) {
-      std::lock_guard<std::mutex> lr(h->mu_ring);
-      const u64 newest = h->routed ? h->last_stamp[cam] : (h->ts_host[cam].empty() ? 0 : h->ts_host[cam].back());
-      in_order = stamp(0) >= newest;
-    }
-    if (!in_order) return push_unsorted(h, cam, n, [&](size_t i) { return ev[i]; });
-  }
-  std::lock_guard<std::mutex> lp(h->mu_push[cam]);
-  HIPCHK(hipSetDevice(h->device));
-  if (h->routed) return push_routed(h, cam, n, [&](size_t i) { return ev[i]; });
-  PushTicket tk;
-  { int rc = push_begin(h, cam, n, stamp(0), tk); if (rc) return rc; }
-  { int rc = push_drain(h, cam, tk); if (rc) return rc; }
-  const size_t first = (size_t)std::min<u64>(n, h->ring_cap - tk.slot);
-  PUSH_HIPCHK(hipMemcpyAsync(h->d_ring[cam] + tk.slot, ev, sizeof(esvo_event_t) * first, hipMemcpyHostToDevice, h->stream_i));
-  if (first < n)
-    PUSH_HIPCHK(hipMemcpyAsync(h->d_ring[cam], ev + first, sizeof(esvo_event_t) * (n - first), hipMemcpyHostToDevice, h->stream_i));
-  if (wait) {
-    PUSH_HIPCHK(hipStreamSynchronize(h->stream_i));  // `ev` is borrowed for the duration of the call only; later work sees the copy
-    push_commit(h, cam, n, stamp);
-  } else {
-    // esvo_ts_push_events_async: the caller keeps `ev` alive until esvo_ts_push_wait; whoever reads these ring slots on the
-    // front stream queues behind the copy (ingest_fence)
-    PUSH_HIPCHK(hipEventRecord(h->evt_ingest[cam], h->stream_i));
-    push_commit(h, cam, n, stamp, true);
-  }
-  return ESVO_OK;
-}
-
 // A serialised dvs_msgs/EventArray (ROS1 wire format): std_msgs/Header {u32 seq, u32 sec, u32 nsec, string frame_id},
-// u32 height, u32 width, Event[] {u32 count, count x 13 B}.  The 13-byte records go to the device as they are and are
-// widened to esvo_event_t in the ring by a kernel; the host only walks the time stamps (order check + selection index).
+// u32 height, u32 width, Event[] {u32 count, count x 13 B}: the header is checked here, the records are the packet
+// (WirePacket).
 int esvo_ts_push_event_array(esvo_handle h, int cam, const uint8_t* msg, size_t n_bytes, size_t* n_events) {
   if (!h || cam < 0 || cam > 1 || !msg) return ESVO_ERR_INVALID_ARG;
-  auto rd32 = [&](size_t off) { return (u32)msg[off] | ((u32)msg[off + 1] << 8) | ((u32)msg[off + 2] << 16) | ((u32)msg[off + 3] << 24); };
   if (n_bytes < 16) FAIL(ESVO_ERR_INVALID_ARG, "EventArray message shorter than its header");
-  const size_t id_len = rd32(12);
+  const size_t id_len = rd32(msg + 12);
   size_t off = 16 + id_len;
   if (off < 16 || off + 12 > n_bytes) FAIL(ESVO_ERR_INVALID_ARG, "EventArray message truncated (frame_id / height / width / count)");
-  const u32 height = rd32(off), width = rd32(off + 4), n = rd32(off + 8);
+  const u32 height = rd32(msg + off), width = rd32(msg + off + 4), n = rd32(msg + off + 8);
   off += 12;
   if (n_events) *n_events = n;
   if ((size_t)n * 13 != n_bytes - off) FAIL(ESVO_ERR_INVALID_ARG, "EventArray message length does not match its event count");
   if ((height && (int)height != h->H) || (width && (int)width != h->W)) FAIL(ESVO_ERR_INVALID_ARG, "EventArray sensor size differs from the handle's");
   if (n == 0) return ESVO_OK;
   if (n > h->ring_cap) FAIL(ESVO_ERR_CAPACITY, "event block larger than the event ring");
-  const uint8_t* rec = msg + off;
-  auto stamp = [&](size_t i) {
-    const uint8_t* r = rec + i * 13 + 4;
-    const u32 sec = (u32)r[0] | ((u32)r[1] << 8) | ((u32)r[2] << 16) | ((u32)r[3] << 24);
-    const u32 nsec = (u32)r[4] | ((u32)r[5] << 8) | ((u32)r[6] << 16) | ((u32)r[7] << 24);
-    return (u64)sec * 1000000000ull + nsec;
-  };
-  auto widen = [&](size_t i) {  // a 13-byte record as esvo_event_t, on the host (the paths that filter or sort there)
-    const uint8_t* r = rec + i * 13;
-    esvo_event_t e;
-    std::memset(&e, 0, sizeof(e));
-    e.x = (uint16_t)(r[0] | (r[1] << 8));
-    e.y = (uint16_t)(r[2] | (r[3] << 8));
-    e.sec = (u32)r[4] | ((u32)r[5] << 8) | ((u32)r[6] << 16) | ((u32)r[7] << 24);
-    e.nsec = (u32)r[8] | ((u32)r[9] << 8) | ((u32)r[10] << 16) | ((u32)r[11] << 24);
-    e.polarity = r[12] ? 1 : 0;   // (bit 7 of the byte is the library's: EV_LATE, common.hpp)
-    return e;
-  };
-  {  // in order (as esvo_ts_push_events): the fast path; else sorted in on the host
-    bool in_order = true;
-    u64 last = stamp(0);
-    for (size_t i = 1; i < n && in_order; ++i) {
-      const u64 t = stamp(i);
-      in_order = t >= last;
-      last = t;
-    }
-    if (in_order) {
-      std::lock_guard<std::mutex> lr(h->mu_ring);
-      const u64 newest = h->routed ? h->last_stamp[cam] : (h->ts_host[cam].empty() ? 0 : h->ts_host[cam].back());
-      in_order = stamp(0) >= newest;
-    }
-    if (!in_order) return push_unsorted(h, cam, n, widen);
-  }
-  std::lock_guard<std::mutex> lp(h->mu_push[cam]);
-  HIPCHK(hipSetDevice(h->device));
-  if (h->routed) return push_routed(h, cam, n, widen);
-  if ((size_t)n * 13 > h->d_wire[cam].cap())  // this camera's staging buffer: its pusher is the only user (mu_push)
-    HIPCHK(h->d_wire[cam].alloc(std::max<size_t>((size_t)n * 13, (size_t)1 << 20)));
-  PushTicket tk;
-  { int rc = push_begin(h, cam, n, stamp(0), tk); if (rc) return rc; }
-  { int rc = push_drain(h, cam, tk); if (rc) return rc; }
-  PUSH_HIPCHK(hipMemcpyAsync(h->d_wire[cam], rec, (size_t)n * 13, hipMemcpyHostToDevice, h->stream_i));
-  launch_ts_unpack_wire(h->d_wire[cam], n, h->d_ring[cam], tk.slot, h->ring_cap, h->stream_i);
-  PUSH_HIPCHK(hipGetLastError());
-  PUSH_HIPCHK(hipStreamSynchronize(h->stream_i));  // `msg` is borrowed for the duration of the call only
-  push_commit(h, cam, n, stamp);
-  return ESVO_OK;
+  WirePacket src{{}, h, cam, msg + off, n};
+  return push_packet(h, cam, src);
 }
 
 // ---- column ingest: x / y / t / p arrays in host or device memory (include/esvo_hip.h, esvo_ts_push_event_columns) ----------------
@@ -642,12 +645,12 @@ const char* columns_arg_error(const esvo_event_columns_t* c, size_t n) {
   return nullptr;
 }
 std::string columns_bad_element(size_t i) { return "event columns: element " + std::to_string(i) + " has no valid time stamp ((t + t_offset) * unit outside [0, 2^32 * 10^9))"; }
-// the records of host columns whose stamps are known and valid
-void columns_materialise(const uint16_t* x, const uint16_t* y, const void* p, int p_type, const u64* stamps, size_t n, esvo_event_t* out) {
-  for (size_t i = 0; i < n; ++i) {
-    const uint4 w = columns_record(x[i], y[i], stamps[i], columns_polarity(p, i, p_type));
-    std::memcpy(out + i, &w, sizeof(w));
-  }
+// the record of element i of host columns, its stamp known and valid
+esvo_event_t columns_event(const void* x, const void* y, const void* p, int p_type, u64 stamp, size_t i) {
+  const uint4 w = columns_record(static_cast<const uint16_t*>(x)[i], static_cast<const uint16_t*>(y)[i], stamp, columns_polarity(p, i, p_type));
+  esvo_event_t e;
+  std::memcpy(&e, &w, sizeof(w));
+  return e;
 }
 // What the runtime knows of a pointer: 0 host memory (pageable, pinned or registered), 1 plain device memory of `device`,
 // 2 anything else (managed memory, another GPU's).  Launches nothing, copies nothing.
@@ -659,6 +662,51 @@ int column_memory_kind(const void* p, int device) {
   if (a.type == hipMemoryTypeUnregistered || a.type == hipMemoryTypeHost) return 0;
   return a.type == hipMemoryTypeDevice && a.device == device ? 1 : 2;
 }
+// Columns whose valid stamps lie in h_col_stamps: host columns go to the device as they are, beside their stamps (d_col), device
+// columns are read where they lie; a kernel packs the records into the ring.
+struct ColumnsPacket : PacketDefaults<ColumnsPacket> {
+  esvo_context* h; int cam; const esvo_event_columns_t* c; size_t n; const u64* stamps; bool in_itself;
+  bool sorted() const { return in_itself; }
+  std::vector<esvo_event_t>* E;  // the slow paths take records: what esvo_ts_push_events does with them, nothing of it twice
+  StampArray stamp_fn() const { return {stamps}; }
+  esvo_event_t record(size_t i) const { return (*E)[i]; }
+  int materialise() {
+    const void *x = c->x, *y = c->y, *p = c->p;
+    std::vector<uint16_t> hx, hy;
+    std::vector<uint8_t> hp;
+    if (c->memory == ESVO_MEM_DEVICE) {  // down first
+      hx.resize(n); hy.resize(n); hp.resize(c->p ? n : 0);
+      HIPCHK(hipMemcpyAsync(hx.data(), c->x, 2 * n, hipMemcpyDeviceToHost, h->stream_i));
+      HIPCHK(hipMemcpyAsync(hy.data(), c->y, 2 * n, hipMemcpyDeviceToHost, h->stream_i));
+      if (c->p) HIPCHK(hipMemcpyAsync(hp.data(), c->p, n, hipMemcpyDeviceToHost, h->stream_i));
+      HIPCHK(hipStreamSynchronize(h->stream_i));
+      x = hx.data(); y = hy.data(); p = c->p ? hp.data() : nullptr;
+    }
+    E->resize(n);
+    for (size_t i = 0; i < n; ++i) (*E)[i] = columns_event(x, y, p, c->p_type, stamps[i], i);
+    return ESVO_OK;
+  }
+  int enqueue(const PushTicket& tk) {
+    const size_t cap = h->col_cap[cam];
+    uint8_t* const d = h->d_col[cam];
+    u64* const d_stamps = reinterpret_cast<u64*>(d);
+    const uint16_t* kx = static_cast<const uint16_t*>(c->x);
+    const uint16_t* ky = static_cast<const uint16_t*>(c->y);
+    const void* kp = c->p;
+    if (c->memory == ESVO_MEM_HOST) {
+      HIPCHK(hipMemcpyAsync(d_stamps, stamps, sizeof(u64) * n, hipMemcpyHostToDevice, h->stream_i));
+      HIPCHK(hipMemcpyAsync(d + 8 * cap, c->x, 2 * n, hipMemcpyHostToDevice, h->stream_i));
+      HIPCHK(hipMemcpyAsync(d + 10 * cap, c->y, 2 * n, hipMemcpyHostToDevice, h->stream_i));
+      if (c->p) HIPCHK(hipMemcpyAsync(d + 12 * cap, c->p, n, hipMemcpyHostToDevice, h->stream_i));
+      kx = reinterpret_cast<const uint16_t*>(d + 8 * cap);
+      ky = reinterpret_cast<const uint16_t*>(d + 10 * cap);
+      if (c->p) kp = d + 12 * cap;
+    }
+    launch_ts_pack_columns(kx, ky, d_stamps, kp, c->p_type, n, h->d_ring[cam], tk.slot, h->ring_cap, h->stream_i);
+    HIPCHK(hipGetLastError());
+    return ESVO_OK;
+  }
+};
 }  // namespace
 }  // extern "C++"
 
@@ -668,16 +716,13 @@ int esvo_event_columns_to_events(const esvo_event_columns_t* c, size_t n, esvo_e
   if (!c || (n && !out)) return ESVO_ERR_INVALID_ARG;
   if (const char* msg = columns_arg_error(c, n)) FAIL(ESVO_ERR_INVALID_ARG, msg);
   if (c->memory != ESVO_MEM_HOST) FAIL(ESVO_ERR_INVALID_ARG, "esvo_event_columns_to_events: host memory only");
-  const uint16_t* x = static_cast<const uint16_t*>(c->x);
-  const uint16_t* y = static_cast<const uint16_t*>(c->y);
   for (size_t i = 0; i < n; ++i) {
     const u64 s = columns_stamp_ns(c->t, i, c->t_type, c->t_offset);
     if (s == COL_BAD_STAMP) {
       if (first_bad) *first_bad = i;
       FAIL(ESVO_ERR_INVALID_ARG, columns_bad_element(i));
     }
-    const uint4 w = columns_record(x[i], y[i], s, columns_polarity(c->p, i, c->p_type));
-    std::memcpy(out + i, &w, sizeof(w));
+    out[i] = columns_event(c->x, c->y, c->p, c->p_type, s, i);
   }
   return ESVO_OK;
 }
@@ -692,8 +737,6 @@ int esvo_ts_push_event_columns(esvo_handle h, int cam, const esvo_event_columns_
   if (const char* msg = columns_arg_error(c, n)) FAIL(ESVO_ERR_INVALID_ARG, msg);
   if (n > h->ring_cap) FAIL(ESVO_ERR_CAPACITY, "event block larger than the event ring");
   const bool on_device = c->memory == ESVO_MEM_DEVICE;
-  const uint16_t* x = static_cast<const uint16_t*>(c->x);
-  const uint16_t* y = static_cast<const uint16_t*>(c->y);
   std::unique_lock<std::mutex> lp(h->mu_push[cam]);
   HIPCHK(hipSetDevice(h->device));
   {  // where the columns lie, first and last byte of each, before anything is launched or copied
@@ -715,69 +758,26 @@ int esvo_ts_push_event_columns(esvo_handle h, int cam, const esvo_event_columns_
     HIPCHK(h->h_col_stamps[cam].alloc(cap));
     h->col_cap[cam] = cap;
   }
-  const size_t cap = h->col_cap[cam];
-  u64* const d_stamps = reinterpret_cast<u64*>(h->d_col[cam].get());
   u64* const stamps = h->h_col_stamps[cam];
   if (on_device) {  // t -> stamps on the device, down once
+    u64* const d_stamps = reinterpret_cast<u64*>(h->d_col[cam].get());
     launch_ts_columns_stamps(c->t, c->t_type, c->t_offset, n, d_stamps, h->stream_i);
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpyAsync(stamps, d_stamps, sizeof(u64) * n, hipMemcpyDeviceToHost, h->stream_i));
     HIPCHK(hipStreamSynchronize(h->stream_i));
   }
-  // the walk: the stamps (host columns: computed here), their validity, their order
   bool in_order = true;
   u64 last = 0;
-  for (size_t i = 0; i < n; ++i) {
+  for (size_t i = 0; i < n; ++i) {  // the stamps (host columns: computed here), their validity, their order
     const u64 s = on_device ? stamps[i] : columns_stamp_ns(c->t, i, c->t_type, c->t_offset);
     if (s == COL_BAD_STAMP) FAIL(ESVO_ERR_INVALID_ARG, columns_bad_element(i));
     stamps[i] = s;
     in_order = in_order && s >= last;
     last = s;
   }
-  if (in_order) {
-    std::lock_guard<std::mutex> lr(h->mu_ring);
-    const u64 newest = h->routed ? h->last_stamp[cam] : (h->ts_host[cam].empty() ? 0 : h->ts_host[cam].back());
-    in_order = stamps[0] >= newest;
-  }
-  if (!in_order || h->routed) {  // the slow paths take records: what esvo_ts_push_events does with them, nothing of it twice
-    std::vector<esvo_event_t> E(n);
-    if (on_device) {
-      std::vector<uint16_t> hx(n), hy(n);
-      std::vector<uint8_t> hp(c->p ? n : 0);
-      HIPCHK(hipMemcpyAsync(hx.data(), c->x, 2 * n, hipMemcpyDeviceToHost, h->stream_i));
-      HIPCHK(hipMemcpyAsync(hy.data(), c->y, 2 * n, hipMemcpyDeviceToHost, h->stream_i));
-      if (c->p) HIPCHK(hipMemcpyAsync(hp.data(), c->p, n, hipMemcpyDeviceToHost, h->stream_i));
-      HIPCHK(hipStreamSynchronize(h->stream_i));
-      columns_materialise(hx.data(), hy.data(), c->p ? hp.data() : nullptr, c->p_type, stamps, n, E.data());
-    } else {
-      columns_materialise(x, y, c->p, c->p_type, stamps, n, E.data());
-    }
-    const auto get = [&](size_t i) { return E[i]; };
-    if (in_order) return push_routed(h, cam, n, get);
-    lp.unlock();  // (push_unsorted takes mu_api before mu_push: the order esvo_reset takes them in)
-    return push_unsorted(h, cam, n, get);
-  }
-  PushTicket tk;
-  { int rc = push_begin(h, cam, n, stamps[0], tk); if (rc) return rc; }
-  { int rc = push_drain(h, cam, tk); if (rc) return rc; }
-  const uint16_t* kx = x;
-  const uint16_t* ky = y;
-  const void* kp = c->p;
-  if (!on_device) {  // the columns as they are, beside their stamps
-    uint8_t* const d = h->d_col[cam];
-    PUSH_HIPCHK(hipMemcpyAsync(d_stamps, stamps, sizeof(u64) * n, hipMemcpyHostToDevice, h->stream_i));
-    PUSH_HIPCHK(hipMemcpyAsync(d + 8 * cap, x, 2 * n, hipMemcpyHostToDevice, h->stream_i));
-    PUSH_HIPCHK(hipMemcpyAsync(d + 10 * cap, y, 2 * n, hipMemcpyHostToDevice, h->stream_i));
-    if (c->p) PUSH_HIPCHK(hipMemcpyAsync(d + 12 * cap, c->p, n, hipMemcpyHostToDevice, h->stream_i));
-    kx = reinterpret_cast<const uint16_t*>(d + 8 * cap);
-    ky = reinterpret_cast<const uint16_t*>(d + 10 * cap);
-    if (c->p) kp = d + 12 * cap;
-  }
-  launch_ts_pack_columns(kx, ky, d_stamps, kp, c->p_type, n, h->d_ring[cam], tk.slot, h->ring_cap, h->stream_i);
-  PUSH_HIPCHK(hipGetLastError());
-  PUSH_HIPCHK(hipStreamSynchronize(h->stream_i));  // the columns are borrowed for the duration of the call only
-  push_commit(h, cam, n, [&](size_t i) { return stamps[i]; });
-  return ESVO_OK;
+  std::vector<esvo_event_t> E;
+  ColumnsPacket src{{}, h, cam, c, n, stamps, in_order, &E};
+  return push_packet(h, cam, src, std::move(lp));
 }
 
 namespace {
@@ -831,24 +831,11 @@ int esvo_ts_render_forward(esvo_handle h, int cam, uint64_t t_ns, uint8_t* out_m
   {
     std::lock_guard<std::mutex> lr(h->mu_ring);
     ingest_fence(h, cam);
-    const auto& tsq = h->ts_host[cam];
-    const size_t k = std::lower_bound(tsq.begin(), tsq.end(), (u64)t_ns) - tsq.begin();
-    const u64 upto = h->ring_base[cam] + k;
+    const u64 upto = first_staged_at(h, cam, (u64)t_ns);
     if (h->tsq_len) queue_prepare(h, cam, (u64)t_ns);
-    else if (upto < h->scattered[cam])
-      FAIL(ESVO_ERR_STATE, "esvo_ts_render_forward: t_ns precedes events of an earlier render (render times must not decrease; esvo_reset to replay)");
-    if (!h->tsq_len && upto > h->scattered[cam]) {  // events with ts < T that are not in the SAE yet (as esvo_ts_render)
-      u64 a = h->scattered[cam];
-      h->scatter_pending_lo[cam] = std::min(h->scatter_pending_lo[cam], a);
-      h->scatter_seq++;
-      h->stats.events_scattered[cam] += upto - a;
-      while (a < upto) {
-        const u64 slot = a % h->ring_cap;
-        const u64 cnt = std::min<u64>(upto - a, h->ring_cap - slot);
-        launch_ts_scatter(h->d_ring[cam] + slot, (size_t)cnt, h->d_sae[cam], h->W, h->H, h->stream);
-        a += cnt;
-      }
-      h->scattered[cam] = upto;
+    else {  // events with ts < T that are not in the SAE yet (as esvo_ts_render)
+      { int rc = refuse_decreasing_render(h, cam, upto, "esvo_ts_render_forward"); if (rc) return rc; }
+      scatter_upto(h, cam, upto, [&](const esvo_event_t* ev, size_t n) { launch_ts_scatter(ev, n, h->d_sae[cam], h->W, h->H, h->stream); });
     }
   }
   {
@@ -880,31 +867,12 @@ int esvo_ts_render(esvo_handle h, int cam, uint64_t t_ns, uint8_t* out_mono8) {
   {
     std::lock_guard<std::mutex> lr(h->mu_ring);
     ingest_fence(h, cam);
-    // events with ts < T (strict, TimeSurface.h:68) that are not in the SAE yet
-    const auto& tsq = h->ts_host[cam];
-    const size_t k = std::lower_bound(tsq.begin(), tsq.end(), (u64)t_ns) - tsq.begin();
-    const u64 upto = h->ring_base[cam] + k;
-    // The SAE keeps ONE stamp per pixel, the reference a queue of 20 (TimeSurface.h:28-96): rendering at a T that precedes
-    // events already scattered would read pixels as empty where getMostRecentEventBeforeT finds the older event.
-    if (!h->tsq_len && upto < h->scattered[cam])
-      FAIL(ESVO_ERR_STATE, "esvo_ts_render: t_ns precedes events of an earlier render (render times must not decrease; esvo_reset to replay)");
+    const u64 upto = first_staged_at(h, cam, (u64)t_ns);  // events below it that are not in the SAE yet are scattered
+    if (!h->tsq_len) { int rc = refuse_decreasing_render(h, cam, upto, "esvo_ts_render"); if (rc) return rc; }
     if (h->ts_timing_pending[cam] && hipEventQuery(T.e[TE_R1]) == hipSuccess) collect_ts_timing(h, cam);
     if (timed) hipEventRecord(T.e[TE_SC0], h->stream);
     if (h->tsq_len) queue_prepare(h, cam, (u64)t_ns);
-    else if (upto > h->scattered[cam]) {
-      u64 a = h->scattered[cam];
-      h->scatter_pending_lo[cam] = std::min(h->scatter_pending_lo[cam], a);
-      h->scatter_seq++;
-      const u64 total = upto - a;
-      while (a < upto) {
-        const u64 slot = a % h->ring_cap;
-        const u64 cnt = std::min<u64>(upto - a, h->ring_cap - slot);
-        launch_ts_scatter(h->d_ring[cam] + slot, (size_t)cnt, h->d_sae[cam], h->W, h->H, h->stream);
-        a += cnt;
-      }
-      h->scattered[cam] = upto;
-      h->stats.events_scattered[cam] += total;
-    }
+    else scatter_upto(h, cam, upto, [&](const esvo_event_t* ev, size_t n) { launch_ts_scatter(ev, n, h->d_sae[cam], h->W, h->H, h->stream); });
     if (timed) hipEventRecord(T.e[TE_SC1], h->stream);
   }
   {

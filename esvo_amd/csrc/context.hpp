@@ -31,6 +31,7 @@
 
 #include "common.hpp"
 #include "devmem.hpp"
+#include "ring_spans.hpp"
 
 using namespace esvo;
 
