@@ -243,6 +243,85 @@ def columns_to_events(x, y, t, p=None, unit="ns", t_offset=0):
     return ev
 
 
+# ---- Prophesee EVT 3.0 words (esvo_ts_push_evt3 of include/esvo_hip.h)
+class Evt3State(C.Structure):
+    """esvo_evt3_state_t: flags bit0 have_th, bit1 have_y, bit2 have_base, bit3 vect_pol"""
+    _fields_ = [("flags", C.c_uint32), ("y", C.c_uint16), ("base_x", C.c_uint16), ("time_high", C.c_uint16), ("time_low", C.c_uint16),
+                ("loops", C.c_uint32), ("reserved", C.c_uint32)]
+
+    def as_tuple(self):
+        return (self.flags, self.y, self.base_x, self.time_high, self.time_low, self.loops)
+
+    def copy(self):
+        return Evt3State.from_buffer_copy(self)
+
+
+class Evt3Counts(C.Structure):
+    """esvo_evt3_counts_t"""
+    _fields_ = [(k, C.c_uint64) for k in ("words", "events", "dropped_events", "ignored_words", "ext_triggers", "time_loops")]
+
+    def as_dict(self):
+        return {k: int(getattr(self, k)) for k, _ in self._fields_}
+
+
+class Evt3Error(ValueError):
+    """an event of the words has no valid stamp; `first_bad` is its index among the events"""
+
+    def __init__(self, first_bad):
+        super().__init__(f"EVT3 words: event {first_bad} has no valid time stamp ((t_us + t_offset_us) * 1000 outside [0, 2^32 * 10^9))")
+        self.first_bad = int(first_bad)
+
+
+def evt3_words(words):
+    """a contiguous uint16 host array over bytes / bytearray / memoryview (little-endian words) or anything numpy takes"""
+    if isinstance(words, (bytes, bytearray, memoryview)):
+        if len(words) % 2:
+            raise ValueError("EVT3 words: an odd number of bytes")
+        return np.frombuffer(words, "<u2")
+    words = np.asarray(words)
+    if words.dtype != np.uint16 or words.ndim != 1:
+        raise ValueError(f"EVT3 words: a one-dimensional uint16 array is expected, not {words.dtype} with {words.ndim} dimensions")
+    return np.ascontiguousarray(words)
+
+
+def evt3_to_events(words, state=None, t_offset_us=0, count_only=False, cap=None):
+    """esvo_evt3_to_events (the library's host decoder; no GPU): -> (events or None, the state behind the words, counts as a dict).
+    state: an Evt3State (not changed) or None for a stream's start.  cap: room for that many records (default: as many as the words
+    hold).  Raises Evt3Error (first_bad) for a bad stamp, lib.EsvoError (code -4, capacity) where cap is too small."""
+    from . import lib
+    words = evt3_words(words)
+    st = state.copy() if state is not None else Evt3State()
+    so, n_out, counts = lib.load(), C.c_size_t(0), Evt3Counts()
+    off = check_t_offset(t_offset_us)
+    out, room = None, 0
+    if not count_only:
+        if cap is None:  # count first (a bad stamp shows again below)
+            so.esvo_evt3_to_events(C.byref(st.copy()), words.ctypes.data, words.size, off, None, 0, C.byref(n_out), None)
+            cap = n_out.value
+        room = int(cap)
+        out = np.zeros(max(room, 1), EVENT_DTYPE)   # (never NULL: a NULL `out` counts)
+    rc = so.esvo_evt3_to_events(C.byref(st), words.ctypes.data, words.size, off, None if out is None else out.ctypes.data, room,
+                                C.byref(n_out), C.byref(counts))
+    if rc == -1 and "no valid time stamp" in so.esvo_last_error(None).decode(errors="replace"):
+        raise Evt3Error(n_out.value)
+    if rc != 0:
+        raise lib.EsvoError(f"esvo_evt3_to_events failed ({rc}): {so.esvo_last_error(None).decode(errors='replace')}", code=rc)
+    return (None if count_only else out[:n_out.value]), st, counts.as_dict()
+
+
+def evt3_raw_header(data):
+    """esvo_evt3_raw_header on the first bytes of a Prophesee .raw file -> (data_offset, width, height); width / height 0 if absent.
+    lib.EsvoError (code -5, unsupported) for a file that is not EVT 3.0."""
+    from . import lib
+    buf = np.frombuffer(bytes(data), np.uint8)
+    off, w, h = C.c_size_t(0), C.c_int(0), C.c_int(0)
+    so = lib.load()
+    rc = so.esvo_evt3_raw_header(buf.ctypes.data if buf.size else None, buf.size, C.byref(off), C.byref(w), C.byref(h))
+    if rc != 0:
+        raise lib.EsvoError(f"esvo_evt3_raw_header failed ({rc}): {so.esvo_last_error(None).decode(errors='replace')}", code=rc)
+    return int(off.value), int(w.value), int(h.value)
+
+
 def event_ns(ev):
     return ev["sec"].astype(np.uint64) * np.uint64(1_000_000_000) + ev["nsec"].astype(np.uint64)
 

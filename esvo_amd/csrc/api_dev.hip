@@ -511,6 +511,16 @@ int esvo_debug_ts_ring(esvo_handle h, int cam, uint64_t first_abs, size_t n, esv
   return ESVO_OK;
 }
 
+// esvo_ts_push_evt3 decodes packets of fewer than n_words words on the host (0: every packet on the device).  The tests of the
+// device decode's small shapes move the threshold; *previous (nullable) receives the old one.
+int esvo_debug_evt3_device_min(esvo_handle h, size_t n_words, size_t* previous) {
+  if (!h) return ESVO_ERR_INVALID_ARG;
+  std::lock_guard<std::mutex> lp0(h->mu_push[0]), lp1(h->mu_push[1]);
+  if (previous) *previous = h->evt3_device_min;
+  h->evt3_device_min = n_words;
+  return ESVO_OK;
+}
+
 // The ledger of devmem.hpp: live allocations and live bytes of every DevBuf / PinBuf of the process (tests/test_gpu_lifecycle.py
 // asserts on its deltas around its own handles).  The guarded buffers above and esvo_ts_alloc_pinned are not in it.
 void esvo_debug_live_allocations(size_t out[2]) {

@@ -662,6 +662,17 @@ int column_memory_kind(const void* p, int device) {
   if (a.type == hipMemoryTypeUnregistered || a.type == hipMemoryTypeHost) return 0;
   return a.type == hipMemoryTypeDevice && a.device == device ? 1 : 2;
 }
+// the camera's column staging for n events (caller holds its mu_push; idle: every column push ends with a wait for the ingest stream)
+int columns_staging(esvo_context* h, int cam, size_t n) {
+  if (n <= h->col_cap[cam]) return ESVO_OK;
+  const size_t cap = (std::max<size_t>(n + n / 2, 256) + 255) / 256 * 256;
+  h->col_cap[cam] = 0;
+  (void)h->d_col[cam].release(); (void)h->h_col_stamps[cam].release();
+  HIPCHK(h->d_col[cam].alloc(cap * 13));
+  HIPCHK(h->h_col_stamps[cam].alloc(cap));
+  h->col_cap[cam] = cap;
+  return ESVO_OK;
+}
 // Columns whose valid stamps lie in h_col_stamps: host columns go to the device as they are, beside their stamps (d_col), device
 // columns are read where they lie; a kernel packs the records into the ring.
 struct ColumnsPacket : PacketDefaults<ColumnsPacket> {
@@ -750,14 +761,7 @@ int esvo_ts_push_event_columns(esvo_handle h, int cam, const esvo_event_columns_
                                              : "event columns labelled ESVO_MEM_HOST must be host memory (a device or managed pointer was given)");
     }
   }
-  if (n > h->col_cap[cam]) {  // (idle: every column push ends with a wait for the ingest stream)
-    const size_t cap = (std::max<size_t>(n + n / 2, 256) + 255) / 256 * 256;
-    h->col_cap[cam] = 0;
-    (void)h->d_col[cam].release(); (void)h->h_col_stamps[cam].release();
-    HIPCHK(h->d_col[cam].alloc(cap * 13));
-    HIPCHK(h->h_col_stamps[cam].alloc(cap));
-    h->col_cap[cam] = cap;
-  }
+  { int rc = columns_staging(h, cam, n); if (rc) return rc; }
   u64* const stamps = h->h_col_stamps[cam];
   if (on_device) {  // t -> stamps on the device, down once
     u64* const d_stamps = reinterpret_cast<u64*>(h->d_col[cam].get());
@@ -778,6 +782,263 @@ int esvo_ts_push_event_columns(esvo_handle h, int cam, const esvo_event_columns_
   std::vector<esvo_event_t> E;
   ColumnsPacket src{{}, h, cam, c, n, stamps, in_order, &E};
   return push_packet(h, cam, src, std::move(lp));
+}
+
+// ---- EVT 3.0 ingest: Prophesee's 16-bit word stream in host or device memory (include/esvo_hip.h, esvo_ts_push_evt3) -------------
+extern "C++" {
+namespace {
+enum { EVT3_DEC_OK, EVT3_DEC_BAD_STAMP, EVT3_DEC_FULL };
+// The word state machine as written in the header, every rule through common.hpp's functions.  emit(record) -> false: no room.
+// c.events counts the events emitted so far: at EVT3_DEC_BAD_STAMP the index of the bad one.
+template <class Emit>
+int evt3_decode_host(esvo_evt3_state_t& s, const uint16_t* words, size_t n_words, int64_t t_offset_us, esvo_evt3_counts_t& c, Emit emit) {
+  for (size_t i = 0; i < n_words; ++i) {
+    const u32 w = words[i], t = evt3_type(w), m = evt3_mask(w);
+    ++c.words;
+    if (m) {
+      if (!evt3_emits(w, s.flags)) c.dropped_events += (u64)__builtin_popcount(m);
+      else {
+        const u64 stamp = evt3_stamp_ns(evt3_t_us(s.loops, s.time_high, s.time_low), t_offset_us);
+        if (stamp == COL_BAD_STAMP) return EVT3_DEC_BAD_STAMP;
+        const u32 x0 = t == EVT3_ADDR_X ? (w & 0x7FFu) : (u32)s.base_x;
+        const u32 pol = t == EVT3_ADDR_X ? ((w >> 11) & 1u) : ((s.flags & EVT3_VECT_POL) ? 1u : 0u);
+        for (u32 mm = m; mm; mm &= mm - 1u) {
+          const uint4 r = columns_record((uint16_t)((x0 + (u32)__builtin_ctz(mm)) & 0xFFFFu), s.y, stamp, pol);
+          esvo_event_t e;
+          std::memcpy(&e, &r, sizeof(r));
+          if (!emit(e)) return EVT3_DEC_FULL;
+          ++c.events;
+        }
+      }
+    }
+    switch (t) {
+      case EVT3_ADDR_Y: s.y = (uint16_t)(w & 0x7FFu); s.flags |= EVT3_HAVE_Y; break;
+      case EVT3_ADDR_X: break;
+      case EVT3_VECT_BASE_X:
+        s.base_x = (uint16_t)(w & 0x7FFu);
+        s.flags = (s.flags & ~(u32)EVT3_VECT_POL) | (((w >> 11) & 1u) ? (u32)EVT3_VECT_POL : 0u) | EVT3_HAVE_BASE;
+        break;
+      case EVT3_VECT_12: case EVT3_VECT_8: s.base_x = (uint16_t)((s.base_x + evt3_base_advance(w)) & 0xFFFFu); break;
+      case EVT3_TIME_LOW: s.time_low = (uint16_t)(w & 0xFFFu); break;
+      case EVT3_TIME_HIGH:
+        if (evt3_time_loop((s.flags & EVT3_HAVE_TH) != 0, s.time_high, w & 0xFFFu)) { ++s.loops; ++c.time_loops; }
+        s.time_high = (uint16_t)(w & 0xFFFu); s.flags |= EVT3_HAVE_TH;
+        break;
+      case EVT3_EXT_TRIGGER: ++c.ext_triggers; break;
+      default: ++c.ignored_words;
+    }
+  }
+  return EVT3_DEC_OK;
+}
+std::string evt3_bad_event(size_t i) { return "EVT3 words: event " + std::to_string(i) + " has no valid time stamp ((t_us + t_offset_us) * 1000 outside [0, 2^32 * 10^9))"; }
+void evt3_add(esvo_evt3_counts_t& a, const esvo_evt3_counts_t& b) {
+  a.words += b.words; a.events += b.events; a.dropped_events += b.dropped_events; a.ignored_words += b.ignored_words;
+  a.ext_triggers += b.ext_triggers; a.time_loops += b.time_loops;
+}
+// A packet the device decoded into the camera's column staging: a device-resident ColumnsPacket, whose slow paths take the records
+// of the host decoder (the words come down first where they lie on the device).
+struct Evt3Packet : ColumnsPacket {
+  const uint16_t* words; size_t n_words; bool on_device; esvo_evt3_state_t st0; int64_t t_offset_us;
+  int materialise() {
+    std::vector<uint16_t> hw;
+    const uint16_t* w = words;
+    if (on_device) {
+      hw.resize(n_words);
+      HIPCHK(hipMemcpyAsync(hw.data(), words, 2 * n_words, hipMemcpyDeviceToHost, h->stream_i));
+      HIPCHK(hipStreamSynchronize(h->stream_i));
+      w = hw.data();
+    }
+    E->clear(); E->reserve(n);
+    esvo_evt3_state_t s = st0;
+    esvo_evt3_counts_t c{};
+    if (evt3_decode_host(s, w, n_words, t_offset_us, c, [&](const esvo_event_t& e) { E->push_back(e); return true; }) != EVT3_DEC_OK || E->size() != n)
+      FAIL(ESVO_ERR_STATE, "EVT3: the host decode disagrees with the device decode");
+    return ESVO_OK;
+  }
+};
+}  // namespace
+}  // extern "C++"
+
+int esvo_evt3_to_events(esvo_evt3_state_t* st, const uint16_t* words, size_t n_words, int64_t t_offset_us, esvo_event_t* out, size_t cap,
+                        size_t* n_out, esvo_evt3_counts_t* counts) {
+  esvo_context* h = nullptr;
+  if (n_out) *n_out = 0;
+  if (!st || (n_words && !words) || (uintptr_t)words % 2) return ESVO_ERR_INVALID_ARG;
+  esvo_evt3_state_t s = *st;
+  esvo_evt3_counts_t c{};
+  const int rc = evt3_decode_host(s, words, n_words, t_offset_us, c, [&](const esvo_event_t& e) {
+    if (!out) return true;
+    if (c.events >= cap) return false;
+    out[c.events] = e;
+    return true;
+  });
+  if (n_out) *n_out = (size_t)c.events;
+  if (rc == EVT3_DEC_BAD_STAMP) FAIL(ESVO_ERR_INVALID_ARG, evt3_bad_event((size_t)c.events));
+  if (rc == EVT3_DEC_FULL) FAIL(ESVO_ERR_CAPACITY, "esvo_evt3_to_events: the words hold more events than `out` has room for");
+  *st = s;
+  if (counts) *counts = c;
+  return ESVO_OK;
+}
+void esvo_evt3_sizes(size_t out[4]) {
+  out[0] = sizeof(esvo_evt3_state_t); out[1] = sizeof(esvo_evt3_counts_t);
+  out[2] = out[3] = 0;
+}
+int esvo_evt3_raw_header(const uint8_t* file, size_t n_bytes, size_t* data_offset, int* width, int* height) {
+  esvo_context* h = nullptr;
+  if (data_offset) *data_offset = 0;
+  if (width) *width = 0;
+  if (height) *height = 0;
+  if ((n_bytes && !file) || !data_offset) return ESVO_ERR_INVALID_ARG;
+  const auto number_after = [](const std::string& line, const char* key) {  // the decimal number behind `key`, or 0
+    const size_t at = line.find(key);
+    return at == std::string::npos ? 0 : std::atoi(line.c_str() + at + std::strlen(key));
+  };
+  size_t off = 0;
+  while (off < n_bytes && file[off] == '%') {
+    size_t eol = off;
+    while (eol < n_bytes && file[eol] != '\n') ++eol;
+    std::string line(reinterpret_cast<const char*>(file) + off, eol - off);
+    while (!line.empty() && (line.back() == '\r' || line.back() == ' ')) line.pop_back();
+    off = eol < n_bytes ? eol + 1 : n_bytes;
+    if (line == "% end") break;
+    if (line.rfind("% evt ", 0) == 0 && line.substr(6) != "3.0") FAIL(ESVO_ERR_UNSUPPORTED, "Prophesee .raw: '" + line + "' -- only EVT 3.0 is decoded");
+    if (line.rfind("% format ", 0) == 0) {
+      if (line.compare(9, 4, "EVT3") != 0) FAIL(ESVO_ERR_UNSUPPORTED, "Prophesee .raw: '" + line + "' -- only EVT3 is decoded");
+      if (width && number_after(line, "width=")) *width = number_after(line, "width=");
+      if (height && number_after(line, "height=")) *height = number_after(line, "height=");
+    }
+    if (line.rfind("% geometry ", 0) == 0) {
+      const size_t xat = line.find('x', 11);
+      if (width) *width = std::atoi(line.c_str() + 11);
+      if (height && xat != std::string::npos) *height = std::atoi(line.c_str() + xat + 1);
+    }
+  }
+  *data_offset = off;
+  return ESVO_OK;
+}
+
+int esvo_ts_evt3_state(esvo_handle h, int cam, esvo_evt3_state_t* get, const esvo_evt3_state_t* set) {
+  if (!h || cam < 0 || cam > 1) return ESVO_ERR_INVALID_ARG;
+  std::lock_guard<std::mutex> lp(h->mu_push[cam]);
+  if (get) *get = h->evt3_state[cam];
+  if (set) {
+    esvo_evt3_state_t s = *set;
+    s.flags &= 0xFu; s.y &= 0x7FFu; s.time_high &= 0xFFFu; s.time_low &= 0xFFFu; s.reserved = 0;  // what a stream can leave
+    h->evt3_state[cam] = s;
+  }
+  return ESVO_OK;
+}
+int esvo_ts_evt3_stats(esvo_handle h, int cam, esvo_evt3_counts_t* totals) {
+  if (!h || cam < 0 || cam > 1 || !totals) return ESVO_ERR_INVALID_ARG;
+  std::lock_guard<std::mutex> lp(h->mu_push[cam]);
+  *totals = h->evt3_totals[cam];
+  return ESVO_OK;
+}
+
+int esvo_ts_push_evt3(esvo_handle h, int cam, const void* words_v, size_t n_bytes, int memory, int64_t t_offset_us, size_t* n_events) {
+  if (n_events) *n_events = 0;
+  if (!h || cam < 0 || cam > 1) return ESVO_ERR_INVALID_ARG;
+  if (memory != ESVO_MEM_HOST && memory != ESVO_MEM_DEVICE) FAIL(ESVO_ERR_INVALID_ARG, "EVT3 words: unknown memory");
+  if (n_bytes % 2) FAIL(ESVO_ERR_INVALID_ARG, "EVT3 words: an odd number of bytes");
+  if (n_bytes && !words_v) FAIL(ESVO_ERR_INVALID_ARG, "EVT3 words: NULL");
+  if ((uintptr_t)words_v % 2) FAIL(ESVO_ERR_INVALID_ARG, "EVT3 words: the base is not 2-byte aligned");
+  const size_t n_words = n_bytes / 2;
+  if (n_words > 0x7fffffffull) FAIL(ESVO_ERR_INVALID_ARG, "EVT3 words: more than 2^31 - 1 words in one call");
+  if (n_words == 0) return ESVO_OK;
+  const uint16_t* const words = static_cast<const uint16_t*>(words_v);
+  const bool on_device = memory == ESVO_MEM_DEVICE;
+  std::unique_lock<std::mutex> lp(h->mu_push[cam]);
+  HIPCHK(hipSetDevice(h->device));
+  {  // where the words lie, first and last byte, before anything is launched or copied
+    const int want = on_device ? 1 : 0;
+    if (column_memory_kind(words, h->device) != want || column_memory_kind(static_cast<const uint8_t*>(words_v) + n_bytes - 1, h->device) != want)
+      FAIL(ESVO_ERR_INVALID_ARG, on_device ? "EVT3 words labelled ESVO_MEM_DEVICE must be plain device memory of the handle's GPU (not host, managed or another GPU's)"
+                                           : "EVT3 words labelled ESVO_MEM_HOST must be host memory (a device or managed pointer was given)");
+  }
+  const esvo_evt3_state_t st0 = h->evt3_state[cam];
+  esvo_evt3_state_t st1 = st0;
+  esvo_evt3_counts_t cnt{};
+  const auto commit = [&]() {  // (under mu_push[cam])
+    h->evt3_state[cam] = st1;
+    evt3_add(h->evt3_totals[cam], cnt);
+    if (n_events) *n_events = (size_t)cnt.events;
+  };
+  int rc = ESVO_OK;
+  if (h->routed || n_words < h->evt3_device_min || n_words > EVT3_DEVICE_MAX_WORDS) {
+    // decoded on the host: the record paths.  (Small packets: three launches and a read-back cost more than the walk.)
+    std::vector<uint16_t> hw;
+    const uint16_t* w = words;
+    if (on_device) {
+      hw.resize(n_words);
+      HIPCHK(hipMemcpyAsync(hw.data(), words, n_bytes, hipMemcpyDeviceToHost, h->stream_i));
+      HIPCHK(hipStreamSynchronize(h->stream_i));
+      w = hw.data();
+    }
+    std::vector<esvo_event_t> E;
+    const size_t room = (size_t)h->ring_cap;
+    const int drc = evt3_decode_host(st1, w, n_words, t_offset_us, cnt, [&](const esvo_event_t& e) {
+      if (E.size() >= room) return false;
+      E.push_back(e);
+      return true;
+    });
+    if (drc == EVT3_DEC_BAD_STAMP) FAIL(ESVO_ERR_INVALID_ARG, evt3_bad_event((size_t)cnt.events));
+    if (drc == EVT3_DEC_FULL) FAIL(ESVO_ERR_CAPACITY, "event block larger than the event ring");
+    if (E.empty()) { commit(); return ESVO_OK; }
+    RecordPacket src{{}, h, cam, E.data(), E.size(), false};
+    rc = push_packet(h, cam, src, std::move(lp));
+  } else {
+    const uint16_t* d_words = words;
+    if (!on_device) {
+      if (n_words > h->d_evt3_words[cam].cap()) HIPCHK(h->d_evt3_words[cam].alloc(std::max<size_t>(n_words + n_words / 2, (size_t)1 << 16)));
+      d_words = h->d_evt3_words[cam];
+    }
+    const size_t n_tiles = evt3_tiles(n_words, d_words);
+    if (n_tiles * EVT3_TILE_WORDS > h->d_evt3_tiles[cam].cap()) HIPCHK(h->d_evt3_tiles[cam].alloc(std::max<size_t>(2 * n_tiles, 64) * EVT3_TILE_WORDS));
+    if (!h->d_evt3_hdr[cam]) { HIPCHK(h->d_evt3_hdr[cam].alloc(EVT3_HDR_WORDS)); HIPCHK(h->h_evt3_hdr[cam].alloc(EVT3_HDR_WORDS)); }
+    { int rcs = columns_staging(h, cam, std::min<size_t>(2 * n_words, (size_t)h->ring_cap)); if (rcs) return rcs; }  // (a guess: the header tells)
+    u32* const hdr = h->h_evt3_hdr[cam];
+    const auto decode = [&]() -> int {  // the three launches and the header's way down
+      const size_t cap = h->col_cap[cam];
+      uint8_t* const d = h->d_col[cam];
+      launch_evt3_decode(d_words, n_words, st0, t_offset_us, h->d_evt3_tiles[cam], h->d_evt3_hdr[cam], reinterpret_cast<u64*>(d),
+                         reinterpret_cast<uint16_t*>(d + 8 * cap), reinterpret_cast<uint16_t*>(d + 10 * cap), d + 12 * cap, cap, h->stream_i);
+      HIPCHK(hipGetLastError());
+      HIPCHK(hipMemcpyAsync(hdr, h->d_evt3_hdr[cam], sizeof(u32) * EVT3_HDR_WORDS, hipMemcpyDeviceToHost, h->stream_i));
+      HIPCHK(hipStreamSynchronize(h->stream_i));
+      return ESVO_OK;
+    };
+    if (!on_device) HIPCHK(hipMemcpyAsync(h->d_evt3_words[cam], words, n_bytes, hipMemcpyHostToDevice, h->stream_i));
+    { int rcd = decode(); if (rcd) return rcd; }
+    const size_t n = hdr[EVT3_H_EVENTS];
+    if (hdr[EVT3_H_FIRST_BAD] != 0xffffffffu) FAIL(ESVO_ERR_INVALID_ARG, evt3_bad_event(hdr[EVT3_H_FIRST_BAD]));
+    if (n > h->ring_cap) FAIL(ESVO_ERR_CAPACITY, "event block larger than the event ring");
+    if (n > h->col_cap[cam]) {  // the guess was too small: once more into staging that holds them
+      { int rcs = columns_staging(h, cam, n); if (rcs) return rcs; }
+      { int rcd = decode(); if (rcd) return rcd; }
+    }
+    st1.flags = hdr[EVT3_H_FLAGS]; st1.y = (uint16_t)(hdr[EVT3_H_Y_BASE] & 0xffffu); st1.base_x = (uint16_t)(hdr[EVT3_H_Y_BASE] >> 16);
+    st1.time_high = (uint16_t)(hdr[EVT3_H_TIME] & 0xffffu); st1.time_low = (uint16_t)(hdr[EVT3_H_TIME] >> 16); st1.loops = hdr[EVT3_H_LOOPS_END];
+    cnt.words = n_words; cnt.events = n; cnt.dropped_events = hdr[EVT3_H_DROPPED]; cnt.ignored_words = hdr[EVT3_H_IGNORED];
+    cnt.ext_triggers = hdr[EVT3_H_EXT]; cnt.time_loops = hdr[EVT3_H_LOOPS];
+    if (n == 0) { commit(); return ESVO_OK; }
+    const size_t cap = h->col_cap[cam];
+    uint8_t* const d = h->d_col[cam];
+    u64* const stamps = h->h_col_stamps[cam];
+    HIPCHK(hipMemcpyAsync(stamps, d, sizeof(u64) * n, hipMemcpyDeviceToHost, h->stream_i));
+    HIPCHK(hipStreamSynchronize(h->stream_i));
+    bool in_order = true;
+    for (size_t i = 1; i < n && in_order; ++i) in_order = stamps[i] >= stamps[i - 1];
+    esvo_event_columns_t c{};
+    c.x = d + 8 * cap; c.y = d + 10 * cap; c.p = d + 12 * cap; c.t = d;
+    c.t_type = ESVO_T_NS_I64; c.p_type = ESVO_P_U8; c.memory = ESVO_MEM_DEVICE;
+    std::vector<esvo_event_t> E;
+    Evt3Packet src{{{}, h, cam, &c, n, stamps, in_order, &E}, words, n_words, on_device, st0, t_offset_us};
+    rc = push_packet(h, cam, src, std::move(lp));
+  }
+  if (rc) return rc;
+  std::lock_guard<std::mutex> lp2(h->mu_push[cam]);  // (push_packet gave the lock back)
+  commit();
+  return ESVO_OK;
 }
 
 namespace {

@@ -255,6 +255,44 @@ __host__ __device__ inline uint4 columns_record(uint16_t x, uint16_t y, u64 stam
 void launch_ts_columns_stamps(const void* t, int t_type, int64_t t_offset, size_t n, u64* stamps, hipStream_t s);
 void launch_ts_pack_columns(const uint16_t* x, const uint16_t* y, const u64* stamps, const void* p, int p_type, size_t n,
                             esvo_event_t* ring, u64 first_slot, u64 ring_cap, hipStream_t s);
+// EVT 3.0 ingest (esvo_ts_push_evt3, include/esvo_hip.h): ONE function per rule of the format, shared by the host decoder
+// (esvo_evt3_to_events) and the device decode (kernels_ts.hip), so both produce the same bytes.
+enum { EVT3_ADDR_Y = 0x0, EVT3_ADDR_X = 0x2, EVT3_VECT_BASE_X = 0x3, EVT3_VECT_12 = 0x4, EVT3_VECT_8 = 0x5, EVT3_TIME_LOW = 0x6,
+       EVT3_TIME_HIGH = 0x8, EVT3_EXT_TRIGGER = 0xA };
+enum { EVT3_HAVE_TH = 1u, EVT3_HAVE_Y = 2u, EVT3_HAVE_BASE = 4u, EVT3_VECT_POL = 8u };  // esvo_evt3_state_t::flags
+__host__ __device__ inline u32 evt3_type(u32 w) { return (w >> 12) & 0xFu; }
+// the mask of the events a word stands for (bit i: x offset i); 1 for ADDR_X, 0 for a word that never emits
+__host__ __device__ inline u32 evt3_mask(u32 w) {
+  const u32 t = evt3_type(w);
+  return t == EVT3_ADDR_X ? 1u : t == EVT3_VECT_12 ? (w & 0xFFFu) : t == EVT3_VECT_8 ? (w & 0xFFu) : 0u;
+}
+__host__ __device__ inline u32 evt3_base_advance(u32 w) {
+  const u32 t = evt3_type(w);
+  return t == EVT3_VECT_12 ? 12u : t == EVT3_VECT_8 ? 8u : 0u;
+}
+// the emission condition of an ADDR_X / VECT word under the have-flags in front of it
+__host__ __device__ inline bool evt3_emits(u32 w, u32 flags) {
+  const u32 need = evt3_type(w) == EVT3_ADDR_X ? (EVT3_HAVE_TH | EVT3_HAVE_Y) : (EVT3_HAVE_TH | EVT3_HAVE_Y | EVT3_HAVE_BASE);
+  return (flags & need) == need;
+}
+// a TIME_HIGH payload v behind the payload prev: one more time loop?  (threshold 2048: not pinned to any third-party decoder)
+__host__ __device__ inline bool evt3_time_loop(bool have_th, u32 prev, u32 v) { return have_th && v < prev && prev - v >= 2048u; }
+__host__ __device__ inline u64 evt3_t_us(u32 loops, u32 time_high, u32 time_low) { return ((u64)loops << 24) | ((u64)time_high << 12) | (u64)time_low; }
+// (t_us + t_offset_us) * 1000 through the columns' conversion; COL_BAD_STAMP outside [0, 2^32 * 10^9)
+__host__ __device__ inline u64 evt3_stamp_ns(u64 t_us, int64_t t_offset_us) {
+  const int64_t v = (int64_t)t_us;  // below 2^56
+  return columns_stamp_ns(&v, 0, ESVO_T_US_I64, t_offset_us);
+}
+// Device decode of one packet into column staging (kernels_ts.hip).  hdr: EVT3_HDR_WORDS u32 the host reads back once.
+// tiles: evt3_tiles(n_words, words) * EVT3_TILE_WORDS u32 of scratch.  Nothing is written to the columns where the packet's
+// event count exceeds col_cap (the header is complete all the same).
+enum { EVT3_H_EVENTS, EVT3_H_DROPPED, EVT3_H_IGNORED, EVT3_H_EXT, EVT3_H_LOOPS, EVT3_H_FIRST_BAD, EVT3_H_FLAGS, EVT3_H_Y_BASE, EVT3_H_TIME, EVT3_H_LOOPS_END,
+       EVT3_HDR_WORDS = 16 };
+constexpr u32 EVT3_TILE_WORDS = 8;
+constexpr size_t EVT3_DEVICE_MAX_WORDS = (size_t)1 << 22;  // above it a packet is decoded on the host (tile sums are folded in by every tile)
+u32 evt3_tiles(size_t n_words, const void* words);
+void launch_evt3_decode(const uint16_t* words, size_t n_words, const esvo_evt3_state_t& st, int64_t t_offset_us, u32* tiles, u32* hdr,
+                        u64* stamps, uint16_t* x, uint16_t* y, uint8_t* p, size_t col_cap, hipStream_t s);
 void launch_ts_scatter(const esvo_event_t* d_ev, size_t n, u64* d_sae, int W, int H, hipStream_t s);
 // (row0, row1: the rectified rows to render -- whole tiles of TS_TILE_ROWS; a routed band handle renders its band + halo only)
 #define TS_TILE_ROWS 16

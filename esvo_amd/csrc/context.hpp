@@ -71,6 +71,10 @@ struct IngestSession {  // under mu_ring: the event rings
   // queue mode, out-of-order packets (api_ts.hip, push_unsorted): the copies of the then-newest event that take a late event's place
   // in the per-pixel queues, inserted with the next batch
   std::vector<esvo_event_t> tsq_dup[2];
+  // EVT 3.0 ingest (esvo_ts_push_evt3): the decoder state a camera's stream is in, and the totals of its successful calls -- under
+  // that camera's mu_push, not mu_ring
+  esvo_evt3_state_t evt3_state[2] = {};
+  esvo_evt3_counts_t evt3_totals[2] = {};
 };
 struct TsSession {  // under mu_ts (the right camera's flag: mapper group only)
   bool ts_valid[2] = {false, false};  // d_ts[cam] holds a render
@@ -294,6 +298,14 @@ struct esvo_context : IngestSession, TsSession, SchedSession, MapSession, CloudS
   DevBuf<uint8_t> d_col[2];
   PinBuf<u64> h_col_stamps[2];
   size_t col_cap[2] = {0, 0};
+  // staging of EVT 3.0 packets (esvo_ts_push_evt3), per camera and under its mu_push, grown on demand: host words on the device, the
+  // tile tuples of the scans, the header the decode leaves (device / pinned).  The events land in d_col.
+  DevBuf<uint16_t> d_evt3_words[2];
+  DevBuf<u32> d_evt3_tiles[2], d_evt3_hdr[2];
+  PinBuf<u32> h_evt3_hdr[2];
+  // packets of fewer words are decoded on the host: the measured crossover, ~12 800 events at 2.03 words per event
+  // (profiles/evt3_ingest_ab.txt); esvo_debug_evt3_device_min moves it for tests
+  size_t evt3_device_min = 24576;
   u64 ring_cap = 0;
   // esvo_ts_push_events_async: the newest enqueued (not awaited) copy of a camera; consumers of the ring on the front stream
   // queue behind it (ingest_fence, api_ts.hip) -- under mu_ring, with IngestSession::ingest_pending

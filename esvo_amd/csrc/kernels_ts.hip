@@ -13,6 +13,7 @@
 // T, which is exactly what getMostRecentEventBeforeT (TimeSurface.h:52-75) returns.
 #include <cstdlib>
 #include "common.hpp"
+#include "scan.hpp"
 
 namespace esvo {
 
@@ -737,6 +738,265 @@ void launch_ts_pack_columns(const uint16_t* x, const uint16_t* y, const u64* sta
   if (n == 0) return;
   hipLaunchKernelGGL(ts_pack_columns_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, x, y, stamps, p, p_type, n,
                      reinterpret_cast<uint4*>(ring), first_slot, ring_cap);
+}
+
+// ---- EVT 3.0 ingest (esvo_ts_push_evt3): 16-bit words -> the camera's column staging (stamps, x, y, p) -----------------------
+// The word state machine as scans over the packet, the previous call's state standing in for "element -1":
+//   1  evt3_lw_kernel      per tile of 2048 words the join of its words' tuples: index + 1 of the newest ADDR_Y / TIME_HIGH /
+//                          TIME_LOW / VECT_BASE_X word (operator max; 0: none) and the base_x advance behind the newest VECT_BASE_X
+//   2  evt3_count_kernel   every tile folds the tuples of the tiles in front of it in, scans its own words and so knows the
+//                          state in front of each of them: the events it emits, its time-loop flag (a TIME_HIGH word needs the
+//                          TIME_HIGH in front of it alone) -> per-tile sums, the packet's totals
+//   3  evt3_expand_kernel  the same scan once more, with the sums of the tiles in front: every emitting word writes its <= 12
+//                          events at its exclusive offset; the last tile leaves the end state
+// Three dependent launches (scan.hip's reduce -> down-sweep shape with the tile sums folded in by every tile: at most 2048 tiles,
+// EVT3_DEVICE_MAX_WORDS); no workgroup waits for another.  A thread owns 8 consecutive words: one 16-byte load where the packet
+// covers them, guarded element loads at the packet's two ends (a packet may begin at any even address: the tiles are laid over
+// the 16-byte blocks of memory, `skip` words of the first block lying in front of the packet).
+namespace {
+constexpr int EVT3_B = 256, EVT3_V = 8, EVT3_TILE = EVT3_B * EVT3_V;
+constexpr u32 EVT3_NO_WORD = 0x11000u;  // outside the packet: reads as a reserved type, bit 16 keeps it out of the counts
+
+struct Evt3Lw { u32 y, th, tl, base, inc; };
+__device__ inline Evt3Lw evt3_join(const Evt3Lw& a, const Evt3Lw& b) {  // a in front of b
+  Evt3Lw r;
+  r.y = max(a.y, b.y); r.th = max(a.th, b.th); r.tl = max(a.tl, b.tl); r.base = max(a.base, b.base);
+  r.inc = b.base ? b.inc : a.inc + b.inc;
+  return r;
+}
+__device__ inline void evt3_step(Evt3Lw& s, u32 w, u32 v) {  // word w at index v joins the state in front of it
+  const u32 t = evt3_type(w);
+  if (t == EVT3_ADDR_Y) s.y = v + 1;
+  else if (t == EVT3_TIME_HIGH) s.th = v + 1;
+  else if (t == EVT3_TIME_LOW) s.tl = v + 1;
+  else if (t == EVT3_VECT_BASE_X) { s.base = v + 1; s.inc = 0; }
+  else s.inc += evt3_base_advance(w);
+}
+__device__ inline Evt3Lw evt3_shfl_up(const Evt3Lw& a, int d) {
+  Evt3Lw r;
+  r.y = __shfl_up(a.y, d, ESVO_WAVE); r.th = __shfl_up(a.th, d, ESVO_WAVE); r.tl = __shfl_up(a.tl, d, ESVO_WAVE);
+  r.base = __shfl_up(a.base, d, ESVO_WAVE); r.inc = __shfl_up(a.inc, d, ESVO_WAVE);
+  return r;
+}
+// exclusive scan of one tuple per thread across the block, `carry` in front of thread 0; *total: carry joined with every thread's
+__device__ inline Evt3Lw evt3_block_excl(const Evt3Lw& mine, const Evt3Lw& carry, Evt3Lw* total, Evt3Lw* lds /* 4 */) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  Evt3Lw incl = mine;
+#pragma unroll
+  for (int d = 1; d < ESVO_WAVE; d <<= 1) {
+    const Evt3Lw t = evt3_shfl_up(incl, d);
+    if (lane >= d) incl = evt3_join(t, incl);
+  }
+  if (lane == 63) lds[wave] = incl;
+  __syncthreads();
+  Evt3Lw ex = carry, tot = carry;
+#pragma unroll
+  for (int w = 0; w < EVT3_B / ESVO_WAVE; ++w) {
+    const Evt3Lw s = lds[w];
+    if (w < wave) ex = evt3_join(ex, s);
+    tot = evt3_join(tot, s);
+  }
+  __syncthreads();
+  const Evt3Lw prev = evt3_shfl_up(incl, 1);
+  if (lane > 0) ex = evt3_join(ex, prev);
+  *total = tot;
+  return ex;
+}
+// N values per thread reduced across the block (sum or max), the result in every thread
+template <bool SUM, int N>
+__device__ inline void evt3_block_reduce(u32 (&v)[N], u32* lds /* 4 N */) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+  for (int k = 0; k < N; ++k) {
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) {
+      const u32 o = __shfl_xor(v[k], d, ESVO_WAVE);
+      v[k] = SUM ? v[k] + o : max(v[k], o);
+    }
+    if (lane == 0) lds[wave * N + k] = v[k];
+  }
+  __syncthreads();
+#pragma unroll
+  for (int k = 0; k < N; ++k) {
+    u32 r = lds[k];
+#pragma unroll
+    for (int w = 1; w < EVT3_B / ESVO_WAVE; ++w) r = SUM ? r + lds[w * N + k] : max(r, lds[w * N + k]);
+    v[k] = r;
+  }
+  __syncthreads();
+}
+
+struct Evt3Args {
+  const uint16_t* words;  // the packet
+  u32 n, skip;            // its words; words of the first 16-byte block in front of it
+  esvo_evt3_state_t st;   // the state in front of the packet
+  int64_t t_offset_us;
+  u32* tiles;             // per tile: [0..4] its tuple (launch 1), [5] events, [6] time loops (launch 2)
+  u32* hdr;
+};
+// the 8 words of the thread (tile-relative layout over the 16-byte blocks); first: their index in the laid-out sequence
+__device__ inline void evt3_load(const Evt3Args& a, u32 (&w)[EVT3_V], u32* first) {
+  const u32 g = blockIdx.x * (u32)EVT3_TILE + threadIdx.x * (u32)EVT3_V, end = a.skip + a.n;
+  *first = g;
+  if (g >= a.skip && g + EVT3_V <= end) {
+    const uint4 q = *reinterpret_cast<const uint4*>(a.words + (g - a.skip));  // 16-byte aligned: (address of words - 2 skip) is
+    w[0] = q.x & 0xffffu; w[1] = q.x >> 16; w[2] = q.y & 0xffffu; w[3] = q.y >> 16;
+    w[4] = q.z & 0xffffu; w[5] = q.z >> 16; w[6] = q.w & 0xffffu; w[7] = q.w >> 16;
+  } else {
+#pragma unroll
+    for (int k = 0; k < EVT3_V; ++k) w[k] = (g + k >= a.skip && g + k < end) ? (u32)a.words[g + k - a.skip] : EVT3_NO_WORD;
+  }
+}
+__device__ inline u32 evt3_word_at(const Evt3Args& a, u32 index1) { return a.words[index1 - 1 - a.skip]; }  // a writer's word
+__device__ inline u32 evt3_flags(const Evt3Args& a, const Evt3Lw& s) {
+  return a.st.flags | (s.th ? EVT3_HAVE_TH : 0u) | (s.y ? EVT3_HAVE_Y : 0u) | (s.base ? EVT3_HAVE_BASE : 0u);
+}
+__device__ inline bool evt3_loop_at(const Evt3Args& a, const Evt3Lw& s, u32 w) {  // w: a TIME_HIGH word, s: the state in front of it
+  const u32 prev = s.th ? (evt3_word_at(a, s.th) & 0xFFFu) : (u32)a.st.time_high;
+  return evt3_time_loop((evt3_flags(a, s) & EVT3_HAVE_TH) != 0, prev, w & 0xFFFu);
+}
+__device__ inline Evt3Lw evt3_own(const u32 (&w)[EVT3_V], u32 first) {
+  Evt3Lw s{0, 0, 0, 0, 0};
+#pragma unroll
+  for (int k = 0; k < EVT3_V; ++k) evt3_step(s, w[k], first + k);
+  return s;
+}
+// the join of the tiles in front of this one.  max commutes; the advance counts from the newest VECT_BASE_X word's tile on
+__device__ inline Evt3Lw evt3_tile_carry(const Evt3Args& a, u32* lds) {
+  u32 m[4] = {0, 0, 0, 0};
+  for (u32 j = threadIdx.x; j < blockIdx.x; j += EVT3_B)
+#pragma unroll
+    for (int k = 0; k < 4; ++k) m[k] = max(m[k], a.tiles[j * EVT3_TILE_WORDS + k]);
+  evt3_block_reduce<false, 4>(m, lds);
+  u32 inc[1] = {0};
+  for (u32 j = (m[3] ? (m[3] - 1) / (u32)EVT3_TILE : 0u) + threadIdx.x; j < blockIdx.x; j += EVT3_B) inc[0] += a.tiles[j * EVT3_TILE_WORDS + 4];
+  evt3_block_reduce<true, 1>(inc, lds);
+  return Evt3Lw{m[0], m[1], m[2], m[3], inc[0]};
+}
+
+__global__ void __launch_bounds__(256) evt3_lw_kernel(Evt3Args a) {
+  __shared__ Evt3Lw lds[EVT3_B / ESVO_WAVE];
+  u32 w[EVT3_V], first;
+  evt3_load(a, w, &first);
+  Evt3Lw tot;
+  (void)evt3_block_excl(evt3_own(w, first), Evt3Lw{0, 0, 0, 0, 0}, &tot, lds);
+  if (threadIdx.x == 0) {
+    u32* t = a.tiles + (size_t)blockIdx.x * EVT3_TILE_WORDS;
+    t[0] = tot.y; t[1] = tot.th; t[2] = tot.tl; t[3] = tot.base; t[4] = tot.inc;
+  }
+  if (blockIdx.x == 0 && threadIdx.x < EVT3_HDR_WORDS) a.hdr[threadIdx.x] = threadIdx.x == EVT3_H_FIRST_BAD ? 0xffffffffu : 0u;
+}
+
+__global__ void __launch_bounds__(256) evt3_count_kernel(Evt3Args a) {
+  __shared__ Evt3Lw lds[EVT3_B / ESVO_WAVE];
+  __shared__ u32 red[5 * EVT3_B / ESVO_WAVE];
+  const Evt3Lw carry = evt3_tile_carry(a, red);
+  u32 w[EVT3_V], first;
+  evt3_load(a, w, &first);
+  Evt3Lw tot;
+  Evt3Lw s = evt3_block_excl(evt3_own(w, first), carry, &tot, lds);
+  u32 c[5] = {0, 0, 0, 0, 0};  // events, time loops, dropped events, ignored words, external triggers
+#pragma unroll
+  for (int k = 0; k < EVT3_V; ++k) {
+    const u32 t = evt3_type(w[k]), m = evt3_mask(w[k]);
+    if (m) c[evt3_emits(w[k], evt3_flags(a, s)) ? 0 : 2] += __popc(m);
+    if (t == EVT3_TIME_HIGH) c[1] += evt3_loop_at(a, s, w[k]) ? 1u : 0u;
+    else if (t == EVT3_EXT_TRIGGER) c[4] += 1u;
+    else if (w[k] != EVT3_NO_WORD && (t == 0x1 || t == 0x7 || t == 0x9 || t >= 0xB)) c[3] += 1u;
+    evt3_step(s, w[k], first + k);
+  }
+  evt3_block_reduce<true, 5>(c, red);
+  if (threadIdx.x == 0) {
+    u32* t = a.tiles + (size_t)blockIdx.x * EVT3_TILE_WORDS;
+    t[5] = c[0]; t[6] = c[1];
+    if (c[0]) atomicAdd(a.hdr + EVT3_H_EVENTS, c[0]);
+    if (c[1]) atomicAdd(a.hdr + EVT3_H_LOOPS, c[1]);
+    if (c[2]) atomicAdd(a.hdr + EVT3_H_DROPPED, c[2]);
+    if (c[3]) atomicAdd(a.hdr + EVT3_H_IGNORED, c[3]);
+    if (c[4]) atomicAdd(a.hdr + EVT3_H_EXT, c[4]);
+  }
+}
+
+__global__ void __launch_bounds__(256) evt3_expand_kernel(Evt3Args a, u64* __restrict__ stamps, uint16_t* __restrict__ x,
+                                                          uint16_t* __restrict__ y, uint8_t* __restrict__ p, size_t col_cap) {
+  __shared__ Evt3Lw lds[EVT3_B / ESVO_WAVE];
+  __shared__ u32 red[4 * EVT3_B / ESVO_WAVE];
+  const Evt3Lw carry = evt3_tile_carry(a, red);
+  u32 before[2] = {0, 0};  // events and time loops of the tiles in front
+  for (u32 j = threadIdx.x; j < blockIdx.x; j += EVT3_B) { before[0] += a.tiles[j * EVT3_TILE_WORDS + 5]; before[1] += a.tiles[j * EVT3_TILE_WORDS + 6]; }
+  evt3_block_reduce<true, 2>(before, red);
+  const bool write = (size_t)a.hdr[EVT3_H_EVENTS] <= col_cap;  // (launch 2's total: complete)
+  u32 w[EVT3_V], first;
+  evt3_load(a, w, &first);
+  Evt3Lw tot;
+  const Evt3Lw s0 = evt3_block_excl(evt3_own(w, first), carry, &tot, lds);
+  u32 n_ev = 0, n_loop = 0;
+  {
+    Evt3Lw s = s0;
+#pragma unroll
+    for (int k = 0; k < EVT3_V; ++k) {
+      const u32 m = evt3_mask(w[k]);
+      if (m && evt3_emits(w[k], evt3_flags(a, s))) n_ev += __popc(m);
+      if (evt3_type(w[k]) == EVT3_TIME_HIGH) n_loop += evt3_loop_at(a, s, w[k]) ? 1u : 0u;
+      evt3_step(s, w[k], first + k);
+    }
+  }
+  u32 tile_ev, tile_loop;
+  u32 at = before[0] + block_excl_scan(n_ev, &tile_ev, red);
+  u32 loops = a.st.loops + before[1] + block_excl_scan(n_loop, &tile_loop, red);
+  Evt3Lw s = s0;
+#pragma unroll
+  for (int k = 0; k < EVT3_V; ++k) {
+    const u32 t = evt3_type(w[k]), m = evt3_mask(w[k]);
+    if (t == EVT3_TIME_HIGH) loops += evt3_loop_at(a, s, w[k]) ? 1u : 0u;
+    if (m && evt3_emits(w[k], evt3_flags(a, s))) {
+      // (the word itself writes no state: the state in front of it is its own; a TIME_HIGH counted above is no such word)
+      const u32 th = s.th ? (evt3_word_at(a, s.th) & 0xFFFu) : (u32)a.st.time_high;
+      const u32 tl = s.tl ? (evt3_word_at(a, s.tl) & 0xFFFu) : (u32)a.st.time_low;
+      const u32 yy = s.y ? (evt3_word_at(a, s.y) & 0x7FFu) : (u32)a.st.y;
+      u32 x0, pol;
+      if (t == EVT3_ADDR_X) { x0 = w[k] & 0x7FFu; pol = (w[k] >> 11) & 1u; }
+      else {
+        const u32 bw = s.base ? evt3_word_at(a, s.base) : 0u;
+        x0 = (s.base ? (bw & 0x7FFu) : (u32)a.st.base_x) + s.inc;
+        pol = s.base ? ((bw >> 11) & 1u) : ((a.st.flags & EVT3_VECT_POL) ? 1u : 0u);
+      }
+      const u64 stamp = evt3_stamp_ns(evt3_t_us(loops, th, tl), a.t_offset_us);
+      if (stamp == COL_BAD_STAMP) atomicMin(a.hdr + EVT3_H_FIRST_BAD, at);
+      if (write) {
+        u32 o = at;
+        for (u32 mm = m; mm; mm &= mm - 1u, ++o) {
+          stamps[o] = stamp; x[o] = (uint16_t)((x0 + (u32)__ffs(mm) - 1u) & 0xFFFFu); y[o] = (uint16_t)yy; p[o] = (uint8_t)pol;
+        }
+      }
+      at += __popc(m);
+    }
+    evt3_step(s, w[k], first + k);
+  }
+  if (blockIdx.x == gridDim.x - 1 && threadIdx.x == 0) {  // the end state: the state in front of the packet joined with all of it
+    const u32 bw = tot.base ? evt3_word_at(a, tot.base) : 0u;
+    u32 flags = evt3_flags(a, tot);
+    if (tot.base) flags = (flags & ~(u32)EVT3_VECT_POL) | (((bw >> 11) & 1u) ? (u32)EVT3_VECT_POL : 0u);
+    const u32 yy = tot.y ? (evt3_word_at(a, tot.y) & 0x7FFu) : (u32)a.st.y;
+    const u32 bx = ((tot.base ? (bw & 0x7FFu) : (u32)a.st.base_x) + tot.inc) & 0xFFFFu;
+    const u32 th = tot.th ? (evt3_word_at(a, tot.th) & 0xFFFu) : (u32)a.st.time_high;
+    const u32 tl = tot.tl ? (evt3_word_at(a, tot.tl) & 0xFFFu) : (u32)a.st.time_low;
+    a.hdr[EVT3_H_FLAGS] = flags; a.hdr[EVT3_H_Y_BASE] = yy | (bx << 16); a.hdr[EVT3_H_TIME] = th | (tl << 16);
+    a.hdr[EVT3_H_LOOPS_END] = a.st.loops + before[1] + tile_loop;
+  }
+}
+}  // namespace
+
+static u32 evt3_skip(const void* words) { return (u32)(((uintptr_t)words & 15u) / 2u); }
+u32 evt3_tiles(size_t n_words, const void* words) { return (u32)((n_words + evt3_skip(words) + EVT3_TILE - 1) / EVT3_TILE); }
+void launch_evt3_decode(const uint16_t* words, size_t n_words, const esvo_evt3_state_t& st, int64_t t_offset_us, u32* tiles, u32* hdr,
+                        u64* stamps, uint16_t* x, uint16_t* y, uint8_t* p, size_t col_cap, hipStream_t s) {
+  if (n_words == 0 || n_words > EVT3_DEVICE_MAX_WORDS) return;
+  const Evt3Args a{words, (u32)n_words, evt3_skip(words), st, t_offset_us, tiles, hdr};
+  const dim3 grid(evt3_tiles(n_words, words)), block(EVT3_B);
+  hipLaunchKernelGGL(evt3_lw_kernel, grid, block, 0, s, a);
+  hipLaunchKernelGGL(evt3_count_kernel, grid, block, 0, s, a);
+  hipLaunchKernelGGL(evt3_expand_kernel, grid, block, 0, s, a, stamps, x, y, p, col_cap);
 }
 
 }  // namespace esvo

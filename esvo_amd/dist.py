@@ -154,6 +154,9 @@ class ShardedEsvo:
     def ts_push_columns(self, cam, x, y, t, p=None, unit="ns", t_offset=0):
         self.dev.ts_push_columns(cam, x, y, t, p, unit, t_offset)
 
+    def ts_push_evt3(self, cam, words, t_offset_us=0):
+        return self.dev.ts_push_evt3(cam, words, t_offset_us)
+
     def ts_render(self, cam, t_ns, download=True):
         return self.dev.ts_render(cam, t_ns, download)
 
@@ -264,6 +267,9 @@ class TickShardedEsvo:
     def ts_push_columns(self, cam, x, y, t, p=None, unit="ns", t_offset=0):
         self.dev.ts_push_columns(cam, x, y, t, p, unit, t_offset)
 
+    def ts_push_evt3(self, cam, words, t_offset_us=0):
+        return self.dev.ts_push_evt3(cam, words, t_offset_us)
+
     def ts_render(self, cam, t_ns, download=True):
         if self._is_mine():  # the SAE only has to be current at this rank's own ticks
             return self.dev.ts_render(cam, t_ns, download)
@@ -370,6 +376,9 @@ class NativeTickSharded:
     def ts_push_columns(self, cam, x, y, t, p=None, unit="ns", t_offset=0):
         self.dev.ts_push_columns(cam, x, y, t, p, unit, t_offset)
 
+    def ts_push_evt3(self, cam, words, t_offset_us=0):
+        return self.dev.ts_push_evt3(cam, words, t_offset_us)
+
     def ts_render(self, cam, t_ns, download=True):
         if self.dev.comm_owns_next_tick():  # the SAE only has to be current at this rank's own ticks
             return self.dev.ts_render(cam, t_ns, download)
@@ -446,6 +455,9 @@ class NativeBandSharded:
 
     def ts_push_columns(self, cam, x, y, t, p=None, unit="ns", t_offset=0):
         self.dev.ts_push_columns(cam, x, y, t, p, unit, t_offset)
+
+    def ts_push_evt3(self, cam, words, t_offset_us=0):
+        return self.dev.ts_push_evt3(cam, words, t_offset_us)
 
     def ts_render(self, cam, t_ns, download=True):
         return self.dev.ts_render(cam, t_ns, download)

@@ -10,7 +10,7 @@ import subprocess
 
 import numpy as np
 
-from .abi import (MEM_DEVICE, MEM_HOST, P_U8, ColumnsError, EventColumnsStruct, check_t_offset, column_p_type, column_t_type,
+from .abi import (MEM_DEVICE, MEM_HOST, P_U8, ColumnsError, EventColumnsStruct, Evt3Counts, Evt3State, evt3_words, check_t_offset, column_p_type, column_t_type,
                   DEPTH_POINT_DTYPE, EM_POSE_FN, ERR_CAPACITY, ERR_INVALID_ARG, ERR_STATE, EVENT_DTYPE, MATCH_DTYPE, CalibStruct, EmSelectionStruct,
                   EmStatsStruct, GpcParamsStruct, GpcStatsStruct, LmStatsStruct, ParamsStruct, SgmStatsStruct, StatsStruct, TRACK_ITER_DTYPE, TRACK_SOLVE_MAX_ITERATIONS,
                   TrackSolveInfoStruct, TrackSolveParamsStruct)
@@ -46,6 +46,8 @@ SYMBOLS = [
     "esvo_ts_history_configure", "esvo_ts_history_list", "esvo_ts_history_get", "esvo_ts_history_put", "esvo_map_set_observation_at",
     "esvo_track_set_current_at", "esvo_ts_history_select", "esvo_ts_history_select_observation",
 ]
+# the EVT 3.0 entry points, listed apart: their names carry a digit (SYMBOLS is compared with a scan of the header for [a-z_] names)
+SYMBOLS_EVT3 = ["esvo_ts_push_evt3", "esvo_ts_evt3_state", "esvo_ts_evt3_stats", "esvo_evt3_to_events", "esvo_evt3_raw_header", "esvo_evt3_sizes"]
 
 ALL_GATHER_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p)
 
@@ -132,7 +134,7 @@ def load():
 
             def __call__(self, *a):
                 raise EsvoError("entry point missing in the ESVO_HIP_LIB build")
-        for s in SYMBOLS:
+        for s in SYMBOLS + SYMBOLS_EVT3:
             if not hasattr(lib, s):
                 setattr(lib, s, _Missing())
     vp, u64, sz, i32 = C.c_void_p, C.c_uint64, C.c_size_t, C.c_int
@@ -157,6 +159,13 @@ def load():
     lib.esvo_event_columns_to_events.argtypes = [vp, sz, vp, psz]
     lib.esvo_event_columns_sizes.argtypes = [vp]
     lib.esvo_event_columns_sizes.restype = None
+    lib.esvo_ts_push_evt3.argtypes = [vp, i32, vp, sz, i32, C.c_int64, psz]
+    lib.esvo_ts_evt3_state.argtypes = [vp, i32, vp, vp]
+    lib.esvo_ts_evt3_stats.argtypes = [vp, i32, vp]
+    lib.esvo_evt3_to_events.argtypes = [vp, vp, sz, C.c_int64, vp, sz, psz, vp]
+    lib.esvo_evt3_raw_header.argtypes = [vp, sz, psz, C.POINTER(C.c_int), C.POINTER(C.c_int)]
+    lib.esvo_evt3_sizes.argtypes = [vp]
+    lib.esvo_evt3_sizes.restype = None
     lib.esvo_ts_render.argtypes = [vp, i32, u64, vp]
     lib.esvo_ts_render_forward.argtypes = [vp, i32, u64, vp]
     lib.esvo_map_set_observation.argtypes = [vp, u64, vp, vp, vp]
@@ -257,9 +266,9 @@ def load():
     lib.esvo_track_set_current_at.argtypes = [vp, u64, i32]
     lib.esvo_ts_history_select.argtypes = [vp, sz, i32, EM_POSE_FN, vp, psz, vp]
     lib.esvo_ts_history_select_observation.argtypes = [vp, i32, EM_POSE_FN, vp, C.POINTER(C.c_uint64), vp]
-    for s in SYMBOLS:
+    for s in SYMBOLS + SYMBOLS_EVT3:
         if s not in ("esvo_default_params", "esvo_last_error", "esvo_abi_sizes", "esvo_bag_last_error", "esvo_em_sizes", "esvo_lm_sizes", "esvo_sgm_sizes",
-                     "esvo_track_sizes", "esvo_gpc_sizes", "esvo_event_columns_sizes"):
+                     "esvo_track_sizes", "esvo_gpc_sizes", "esvo_event_columns_sizes", "esvo_evt3_sizes"):
             getattr(lib, s).restype = C.c_int
     lib.esvo_abi_sizes.argtypes = [vp]
     lib.esvo_abi_sizes.restype = None
@@ -727,6 +736,13 @@ def event_columns_sizes():
     return list(out)
 
 
+def evt3_sizes():
+    """sizeof(esvo_evt3_state_t), sizeof(esvo_evt3_counts_t), 0, 0 (esvo_evt3_sizes)"""
+    out = (C.c_size_t * 4)()
+    load().esvo_evt3_sizes(out)
+    return list(out)
+
+
 def abi_sizes():
     out = (C.c_size_t * 8)()
     load().esvo_abi_sizes(out)
@@ -850,6 +866,45 @@ class Esvo:
             if torch is not None and torch.cuda.is_available():
                 torch.cuda.current_stream().synchronize()
         self._ck(self.lib.esvo_ts_push_event_columns(self.h, int(cam), C.addressof(s), keep[0]))
+
+    def ts_push_evt3(self, cam, words, t_offset_us=0):
+        """stage events from Prophesee EVT 3.0 words (esvo_ts_push_evt3): `words` is bytes / bytearray / memoryview, a numpy uint16
+        array, or uint16 / int16 device memory behind data_ptr() / is_cuda (a torch tensor) or __cuda_array_interface__, one-dimensional
+        and contiguous.  The camera's decoder state carries over from call to call (evt3_state / reset).  Device words must be
+        complete: torch's current stream is synchronised here.  Synchronous.  Returns the number of events the words emitted."""
+        if isinstance(words, (bytes, bytearray, memoryview)):
+            words = evt3_words(words)
+        addr, dt, n, on_device, _keep = _column(words, "words")
+        if dt.itemsize != 2 or dt.kind not in "iu":
+            raise ValueError(f"EVT3 words: uint16 is expected, not {dt}")
+        if on_device:
+            import sys
+            torch = sys.modules.get("torch")
+            if torch is not None and torch.cuda.is_available():
+                torch.cuda.current_stream().synchronize()
+        n_ev = C.c_size_t(0)
+        self._ck(self.lib.esvo_ts_push_evt3(self.h, int(cam), addr or None, 2 * n, MEM_DEVICE if on_device else MEM_HOST,
+                                            check_t_offset(t_offset_us), C.byref(n_ev)))
+        return int(n_ev.value)
+
+    def evt3_state(self, cam, set=None):
+        """the camera's EVT 3.0 decoder state (an abi.Evt3State); set: an Evt3State that replaces it (a reader seeks or resumes)"""
+        got = Evt3State()
+        self._ck(self.lib.esvo_ts_evt3_state(self.h, int(cam), C.addressof(got), None if set is None else C.addressof(set)))
+        return got
+
+    def evt3_stats(self, cam):
+        """running totals of the camera's ts_push_evt3 calls as a dict (esvo_ts_evt3_stats); cleared by reset"""
+        tot = Evt3Counts()
+        self._ck(self.lib.esvo_ts_evt3_stats(self.h, int(cam), C.addressof(tot)))
+        return tot.as_dict()
+
+    def debug_evt3_device_min(self, n_words):
+        """packets of fewer words are decoded on the host (esvo_debug_evt3_device_min; not part of the ABI) -> the previous bound"""
+        fn = _dbg_fn("esvo_debug_evt3_device_min", [C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)])
+        prev = C.c_size_t(0)
+        self._ck(fn(self.h, int(n_words), C.byref(prev)))
+        return int(prev.value)
 
     def debug_ts_ring(self, cam, first_abs=None, n=None):
         """(records, stamps, ring_base, ring_next) of a camera's event ring (esvo_debug_ts_ring; not part of the ABI): the records and

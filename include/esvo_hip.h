@@ -18,7 +18,7 @@
  *     concurrently, one thread per group -- the threading of the reference's nodes (esvo_Mapping.cpp:160,179-247: the
  *     MappingLoop worker thread; :669-703 and TimeSurface.cpp:403-425: eventsCallback on the ROS spinner under
  *     data_mutex_; esvo_Tracking's own loop):
- *       INGEST   esvo_ts_push_events(_async), esvo_ts_push_wait, esvo_ts_push_event_array, esvo_ts_push_event_columns, esvo_ts_push_bag (one thread per camera is fine)
+ *       INGEST   esvo_ts_push_events(_async), esvo_ts_push_wait, esvo_ts_push_event_array, esvo_ts_push_event_columns, esvo_ts_push_evt3, esvo_ts_push_bag (one thread per camera is fine)
  *       TRACKER  esvo_track_*
  *       MAPPER   every other call that takes the handle (renders, observation, ticks, stage-wise calls, outputs,
  *                parameters, esvo_comm_*, esvo_reset -- which excludes the other two groups while it runs)
@@ -341,6 +341,68 @@ int esvo_ts_push_event_columns(esvo_handle h, int cam, const esvo_event_columns_
 int esvo_event_columns_to_events(const esvo_event_columns_t* c, size_t n, esvo_event_t* out, size_t* first_bad);
 /* sizeof(esvo_event_columns_t), 0, 0, 0 */
 void esvo_event_columns_sizes(size_t out[4]);
+/* The same from Prophesee EVT 3.0 words (Metavision SDK callbacks, the data of .raw files), decoded on the device: a stateful stream
+ * of little-endian uint16 words, 2-4 bytes per event, in host or in device memory.  No esvo_event_t exists on the host for an
+ * in-order packet on an unrouted handle.  type = w >> 12:
+ *   0x0 ADDR_Y       y_cur = w & 0x7FF (bit 11 ignored); have_y
+ *   0x2 ADDR_X       one event (w & 0x7FF, y_cur, t_cur, (w >> 11) & 1)
+ *   0x3 VECT_BASE_X  base_x = w & 0x7FF; vect_pol = (w >> 11) & 1; have_base
+ *   0x4 VECT_12      for i = 0..11 ascending with bit i of w & 0xFFF set: event ((base_x + i) & 0xFFFF, y_cur, t_cur, vect_pol); then
+ *                    base_x = (base_x + 12) & 0xFFFF
+ *   0x5 VECT_8       the same with w & 0xFF, i = 0..7 and base_x + 8
+ *   0x6 TIME_LOW     time_low = w & 0xFFF
+ *   0x8 TIME_HIGH    v = w & 0xFFF; if have_th && v < time_high && time_high - v >= 2048: loops += 1.  time_high = v; have_th.
+ *                    time_low is KEPT.
+ *   0xA EXT_TRIGGER  ignored, counted in ext_triggers;   every other type: ignored, counted in ignored_words
+ *   t_us = loops << 24 | time_high << 12 | time_low;  stamp_ns = (t_us + t_offset_us) * 1000, by the conversion of ESVO_T_US_I64 columns
+ *   above: a stamp outside [0, 2^32 * 10^9) makes the call fail.  An ADDR_X word emits iff have_th && have_y, a VECT word iff
+ *   have_base as well; the events a word would have emitted otherwise are counted in dropped_events.  base_x advances on every VECT
+ *   word whether it emits or not.  x and y are not checked against the sensor: the scatter skips events outside the image, as for
+ *   every other source.  A stream starts with all state zero.
+ *   PARITY UNPINNED in two points, which follow no third-party decoder: the time-loop threshold (a TIME_HIGH step back of 2048 units
+ *   or more is a loop, a smaller one is not) and TIME_LOW being kept across a TIME_HIGH word.  Cameras send monotone TIME_HIGH words
+ *   many times per millisecond, so every sane rule agrees on their streams.  Out of scope: EVT 2.0 / 2.1, delivery of EXT_TRIGGER
+ *   events, AEDAT4.
+ *   The decoder state is kept per camera and carried from one call to the next: a stream may be cut at any word boundary.
+ *   esvo_reset clears the state and the totals of both cameras; esvo_ts_evt3_state(set) lets a reader seek or resume.
+ *   Behaviour: exactly that of esvo_ts_push_events handed the decoded records, in everything a later call can observe -- the in-order
+ *   fast path; the out-of-order merge with its late marks, stats.late_events and the queue mode's second copies; the routed band
+ *   path and its refusals; the same capacity and state errors.  ALL OR NOTHING: any failure (arguments, a bad stamp, ring capacity,
+ *   a refusal) stages nothing and leaves the decoder state and the totals as they were; for a bad stamp esvo_last_error names the
+ *   first bad EVENT index.  A packet that emits no event still advances the state and the totals and returns ESVO_OK with
+ *   *n_events = 0.  n_bytes odd, words not 2-byte aligned, more than 2^31 - 1 words: ESVO_ERR_INVALID_ARG; a decoded count above
+ *   the ring's capacity: ESVO_ERR_CAPACITY (the caller cuts the chunk).  Synchronous: words may be reused when the call returns.
+ *   memory = ESVO_MEM_DEVICE: the words must be COMPLETE before the call and plain device memory of the handle's GPU; the library
+ *   checks first and last byte with hipPointerGetAttributes before any launch or copy, as for columns.
+ *   In-order packets on an unrouted handle are decoded by three dependent launches (a last-writer / sum scan over the words, the
+ *   time-loop and event counts, the expansion into the column staging) and packed into the ring like device columns; one small
+ *   read-back (event count, end state, counts, first bad stamp) decides before anything touches the ring.  The other packets -- out
+ *   of order inside themselves, reaching back behind the newest staged stamp, any packet on a routed handle -- and packets too small
+ *   to pay for the launches are decoded on the host by esvo_evt3_to_events and take the paths of esvo_ts_push_events. */
+typedef struct esvo_evt3_state_t {
+  uint32_t flags;   /* bit0 have_th, bit1 have_y, bit2 have_base, bit3 vect_pol */
+  uint16_t y, base_x, time_high, time_low;
+  uint32_t loops;
+  uint32_t reserved;
+} esvo_evt3_state_t;
+typedef struct esvo_evt3_counts_t { uint64_t words, events, dropped_events, ignored_words, ext_triggers, time_loops; } esvo_evt3_counts_t;
+int esvo_ts_push_evt3(esvo_handle h, int cam, const void* words, size_t n_bytes, int memory /* ESVO_MEM_HOST | ESVO_MEM_DEVICE */,
+                      int64_t t_offset_us, size_t* n_events /* nullable */);
+/* get (nullable) receives the camera's decoder state, then set (nullable) replaces it */
+int esvo_ts_evt3_state(esvo_handle h, int cam, esvo_evt3_state_t* get, const esvo_evt3_state_t* set);
+/* running totals of the camera's successful esvo_ts_push_evt3 calls; cleared by esvo_reset */
+int esvo_ts_evt3_stats(esvo_handle h, int cam, esvo_evt3_counts_t* totals);
+/* The decoder alone: host only, no handle, no GPU.  out == NULL counts (cap is ignored).  *n_out (nullable) receives the number of
+ * events; *counts (nullable) what this call decoded.  More events than cap: ESVO_ERR_CAPACITY.  A bad stamp: ESVO_ERR_INVALID_ARG,
+ * *n_out is the index of the first bad event (esvo_last_error(NULL) names it).  *st is advanced only on ESVO_OK. */
+int esvo_evt3_to_events(esvo_evt3_state_t* st, const uint16_t* words, size_t n_words, int64_t t_offset_us,
+                        esvo_event_t* out, size_t cap, size_t* n_out, esvo_evt3_counts_t* counts);
+/* Prophesee .raw: ASCII header lines each starting with '%', ended by the first line that does not (or by "% end\n").
+ * *data_offset = first byte of the word data; *width / *height (nullable) from a "% geometry WxH" line, or width= / height= fields
+ * of a "% format" line, 0 if absent.  A "% evt" / "% format" line naming anything but 3.0 / EVT3: ESVO_ERR_UNSUPPORTED. */
+int esvo_evt3_raw_header(const uint8_t* file, size_t n_bytes, size_t* data_offset, int* width, int* height);
+/* sizeof(esvo_evt3_state_t), sizeof(esvo_evt3_counts_t), 0, 0 */
+void esvo_evt3_sizes(size_t out[4]);
 /* rosbag (format 2.0) ingest, SURVEY.md §8(f).2: the reading side of events_repacking_helper
  * (events_repacking_helper/src/EventMessageEditor.cpp:66-119: rosbag::Bag::open, rosbag::View over an event topic,
  * MessageInstance::instantiate<dvs_msgs::EventArray>).  Chunks (compression none / bz2 / lz4) are walked in file order;

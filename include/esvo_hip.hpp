@@ -113,6 +113,13 @@ class TimeSurface {
   void eventColumns(const esvo_event_columns_t& columns, size_t n) {
     ctx_->check(esvo_ts_push_event_columns(ctx_->handle(), cam_, &columns, n), "esvo_ts_push_event_columns");
   }
+  // the same from Prophesee EVT 3.0 words in host or device memory (a Metavision raw-data callback, a .raw file's data): esvo_ts_push_evt3.
+  // The camera's decoder state carries over from call to call; returns the number of events the words emitted.
+  size_t evt3Words(const void* words, size_t n_bytes, int memory = ESVO_MEM_HOST, int64_t t_offset_us = 0) {
+    size_t n_events = 0;
+    ctx_->check(esvo_ts_push_evt3(ctx_->handle(), cam_, words, n_bytes, memory, t_offset_us, &n_events), "esvo_ts_push_evt3");
+    return n_events;
+  }
   // TimeSurface::createTimeSurfaceAtTime: the rectified mono8 Time Surface at the sync time
   void createTimeSurfaceAtTime(uint64_t external_sync_time_ns, uint8_t* out_mono8 /*nullable*/) {
     ctx_->check(esvo_ts_render(ctx_->handle(), cam_, external_sync_time_ns, out_mono8), "esvo_ts_render");
