@@ -2,9 +2,10 @@
 //
 // Replaces DepthProblemSolver::solve_multiple_problems / solve_single_problem_numerical
 // (esvo_core/src/core/DepthProblemSolver.cpp:80-214), DepthProblem::operator() / warping /
-// patchInterpolation (esvo_core/src/core/DepthProblem.cpp:34-262) and the third-party
+// patchInterpolation (esvo_core/src/core/DepthProblem.cpp:34-262) here; the third-party
 // Eigen::LevenbergMarquardt<NumericalDiff<...>> for one unknown (MINPACK lmdif logic,
-// SURVEY.md Appendix B.1), plus DepthProblemSolver::pointCulling (:216-244).
+// SURVEY.md Appendix B.1) and the point and culling epilogue (:190-244) in lm_common.hpp,
+// shared with kernels_lm_any.hip.
 //
 // Work decomposition: the 15x7 patch needs a 16x8 source block per image, so a match maps
 // onto a 16-lane group: lane c loads column c of the block (8 rows, both images), takes
@@ -247,7 +248,6 @@ __device__ inline void interp_column(__amdgpu_buffer_rsrc_t img, int W, const Pa
 // failure fill and on the shortcut), ge->shortcut, and ge->over = the loop had completed ge->limit passes when its test asked
 // for another -- it ends there, the caller abandons the match.  All three are uniform over the match's lanes, like the loop.
 // (ge is the one element of the pack GE, which is empty in the unguarded instantiations: their signature is what it was.)
-struct LmGuardEval { int limit, passes; bool shortcut, over; };
 template <bool WIDE, bool L2, bool COUNT = false, bool BAND = false, bool GUARD = false, typename... GE>
 __device__ bool lm_eval(const DevParams& p, const LmProblem& pr, LmCache<WIDE>& cc, double x, double* fv, int* n_iter = nullptr,
                         bool* viol = nullptr, GE*... ge_pack) {
@@ -542,10 +542,10 @@ __device__ inline u32 lm_split_stripe(u32 slot) { return (slot >> 2) & (LM_SPLIT
 // would have run beside a match that converged at that point.  Behind the loop the wave adds its matches' counts up and its
 // first lane leaves them in the launch's striped block.  Single launches only: the pair layout's second wave evaluates points
 // the solver may never ask for, and the split launch's first stage is not a whole solve.
-template <bool GUARD> struct LmGuardCounts {};
-template <> struct LmGuardCounts<true> { int evals = 0, passes = 0, max_eval = 0, shortcut = 0; bool abandoned = false; };
+// (Waves per SIMD: the plain l2 instance has no scale loop and fits three -- 166 VGPRs, nothing spilled -- and is told so: asked
+// for two it settles at 167 or at 172 registers, a wave less, with how the code around the evaluator happens to be scheduled.)
 template <bool WIDE, bool L2 = false, int STAGE = 0, bool PAIR = false, bool BAND = false, bool GUARD = false>
-__global__ void __launch_bounds__(PAIR ? 128 : LM_BLOCK, WIDE ? LM_WIDE_WAVES : LM_WAVES) lm_refine_kernel(LmArgs a, DevParams p, u32* n_solved, LmSplitArg<GUARD> sp) {
+__global__ void __launch_bounds__(PAIR ? 128 : LM_BLOCK, WIDE ? LM_WIDE_WAVES : (L2 && !BAND) ? 3 : LM_WAVES) lm_refine_kernel(LmArgs a, DevParams p, u32* n_solved, LmSplitArg<GUARD> sp) {
   static_assert(!PAIR || (WIDE && !L2 && STAGE == 0), "the pair layout is a variant of the wide one");
   static_assert(!GUARD || (STAGE == 0 && !PAIR && !BAND && !L2 && LM_BLOCK == 64), "the guard: single launches of the Student-t model on a plain handle, one wave per workgroup");
   static_assert(!BAND || (STAGE == 0 && !PAIR), "routed band launches are single launches of the narrow or the wide layout");
@@ -625,35 +625,17 @@ __global__ void __launch_bounds__(PAIR ? 128 : LM_BLOCK, WIDE ? LM_WIDE_WAVES : 
   pr.vy0 = a.vy0; pr.vy1 = a.vy1;
   bool viol = false;
   DEV_LM_SET_SLOT(pr, active ? s : 0xffffffffu);
-  {  // DepthProblem::setProblem, DepthProblem.cpp:17-32
-    double Tlw[16], Tlv[16];
-    rigid_inverse(a.T_world_obs, Tlw);
-    mat4_mul(Tlw, a.pose_T + (size_t)m.pose_idx * 16, Tlv);
-#pragma unroll
-    for (int i = 0; i < 12; ++i) pr.T[i] = Tlv[i];
-  }
-  const int N = LM_ROWS * LM_COLS;
-  const double ftol = 1e-6, xtol = 1e-6, gtol = 0., factor = 100.;
-  const double eps = 2.220446049250313e-16;
-  const double sqrt_eps = 1.4901161193847656e-08;  // sqrt(DBL_EPSILON), exact
+  lm_set_problem(a, m, pr.T);
   const int maxfev = p.lm_maxfev;
 
-  // The solver is written as a state machine around ONE call site of the residual evaluator
-  // (phase 0: F(x0) of minimizeInit; phase 1: F(x+h) of NumericalDiff; phase 2: F(x+p) of the
-  // trust-region trial).  Arithmetic and control flow are those of Eigen's
-  // minimizeInit/minimizeOneStep driven by the loop of DepthProblemSolver.cpp:161-188; a single
+  // The solver (lm_common.hpp: LmSolver) is a state machine around ONE call site of the residual evaluator; a single
   // inlined evaluator keeps the kernel ~3x smaller (I-cache, register pressure).
-  double x = m.inv_depth;
   double fvec[RL], out[RL];
   LmCache<WIDE> cc;
   cc.clear();
-  double fnorm = 0., par = 0., diag = 0., xnorm = 0., delta = 0., r = 0., qtf = 0., gnorm = 0.;
-  double h = 0., xnew = 0., wa1 = 0., pnorm = 0.;
-  int nfev = 1, iter = 1, iteration = 0, optState = 0;
-  int phase = 0;
-  bool need_step = false;
+  LmSolver S;
+  lm_start(S, m.inv_depth);
   bool fvec_tight = false;  // fvec comes from a tight evaluation (lm_eval's return value)
-  double xe = x;
   // pair layout: the point wave 1 evaluated in the last exchange, which LDS buffer holds it, whether it is still there
   double xs = 0.;
   int xpar = 0;
@@ -661,7 +643,7 @@ __global__ void __launch_bounds__(PAIR ? 128 : LM_BLOCK, WIDE ? LM_WIDE_WAVES : 
   LmGuardCounts<GUARD> gc;
   if constexpr (STAGE == 1) {  // minimizeInit only: F(x0), |F(x0)|, what the evaluation cost
     int n_it = 0;
-    const bool tgt = lm_eval<WIDE, L2, true>(p, pr, cc, x, out, &n_it);
+    const bool tgt = lm_eval<WIDE, L2, true>(p, pr, cc, S.x, out, &n_it);
     const double f0 = sqrt(patch_dot<WIDE>(out, out, rg));
     if (active) {
       double* dst = sp.fvec0 + (size_t)s * (LM_ROWS * 16) + c;
@@ -676,51 +658,36 @@ __global__ void __launch_bounds__(PAIR ? 128 : LM_BLOCK, WIDE ? LM_WIDE_WAVES : 
     }
     return;
   }
-  if constexpr (STAGE == 2) {  // resume behind minimizeInit (the `phase == 0` branch and the step to phase 1 below)
+  if constexpr (STAGE == 2) {  // resume behind minimizeInit: what phase 0 and the step to phase 1 do below
+    double fnorm0 = 0.;
     if (active) {
       const double* src = sp.fvec0 + (size_t)s * (LM_ROWS * 16) + c;
 #pragma unroll
       for (int y = 0; y < RL; ++y) fvec[y] = src[y * 16];
-      fnorm = sp.fnorm0[s];
+      fnorm0 = sp.fnorm0[s];
       fvec_tight = (sp.meta[s] & 0x100u) != 0;
     } else {
 #pragma unroll
       for (int y = 0; y < RL; ++y) fvec[y] = 0.0;
     }
-    par = 0.;
-    iter = 1;
-    phase = 1;
-    h = sqrt_eps * fabs(x);
-    if (h == 0.) h = sqrt_eps;
-    xe = x + h;
+    lm_after_init(S, fnorm0);
+    lm_next(S, false, -1, p.lm_max_iter);
   }
   DEV_LM_JAC_DECL
   while (true) {
-    if (need_step) {  // determine the LM parameter and the trial point (minimizeOneStep, inner loop head)
-      const double pstep = lm_lmpar2(r, diag, qtf, delta, par);
-      wa1 = -pstep;
-      xnew = x + wa1;
-      pnorm = fabs(diag * wa1);
-      if (iter == 1) delta = (pnorm < delta) ? pnorm : delta;
-      xe = xnew;
-      need_step = false;
-    }
+    lm_trial_point(S);  // determine the LM parameter and the trial point
     bool out_tight;
     if constexpr (PAIR) {
-      const bool reuse = phase == 1 && have_spec && __double_as_longlong(xe) == __double_as_longlong(xs);
+      const bool reuse = S.phase == 1 && have_spec && __double_as_longlong(S.xe) == __double_as_longlong(xs);
       if (reuse) {  // F(x + h): wave 1 evaluated it beside the trial point
 #pragma unroll
         for (int y = 0; y < RL; ++y) out[y] = lds_pair[xpar][1][y][ln];
         out_tight = lds_pair_tight[xpar][1] != 0;
         have_spec = false;
       } else {
-        const bool side = phase != 1;  // beside F(xe): the difference point that follows if the driver moves to xe
-        if (side) {
-          double hs = sqrt_eps * fabs(xe);
-          if (hs == 0.) hs = sqrt_eps;
-          xs = xe + hs;
-        }
-        const bool t_mine = lm_eval<WIDE, L2>(p, pr, cc, (side && wv) ? xs : xe, out);
+        const bool side = S.phase != 1;  // beside F(xe): the difference point that follows if the driver moves to xe
+        if (side) xs = S.xe + lm_diff_step(S.xe);
+        const bool t_mine = lm_eval<WIDE, L2>(p, pr, cc, (side && wv) ? xs : S.xe, out);
         out_tight = t_mine;
         if (side) {
           xpar ^= 1;
@@ -737,126 +704,48 @@ __global__ void __launch_bounds__(PAIR ? 128 : LM_BLOCK, WIDE ? LM_WIDE_WAVES : 
     } else if constexpr (GUARD) {
       LmGuardEval ge;
       ge.limit = sp.guard.limit;
-      out_tight = lm_eval<WIDE, L2, false, BAND, true>(p, pr, cc, xe, out, nullptr, &viol, &ge);
-      ++gc.evals;
-      gc.passes += ge.passes;
-      gc.max_eval = max(gc.max_eval, ge.passes);
-      gc.shortcut += ge.shortcut ? 1 : 0;
+      out_tight = lm_eval<WIDE, L2, false, BAND, true>(p, pr, cc, S.xe, out, nullptr, &viol, &ge);
+      gc.add(ge);
       if (ge.over) { gc.abandoned = true; break; }
     } else {
-      out_tight = lm_eval<WIDE, L2, false, BAND>(p, pr, cc, xe, out, nullptr, &viol);
+      out_tight = lm_eval<WIDE, L2, false, BAND>(p, pr, cc, S.xe, out, nullptr, &viol);
     }
     int status = -1;
-    bool outer_tail = false;
-    if (phase == 0) {  // minimizeInit
+    bool returned = false;  // minimizeOneStep returned (status, or Running)
+    if (S.phase == 0) {  // minimizeInit
       fvec_tight = out_tight;
 #pragma unroll
       for (int y = 0; y < RL; ++y) fvec[y] = out[y];
-      fnorm = sqrt(patch_dot<WIDE>(fvec, fvec, rg));
-      par = 0.;
-      iter = 1;
-    } else if (phase == 1) {
-      DEV_LM_JAC_PASS(pr, active, x);
-      // NumericalDiff<Forward>::df: the reference evaluates F(x) again (val1) and F(x + h); F is a
-      // pure function and fvec already holds F(x) at the current x, so val1 == fvec bit for bit and
-      // only F(x + h) is computed.  nfev still advances by 2 (it drives the maxfev test).
+      lm_after_init(S, sqrt(patch_dot<WIDE>(fvec, fvec, rg)));
+    } else if (S.phase == 1) {  // forward difference: J = (F(x + h) - F(x)) / h
+      DEV_LM_JAC_PASS(pr, active, S.x);
       double fjac[RL];
       {
         // Both evaluations tight: every entry is 0 or has 2^-150 <= |f| < 2^11, so a non-zero difference has
         // 2^-202 <= |d| < 2^12; with h inside the window too the seven quotients share one refined reciprocal (fdiv.hpp:
         // bit for bit the IEEE quotient), 3 instead of 13 instructions each.
-        const Recip rh = make_recip(h);
+        const Recip rh = make_recip(S.h);
         if (out_tight && fvec_tight && rh.fast) {
 #pragma unroll
           for (int y = 0; y < RL; ++y) fjac[y] = div_fast(out[y] - fvec[y], rh);
         } else {
 #pragma unroll
-          for (int y = 0; y < RL; ++y) fjac[y] = (out[y] - fvec[y]) / h;
+          for (int y = 0; y < RL; ++y) fjac[y] = (out[y] - fvec[y]) / S.h;
         }
       }
-      nfev += 2;
       const double wa2n = sqrt(patch_dot<WIDE>(fjac, fjac, rg));
       const double jtf = patch_dot<WIDE>(fjac, fvec, rg);
-      r = wa2n;
       const double fvec0 = WIDE ? bcast_f64(fvec[0], 0) : __shfl(fvec[0], 0, 16);  // element (0, 0) of the patch
-      qtf = (r != 0.) ? jtf / r : fvec0;
-      if (iter == 1) {
-        diag = (wa2n == 0.) ? 1. : wa2n;
-        xnorm = fabs(diag * x);
-        delta = factor * xnorm;
-        if (delta == 0.) delta = factor;
-      }
-      gnorm = 0.;
-      if (fnorm != 0.)
-        if (wa2n != 0.) { const double g = fabs(r * (qtf / fnorm) / wa2n); gnorm = (gnorm < g) ? g : gnorm; }
-      if (gnorm <= gtol) {
-        status = 4;
-        outer_tail = true;
-      } else {
-        diag = (diag < wa2n) ? wa2n : diag;
-        need_step = true;
-        phase = 2;
-      }
+      status = lm_after_diff(S, wa2n, jtf, fvec0);
+      returned = status >= 0;
     } else {  // phase 2: trust-region trial at xnew
-      ++nfev;
-      const double fnorm1 = sqrt(patch_dot<WIDE>(out, out, rg));
-      double actred = -1.;
-      if (0.1 * fnorm1 < fnorm) actred = 1. - (fnorm1 / fnorm) * (fnorm1 / fnorm);
-      const double wa3 = r * wa1;
-      const double t1 = fabs(wa3) / fnorm, temp1 = t1 * t1;
-      const double t2 = sqrt(par) * pnorm / fnorm, temp2 = t2 * t2;
-      const double prered = temp1 + temp2 / 0.5;
-      const double dirder = -(temp1 + temp2);
-      double ratio = 0.;
-      if (prered != 0.) ratio = actred / prered;
-      if (ratio <= 0.25) {
-        double temp = 0.5;
-        if (actred >= 0.) temp = 0.5;
-        if (actred < 0.) temp = 0.5 * dirder / (dirder + 0.5 * actred);
-        if (0.1 * fnorm1 >= fnorm || temp < 0.1) temp = 0.1;
-        const double pn = pnorm / 0.1;
-        delta = temp * ((pn < delta) ? pn : delta);
-        par /= temp;
-      } else if (!(par != 0. && ratio < 0.75)) {
-        delta = pnorm / 0.5;
-        par = 0.5 * par;
-      }
-      if (ratio >= 1e-4) {
-        x = xnew;
+      returned = lm_after_trial(S, sqrt(patch_dot<WIDE>(out, out, rg)), maxfev, status, [&]() {
         fvec_tight = out_tight;
 #pragma unroll
         for (int y = 0; y < RL; ++y) fvec[y] = out[y];
-        xnorm = fabs(diag * x);
-        fnorm = fnorm1;
-        ++iter;
-      }
-      if (fabs(actred) <= ftol && prered <= ftol && 0.5 * ratio <= 1. && delta <= xtol * xnorm) status = 3;
-      else if (fabs(actred) <= ftol && prered <= ftol && 0.5 * ratio <= 1.) status = 1;
-      else if (delta <= xtol * xnorm) status = 2;
-      else if (nfev >= maxfev) status = 5;
-      else if (fabs(actred) <= eps && prered <= eps && 0.5 * ratio <= 1.) status = 6;
-      else if (delta <= eps * xnorm) status = 7;
-      else if (gnorm <= eps) status = 8;
-      if (status >= 0 || !(ratio < 1e-4)) outer_tail = true;  // minimizeOneStep returns (status or Running)
-      else need_step = true;                                   // do { ... } while (ratio < 1e-4)
+      });
     }
-    if (phase == 0) {
-      phase = 1;
-    } else if (outer_tail) {
-      // ---- the reference's outer loop, DepthProblemSolver.cpp:161-188 ----
-      iteration++;
-      if (iteration >= p.lm_max_iter) break;
-      if (status == 2 || status == 3) {
-        if (optState == 0) optState++;
-        else break;
-      }
-      phase = 1;
-    }
-    if (phase == 1) {  // next evaluation: F(x + h) for the forward difference
-      h = sqrt_eps * fabs(x);
-      if (h == 0.) h = sqrt_eps;
-      xe = x + h;
-    }
+    if (lm_next(S, returned, status, p.lm_max_iter)) break;  // the reference's outer loop; the next difference point
   }
 
   if (probe) {
@@ -893,43 +782,7 @@ __global__ void __launch_bounds__(PAIR ? 128 : LM_BLOCK, WIDE ? LM_WIDE_WAVES : 
   if (!active || !lead) return;
   if constexpr (GUARD) { if (gc.abandoned) { a.out_flags[s] = 0u; return; } }  // no point, not solved
   if constexpr (BAND) { if (viol) atomicAdd(a.halo_viol, 1u); }
-  const bool solved = !(x <= 0.001);  // DepthProblemSolver.cpp:192
-  bool keep = solved;
-  if (solved) {
-    atomicAdd(n_solved, 1u);
-    const double invJtJ = (r != 0.) ? (1. / r) * (1. / r) : 0.;  // internal::covar, n == 1
-    double variance;
-    if constexpr (L2) {  // :200-206: cov = |f|^2 / (values - inputs) * (J^T J)^-1; DepthPoint::update on a new point bounds it
-      // (upstream takes lm.fvec.blueNorm() here and lm.fnorm -- stableNorm -- for the residual below: two Eigen algorithms for
-      // the same |f| that may round differently in the last place.  Both are third-party code absent from the reference tree;
-      // this path and the oracle use the solver's one canonical |f| for both.  Stated deviation, DESIGN.md "Deviations".)
-      variance = fnorm * fnorm / (double)(N - 1) * invJtJ;
-      if (variance < 1e-6) variance = 1e-6;
-    } else {
-      variance = p.td_stdvar2 * invJtJ;                          // :210
-    }
-    const double residual = fnorm * fnorm;                       // :212
-    DevPoint o;
-    o.row = (u32)(size_t)floor(pr.cy);  // :116
-    o.col = (u32)(size_t)floor(pr.cx);
-    o.x[0] = pr.cx;
-    o.x[1] = pr.cy;
-    cam2World(p.camL, pr.cx, pr.cy, x, o.p_cam);                 // :119
-    DEV_PERTURB_POINT(o, s);  // (empty in the product: dev_hooks.hpp)
-    o.inv_depth = x;                                             // update_studentT, new-point branch
-
-    o.scale2 = L2 ? 0.0 : variance * (p.td_nu - 2) / p.td_nu;    // :125 (l2: the Gaussian update leaves scaleSquared_ / nu_
-    o.nu = L2 ? 0.0 : p.td_nu;                                   //  as constructed -- zero here and in the oracle, Appendix A-8)
-    o.variance = variance;
-    o.residual = residual;
-    o.age = 0;
-    o.pose_idx = m.pose_idx;
-    o.seq = j;
-    if (a.cull)  // pointCulling, :230-234
-      keep = variance <= p.var_thr && residual <= p.cost_thr && x > -1e-6 && x >= p.invdepth_min && x <= p.invdepth_max;
-    if (keep) a.out_slots[s] = o;
-  }
-  a.out_flags[s] = keep ? 1u : 0u;
+  lm_store_point<L2>(a, p, n_solved, m, s, j, S.x, S.r, S.fnorm, LM_ROWS * LM_COLS);
 }
 
 // counting sort of the slots by the cost of F(x0), most expensive first: offsets from the (complete) histogram, computed

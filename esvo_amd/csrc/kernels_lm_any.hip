@@ -2,12 +2,11 @@
 // the reference, code default 25 x 25 -- esvo_core/src/esvo_Mapping.cpp:38-39,93-94,127; every shipped configuration sets
 // 15 x 7, which kernels_lm.hip serves with its register layouts).
 //
-// Same algorithm, same order of every floating-point operation as kernels_lm.hip and the oracle's canonical mode
-// (DepthProblem::operator() / warping / patchInterpolation, DepthProblem.cpp:34-262; Eigen's LevenbergMarquardt over
-// NumericalDiff for one unknown, DepthProblemSolver.cpp:138-214; pointCulling :216-244) -- written for generality, not for
-// speed: ONE wave per match, lane = patch column (wx <= 64), the rows in a loop, the three per-element arrays of the solver
-// (raw residuals, F(x), the evaluation in flight) in LDS as [row][64 lanes] (no bank conflicts), plain IEEE division and
-// square root everywhere.  Patch sums reduce in the canonical order: per column the sequential sum over the rows top to
+// The residual evaluator (DepthProblem::operator() / warping / patchInterpolation, DepthProblem.cpp:34-262) in the order of
+// floating-point operations of kernels_lm.hip and the oracle's canonical mode, under the solver and the point epilogue both
+// kernels take from lm_common.hpp -- written for generality, not for speed: ONE wave per match, lane = patch column
+// (wx <= 64), the rows in a loop, the three per-element arrays of the solver (raw residuals, F(x), the evaluation in flight)
+// in LDS as [row][64 lanes] (no bank conflicts), plain IEEE division and square root everywhere.  Patch sums reduce in the canonical order: per column the sequential sum over the rows top to
 // bottom, then the xor butterfly over the columns padded with zeros to P = the next power of two (oracle: reduce_patch).
 #include "common.hpp"
 #include "lm_common.hpp"
@@ -63,11 +62,9 @@ __device__ inline AnyGeom any_geom(const DevParams& p, int wx, int wy, double lx
 
 // DepthProblem::operator(): fv[y][c] = residual of patch element (y, c) (0 in the padding lanes); rr = scratch for the raw
 // residuals.  L2: LSnorm "l2" (the plain temporal residual, 255 on failure).
-// GUARD (the scale-loop guard, common.hpp: LmGuard; wave-uniform): ge.passes = completed updates s2 = sum / N with a non-zero
-// sum, ge.shortcut, ge.over = the loop had completed ge.limit passes when its test asked for another (it ends there).
-struct AnyGuardEval { int limit, passes; bool shortcut, over; };
+// GUARD (the scale-loop guard; wave-uniform): what the evaluation reports in *ge, lm_common.hpp: LmGuardEval.
 template <bool L2, bool GUARD = false>
-__device__ void any_eval(const DevParams& p, const AnyProblem& pr, double x, double* fv, double* rr, bool& viol, AnyGuardEval* ge = nullptr) {
+__device__ void any_eval(const DevParams& p, const AnyProblem& pr, double x, double* fv, double* rr, bool& viol, LmGuardEval* ge = nullptr) {
   if constexpr (GUARD) { ge->passes = 0; ge->shortcut = false; ge->over = false; }
   const int wx = pr.wx, wy = pr.wy, c = pr.c, P = pr.P;
   const bool el = c < wx;
@@ -196,196 +193,62 @@ __global__ void __launch_bounds__(64) lm_refine_any_kernel(LmArgs a, DevParams p
   pr.wx = wx; pr.wy = wy; pr.P = P; pr.c = c;
   pr.vy0 = a.halo_viol ? a.vy0 : 0; pr.vy1 = a.halo_viol ? a.vy1 : p.H;
   bool viol = false;
-  {  // DepthProblem::setProblem, DepthProblem.cpp:17-32
-    double Tlw[16], Tlv[16];
-    rigid_inverse(a.T_world_obs, Tlw);
-    mat4_mul(Tlw, a.pose_T + (size_t)m.pose_idx * 16, Tlv);
-#pragma unroll
-    for (int i = 0; i < 12; ++i) pr.T[i] = Tlv[i];
-  }
-  const int N = wx * wy;
-  const double ftol = 1e-6, xtol = 1e-6, gtol = 0., factor = 100.;
-  const double eps = 2.220446049250313e-16;
-  const double sqrt_eps = 1.4901161193847656e-08;  // sqrt(DBL_EPSILON), exact
+  lm_set_problem(a, m, pr.T);
   const int maxfev = p.lm_maxfev;
 
-  // Eigen's minimizeInit / minimizeOneStep driven by the loop of DepthProblemSolver.cpp:161-188, as a state machine around one
-  // call site of the evaluator (phase 0: F(x0); 1: F(x + h) of NumericalDiff; 2: F(x + p) of the trust-region trial) -- the
-  // same control flow and arithmetic as kernels_lm.hip's driver.
-  double x = m.inv_depth;
-  double fnorm = 0., par = 0., diag = 0., xnorm = 0., delta = 0., r = 0., qtf = 0., gnorm = 0.;
-  double h = 0., xnew = 0., wa1 = 0., pnorm = 0.;
-  int nfev = 1, iter = 1, iteration = 0, optState = 0;
-  int phase = 0;
-  bool need_step = false;
-  double xe = x;
-  int g_evals = 0, g_passes = 0, g_max_eval = 0, g_shortcut = 0;  // GUARD
-  bool g_abandoned = false;
+  // the solver (lm_common.hpp: LmSolver) around one call site of the evaluator
+  LmSolver S;
+  lm_start(S, m.inv_depth);
+  LmGuardCounts<GUARD> gc;
   while (true) {
-    if (need_step) {
-      const double pstep = lm_lmpar2(r, diag, qtf, delta, par);
-      wa1 = -pstep;
-      xnew = x + wa1;
-      pnorm = fabs(diag * wa1);
-      if (iter == 1) delta = (pnorm < delta) ? pnorm : delta;
-      xe = xnew;
-      need_step = false;
-    }
+    lm_trial_point(S);
     if constexpr (GUARD) {
-      AnyGuardEval ge;
+      LmGuardEval ge;
       ge.limit = g.limit;
-      any_eval<L2, true>(p, pr, xe, out, rr, viol, &ge);
-      ++g_evals;
-      g_passes += ge.passes;
-      g_max_eval = max(g_max_eval, ge.passes);
-      g_shortcut += ge.shortcut ? 1 : 0;
-      if (ge.over) { g_abandoned = true; break; }
+      any_eval<L2, true>(p, pr, S.xe, out, rr, viol, &ge);
+      gc.add(ge);
+      if (ge.over) { gc.abandoned = true; break; }
     } else {
-      any_eval<L2>(p, pr, xe, out, rr, viol);
+      any_eval<L2>(p, pr, S.xe, out, rr, viol);
     }
     __syncthreads();  // one wave per workgroup: orders the LDS writes of all lanes before the cross-lane read of element (0, 0)
     int status = -1;
-    bool outer_tail = false;
-    if (phase == 0) {  // minimizeInit
+    bool returned = false;
+    if (S.phase == 0) {  // minimizeInit
       double* t = fvec; fvec = out; out = t;
-      fnorm = sqrt(any_dot(fvec, fvec, wy, c, P));
-      par = 0.;
-      iter = 1;
-    } else if (phase == 1) {  // NumericalDiff<Forward>::df: val1 == fvec (F is pure); nfev advances by 2
+      lm_after_init(S, sqrt(any_dot(fvec, fvec, wy, c, P)));
+    } else if (S.phase == 1) {  // forward difference: J = (F(x + h) - F(x)) / h, |J|^2 and J^T F(x) in one pass over the rows
       double sjj, sjf;
       {
-        const double f0 = (out[c] - fvec[c]) / h;
+        const double f0 = (out[c] - fvec[c]) / S.h;
         sjj = f0 * f0;
         sjf = f0 * fvec[c];
         for (int y = 1; y < wy; ++y) {
-          const double fj = (out[y * 64 + c] - fvec[y * 64 + c]) / h;
+          const double fj = (out[y * 64 + c] - fvec[y * 64 + c]) / S.h;
           sjj = sjj + fj * fj;
           sjf = sjf + fj * fvec[y * 64 + c];
         }
       }
-      nfev += 2;
       const double wa2n = sqrt(any_butterfly(sjj, P));
       const double jtf = any_butterfly(sjf, P);
-      r = wa2n;
-      const double fvec0 = fvec[0];  // element (0, 0) of the patch
-      qtf = (r != 0.) ? jtf / r : fvec0;
-      if (iter == 1) {
-        diag = (wa2n == 0.) ? 1. : wa2n;
-        xnorm = fabs(diag * x);
-        delta = factor * xnorm;
-        if (delta == 0.) delta = factor;
-      }
-      gnorm = 0.;
-      if (fnorm != 0.)
-        if (wa2n != 0.) { const double g = fabs(r * (qtf / fnorm) / wa2n); gnorm = (gnorm < g) ? g : gnorm; }
-      if (gnorm <= gtol) {
-        status = 4;
-        outer_tail = true;
-      } else {
-        diag = (diag < wa2n) ? wa2n : diag;
-        need_step = true;
-        phase = 2;
-      }
+      status = lm_after_diff(S, wa2n, jtf, fvec[0]);  // fvec[0]: element (0, 0) of the patch
+      returned = status >= 0;
     } else {  // phase 2: trust-region trial at xnew
-      ++nfev;
-      const double fnorm1 = sqrt(any_dot(out, out, wy, c, P));
-      double actred = -1.;
-      if (0.1 * fnorm1 < fnorm) actred = 1. - (fnorm1 / fnorm) * (fnorm1 / fnorm);
-      const double wa3 = r * wa1;
-      const double t1 = fabs(wa3) / fnorm, temp1 = t1 * t1;
-      const double t2 = sqrt(par) * pnorm / fnorm, temp2 = t2 * t2;
-      const double prered = temp1 + temp2 / 0.5;
-      const double dirder = -(temp1 + temp2);
-      double ratio = 0.;
-      if (prered != 0.) ratio = actred / prered;
-      if (ratio <= 0.25) {
-        double temp = 0.5;
-        if (actred >= 0.) temp = 0.5;
-        if (actred < 0.) temp = 0.5 * dirder / (dirder + 0.5 * actred);
-        if (0.1 * fnorm1 >= fnorm || temp < 0.1) temp = 0.1;
-        const double pn = pnorm / 0.1;
-        delta = temp * ((pn < delta) ? pn : delta);
-        par /= temp;
-      } else if (!(par != 0. && ratio < 0.75)) {
-        delta = pnorm / 0.5;
-        par = 0.5 * par;
-      }
-      if (ratio >= 1e-4) {
-        x = xnew;
-        double* t = fvec; fvec = out; out = t;
-        xnorm = fabs(diag * x);
-        fnorm = fnorm1;
-        ++iter;
-      }
-      if (fabs(actred) <= ftol && prered <= ftol && 0.5 * ratio <= 1. && delta <= xtol * xnorm) status = 3;
-      else if (fabs(actred) <= ftol && prered <= ftol && 0.5 * ratio <= 1.) status = 1;
-      else if (delta <= xtol * xnorm) status = 2;
-      else if (nfev >= maxfev) status = 5;
-      else if (fabs(actred) <= eps && prered <= eps && 0.5 * ratio <= 1.) status = 6;
-      else if (delta <= eps * xnorm) status = 7;
-      else if (gnorm <= eps) status = 8;
-      if (status >= 0 || !(ratio < 1e-4)) outer_tail = true;
-      else need_step = true;
+      returned = lm_after_trial(S, sqrt(any_dot(out, out, wy, c, P)), maxfev, status, [&]() { double* t = fvec; fvec = out; out = t; });
     }
-    if (phase == 0) {
-      phase = 1;
-    } else if (outer_tail) {  // the reference's outer loop, DepthProblemSolver.cpp:161-188
-      iteration++;
-      if (iteration >= p.lm_max_iter) break;
-      if (status == 2 || status == 3) {
-        if (optState == 0) optState++;
-        else break;
-      }
-      phase = 1;
-    }
-    if (phase == 1) {
-      h = sqrt_eps * fabs(x);
-      if (h == 0.) h = sqrt_eps;
-      xe = x + h;
-    }
+    if (lm_next(S, returned, status, p.lm_max_iter)) break;
   }
   if (c != 0) return;
   if constexpr (GUARD) {
     u32* gs = g.stripes + (size_t)(blockIdx.x & (LM_GUARD_STRIPES - 1u)) * LM_GUARD_WORDS;
-    if (g_passes) atomicAdd(gs + 0, (u32)g_passes);
-    atomicAdd(gs + 1, (u32)g_evals);
-    if (g_shortcut) atomicAdd(gs + 2, (u32)g_shortcut);
-    if (g_passes) { atomicMax(gs + 4, (u32)g_max_eval); atomicMax(gs + 5, (u32)g_passes); }
-    if (g_abandoned) { atomicAdd(gs + 3, 1u); a.out_flags[s] = 0u; return; }  // no point, not solved
+    if (gc.passes) atomicAdd(gs + 0, (u32)gc.passes);
+    atomicAdd(gs + 1, (u32)gc.evals);
+    if (gc.shortcut) atomicAdd(gs + 2, (u32)gc.shortcut);
+    if (gc.passes) { atomicMax(gs + 4, (u32)gc.max_eval); atomicMax(gs + 5, (u32)gc.passes); }
+    if (gc.abandoned) { atomicAdd(gs + 3, 1u); a.out_flags[s] = 0u; return; }  // no point, not solved
   }
   if (a.halo_viol && viol) atomicAdd(a.halo_viol, 1u);
-  const bool solved = !(x <= 0.001);  // DepthProblemSolver.cpp:192
-  bool keep = solved;
-  if (solved) {
-    atomicAdd(n_solved, 1u);
-    const double invJtJ = (r != 0.) ? (1. / r) * (1. / r) : 0.;  // internal::covar, n == 1
-    double variance;
-    if constexpr (L2) {  // :200-206 (the solver's |f| for both norms: kernels_lm.hip)
-      variance = fnorm * fnorm / (double)(N - 1) * invJtJ;
-      if (variance < 1e-6) variance = 1e-6;
-    } else {
-      variance = p.td_stdvar2 * invJtJ;  // :210
-    }
-    const double residual = fnorm * fnorm;  // :212
-    DevPoint o;
-    o.row = (u32)(size_t)floor(pr.cy);  // :116
-    o.col = (u32)(size_t)floor(pr.cx);
-    o.x[0] = pr.cx;
-    o.x[1] = pr.cy;
-    cam2World(p.camL, pr.cx, pr.cy, x, o.p_cam);  // :119
-    o.inv_depth = x;
-    o.scale2 = L2 ? 0.0 : variance * (p.td_nu - 2) / p.td_nu;  // :125
-    o.nu = L2 ? 0.0 : p.td_nu;
-    o.variance = variance;
-    o.residual = residual;
-    o.age = 0;
-    o.pose_idx = m.pose_idx;
-    o.seq = j;
-    if (a.cull)  // pointCulling, :230-234
-      keep = variance <= p.var_thr && residual <= p.cost_thr && x > -1e-6 && x >= p.invdepth_min && x <= p.invdepth_max;
-    if (keep) a.out_slots[s] = o;
-  }
-  a.out_flags[s] = keep ? 1u : 0u;
+  lm_store_point<L2>(a, p, n_solved, m, s, j, S.x, S.r, S.fnorm, wx * wy);
 }
 
 void launch_lm_refine_any(const LmArgs& a, const DevParams& p, u32* n_solved, hipStream_t s, const LmGuard& g) {

@@ -71,7 +71,7 @@ def build(force=False, verbose=False, perturbed=False):
     """hipcc cross-compiles the extension for gfx950 in-tree (works without a GPU): one object per source file (in parallel,
     only the files that changed), then one link.
     perturbed=True additionally links libesvo_hip_perturbed.so: the same library with -DESVO_PERTURB_ONE_ULP, i.e. the depth
-    of every eighth solver slot's point off by one unit in the last place (kernels_lm.hip) -- never loaded by the product; tests/test_gpu_bench_parity.py
+    of every eighth solver slot's point off by one unit in the last place (lm_common.hpp, both refinement kernels) -- never loaded by the product; tests/test_gpu_bench_parity.py
     points ESVO_HIP_LIB at it to show that bench.py's `parity.oracle_equal` notices a single flipped bit."""
     from concurrent.futures import ThreadPoolExecutor
     inc = os.path.join(_CSRC, "..", "..", "include")
@@ -96,8 +96,8 @@ def build(force=False, verbose=False, perturbed=False):
         return True
 
     jobs = [(os.path.join(_CSRC, s), os.path.join(objdir, s[:-4] + ".o"), []) for s in _SOURCES]
-    if perturbed:
-        jobs.append((os.path.join(_CSRC, "kernels_lm.hip"), os.path.join(objdir, "kernels_lm_perturbed.o"), ["-DESVO_PERTURB_ONE_ULP"]))
+    twins = ("kernels_lm", "kernels_lm_any") if perturbed else ()   # the files whose kernels end in lm_common.hpp's lm_store_point
+    jobs += [(os.path.join(_CSRC, t + ".hip"), os.path.join(objdir, t + "_perturbed.o"), ["-DESVO_PERTURB_ONE_ULP"]) for t in twins]
     with ThreadPoolExecutor(max_workers=min(len(jobs), 16, os.cpu_count() or 4)) as ex:
         rebuilt = list(ex.map(compile_one, jobs))
     objs = [j[1] for j in jobs[:len(_SOURCES)]]
@@ -112,7 +112,7 @@ def build(force=False, verbose=False, perturbed=False):
 
     link(lib_path, objs, any(rebuilt[:len(_SOURCES)]))
     if perturbed:
-        pobjs = [jobs[-1][1] if o.endswith(os.sep + "kernels_lm.o") else o for o in objs]
+        pobjs = [o[:-2] + "_perturbed.o" if os.path.basename(o)[:-2] in twins else o for o in objs]
         link(_PERTURBED_PATH, pobjs, any(rebuilt))
     return lib_path
 

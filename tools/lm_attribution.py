@@ -11,7 +11,8 @@
   table    python tools/lm_attribution.py table STATIC.json DYNAMIC.json [SQ_INSTS_VALU per launch] [SQ_WAVES per launch]
            static counts x dynamic multiplicities, against the hardware counter.
 Regions are line ranges of esvo_amd/csrc/kernels_lm.hip found by their opening statements (so the tool follows edits); an
-instruction inlined from fdiv.hpp / lm_common.hpp / the HIP headers belongs to the region of the last kernels_lm.hip line before it."""
+instruction inlined from fdiv.hpp / lm_common.hpp / the HIP headers belongs to the region of the last kernels_lm.hip line before it:
+the solver's steps and the epilogue live in lm_common.hpp, so their regions open at the kernel's calls of them."""
 import json
 import os
 import re
@@ -34,12 +35,12 @@ MARKS = [  # (region, first line = the line holding this text); a region lasts u
     ("weights sqrt((nu+1)/(nu+r^2/s2)) r (tight)", "// The weights sqrt((nu + 1) / (nu + r^2 / s2))"),
     ("weights (general, rare)", "  const Recip rs2 = make_recip(s2);"),
     ("kernel prologue (match, pose, set-up)", "lm_refine_kernel(LmArgs a, DevParams p, u32* n_solved, LmSplitArg<GUARD> sp) {"),
-    ("solver: lmpar + trial point", "    if (need_step) {  // determine the LM parameter"),
+    ("solver: lmpar + trial point", "    lm_trial_point(S);  // determine the LM parameter"),
     ("solver: evaluator call site / pair exchange", "    bool out_tight;"),
-    ("solver: phase 0 (minimizeInit)", "    if (phase == 0) {  // minimizeInit"),
-    ("solver: phase 1 (forward difference, J, qtf)", "    } else if (phase == 1) {"),
+    ("solver: phase 0 (minimizeInit)", "    if (S.phase == 0) {  // minimizeInit"),
+    ("solver: phase 1 (forward difference, J, qtf)", "    } else if (S.phase == 1) {"),
     ("solver: phase 2 (trust-region test)", "    } else {  // phase 2: trust-region trial at xnew"),
-    ("solver: outer loop (DepthProblemSolver.cpp:161-188)", "    if (phase == 0) {\n"),
+    ("solver: outer loop (DepthProblemSolver.cpp:161-188)", "    if (lm_next(S, returned, status, p.lm_max_iter)) break;"),
     ("kernel epilogue (point, culling, store)", "  if (!active || !lead) return;\n  if constexpr (GUARD) { if (gc.abandoned)"),
     ("(other kernels / host)", "// counting sort of the slots by the cost of F(x0)"),
 ]
