@@ -322,6 +322,88 @@ def evt3_raw_header(data):
     return int(off.value), int(w.value), int(h.value)
 
 
+# ---- Prophesee EVT 2.0 / 2.1 words (esvo_ts_push_evt2 of include/esvo_hip.h)
+EVT_2_0, EVT_2_1, EVT_2_1_LEGACY, EVT_3_0 = 20, 21, 121, 30
+EVT2_FORMATS = (EVT_2_0, EVT_2_1, EVT_2_1_LEGACY)
+
+
+class Evt2State(C.Structure):
+    """esvo_evt2_state_t: flags bit0 have_th"""
+    _fields_ = [("flags", C.c_uint32), ("time_high", C.c_uint32), ("loops", C.c_uint32), ("reserved", C.c_uint32)]
+
+    def as_tuple(self):
+        return (self.flags, self.time_high, self.loops)
+
+    def copy(self):
+        return Evt2State.from_buffer_copy(self)
+
+
+Evt2Counts = Evt3Counts   # esvo_evt2_counts_t; `words` counts 32- or 64-bit words, by format
+
+
+class Evt2Error(ValueError):
+    """an event of the words has no valid stamp; `first_bad` is its index among the events"""
+
+    def __init__(self, first_bad):
+        super().__init__(f"EVT2 words: event {first_bad} has no valid time stamp ((t_us + t_offset_us) * 1000 outside [0, 2^32 * 10^9))")
+        self.first_bad = int(first_bad)
+
+
+def evt2_words(words, format):
+    """a contiguous host array of 4- or 8-byte integers over bytes / bytearray / memoryview (the words as they lie in memory) or
+    anything numpy takes: uint32 / int32 for every format (two per EVT 2.1 word), uint64 / int64 for EVT 2.1 as well"""
+    if format not in EVT2_FORMATS:
+        raise ValueError(f"EVT2 words: unknown format {format}")
+    size = 4 if format == EVT_2_0 else 8
+    if isinstance(words, (bytes, bytearray, memoryview)):
+        if len(words) % size:
+            raise ValueError(f"EVT2 words: the number of bytes is not a multiple of {size}")
+        return np.frombuffer(words, "<u4")
+    words = np.asarray(words)
+    if words.dtype.kind not in "iu" or words.dtype.itemsize not in (4, size) or words.ndim != 1:
+        raise ValueError(f"EVT2 words: a one-dimensional array of {size}-byte (or 4-byte) integers is expected, not {words.dtype} with {words.ndim} dimensions")
+    return np.ascontiguousarray(words)
+
+
+def evt2_to_events(words, format, state=None, t_offset_us=0, count_only=False, cap=None):
+    """esvo_evt2_to_events (the library's host decoder; no GPU): -> (events or None, the state behind the words, counts as a dict).
+    state: an Evt2State (not changed) or None for a stream's start.  cap: room for that many records (default: as many as the words
+    hold).  Raises Evt2Error (first_bad) for a bad stamp, lib.EsvoError (code -4, capacity) where cap is too small."""
+    from . import lib
+    words = evt2_words(words, format)
+    st = state.copy() if state is not None else Evt2State()
+    so, n_out, counts = lib.load(), C.c_size_t(0), Evt2Counts()
+    off = check_t_offset(t_offset_us)
+    out, room = None, 0
+    if not count_only:
+        if cap is None:  # count first (a bad stamp shows again below)
+            so.esvo_evt2_to_events(C.byref(st.copy()), words.ctypes.data, words.nbytes, int(format), off, None, 0, C.byref(n_out), None)
+            cap = n_out.value
+        room = int(cap)
+        out = np.zeros(max(room, 1), EVENT_DTYPE)   # (never NULL: a NULL `out` counts)
+    rc = so.esvo_evt2_to_events(C.byref(st), words.ctypes.data, words.nbytes, int(format), off, None if out is None else out.ctypes.data, room,
+                                C.byref(n_out), C.byref(counts))
+    if rc == -1 and "no valid time stamp" in so.esvo_last_error(None).decode(errors="replace"):
+        raise Evt2Error(n_out.value)
+    if rc != 0:
+        raise lib.EsvoError(f"esvo_evt2_to_events failed ({rc}): {so.esvo_last_error(None).decode(errors='replace')}", code=rc)
+    return (None if count_only else out[:n_out.value]), st, counts.as_dict()
+
+
+def raw_header(data):
+    """esvo_raw_header on the first bytes of a Prophesee .raw file -> (data_offset, width, height, format); width / height 0 if absent,
+    format EVT_2_0 / EVT_2_1 / EVT_2_1_LEGACY / EVT_3_0, or 0 where no line names one.  lib.EsvoError (code -5, unsupported) for
+    any other named format."""
+    from . import lib
+    buf = np.frombuffer(bytes(data), np.uint8)
+    off, w, h, fmt = C.c_size_t(0), C.c_int(0), C.c_int(0), C.c_int(0)
+    so = lib.load()
+    rc = so.esvo_raw_header(buf.ctypes.data if buf.size else None, buf.size, C.byref(off), C.byref(w), C.byref(h), C.byref(fmt))
+    if rc != 0:
+        raise lib.EsvoError(f"esvo_raw_header failed ({rc}): {so.esvo_last_error(None).decode(errors='replace')}", code=rc)
+    return int(off.value), int(w.value), int(h.value), int(fmt.value)
+
+
 def event_ns(ev):
     return ev["sec"].astype(np.uint64) * np.uint64(1_000_000_000) + ev["nsec"].astype(np.uint64)
 

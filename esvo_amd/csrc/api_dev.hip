@@ -521,6 +521,16 @@ int esvo_debug_evt3_device_min(esvo_handle h, size_t n_words, size_t* previous) 
   return ESVO_OK;
 }
 
+// The same for esvo_ts_push_evt2, in BYTES of words and for every EVT 2.x format at once; *previous (nullable) receives the old bound
+// of EVT 2.0.
+int esvo_debug_evt2_device_min(esvo_handle h, size_t n_bytes, size_t* previous) {
+  if (!h) return ESVO_ERR_INVALID_ARG;
+  std::lock_guard<std::mutex> lp0(h->mu_push[0]), lp1(h->mu_push[1]);
+  if (previous) *previous = h->evt2_device_min[0];
+  h->evt2_device_min[0] = h->evt2_device_min[1] = n_bytes;
+  return ESVO_OK;
+}
+
 // The ledger of devmem.hpp: live allocations and live bytes of every DevBuf / PinBuf of the process (tests/test_gpu_lifecycle.py
 // asserts on its deltas around its own handles).  The guarded buffers above and esvo_ts_alloc_pinned are not in it.
 void esvo_debug_live_allocations(size_t out[2]) {

@@ -830,32 +830,261 @@ int evt3_decode_host(esvo_evt3_state_t& s, const uint16_t* words, size_t n_words
   }
   return EVT3_DEC_OK;
 }
-std::string evt3_bad_event(size_t i) { return "EVT3 words: event " + std::to_string(i) + " has no valid time stamp ((t_us + t_offset_us) * 1000 outside [0, 2^32 * 10^9))"; }
+// The same for EVT 2.0 / 2.1: every word through evt2_word as a 64-bit word of the EVT 2.1 layout.
+template <class Emit>
+int evt2_decode_host(esvo_evt2_state_t& s, const u32* words, size_t n_words, int format, int64_t t_offset_us, esvo_evt2_counts_t& c, Emit emit) {
+  for (size_t i = 0; i < n_words; ++i) {
+    const u64 W = evt2_word(words, i, format);
+    const u32 t = evt2_type(W), m = evt2_mask(W);
+    ++c.words;
+    if (m) {
+      if (!evt2_emits(s.flags)) c.dropped_events += (u64)__builtin_popcount(m);
+      else {
+        const u64 stamp = evt2_stamp_ns(s.loops, s.time_high, W, t_offset_us);
+        if (stamp == COL_BAD_STAMP) return EVT3_DEC_BAD_STAMP;
+        for (u32 mm = m; mm; mm &= mm - 1u) {
+          const uint4 r = columns_record((uint16_t)((evt2_x0(W) + (u32)__builtin_ctz(mm)) & 0xFFFFu), (uint16_t)evt2_y(W), stamp, t);
+          esvo_event_t e;
+          std::memcpy(&e, &r, sizeof(r));
+          if (!emit(e)) return EVT3_DEC_FULL;
+          ++c.events;
+        }
+      }
+    } else if (t == EVT2_TIME_HIGH) {
+      const u32 v = evt2_time_high(W);
+      if (evt2_time_loop(evt2_emits(s.flags), s.time_high, v)) { ++s.loops; ++c.time_loops; }
+      s.time_high = v; s.flags |= EVT2_HAVE_TH;
+    } else if (t == EVT2_EXT_TRIGGER) ++c.ext_triggers;
+    else if (evt2_counts_as_ignored(t)) ++c.ignored_words;
+  }
+  return EVT3_DEC_OK;
+}
+std::string words_bad_event(const char* name, size_t i) {
+  return std::string(name) + " words: event " + std::to_string(i) + " has no valid time stamp ((t_us + t_offset_us) * 1000 outside [0, 2^32 * 10^9))";
+}
 void evt3_add(esvo_evt3_counts_t& a, const esvo_evt3_counts_t& b) {
   a.words += b.words; a.events += b.events; a.dropped_events += b.dropped_events; a.ignored_words += b.ignored_words;
   a.ext_triggers += b.ext_triggers; a.time_loops += b.time_loops;
 }
+// What a word format gives the one push path below (push_words): its names and sizes, where the handle keeps its state, its host
+// decoder, its device decode and the end state in the header the decode leaves.
+struct Evt3Format {
+  using State = esvo_evt3_state_t;
+  const char* name() const { return "EVT3"; }
+  size_t word_bytes() const { return 2; }
+  size_t alignment() const { return 2; }
+  const char* size_error() const { return "EVT3 words: an odd number of bytes"; }
+  const char* alignment_error() const { return "EVT3 words: the base is not 2-byte aligned"; }
+  State& state(esvo_context* h, int cam) const { return h->evt3_state[cam]; }
+  esvo_evt3_counts_t& totals(esvo_context* h, int cam) const { return h->evt3_totals[cam]; }
+  bool decoded_on_host(const esvo_context* h, size_t n_words) const { return n_words < h->evt3_device_min || n_words > EVT3_DEVICE_MAX_WORDS; }
+  size_t events_guess(size_t n_words) const { return 2 * n_words; }
+  template <class Emit>
+  int decode_host(State& s, const void* w, size_t n_words, int64_t t_offset_us, esvo_evt3_counts_t& c, Emit emit) const {
+    return evt3_decode_host(s, static_cast<const uint16_t*>(w), n_words, t_offset_us, c, emit);
+  }
+  size_t tiles(size_t n_words, const void* d_words) const { return evt3_tiles(n_words, d_words); }
+  void launch(const void* d_words, size_t n_words, const State& st0, int64_t t_offset_us, u32* tiles, u32* hdr, uint8_t* d, size_t cap, hipStream_t s) const {
+    launch_evt3_decode(static_cast<const uint16_t*>(d_words), n_words, st0, t_offset_us, tiles, hdr, reinterpret_cast<u64*>(d),
+                       reinterpret_cast<uint16_t*>(d + 8 * cap), reinterpret_cast<uint16_t*>(d + 10 * cap), d + 12 * cap, cap, s);
+  }
+  void end_state(const u32* hdr, State& st1) const {
+    st1.flags = hdr[EVT3_H_FLAGS]; st1.y = (uint16_t)(hdr[EVT3_H_Y_BASE] & 0xffffu); st1.base_x = (uint16_t)(hdr[EVT3_H_Y_BASE] >> 16);
+    st1.time_high = (uint16_t)(hdr[EVT3_H_TIME] & 0xffffu); st1.time_low = (uint16_t)(hdr[EVT3_H_TIME] >> 16); st1.loops = hdr[EVT3_H_LOOPS_END];
+  }
+};
+struct Evt2Format {
+  using State = esvo_evt2_state_t;
+  int format;  // ESVO_EVT_2_0, ESVO_EVT_2_1 or ESVO_EVT_2_1_LEGACY
+  const char* name() const { return "EVT2"; }
+  size_t word_bytes() const { return evt2_word_bytes(format); }
+  size_t alignment() const { return 4; }
+  const char* size_error() const { return format == ESVO_EVT_2_0 ? "EVT2 words: n_bytes is not a multiple of 4 (EVT 2.0)" : "EVT2 words: n_bytes is not a multiple of 8 (EVT 2.1)"; }
+  const char* alignment_error() const { return "EVT2 words: the base is not 4-byte aligned"; }
+  State& state(esvo_context* h, int cam) const { return h->evt2_state[cam]; }
+  esvo_evt2_counts_t& totals(esvo_context* h, int cam) const { return h->evt2_totals[cam]; }
+  bool decoded_on_host(const esvo_context* h, size_t n_words) const {
+    return n_words * word_bytes() < h->evt2_device_min[format == ESVO_EVT_2_0 ? 0 : 1] || n_words > EVT2_DEVICE_MAX_WORDS;
+  }
+  size_t events_guess(size_t n_words) const { return format == ESVO_EVT_2_0 ? n_words : 2 * n_words; }
+  template <class Emit>
+  int decode_host(State& s, const void* w, size_t n_words, int64_t t_offset_us, esvo_evt2_counts_t& c, Emit emit) const {
+    return evt2_decode_host(s, static_cast<const u32*>(w), n_words, format, t_offset_us, c, emit);
+  }
+  size_t tiles(size_t n_words, const void*) const { return evt2_tiles(n_words); }
+  void launch(const void* d_words, size_t n_words, const State& st0, int64_t t_offset_us, u32* tiles, u32* hdr, uint8_t* d, size_t cap, hipStream_t s) const {
+    launch_evt2_decode(static_cast<const u32*>(d_words), n_words, format, st0, t_offset_us, tiles, hdr, reinterpret_cast<u64*>(d),
+                       reinterpret_cast<uint16_t*>(d + 8 * cap), reinterpret_cast<uint16_t*>(d + 10 * cap), d + 12 * cap, cap, s);
+  }
+  void end_state(const u32* hdr, State& st1) const { st1.flags = hdr[EVT3_H_FLAGS]; st1.time_high = hdr[EVT3_H_TIME]; st1.loops = hdr[EVT3_H_LOOPS_END]; }
+};
 // A packet the device decoded into the camera's column staging: a device-resident ColumnsPacket, whose slow paths take the records
 // of the host decoder (the words come down first where they lie on the device).
-struct Evt3Packet : ColumnsPacket {
-  const uint16_t* words; size_t n_words; bool on_device; esvo_evt3_state_t st0; int64_t t_offset_us;
+template <class F>
+struct WordsPacket : ColumnsPacket {
+  F f; const void* words; size_t n_words; bool on_device; typename F::State st0; int64_t t_offset_us;
   int materialise() {
-    std::vector<uint16_t> hw;
-    const uint16_t* w = words;
+    esvo_context* const h = this->h;
+    std::vector<u64> hw;  // (8-byte units: aligned for every word size)
+    const void* w = words;
     if (on_device) {
-      hw.resize(n_words);
-      HIPCHK(hipMemcpyAsync(hw.data(), words, 2 * n_words, hipMemcpyDeviceToHost, h->stream_i));
+      const size_t n_bytes = n_words * f.word_bytes();
+      hw.resize((n_bytes + 7) / 8);
+      HIPCHK(hipMemcpyAsync(hw.data(), words, n_bytes, hipMemcpyDeviceToHost, h->stream_i));
       HIPCHK(hipStreamSynchronize(h->stream_i));
       w = hw.data();
     }
-    E->clear(); E->reserve(n);
-    esvo_evt3_state_t s = st0;
+    std::vector<esvo_event_t>* const E = this->E;
+    E->clear(); E->reserve(this->n);
+    typename F::State s = st0;
     esvo_evt3_counts_t c{};
-    if (evt3_decode_host(s, w, n_words, t_offset_us, c, [&](const esvo_event_t& e) { E->push_back(e); return true; }) != EVT3_DEC_OK || E->size() != n)
-      FAIL(ESVO_ERR_STATE, "EVT3: the host decode disagrees with the device decode");
+    if (f.decode_host(s, w, n_words, t_offset_us, c, [&](const esvo_event_t& e) { E->push_back(e); return true; }) != EVT3_DEC_OK || E->size() != this->n)
+      FAIL(ESVO_ERR_STATE, std::string(f.name()) + ": the host decode disagrees with the device decode");
     return ESVO_OK;
   }
 };
+// esvo_ts_push_evt3 / esvo_ts_push_evt2 behind their own argument checks
+template <class F>
+int push_words(esvo_handle h, int cam, const F& f, const void* words_v, size_t n_bytes, int memory, int64_t t_offset_us, size_t* n_events) {
+  const std::string name = f.name();
+  if (memory != ESVO_MEM_HOST && memory != ESVO_MEM_DEVICE) FAIL(ESVO_ERR_INVALID_ARG, name + " words: unknown memory");
+  if (n_bytes % f.word_bytes()) FAIL(ESVO_ERR_INVALID_ARG, f.size_error());
+  if (n_bytes && !words_v) FAIL(ESVO_ERR_INVALID_ARG, name + " words: NULL");
+  if ((uintptr_t)words_v % f.alignment()) FAIL(ESVO_ERR_INVALID_ARG, f.alignment_error());
+  const size_t n_words = n_bytes / f.word_bytes();
+  if (n_words > 0x7fffffffull) FAIL(ESVO_ERR_INVALID_ARG, name + " words: more than 2^31 - 1 words in one call");
+  if (n_words == 0) return ESVO_OK;
+  const bool on_device = memory == ESVO_MEM_DEVICE;
+  std::unique_lock<std::mutex> lp(h->mu_push[cam]);
+  HIPCHK(hipSetDevice(h->device));
+  {  // where the words lie, first and last byte, before anything is launched or copied
+    const int want = on_device ? 1 : 0;
+    if (column_memory_kind(words_v, h->device) != want || column_memory_kind(static_cast<const uint8_t*>(words_v) + n_bytes - 1, h->device) != want)
+      FAIL(ESVO_ERR_INVALID_ARG, name + (on_device ? " words labelled ESVO_MEM_DEVICE must be plain device memory of the handle's GPU (not host, managed or another GPU's)"
+                                                   : " words labelled ESVO_MEM_HOST must be host memory (a device or managed pointer was given)"));
+  }
+  const typename F::State st0 = f.state(h, cam);
+  typename F::State st1 = st0;
+  esvo_evt3_counts_t cnt{};
+  const auto commit = [&]() {  // (under mu_push[cam])
+    f.state(h, cam) = st1;
+    evt3_add(f.totals(h, cam), cnt);
+    if (n_events) *n_events = (size_t)cnt.events;
+  };
+  int rc = ESVO_OK;
+  if (h->routed || f.decoded_on_host(h, n_words)) {
+    // decoded on the host: the record paths.  (Small packets: three launches and a read-back cost more than the walk.)
+    std::vector<u64> hw;
+    const void* w = words_v;
+    if (on_device) {
+      hw.resize((n_bytes + 7) / 8);
+      HIPCHK(hipMemcpyAsync(hw.data(), words_v, n_bytes, hipMemcpyDeviceToHost, h->stream_i));
+      HIPCHK(hipStreamSynchronize(h->stream_i));
+      w = hw.data();
+    }
+    std::vector<esvo_event_t> E;
+    const size_t room = (size_t)h->ring_cap;
+    const int drc = f.decode_host(st1, w, n_words, t_offset_us, cnt, [&](const esvo_event_t& e) {
+      if (E.size() >= room) return false;
+      E.push_back(e);
+      return true;
+    });
+    if (drc == EVT3_DEC_BAD_STAMP) FAIL(ESVO_ERR_INVALID_ARG, words_bad_event(f.name(), (size_t)cnt.events));
+    if (drc == EVT3_DEC_FULL) FAIL(ESVO_ERR_CAPACITY, "event block larger than the event ring");
+    if (E.empty()) { commit(); return ESVO_OK; }
+    RecordPacket src{{}, h, cam, E.data(), E.size(), false};
+    rc = push_packet(h, cam, src, std::move(lp));
+  } else {
+    const void* d_words = words_v;
+    if (!on_device) {  // (d_evt3_words counts in 2-byte units whatever the word size)
+      const size_t n_half = n_bytes / 2;
+      if (n_half > h->d_evt3_words[cam].cap()) HIPCHK(h->d_evt3_words[cam].alloc(std::max<size_t>(n_half + n_half / 2, (size_t)1 << 16)));
+      d_words = h->d_evt3_words[cam].get();
+    }
+    const size_t n_tiles = f.tiles(n_words, d_words);
+    if (n_tiles * EVT3_TILE_WORDS > h->d_evt3_tiles[cam].cap()) HIPCHK(h->d_evt3_tiles[cam].alloc(std::max<size_t>(2 * n_tiles, 64) * EVT3_TILE_WORDS));
+    if (!h->d_evt3_hdr[cam]) { HIPCHK(h->d_evt3_hdr[cam].alloc(EVT3_HDR_WORDS)); HIPCHK(h->h_evt3_hdr[cam].alloc(EVT3_HDR_WORDS)); }
+    { int rcs = columns_staging(h, cam, std::min<size_t>(f.events_guess(n_words), (size_t)h->ring_cap)); if (rcs) return rcs; }  // (a guess: the header tells)
+    u32* const hdr = h->h_evt3_hdr[cam];
+    const auto decode = [&]() -> int {  // the three launches and the header's way down
+      f.launch(d_words, n_words, st0, t_offset_us, h->d_evt3_tiles[cam], h->d_evt3_hdr[cam], h->d_col[cam], h->col_cap[cam], h->stream_i);
+      HIPCHK(hipGetLastError());
+      HIPCHK(hipMemcpyAsync(hdr, h->d_evt3_hdr[cam], sizeof(u32) * EVT3_HDR_WORDS, hipMemcpyDeviceToHost, h->stream_i));
+      HIPCHK(hipStreamSynchronize(h->stream_i));
+      return ESVO_OK;
+    };
+    if (!on_device) HIPCHK(hipMemcpyAsync(h->d_evt3_words[cam], words_v, n_bytes, hipMemcpyHostToDevice, h->stream_i));
+    { int rcd = decode(); if (rcd) return rcd; }
+    const size_t n = hdr[EVT3_H_EVENTS];
+    if (hdr[EVT3_H_FIRST_BAD] != 0xffffffffu) FAIL(ESVO_ERR_INVALID_ARG, words_bad_event(f.name(), hdr[EVT3_H_FIRST_BAD]));
+    if (n > h->ring_cap) FAIL(ESVO_ERR_CAPACITY, "event block larger than the event ring");
+    if (n > h->col_cap[cam]) {  // the guess was too small: once more into staging that holds them
+      { int rcs = columns_staging(h, cam, n); if (rcs) return rcs; }
+      { int rcd = decode(); if (rcd) return rcd; }
+    }
+    f.end_state(hdr, st1);
+    cnt.words = n_words; cnt.events = n; cnt.dropped_events = hdr[EVT3_H_DROPPED]; cnt.ignored_words = hdr[EVT3_H_IGNORED];
+    cnt.ext_triggers = hdr[EVT3_H_EXT]; cnt.time_loops = hdr[EVT3_H_LOOPS];
+    if (n == 0) { commit(); return ESVO_OK; }
+    const size_t cap = h->col_cap[cam];
+    uint8_t* const d = h->d_col[cam];
+    u64* const stamps = h->h_col_stamps[cam];
+    HIPCHK(hipMemcpyAsync(stamps, d, sizeof(u64) * n, hipMemcpyDeviceToHost, h->stream_i));
+    HIPCHK(hipStreamSynchronize(h->stream_i));
+    bool in_order = true;
+    for (size_t i = 1; i < n && in_order; ++i) in_order = stamps[i] >= stamps[i - 1];
+    esvo_event_columns_t c{};
+    c.x = d + 8 * cap; c.y = d + 10 * cap; c.p = d + 12 * cap; c.t = d;
+    c.t_type = ESVO_T_NS_I64; c.p_type = ESVO_P_U8; c.memory = ESVO_MEM_DEVICE;
+    std::vector<esvo_event_t> E;
+    WordsPacket<F> src{{{}, h, cam, &c, n, stamps, in_order, &E}, f, words_v, n_words, on_device, st0, t_offset_us};
+    rc = push_packet(h, cam, src, std::move(lp));
+  }
+  if (rc) return rc;
+  std::lock_guard<std::mutex> lp2(h->mu_push[cam]);  // (push_packet gave the lock back)
+  commit();
+  return ESVO_OK;
+}
+// The header of a Prophesee .raw file: ASCII lines each starting with '%', ended by the first line that does not or by "% end".
+// named(line, is_format_line) is called for every "% evt " and "% format " line, before the line's fields are read, and ends the
+// walk with its code unless that is ESVO_OK.
+template <class Named>
+int raw_header_walk(const uint8_t* file, size_t n_bytes, size_t* data_offset, int* width, int* height, Named named) {
+  if (data_offset) *data_offset = 0;
+  if (width) *width = 0;
+  if (height) *height = 0;
+  if ((n_bytes && !file) || !data_offset) return ESVO_ERR_INVALID_ARG;
+  const auto number_after = [](const std::string& line, const char* key) {  // the decimal number behind `key`, or 0
+    const size_t at = line.find(key);
+    return at == std::string::npos ? 0 : std::atoi(line.c_str() + at + std::strlen(key));
+  };
+  size_t off = 0;
+  while (off < n_bytes && file[off] == '%') {
+    size_t eol = off;
+    while (eol < n_bytes && file[eol] != '\n') ++eol;
+    std::string line(reinterpret_cast<const char*>(file) + off, eol - off);
+    while (!line.empty() && (line.back() == '\r' || line.back() == ' ')) line.pop_back();
+    off = eol < n_bytes ? eol + 1 : n_bytes;
+    if (line == "% end") break;
+    if (line.rfind("% evt ", 0) == 0) { const int rc = named(line, false); if (rc) return rc; }
+    if (line.rfind("% format ", 0) == 0) {
+      { const int rc = named(line, true); if (rc) return rc; }
+      if (width && number_after(line, "width=")) *width = number_after(line, "width=");
+      if (height && number_after(line, "height=")) *height = number_after(line, "height=");
+    }
+    if (line.rfind("% geometry ", 0) == 0) {
+      const size_t xat = line.find('x', 11);
+      if (width) *width = std::atoi(line.c_str() + 11);
+      if (height && xat != std::string::npos) *height = std::atoi(line.c_str() + xat + 1);
+    }
+  }
+  *data_offset = off;
+  return ESVO_OK;
+}
+int raw_unsupported(const std::string& msg) {
+  esvo_context* h = nullptr;
+  FAIL(ESVO_ERR_UNSUPPORTED, msg);
+}
 }  // namespace
 }  // extern "C++"
 
@@ -873,7 +1102,7 @@ int esvo_evt3_to_events(esvo_evt3_state_t* st, const uint16_t* words, size_t n_w
     return true;
   });
   if (n_out) *n_out = (size_t)c.events;
-  if (rc == EVT3_DEC_BAD_STAMP) FAIL(ESVO_ERR_INVALID_ARG, evt3_bad_event((size_t)c.events));
+  if (rc == EVT3_DEC_BAD_STAMP) FAIL(ESVO_ERR_INVALID_ARG, words_bad_event("EVT3", (size_t)c.events));
   if (rc == EVT3_DEC_FULL) FAIL(ESVO_ERR_CAPACITY, "esvo_evt3_to_events: the words hold more events than `out` has room for");
   *st = s;
   if (counts) *counts = c;
@@ -884,37 +1113,79 @@ void esvo_evt3_sizes(size_t out[4]) {
   out[2] = out[3] = 0;
 }
 int esvo_evt3_raw_header(const uint8_t* file, size_t n_bytes, size_t* data_offset, int* width, int* height) {
-  esvo_context* h = nullptr;
-  if (data_offset) *data_offset = 0;
-  if (width) *width = 0;
-  if (height) *height = 0;
-  if ((n_bytes && !file) || !data_offset) return ESVO_ERR_INVALID_ARG;
-  const auto number_after = [](const std::string& line, const char* key) {  // the decimal number behind `key`, or 0
-    const size_t at = line.find(key);
-    return at == std::string::npos ? 0 : std::atoi(line.c_str() + at + std::strlen(key));
-  };
-  size_t off = 0;
-  while (off < n_bytes && file[off] == '%') {
-    size_t eol = off;
-    while (eol < n_bytes && file[eol] != '\n') ++eol;
-    std::string line(reinterpret_cast<const char*>(file) + off, eol - off);
-    while (!line.empty() && (line.back() == '\r' || line.back() == ' ')) line.pop_back();
-    off = eol < n_bytes ? eol + 1 : n_bytes;
-    if (line == "% end") break;
-    if (line.rfind("% evt ", 0) == 0 && line.substr(6) != "3.0") FAIL(ESVO_ERR_UNSUPPORTED, "Prophesee .raw: '" + line + "' -- only EVT 3.0 is decoded");
-    if (line.rfind("% format ", 0) == 0) {
-      if (line.compare(9, 4, "EVT3") != 0) FAIL(ESVO_ERR_UNSUPPORTED, "Prophesee .raw: '" + line + "' -- only EVT3 is decoded");
-      if (width && number_after(line, "width=")) *width = number_after(line, "width=");
-      if (height && number_after(line, "height=")) *height = number_after(line, "height=");
+  return raw_header_walk(file, n_bytes, data_offset, width, height, [](const std::string& line, bool format_line) {
+    if (!format_line && line.substr(6) != "3.0") return raw_unsupported("Prophesee .raw: '" + line + "' -- only EVT 3.0 is decoded");
+    if (format_line && line.compare(9, 4, "EVT3") != 0) return raw_unsupported("Prophesee .raw: '" + line + "' -- only EVT3 is decoded");
+    return (int)ESVO_OK;
+  });
+}
+int esvo_raw_header(const uint8_t* file, size_t n_bytes, size_t* data_offset, int* width, int* height, int* format) {
+  int named_format = 0;
+  bool legacy = false;
+  if (format) *format = 0;
+  const int rc = raw_header_walk(file, n_bytes, data_offset, width, height, [&](const std::string& line, bool format_line) {
+    std::string name = line.substr(format_line ? 9 : 6);
+    if (format_line) {
+      name = name.substr(0, name.find(';'));
+      if (line.find("endianness=legacy") != std::string::npos) legacy = true;
     }
-    if (line.rfind("% geometry ", 0) == 0) {
-      const size_t xat = line.find('x', 11);
-      if (width) *width = std::atoi(line.c_str() + 11);
-      if (height && xat != std::string::npos) *height = std::atoi(line.c_str() + xat + 1);
-    }
-  }
-  *data_offset = off;
+    if (name == (format_line ? "EVT2" : "2.0")) named_format = ESVO_EVT_2_0;
+    else if (name == (format_line ? "EVT21" : "2.1")) named_format = ESVO_EVT_2_1;
+    else if (name == (format_line ? "EVT3" : "3.0")) named_format = ESVO_EVT_3_0;
+    else return raw_unsupported("Prophesee .raw: '" + line + "' -- EVT 2.0, EVT 2.1 and EVT 3.0 are decoded");
+    return (int)ESVO_OK;
+  });
+  if (rc) return rc;
+  if (format) *format = named_format == ESVO_EVT_2_1 && legacy ? (int)ESVO_EVT_2_1_LEGACY : named_format;
   return ESVO_OK;
+}
+
+int esvo_evt2_to_events(esvo_evt2_state_t* st, const void* words, size_t n_bytes, int format, int64_t t_offset_us, esvo_event_t* out, size_t cap,
+                        size_t* n_out, esvo_evt2_counts_t* counts) {
+  esvo_context* h = nullptr;
+  if (n_out) *n_out = 0;
+  if (!st || !evt2_format_known(format) || (n_bytes && !words) || (uintptr_t)words % 4 || n_bytes % evt2_word_bytes(format)) return ESVO_ERR_INVALID_ARG;
+  esvo_evt2_state_t s = *st;
+  esvo_evt2_counts_t c{};
+  const int rc = evt2_decode_host(s, static_cast<const u32*>(words), n_bytes / evt2_word_bytes(format), format, t_offset_us, c, [&](const esvo_event_t& e) {
+    if (!out) return true;
+    if (c.events >= cap) return false;
+    out[c.events] = e;
+    return true;
+  });
+  if (n_out) *n_out = (size_t)c.events;
+  if (rc == EVT3_DEC_BAD_STAMP) FAIL(ESVO_ERR_INVALID_ARG, words_bad_event("EVT2", (size_t)c.events));
+  if (rc == EVT3_DEC_FULL) FAIL(ESVO_ERR_CAPACITY, "esvo_evt2_to_events: the words hold more events than `out` has room for");
+  *st = s;
+  if (counts) *counts = c;
+  return ESVO_OK;
+}
+void esvo_evt2_sizes(size_t out[4]) {
+  out[0] = sizeof(esvo_evt2_state_t); out[1] = sizeof(esvo_evt2_counts_t);
+  out[2] = out[3] = 0;
+}
+int esvo_ts_evt2_state(esvo_handle h, int cam, esvo_evt2_state_t* get, const esvo_evt2_state_t* set) {
+  if (!h || cam < 0 || cam > 1) return ESVO_ERR_INVALID_ARG;
+  std::lock_guard<std::mutex> lp(h->mu_push[cam]);
+  if (get) *get = h->evt2_state[cam];
+  if (set) {
+    esvo_evt2_state_t s = *set;
+    s.flags &= 0x1u; s.time_high &= 0x0FFFFFFFu; s.reserved = 0;  // what a stream can leave
+    h->evt2_state[cam] = s;
+  }
+  return ESVO_OK;
+}
+int esvo_ts_evt2_stats(esvo_handle h, int cam, esvo_evt2_counts_t* totals) {
+  if (!h || cam < 0 || cam > 1 || !totals) return ESVO_ERR_INVALID_ARG;
+  std::lock_guard<std::mutex> lp(h->mu_push[cam]);
+  *totals = h->evt2_totals[cam];
+  return ESVO_OK;
+}
+int esvo_ts_push_evt2(esvo_handle h, int cam, const void* words, size_t n_bytes, int format, int memory, int64_t t_offset_us, size_t* n_events) {
+  if (n_events) *n_events = 0;
+  if (!h || cam < 0 || cam > 1) return ESVO_ERR_INVALID_ARG;
+  if (!evt2_format_known(format)) FAIL(ESVO_ERR_INVALID_ARG, "EVT2 words: unknown format (ESVO_EVT_2_0, ESVO_EVT_2_1 or ESVO_EVT_2_1_LEGACY; EVT 3.0 words go to esvo_ts_push_evt3)");
+  return push_words(h, cam, Evt2Format{format}, words, n_bytes, memory, t_offset_us, n_events);
 }
 
 int esvo_ts_evt3_state(esvo_handle h, int cam, esvo_evt3_state_t* get, const esvo_evt3_state_t* set) {
@@ -938,107 +1209,7 @@ int esvo_ts_evt3_stats(esvo_handle h, int cam, esvo_evt3_counts_t* totals) {
 int esvo_ts_push_evt3(esvo_handle h, int cam, const void* words_v, size_t n_bytes, int memory, int64_t t_offset_us, size_t* n_events) {
   if (n_events) *n_events = 0;
   if (!h || cam < 0 || cam > 1) return ESVO_ERR_INVALID_ARG;
-  if (memory != ESVO_MEM_HOST && memory != ESVO_MEM_DEVICE) FAIL(ESVO_ERR_INVALID_ARG, "EVT3 words: unknown memory");
-  if (n_bytes % 2) FAIL(ESVO_ERR_INVALID_ARG, "EVT3 words: an odd number of bytes");
-  if (n_bytes && !words_v) FAIL(ESVO_ERR_INVALID_ARG, "EVT3 words: NULL");
-  if ((uintptr_t)words_v % 2) FAIL(ESVO_ERR_INVALID_ARG, "EVT3 words: the base is not 2-byte aligned");
-  const size_t n_words = n_bytes / 2;
-  if (n_words > 0x7fffffffull) FAIL(ESVO_ERR_INVALID_ARG, "EVT3 words: more than 2^31 - 1 words in one call");
-  if (n_words == 0) return ESVO_OK;
-  const uint16_t* const words = static_cast<const uint16_t*>(words_v);
-  const bool on_device = memory == ESVO_MEM_DEVICE;
-  std::unique_lock<std::mutex> lp(h->mu_push[cam]);
-  HIPCHK(hipSetDevice(h->device));
-  {  // where the words lie, first and last byte, before anything is launched or copied
-    const int want = on_device ? 1 : 0;
-    if (column_memory_kind(words, h->device) != want || column_memory_kind(static_cast<const uint8_t*>(words_v) + n_bytes - 1, h->device) != want)
-      FAIL(ESVO_ERR_INVALID_ARG, on_device ? "EVT3 words labelled ESVO_MEM_DEVICE must be plain device memory of the handle's GPU (not host, managed or another GPU's)"
-                                           : "EVT3 words labelled ESVO_MEM_HOST must be host memory (a device or managed pointer was given)");
-  }
-  const esvo_evt3_state_t st0 = h->evt3_state[cam];
-  esvo_evt3_state_t st1 = st0;
-  esvo_evt3_counts_t cnt{};
-  const auto commit = [&]() {  // (under mu_push[cam])
-    h->evt3_state[cam] = st1;
-    evt3_add(h->evt3_totals[cam], cnt);
-    if (n_events) *n_events = (size_t)cnt.events;
-  };
-  int rc = ESVO_OK;
-  if (h->routed || n_words < h->evt3_device_min || n_words > EVT3_DEVICE_MAX_WORDS) {
-    // decoded on the host: the record paths.  (Small packets: three launches and a read-back cost more than the walk.)
-    std::vector<uint16_t> hw;
-    const uint16_t* w = words;
-    if (on_device) {
-      hw.resize(n_words);
-      HIPCHK(hipMemcpyAsync(hw.data(), words, n_bytes, hipMemcpyDeviceToHost, h->stream_i));
-      HIPCHK(hipStreamSynchronize(h->stream_i));
-      w = hw.data();
-    }
-    std::vector<esvo_event_t> E;
-    const size_t room = (size_t)h->ring_cap;
-    const int drc = evt3_decode_host(st1, w, n_words, t_offset_us, cnt, [&](const esvo_event_t& e) {
-      if (E.size() >= room) return false;
-      E.push_back(e);
-      return true;
-    });
-    if (drc == EVT3_DEC_BAD_STAMP) FAIL(ESVO_ERR_INVALID_ARG, evt3_bad_event((size_t)cnt.events));
-    if (drc == EVT3_DEC_FULL) FAIL(ESVO_ERR_CAPACITY, "event block larger than the event ring");
-    if (E.empty()) { commit(); return ESVO_OK; }
-    RecordPacket src{{}, h, cam, E.data(), E.size(), false};
-    rc = push_packet(h, cam, src, std::move(lp));
-  } else {
-    const uint16_t* d_words = words;
-    if (!on_device) {
-      if (n_words > h->d_evt3_words[cam].cap()) HIPCHK(h->d_evt3_words[cam].alloc(std::max<size_t>(n_words + n_words / 2, (size_t)1 << 16)));
-      d_words = h->d_evt3_words[cam];
-    }
-    const size_t n_tiles = evt3_tiles(n_words, d_words);
-    if (n_tiles * EVT3_TILE_WORDS > h->d_evt3_tiles[cam].cap()) HIPCHK(h->d_evt3_tiles[cam].alloc(std::max<size_t>(2 * n_tiles, 64) * EVT3_TILE_WORDS));
-    if (!h->d_evt3_hdr[cam]) { HIPCHK(h->d_evt3_hdr[cam].alloc(EVT3_HDR_WORDS)); HIPCHK(h->h_evt3_hdr[cam].alloc(EVT3_HDR_WORDS)); }
-    { int rcs = columns_staging(h, cam, std::min<size_t>(2 * n_words, (size_t)h->ring_cap)); if (rcs) return rcs; }  // (a guess: the header tells)
-    u32* const hdr = h->h_evt3_hdr[cam];
-    const auto decode = [&]() -> int {  // the three launches and the header's way down
-      const size_t cap = h->col_cap[cam];
-      uint8_t* const d = h->d_col[cam];
-      launch_evt3_decode(d_words, n_words, st0, t_offset_us, h->d_evt3_tiles[cam], h->d_evt3_hdr[cam], reinterpret_cast<u64*>(d),
-                         reinterpret_cast<uint16_t*>(d + 8 * cap), reinterpret_cast<uint16_t*>(d + 10 * cap), d + 12 * cap, cap, h->stream_i);
-      HIPCHK(hipGetLastError());
-      HIPCHK(hipMemcpyAsync(hdr, h->d_evt3_hdr[cam], sizeof(u32) * EVT3_HDR_WORDS, hipMemcpyDeviceToHost, h->stream_i));
-      HIPCHK(hipStreamSynchronize(h->stream_i));
-      return ESVO_OK;
-    };
-    if (!on_device) HIPCHK(hipMemcpyAsync(h->d_evt3_words[cam], words, n_bytes, hipMemcpyHostToDevice, h->stream_i));
-    { int rcd = decode(); if (rcd) return rcd; }
-    const size_t n = hdr[EVT3_H_EVENTS];
-    if (hdr[EVT3_H_FIRST_BAD] != 0xffffffffu) FAIL(ESVO_ERR_INVALID_ARG, evt3_bad_event(hdr[EVT3_H_FIRST_BAD]));
-    if (n > h->ring_cap) FAIL(ESVO_ERR_CAPACITY, "event block larger than the event ring");
-    if (n > h->col_cap[cam]) {  // the guess was too small: once more into staging that holds them
-      { int rcs = columns_staging(h, cam, n); if (rcs) return rcs; }
-      { int rcd = decode(); if (rcd) return rcd; }
-    }
-    st1.flags = hdr[EVT3_H_FLAGS]; st1.y = (uint16_t)(hdr[EVT3_H_Y_BASE] & 0xffffu); st1.base_x = (uint16_t)(hdr[EVT3_H_Y_BASE] >> 16);
-    st1.time_high = (uint16_t)(hdr[EVT3_H_TIME] & 0xffffu); st1.time_low = (uint16_t)(hdr[EVT3_H_TIME] >> 16); st1.loops = hdr[EVT3_H_LOOPS_END];
-    cnt.words = n_words; cnt.events = n; cnt.dropped_events = hdr[EVT3_H_DROPPED]; cnt.ignored_words = hdr[EVT3_H_IGNORED];
-    cnt.ext_triggers = hdr[EVT3_H_EXT]; cnt.time_loops = hdr[EVT3_H_LOOPS];
-    if (n == 0) { commit(); return ESVO_OK; }
-    const size_t cap = h->col_cap[cam];
-    uint8_t* const d = h->d_col[cam];
-    u64* const stamps = h->h_col_stamps[cam];
-    HIPCHK(hipMemcpyAsync(stamps, d, sizeof(u64) * n, hipMemcpyDeviceToHost, h->stream_i));
-    HIPCHK(hipStreamSynchronize(h->stream_i));
-    bool in_order = true;
-    for (size_t i = 1; i < n && in_order; ++i) in_order = stamps[i] >= stamps[i - 1];
-    esvo_event_columns_t c{};
-    c.x = d + 8 * cap; c.y = d + 10 * cap; c.p = d + 12 * cap; c.t = d;
-    c.t_type = ESVO_T_NS_I64; c.p_type = ESVO_P_U8; c.memory = ESVO_MEM_DEVICE;
-    std::vector<esvo_event_t> E;
-    Evt3Packet src{{{}, h, cam, &c, n, stamps, in_order, &E}, words, n_words, on_device, st0, t_offset_us};
-    rc = push_packet(h, cam, src, std::move(lp));
-  }
-  if (rc) return rc;
-  std::lock_guard<std::mutex> lp2(h->mu_push[cam]);  // (push_packet gave the lock back)
-  commit();
-  return ESVO_OK;
+  return push_words(h, cam, Evt3Format{}, words_v, n_bytes, memory, t_offset_us, n_events);
 }
 
 namespace {

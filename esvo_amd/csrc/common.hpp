@@ -293,6 +293,49 @@ constexpr size_t EVT3_DEVICE_MAX_WORDS = (size_t)1 << 22;  // above it a packet 
 u32 evt3_tiles(size_t n_words, const void* words);
 void launch_evt3_decode(const uint16_t* words, size_t n_words, const esvo_evt3_state_t& st, int64_t t_offset_us, u32* tiles, u32* hdr,
                         u64* stamps, uint16_t* x, uint16_t* y, uint8_t* p, size_t col_cap, hipStream_t s);
+// EVT 2.0 / 2.1 ingest (esvo_ts_push_evt2, include/esvo_hip.h): ONE function per rule, shared by the host decoder
+// (esvo_evt2_to_events) and the device decode (kernels_ts.hip).  Every word is read as a 64-bit word W of the EVT 2.1 layout: the
+// two half orders of EVT 2.1 and the lift of an EVT 2.0 word happen where a word is loaded (evt2_word), and nowhere else.
+enum { EVT2_CD_OFF = 0x0, EVT2_CD_ON = 0x1, EVT2_TIME_HIGH = 0x8, EVT2_EXT_TRIGGER = 0xA };
+enum { EVT2_HAVE_TH = 1u };  // esvo_evt2_state_t::flags
+__host__ __device__ inline bool evt2_format_known(int format) { return format == ESVO_EVT_2_0 || format == ESVO_EVT_2_1 || format == ESVO_EVT_2_1_LEGACY; }
+__host__ __device__ inline u32 evt2_word_bytes(int format) { return format == ESVO_EVT_2_0 ? 4u : 8u; }
+// an EVT 2.0 word in the EVT 2.1 layout: a CD word becomes a vector word with the one valid bit 0, every other word keeps its type
+// nibble and its 28 payload bits in the upper half
+__host__ __device__ inline u64 evt2_lift(u32 w) {
+  const u32 t = w >> 28;
+  if (t > EVT2_CD_ON) return (u64)w << 32;
+  return ((u64)t << 60) | ((u64)((w >> 22) & 0x3Fu) << 54) | ((u64)((w >> 11) & 0x7FFu) << 43) | ((u64)(w & 0x7FFu) << 32) | 1ull;
+}
+// word i of a packet of `format` (words: its 4-byte aligned base)
+__host__ __device__ inline u64 evt2_word(const u32* words, size_t i, int format) {
+  if (format == ESVO_EVT_2_0) return evt2_lift(words[i]);
+  const u32 first = words[2 * i], second = words[2 * i + 1];
+  return format == ESVO_EVT_2_1 ? (((u64)second << 32) | first) : (((u64)first << 32) | second);
+}
+__host__ __device__ inline u32 evt2_type(u64 W) { return (u32)(W >> 60); }
+// the mask of the events a word stands for (bit i: x offset i); 0 for a word that never emits
+__host__ __device__ inline u32 evt2_mask(u64 W) { return evt2_type(W) <= EVT2_CD_ON ? (u32)(W & 0xFFFFFFFFull) : 0u; }
+// the emission condition of a CD / vector word under the flags in front of it
+__host__ __device__ inline bool evt2_emits(u32 flags) { return (flags & EVT2_HAVE_TH) != 0; }
+__host__ __device__ inline u32 evt2_time_high(u64 W) { return (u32)(W >> 32) & 0x0FFFFFFFu; }
+__host__ __device__ inline bool evt2_counts_as_ignored(u32 type) { return type > EVT2_CD_ON && type != EVT2_TIME_HIGH && type != EVT2_EXT_TRIGGER; }
+// a TIME_HIGH payload v behind the payload prev: one more time loop?  (threshold 2^27: not pinned to any third-party decoder)
+__host__ __device__ inline bool evt2_time_loop(bool have_th, u32 prev, u32 v) { return have_th && v < prev && prev - v >= (1u << 27); }
+// the stamp of the events of word W; COL_BAD_STAMP for loops >= 2^18 and outside [0, 2^32 * 10^9)
+__host__ __device__ inline u64 evt2_stamp_ns(u32 loops, u32 time_high, u64 W, int64_t t_offset_us) {
+  if (loops >= (1u << 18)) return COL_BAD_STAMP;
+  const int64_t v = (int64_t)(((u64)loops << 34) | ((u64)time_high << 6) | ((W >> 54) & 0x3Full));  // below 2^52
+  return columns_stamp_ns(&v, 0, ESVO_T_US_I64, t_offset_us);
+}
+__host__ __device__ inline u32 evt2_x0(u64 W) { return (u32)(W >> 43) & 0x7FFu; }
+__host__ __device__ inline u32 evt2_y(u64 W) { return (u32)(W >> 32) & 0x7FFu; }
+// Device decode of one packet into column staging (kernels_ts.hip), with the header words and the tile scratch of the EVT 3.0 decode
+// (EVT3_H_TIME holds time_high alone, EVT3_H_Y_BASE is unused).  n_words: words of the format.
+constexpr size_t EVT2_DEVICE_MAX_WORDS = (size_t)1 << 22;  // (as EVT3_DEVICE_MAX_WORDS; at most 2^27 events)
+u32 evt2_tiles(size_t n_words);
+void launch_evt2_decode(const u32* words, size_t n_words, int format, const esvo_evt2_state_t& st, int64_t t_offset_us, u32* tiles, u32* hdr,
+                        u64* stamps, uint16_t* x, uint16_t* y, uint8_t* p, size_t col_cap, hipStream_t s);
 void launch_ts_scatter(const esvo_event_t* d_ev, size_t n, u64* d_sae, int W, int H, hipStream_t s);
 // (row0, row1: the rectified rows to render -- whole tiles of TS_TILE_ROWS; a routed band handle renders its band + halo only)
 #define TS_TILE_ROWS 16

@@ -75,6 +75,9 @@ struct IngestSession {  // under mu_ring: the event rings
   // that camera's mu_push, not mu_ring
   esvo_evt3_state_t evt3_state[2] = {};
   esvo_evt3_counts_t evt3_totals[2] = {};
+  // the same of EVT 2.0 / 2.1 ingest (esvo_ts_push_evt2): one state serves the three formats
+  esvo_evt2_state_t evt2_state[2] = {};
+  esvo_evt2_counts_t evt2_totals[2] = {};
 };
 struct TsSession {  // under mu_ts (the right camera's flag: mapper group only)
   bool ts_valid[2] = {false, false};  // d_ts[cam] holds a render
@@ -306,6 +309,11 @@ struct esvo_context : IngestSession, TsSession, SchedSession, MapSession, CloudS
   // packets of fewer words are decoded on the host: the measured crossover, ~12 800 events at 2.03 words per event
   // (profiles/evt3_ingest_ab.txt); esvo_debug_evt3_device_min moves it for tests
   size_t evt3_device_min = 24576;
+  // esvo_ts_push_evt2 shares the EVT 3.0 staging above (d_evt3_words holds the bytes of either).  Its bounds are in BYTES of words,
+  // [0] EVT 2.0, [1] EVT 2.1 in either half order: the measured crossovers of host decode + record push and the device decode,
+  // ~20 000 events of EVT 2.0 and ~29 000 one-event words of EVT 2.1 (profiles/evt2_ingest_ab.txt);
+  // esvo_debug_evt2_device_min moves both
+  size_t evt2_device_min[2] = {20480 * 4, 28672 * 8};
   u64 ring_cap = 0;
   // esvo_ts_push_events_async: the newest enqueued (not awaited) copy of a camera; consumers of the ring on the front stream
   // queue behind it (ingest_fence, api_ts.hip) -- under mu_ring, with IngestSession::ingest_pending

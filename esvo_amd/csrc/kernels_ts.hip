@@ -758,7 +758,7 @@ constexpr int EVT3_B = 256, EVT3_V = 8, EVT3_TILE = EVT3_B * EVT3_V;
 constexpr u32 EVT3_NO_WORD = 0x11000u;  // outside the packet: reads as a reserved type, bit 16 keeps it out of the counts
 
 struct Evt3Lw { u32 y, th, tl, base, inc; };
-__device__ inline Evt3Lw evt3_join(const Evt3Lw& a, const Evt3Lw& b) {  // a in front of b
+__device__ inline Evt3Lw tuple_join(const Evt3Lw& a, const Evt3Lw& b) {  // a in front of b
   Evt3Lw r;
   r.y = max(a.y, b.y); r.th = max(a.th, b.th); r.tl = max(a.tl, b.tl); r.base = max(a.base, b.base);
   r.inc = b.base ? b.inc : a.inc + b.inc;
@@ -772,39 +772,41 @@ __device__ inline void evt3_step(Evt3Lw& s, u32 w, u32 v) {  // word w at index 
   else if (t == EVT3_VECT_BASE_X) { s.base = v + 1; s.inc = 0; }
   else s.inc += evt3_base_advance(w);
 }
-__device__ inline Evt3Lw evt3_shfl_up(const Evt3Lw& a, int d) {
+__device__ inline Evt3Lw tuple_shfl_up(const Evt3Lw& a, int d) {
   Evt3Lw r;
   r.y = __shfl_up(a.y, d, ESVO_WAVE); r.th = __shfl_up(a.th, d, ESVO_WAVE); r.tl = __shfl_up(a.tl, d, ESVO_WAVE);
   r.base = __shfl_up(a.base, d, ESVO_WAVE); r.inc = __shfl_up(a.inc, d, ESVO_WAVE);
   return r;
 }
-// exclusive scan of one tuple per thread across the block, `carry` in front of thread 0; *total: carry joined with every thread's
-__device__ inline Evt3Lw evt3_block_excl(const Evt3Lw& mine, const Evt3Lw& carry, Evt3Lw* total, Evt3Lw* lds /* 4 */) {
+// exclusive scan of one tuple per thread across the block, `carry` in front of thread 0; *total: carry joined with every thread's.
+// T: any tuple with tuple_join (a in front of b) and tuple_shfl_up (the EVT 3.0 and the EVT 2.x decodes share it)
+template <class T>
+__device__ inline T tuple_block_excl(const T& mine, const T& carry, T* total, T* lds /* 4 */) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  Evt3Lw incl = mine;
+  T incl = mine;
 #pragma unroll
   for (int d = 1; d < ESVO_WAVE; d <<= 1) {
-    const Evt3Lw t = evt3_shfl_up(incl, d);
-    if (lane >= d) incl = evt3_join(t, incl);
+    const T t = tuple_shfl_up(incl, d);
+    if (lane >= d) incl = tuple_join(t, incl);
   }
   if (lane == 63) lds[wave] = incl;
   __syncthreads();
-  Evt3Lw ex = carry, tot = carry;
+  T ex = carry, tot = carry;
 #pragma unroll
   for (int w = 0; w < EVT3_B / ESVO_WAVE; ++w) {
-    const Evt3Lw s = lds[w];
-    if (w < wave) ex = evt3_join(ex, s);
-    tot = evt3_join(tot, s);
+    const T s = lds[w];
+    if (w < wave) ex = tuple_join(ex, s);
+    tot = tuple_join(tot, s);
   }
   __syncthreads();
-  const Evt3Lw prev = evt3_shfl_up(incl, 1);
-  if (lane > 0) ex = evt3_join(ex, prev);
+  const T prev = tuple_shfl_up(incl, 1);
+  if (lane > 0) ex = tuple_join(ex, prev);
   *total = tot;
   return ex;
 }
 // N values per thread reduced across the block (sum or max), the result in every thread
 template <bool SUM, int N>
-__device__ inline void evt3_block_reduce(u32 (&v)[N], u32* lds /* 4 N */) {
+__device__ inline void tile_block_reduce(u32 (&v)[N], u32* lds /* 4 N */) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
 #pragma unroll
   for (int k = 0; k < N; ++k) {
@@ -861,16 +863,22 @@ __device__ inline Evt3Lw evt3_own(const u32 (&w)[EVT3_V], u32 first) {
   for (int k = 0; k < EVT3_V; ++k) evt3_step(s, w[k], first + k);
   return s;
 }
-// the join of the tiles in front of this one.  max commutes; the advance counts from the newest VECT_BASE_X word's tile on
-__device__ inline Evt3Lw evt3_tile_carry(const Evt3Args& a, u32* lds) {
-  u32 m[4] = {0, 0, 0, 0};
-  for (u32 j = threadIdx.x; j < blockIdx.x; j += EVT3_B)
+// The tile carry of both decodes: N scratch words [at, at + N) of every tile j0 <= j < this one, summed or joined by max (max and
+// + commute, so the order in which the threads fold them does not matter); the result in every thread
+template <bool SUM, int N>
+__device__ inline void tile_fold_before(const u32* tiles, int at, u32 j0, u32 (&v)[N], u32* lds /* 4 N */) {
 #pragma unroll
-    for (int k = 0; k < 4; ++k) m[k] = max(m[k], a.tiles[j * EVT3_TILE_WORDS + k]);
-  evt3_block_reduce<false, 4>(m, lds);
-  u32 inc[1] = {0};
-  for (u32 j = (m[3] ? (m[3] - 1) / (u32)EVT3_TILE : 0u) + threadIdx.x; j < blockIdx.x; j += EVT3_B) inc[0] += a.tiles[j * EVT3_TILE_WORDS + 4];
-  evt3_block_reduce<true, 1>(inc, lds);
+  for (int k = 0; k < N; ++k) v[k] = 0;
+  for (u32 j = j0 + threadIdx.x; j < blockIdx.x; j += EVT3_B)
+#pragma unroll
+    for (int k = 0; k < N; ++k) { const u32 t = tiles[j * EVT3_TILE_WORDS + at + k]; v[k] = SUM ? v[k] + t : max(v[k], t); }
+  tile_block_reduce<SUM, N>(v, lds);
+}
+// the join of the tiles in front of this one: the advance counts from the newest VECT_BASE_X word's tile on
+__device__ inline Evt3Lw evt3_tile_carry(const Evt3Args& a, u32* lds) {
+  u32 m[4], inc[1];
+  tile_fold_before<false, 4>(a.tiles, 0, 0u, m, lds);
+  tile_fold_before<true, 1>(a.tiles, 4, m[3] ? (m[3] - 1) / (u32)EVT3_TILE : 0u, inc, lds);
   return Evt3Lw{m[0], m[1], m[2], m[3], inc[0]};
 }
 
@@ -879,7 +887,7 @@ __global__ void __launch_bounds__(256) evt3_lw_kernel(Evt3Args a) {
   u32 w[EVT3_V], first;
   evt3_load(a, w, &first);
   Evt3Lw tot;
-  (void)evt3_block_excl(evt3_own(w, first), Evt3Lw{0, 0, 0, 0, 0}, &tot, lds);
+  (void)tuple_block_excl(evt3_own(w, first), Evt3Lw{0, 0, 0, 0, 0}, &tot, lds);
   if (threadIdx.x == 0) {
     u32* t = a.tiles + (size_t)blockIdx.x * EVT3_TILE_WORDS;
     t[0] = tot.y; t[1] = tot.th; t[2] = tot.tl; t[3] = tot.base; t[4] = tot.inc;
@@ -894,7 +902,7 @@ __global__ void __launch_bounds__(256) evt3_count_kernel(Evt3Args a) {
   u32 w[EVT3_V], first;
   evt3_load(a, w, &first);
   Evt3Lw tot;
-  Evt3Lw s = evt3_block_excl(evt3_own(w, first), carry, &tot, lds);
+  Evt3Lw s = tuple_block_excl(evt3_own(w, first), carry, &tot, lds);
   u32 c[5] = {0, 0, 0, 0, 0};  // events, time loops, dropped events, ignored words, external triggers
 #pragma unroll
   for (int k = 0; k < EVT3_V; ++k) {
@@ -905,7 +913,7 @@ __global__ void __launch_bounds__(256) evt3_count_kernel(Evt3Args a) {
     else if (w[k] != EVT3_NO_WORD && (t == 0x1 || t == 0x7 || t == 0x9 || t >= 0xB)) c[3] += 1u;
     evt3_step(s, w[k], first + k);
   }
-  evt3_block_reduce<true, 5>(c, red);
+  tile_block_reduce<true, 5>(c, red);
   if (threadIdx.x == 0) {
     u32* t = a.tiles + (size_t)blockIdx.x * EVT3_TILE_WORDS;
     t[5] = c[0]; t[6] = c[1];
@@ -922,14 +930,13 @@ __global__ void __launch_bounds__(256) evt3_expand_kernel(Evt3Args a, u64* __res
   __shared__ Evt3Lw lds[EVT3_B / ESVO_WAVE];
   __shared__ u32 red[4 * EVT3_B / ESVO_WAVE];
   const Evt3Lw carry = evt3_tile_carry(a, red);
-  u32 before[2] = {0, 0};  // events and time loops of the tiles in front
-  for (u32 j = threadIdx.x; j < blockIdx.x; j += EVT3_B) { before[0] += a.tiles[j * EVT3_TILE_WORDS + 5]; before[1] += a.tiles[j * EVT3_TILE_WORDS + 6]; }
-  evt3_block_reduce<true, 2>(before, red);
+  u32 before[2];  // events and time loops of the tiles in front
+  tile_fold_before<true, 2>(a.tiles, 5, 0u, before, red);
   const bool write = (size_t)a.hdr[EVT3_H_EVENTS] <= col_cap;  // (launch 2's total: complete)
   u32 w[EVT3_V], first;
   evt3_load(a, w, &first);
   Evt3Lw tot;
-  const Evt3Lw s0 = evt3_block_excl(evt3_own(w, first), carry, &tot, lds);
+  const Evt3Lw s0 = tuple_block_excl(evt3_own(w, first), carry, &tot, lds);
   u32 n_ev = 0, n_loop = 0;
   {
     Evt3Lw s = s0;
@@ -997,6 +1004,165 @@ void launch_evt3_decode(const uint16_t* words, size_t n_words, const esvo_evt3_s
   hipLaunchKernelGGL(evt3_lw_kernel, grid, block, 0, s, a);
   hipLaunchKernelGGL(evt3_count_kernel, grid, block, 0, s, a);
   hipLaunchKernelGGL(evt3_expand_kernel, grid, block, 0, s, a, stamps, x, y, p, col_cap);
+}
+
+// ---- EVT 2.0 / 2.1 ingest (esvo_ts_push_evt2): 32- / 64-bit words -> the camera's column staging ------------------------------
+// The same three dependent launches over tiles of 2048 words, with the block scan, the tile fold and the header of the EVT 3.0
+// decode.  The only carried state is the newest TIME_HIGH: the tuple of a word is index + 1 of the newest TIME_HIGH word at or
+// before it (operator max; 0: the carried state holds), the two sums are emitted events and time-loop flags.
+//   1  evt2_th_kernel      per tile the newest TIME_HIGH index
+//   2  evt2_count_kernel   the tiles in front folded in -> the state in front of every word: events, dropped events, loop flags
+//                          (a TIME_HIGH word needs the TIME_HIGH in front of it alone) -> per-tile sums, the packet's totals
+//   3  evt2_expand_kernel  the same scan with the sums of the tiles in front; the last tile leaves the end state
+// A tile is walked in 8 rounds of 256 words, thread t owning word 256 r + t of the tile: the loads of a wave are consecutive 4-byte
+// words whatever the base's alignment and whichever half comes first (evt2_word), and a round's carry is the scan's total.
+// Expansion: one EVT 2.1 word stands for up to 32 events, so no thread writes "its" events.  A wave takes the words of its 64 lanes
+// two per step: lanes 0-31 are the valid bits of word 2j, lanes 32-63 those of word 2j + 1; a lane whose bit is set writes event
+// offset + popcount(valid & lanes below), so that the stamps / x / y / p stores of a step are two contiguous runs.  Steps whose two
+// words emit nothing are skipped (wave-uniform).  Where no word of a wave's 64 emits more than one event (every EVT 2.0 word; sparse
+// EVT 2.1 words) the lanes write their own event instead, which is the same contiguous run without the 32 steps.
+namespace {
+struct Evt2Th { u32 th; };
+__device__ inline Evt2Th tuple_join(const Evt2Th& a, const Evt2Th& b) { return Evt2Th{max(a.th, b.th)}; }
+__device__ inline Evt2Th tuple_shfl_up(const Evt2Th& a, int d) { return Evt2Th{(u32)__shfl_up(a.th, d, ESVO_WAVE)}; }
+
+struct Evt2Args {
+  const u32* words;      // the packet (4-byte aligned)
+  u32 n;                 // its words, of the format
+  int format;
+  esvo_evt2_state_t st;  // the state in front of the packet
+  int64_t t_offset_us;
+  u32* tiles;            // per tile: [0] its newest TIME_HIGH index + 1 (launch 1), [5] events, [6] time loops (launch 2)
+  u32* hdr;
+};
+// what one word does under the state in front of it (s: newest TIME_HIGH index + 1 in front of it; 0: the carried state)
+struct Evt2Word {
+  u64 W; u32 type, th, ev, dropped, loop; bool valid;
+};
+__device__ inline u32 evt2_th_in_front(const Evt2Args& a, u32 s) { return s ? evt2_time_high(evt2_word(a.words, s - 1, a.format)) : a.st.time_high; }
+__device__ inline Evt2Word evt2_at(const Evt2Args& a, u32 i) {  // word i of the packet, not yet seen under a state
+  Evt2Word w{};
+  w.valid = i < a.n;
+  w.W = w.valid ? evt2_word(a.words, i, a.format) : 0ull;
+  w.type = w.valid ? evt2_type(w.W) : 0xFu;
+  return w;
+}
+__device__ inline void evt2_under(const Evt2Args& a, Evt2Word& w, u32 s) {
+  if (!w.valid) return;
+  const u32 flags = a.st.flags | (s ? (u32)EVT2_HAVE_TH : 0u), m = evt2_mask(w.W);
+  if (m) {
+    if (evt2_emits(flags)) { w.ev = __popc(m); w.th = evt2_th_in_front(a, s); }
+    else w.dropped = __popc(m);
+  } else if (w.type == EVT2_TIME_HIGH)
+    w.loop = evt2_time_loop(evt2_emits(flags), evt2_th_in_front(a, s), evt2_time_high(w.W)) ? 1u : 0u;
+}
+// one round of the tile: the thread's word under the state in front of it; `carry` moves on to the round's end
+__device__ inline Evt2Word evt2_round(const Evt2Args& a, int r, Evt2Th& carry, Evt2Th* lds) {
+  const u32 i = blockIdx.x * (u32)EVT3_TILE + (u32)r * EVT3_B + threadIdx.x;
+  Evt2Word w = evt2_at(a, i);
+  Evt2Th tot;
+  const Evt2Th s = tuple_block_excl(Evt2Th{w.type == EVT2_TIME_HIGH ? i + 1 : 0u}, carry, &tot, lds);
+  carry = tot;
+  evt2_under(a, w, s.th);
+  return w;
+}
+
+__global__ void __launch_bounds__(256) evt2_th_kernel(Evt2Args a) {
+  __shared__ u32 red[EVT3_B / ESVO_WAVE];
+  u32 m[1] = {0};
+  for (int r = 0; r < EVT3_V; ++r) {
+    const u32 i = blockIdx.x * (u32)EVT3_TILE + (u32)r * EVT3_B + threadIdx.x;
+    if (evt2_at(a, i).type == EVT2_TIME_HIGH) m[0] = i + 1;  // (rounds ascend)
+  }
+  tile_block_reduce<false, 1>(m, red);
+  if (threadIdx.x == 0) a.tiles[(size_t)blockIdx.x * EVT3_TILE_WORDS] = m[0];
+  if (blockIdx.x == 0 && threadIdx.x < EVT3_HDR_WORDS) a.hdr[threadIdx.x] = threadIdx.x == EVT3_H_FIRST_BAD ? 0xffffffffu : 0u;
+}
+
+__global__ void __launch_bounds__(256) evt2_count_kernel(Evt2Args a) {
+  __shared__ Evt2Th lds[EVT3_B / ESVO_WAVE];
+  __shared__ u32 red[5 * EVT3_B / ESVO_WAVE];
+  u32 m[1];
+  tile_fold_before<false, 1>(a.tiles, 0, 0u, m, red);
+  Evt2Th carry{m[0]};
+  u32 c[5] = {0, 0, 0, 0, 0};  // events, time loops, dropped events, ignored words, external triggers
+  for (int r = 0; r < EVT3_V; ++r) {
+    const Evt2Word w = evt2_round(a, r, carry, lds);
+    c[0] += w.ev; c[1] += w.loop; c[2] += w.dropped;
+    if (w.valid && evt2_counts_as_ignored(w.type)) c[3] += 1u;
+    if (w.valid && w.type == EVT2_EXT_TRIGGER) c[4] += 1u;
+  }
+  tile_block_reduce<true, 5>(c, red);
+  if (threadIdx.x == 0) {
+    u32* t = a.tiles + (size_t)blockIdx.x * EVT3_TILE_WORDS;
+    t[5] = c[0]; t[6] = c[1];
+    if (c[0]) atomicAdd(a.hdr + EVT3_H_EVENTS, c[0]);
+    if (c[1]) atomicAdd(a.hdr + EVT3_H_LOOPS, c[1]);
+    if (c[2]) atomicAdd(a.hdr + EVT3_H_DROPPED, c[2]);
+    if (c[3]) atomicAdd(a.hdr + EVT3_H_IGNORED, c[3]);
+    if (c[4]) atomicAdd(a.hdr + EVT3_H_EXT, c[4]);
+  }
+}
+
+__global__ void __launch_bounds__(256) evt2_expand_kernel(Evt2Args a, u64* __restrict__ stamps, uint16_t* __restrict__ x,
+                                                          uint16_t* __restrict__ y, uint8_t* __restrict__ p, size_t col_cap) {
+  __shared__ Evt2Th lds[EVT3_B / ESVO_WAVE];
+  __shared__ u32 red[2 * EVT3_B / ESVO_WAVE];
+  u32 m[1], before[2];
+  tile_fold_before<false, 1>(a.tiles, 0, 0u, m, red);
+  tile_fold_before<true, 2>(a.tiles, 5, 0u, before, red);  // events and time loops of the tiles in front
+  const bool write = (size_t)a.hdr[EVT3_H_EVENTS] <= col_cap;  // (launch 2's total: complete)
+  const int lane = threadIdx.x & 63, half = lane >> 5, bit = lane & 31;
+  Evt2Th carry{m[0]};
+  u32 at0 = before[0], loops0 = a.st.loops + before[1];
+  for (int r = 0; r < EVT3_V; ++r) {
+    const Evt2Word w = evt2_round(a, r, carry, lds);
+    u32 round_ev, round_loops;
+    const u32 at = at0 + block_excl_scan(w.ev, &round_ev, red);
+    const u32 loops = loops0 + block_excl_scan(w.loop, &round_loops, red);  // (a TIME_HIGH word's own flag counts for the words behind it)
+    at0 += round_ev; loops0 += round_loops;
+    u64 stamp = 0;
+    if (w.ev) {
+      stamp = evt2_stamp_ns(loops, w.th, w.W, a.t_offset_us);
+      if (stamp == COL_BAD_STAMP) atomicMin(a.hdr + EVT3_H_FIRST_BAD, at);
+    }
+    if (!write) continue;  // (uniform across the grid)
+    const u32 x0 = evt2_x0(w.W), yy = evt2_y(w.W), pol = w.type;
+    const u32 mine = w.ev ? evt2_mask(w.W) : 0u, xyp = x0 | (yy << 11) | (pol << 22);
+    if (!__any(__popc(mine) > 1)) {  // (wave-uniform) no word of the wave emits two events: the lanes' own stores are the contiguous run
+      if (mine) { stamps[at] = stamp; x[at] = (uint16_t)((x0 + (u32)__ffs(mine) - 1u) & 0xFFFFu); y[at] = (uint16_t)yy; p[at] = (uint8_t)pol; }
+      continue;
+    }
+    const unsigned long long any = __ballot(mine != 0u);
+    for (int j = 0; j < ESVO_WAVE / 2; ++j) {
+      if (!((any >> (2 * j)) & 3ull)) continue;  // (wave-uniform)
+      const int src = 2 * j + half;
+      const u32 sm = __shfl(mine, src, ESVO_WAVE), so = __shfl(at, src, ESVO_WAVE), sx = __shfl(xyp, src, ESVO_WAVE);
+      const u32 slo = __shfl((u32)stamp, src, ESVO_WAVE), shi = __shfl((u32)(stamp >> 32), src, ESVO_WAVE);
+      if ((sm >> bit) & 1u) {
+        const u32 o = so + __popc(sm & ((1u << bit) - 1u));
+        stamps[o] = ((u64)shi << 32) | slo;
+        x[o] = (uint16_t)(((sx & 0x7FFu) + (u32)bit) & 0xFFFFu); y[o] = (uint16_t)((sx >> 11) & 0x7FFu); p[o] = (uint8_t)(sx >> 22);
+      }
+    }
+  }
+  if (blockIdx.x == gridDim.x - 1 && threadIdx.x == 0) {  // the end state: the state in front of the packet joined with all of it
+    a.hdr[EVT3_H_FLAGS] = a.st.flags | (carry.th ? (u32)EVT2_HAVE_TH : 0u);
+    a.hdr[EVT3_H_TIME] = evt2_th_in_front(a, carry.th);
+    a.hdr[EVT3_H_LOOPS_END] = loops0;
+  }
+}
+}  // namespace
+
+u32 evt2_tiles(size_t n_words) { return (u32)((n_words + EVT3_TILE - 1) / EVT3_TILE); }
+void launch_evt2_decode(const u32* words, size_t n_words, int format, const esvo_evt2_state_t& st, int64_t t_offset_us, u32* tiles, u32* hdr,
+                        u64* stamps, uint16_t* x, uint16_t* y, uint8_t* p, size_t col_cap, hipStream_t s) {
+  if (n_words == 0 || n_words > EVT2_DEVICE_MAX_WORDS || !evt2_format_known(format)) return;
+  const Evt2Args a{words, (u32)n_words, format, st, t_offset_us, tiles, hdr};
+  const dim3 grid(evt2_tiles(n_words)), block(EVT3_B);
+  hipLaunchKernelGGL(evt2_th_kernel, grid, block, 0, s, a);
+  hipLaunchKernelGGL(evt2_count_kernel, grid, block, 0, s, a);
+  hipLaunchKernelGGL(evt2_expand_kernel, grid, block, 0, s, a, stamps, x, y, p, col_cap);
 }
 
 }  // namespace esvo

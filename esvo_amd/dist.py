@@ -157,6 +157,9 @@ class ShardedEsvo:
     def ts_push_evt3(self, cam, words, t_offset_us=0):
         return self.dev.ts_push_evt3(cam, words, t_offset_us)
 
+    def ts_push_evt2(self, cam, words, format, t_offset_us=0):
+        return self.dev.ts_push_evt2(cam, words, format, t_offset_us)
+
     def ts_render(self, cam, t_ns, download=True):
         return self.dev.ts_render(cam, t_ns, download)
 
@@ -270,6 +273,9 @@ class TickShardedEsvo:
     def ts_push_evt3(self, cam, words, t_offset_us=0):
         return self.dev.ts_push_evt3(cam, words, t_offset_us)
 
+    def ts_push_evt2(self, cam, words, format, t_offset_us=0):
+        return self.dev.ts_push_evt2(cam, words, format, t_offset_us)
+
     def ts_render(self, cam, t_ns, download=True):
         if self._is_mine():  # the SAE only has to be current at this rank's own ticks
             return self.dev.ts_render(cam, t_ns, download)
@@ -379,6 +385,9 @@ class NativeTickSharded:
     def ts_push_evt3(self, cam, words, t_offset_us=0):
         return self.dev.ts_push_evt3(cam, words, t_offset_us)
 
+    def ts_push_evt2(self, cam, words, format, t_offset_us=0):
+        return self.dev.ts_push_evt2(cam, words, format, t_offset_us)
+
     def ts_render(self, cam, t_ns, download=True):
         if self.dev.comm_owns_next_tick():  # the SAE only has to be current at this rank's own ticks
             return self.dev.ts_render(cam, t_ns, download)
@@ -458,6 +467,9 @@ class NativeBandSharded:
 
     def ts_push_evt3(self, cam, words, t_offset_us=0):
         return self.dev.ts_push_evt3(cam, words, t_offset_us)
+
+    def ts_push_evt2(self, cam, words, format, t_offset_us=0):
+        return self.dev.ts_push_evt2(cam, words, format, t_offset_us)
 
     def ts_render(self, cam, t_ns, download=True):
         return self.dev.ts_render(cam, t_ns, download)

@@ -10,7 +10,7 @@ import subprocess
 
 import numpy as np
 
-from .abi import (MEM_DEVICE, MEM_HOST, P_U8, ColumnsError, EventColumnsStruct, Evt3Counts, Evt3State, evt3_words, check_t_offset, column_p_type, column_t_type,
+from .abi import (MEM_DEVICE, MEM_HOST, P_U8, ColumnsError, EventColumnsStruct, Evt2Counts, Evt2State, Evt3Counts, Evt3State, evt2_words, evt3_words, check_t_offset, column_p_type, column_t_type,
                   DEPTH_POINT_DTYPE, EM_POSE_FN, ERR_CAPACITY, ERR_INVALID_ARG, ERR_STATE, EVENT_DTYPE, MATCH_DTYPE, CalibStruct, EmSelectionStruct,
                   EmStatsStruct, GpcParamsStruct, GpcStatsStruct, LmStatsStruct, ParamsStruct, SgmStatsStruct, StatsStruct, TRACK_ITER_DTYPE, TRACK_SOLVE_MAX_ITERATIONS,
                   TrackSolveInfoStruct, TrackSolveParamsStruct)
@@ -24,7 +24,7 @@ HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off"
 
 SYMBOLS = [
     "esvo_default_params", "esvo_create", "esvo_destroy", "esvo_reset", "esvo_set_params", "esvo_last_error",
-    "esvo_set_stream", "esvo_synchronize", "esvo_ts_push_events", "esvo_ts_push_events_async", "esvo_ts_push_wait", "esvo_host_alloc", "esvo_host_free", "esvo_ts_push_event_array", "esvo_ts_push_event_columns", "esvo_event_columns_to_events", "esvo_event_columns_sizes", "esvo_ts_render", "esvo_ts_render_forward", "esvo_map_set_observation",
+    "esvo_set_stream", "esvo_synchronize", "esvo_ts_push_events", "esvo_ts_push_events_async", "esvo_ts_push_wait", "esvo_host_alloc", "esvo_host_free", "esvo_ts_push_event_array", "esvo_ts_push_event_columns", "esvo_event_columns_to_events", "esvo_event_columns_sizes", "esvo_raw_header", "esvo_ts_render", "esvo_ts_render_forward", "esvo_map_set_observation",
     "esvo_map_match", "esvo_map_set_poses", "esvo_map_refine", "esvo_map_push_frame", "esvo_map_fuse",
     "esvo_map_tick", "esvo_map_tick_bm_only", "esvo_map_fuse_matches_naive", "esvo_map_tick_resident", "esvo_map_get_depth_points", "esvo_map_get_committed", "esvo_map_get_pointcloud_xyz", "esvo_map_get_last_frame",
     "esvo_get_stats", "esvo_shard_set_band", "esvo_shard_set_routing", "esvo_shard_get_rows", "esvo_shard_exchange", "esvo_shard_tick_phase", "esvo_abi_sizes",
@@ -47,7 +47,9 @@ SYMBOLS = [
     "esvo_track_set_current_at", "esvo_ts_history_select", "esvo_ts_history_select_observation",
 ]
 # the EVT 3.0 entry points, listed apart: their names carry a digit (SYMBOLS is compared with a scan of the header for [a-z_] names)
-SYMBOLS_EVT3 = ["esvo_ts_push_evt3", "esvo_ts_evt3_state", "esvo_ts_evt3_stats", "esvo_evt3_to_events", "esvo_evt3_raw_header", "esvo_evt3_sizes"]
+SYMBOLS_EVT3 = ["esvo_ts_push_evt3", "esvo_ts_evt3_state", "esvo_ts_evt3_stats", "esvo_evt3_to_events", "esvo_evt3_raw_header", "esvo_evt3_sizes",
+                # EVT 2.0 / 2.1 (esvo_raw_header has no digit and stands in SYMBOLS)
+                "esvo_ts_push_evt2", "esvo_ts_evt2_state", "esvo_ts_evt2_stats", "esvo_evt2_to_events", "esvo_evt2_sizes"]
 
 ALL_GATHER_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p)
 
@@ -166,6 +168,13 @@ def load():
     lib.esvo_evt3_raw_header.argtypes = [vp, sz, psz, C.POINTER(C.c_int), C.POINTER(C.c_int)]
     lib.esvo_evt3_sizes.argtypes = [vp]
     lib.esvo_evt3_sizes.restype = None
+    lib.esvo_ts_push_evt2.argtypes = [vp, i32, vp, sz, i32, i32, C.c_int64, psz]
+    lib.esvo_ts_evt2_state.argtypes = [vp, i32, vp, vp]
+    lib.esvo_ts_evt2_stats.argtypes = [vp, i32, vp]
+    lib.esvo_evt2_to_events.argtypes = [vp, vp, sz, i32, C.c_int64, vp, sz, psz, vp]
+    lib.esvo_raw_header.argtypes = [vp, sz, psz, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]
+    lib.esvo_evt2_sizes.argtypes = [vp]
+    lib.esvo_evt2_sizes.restype = None
     lib.esvo_ts_render.argtypes = [vp, i32, u64, vp]
     lib.esvo_ts_render_forward.argtypes = [vp, i32, u64, vp]
     lib.esvo_map_set_observation.argtypes = [vp, u64, vp, vp, vp]
@@ -268,7 +277,7 @@ def load():
     lib.esvo_ts_history_select_observation.argtypes = [vp, i32, EM_POSE_FN, vp, C.POINTER(C.c_uint64), vp]
     for s in SYMBOLS + SYMBOLS_EVT3:
         if s not in ("esvo_default_params", "esvo_last_error", "esvo_abi_sizes", "esvo_bag_last_error", "esvo_em_sizes", "esvo_lm_sizes", "esvo_sgm_sizes",
-                     "esvo_track_sizes", "esvo_gpc_sizes", "esvo_event_columns_sizes", "esvo_evt3_sizes"):
+                     "esvo_track_sizes", "esvo_gpc_sizes", "esvo_event_columns_sizes", "esvo_evt3_sizes", "esvo_evt2_sizes"):
             getattr(lib, s).restype = C.c_int
     lib.esvo_abi_sizes.argtypes = [vp]
     lib.esvo_abi_sizes.restype = None
@@ -743,6 +752,13 @@ def evt3_sizes():
     return list(out)
 
 
+def evt2_sizes():
+    """sizeof(esvo_evt2_state_t), sizeof(esvo_evt2_counts_t), 0, 0 (esvo_evt2_sizes)"""
+    out = (C.c_size_t * 4)()
+    load().esvo_evt2_sizes(out)
+    return list(out)
+
+
 def abi_sizes():
     out = (C.c_size_t * 8)()
     load().esvo_abi_sizes(out)
@@ -904,6 +920,47 @@ class Esvo:
         fn = _dbg_fn("esvo_debug_evt3_device_min", [C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)])
         prev = C.c_size_t(0)
         self._ck(fn(self.h, int(n_words), C.byref(prev)))
+        return int(prev.value)
+
+    def ts_push_evt2(self, cam, words, format, t_offset_us=0):
+        """stage events from Prophesee EVT 2.0 / 2.1 words (esvo_ts_push_evt2; format: abi.EVT_2_0, EVT_2_1 or EVT_2_1_LEGACY): `words`
+        is bytes / bytearray / memoryview, a numpy array of 4-byte integers (two per EVT 2.1 word; 8-byte integers for EVT 2.1 as
+        well), or such device memory behind data_ptr() / is_cuda (a torch tensor) or __cuda_array_interface__, one-dimensional and
+        contiguous; a 4-byte aligned base suffices.  The camera's decoder state carries over from call to call (evt2_state / reset).
+        Device words must be complete: torch's current stream is synchronised here.  Synchronous.  Returns the number of events."""
+        if isinstance(words, (bytes, bytearray, memoryview)):
+            words = evt2_words(words, format)
+        addr, dt, n, on_device, _keep = _column(words, "words")
+        if dt.kind not in "iu" or dt.itemsize not in ((4,) if format == 20 else (4, 8)):
+            raise ValueError(f"EVT2 words: 4-byte integers (or 8-byte ones for EVT 2.1) are expected, not {dt}")
+        if on_device:
+            import sys
+            torch = sys.modules.get("torch")
+            if torch is not None and torch.cuda.is_available():
+                torch.cuda.current_stream().synchronize()
+        n_ev = C.c_size_t(0)
+        self._ck(self.lib.esvo_ts_push_evt2(self.h, int(cam), addr or None, dt.itemsize * n, int(format), MEM_DEVICE if on_device else MEM_HOST,
+                                            check_t_offset(t_offset_us), C.byref(n_ev)))
+        return int(n_ev.value)
+
+    def evt2_state(self, cam, set=None):
+        """the camera's EVT 2.x decoder state (an abi.Evt2State); set: an Evt2State that replaces it (a reader seeks or resumes)"""
+        got = Evt2State()
+        self._ck(self.lib.esvo_ts_evt2_state(self.h, int(cam), C.addressof(got), None if set is None else C.addressof(set)))
+        return got
+
+    def evt2_stats(self, cam):
+        """running totals of the camera's ts_push_evt2 calls as a dict (esvo_ts_evt2_stats); cleared by reset"""
+        tot = Evt2Counts()
+        self._ck(self.lib.esvo_ts_evt2_stats(self.h, int(cam), C.addressof(tot)))
+        return tot.as_dict()
+
+    def debug_evt2_device_min(self, n_bytes):
+        """packets of fewer bytes are decoded on the host, for every EVT 2.x format (esvo_debug_evt2_device_min; not part of the ABI)
+        -> the previous bound of EVT 2.0"""
+        fn = _dbg_fn("esvo_debug_evt2_device_min", [C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)])
+        prev = C.c_size_t(0)
+        self._ck(fn(self.h, int(n_bytes), C.byref(prev)))
         return int(prev.value)
 
     def debug_ts_ring(self, cam, first_abs=None, n=None):

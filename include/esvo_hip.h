@@ -18,7 +18,7 @@
  *     concurrently, one thread per group -- the threading of the reference's nodes (esvo_Mapping.cpp:160,179-247: the
  *     MappingLoop worker thread; :669-703 and TimeSurface.cpp:403-425: eventsCallback on the ROS spinner under
  *     data_mutex_; esvo_Tracking's own loop):
- *       INGEST   esvo_ts_push_events(_async), esvo_ts_push_wait, esvo_ts_push_event_array, esvo_ts_push_event_columns, esvo_ts_push_evt3, esvo_ts_push_bag (one thread per camera is fine)
+ *       INGEST   esvo_ts_push_events(_async), esvo_ts_push_wait, esvo_ts_push_event_array, esvo_ts_push_event_columns, esvo_ts_push_evt3, esvo_ts_push_evt2, esvo_ts_push_bag (one thread per camera is fine)
  *       TRACKER  esvo_track_*
  *       MAPPER   every other call that takes the handle (renders, observation, ticks, stage-wise calls, outputs,
  *                parameters, esvo_comm_*, esvo_reset -- which excludes the other two groups while it runs)
@@ -361,8 +361,8 @@ void esvo_event_columns_sizes(size_t out[4]);
  *   every other source.  A stream starts with all state zero.
  *   PARITY UNPINNED in two points, which follow no third-party decoder: the time-loop threshold (a TIME_HIGH step back of 2048 units
  *   or more is a loop, a smaller one is not) and TIME_LOW being kept across a TIME_HIGH word.  Cameras send monotone TIME_HIGH words
- *   many times per millisecond, so every sane rule agrees on their streams.  Out of scope: EVT 2.0 / 2.1, delivery of EXT_TRIGGER
- *   events, AEDAT4.
+ *   many times per millisecond, so every sane rule agrees on their streams.  Out of scope: delivery of EXT_TRIGGER events, AEDAT4,
+ *   the Prophesee DAT format.  (EVT 2.0 / 2.1: esvo_ts_push_evt2 below.)
  *   The decoder state is kept per camera and carried from one call to the next: a stream may be cut at any word boundary.
  *   esvo_reset clears the state and the totals of both cameras; esvo_ts_evt3_state(set) lets a reader seek or resume.
  *   Behaviour: exactly that of esvo_ts_push_events handed the decoded records, in everything a later call can observe -- the in-order
@@ -403,6 +403,66 @@ int esvo_evt3_to_events(esvo_evt3_state_t* st, const uint16_t* words, size_t n_w
 int esvo_evt3_raw_header(const uint8_t* file, size_t n_bytes, size_t* data_offset, int* width, int* height);
 /* sizeof(esvo_evt3_state_t), sizeof(esvo_evt3_counts_t), 0, 0 */
 void esvo_evt3_sizes(size_t out[4]);
+/* The same from Prophesee EVT 2.0 words (Gen3.1 / Gen4 kits, most archived .raw recordings) and EVT 2.1 words (the vectorised format of
+ * the high-rate sensors), decoded on the device.
+ *   EVT 2.0: little-endian uint32 words w; type = w >> 28:
+ *     0x0 CD_OFF, 0x1 CD_ON  one event: x = (w >> 11) & 0x7FF, y = w & 0x7FF, ts6 = (w >> 22) & 0x3F, polarity = type.  The word emits
+ *                            iff have_th; otherwise dropped_events += 1.
+ *     0x8 EVT_TIME_HIGH      v = w & 0x0FFFFFFF; if have_th && v < time_high && time_high - v >= 2^27: loops += 1.  Then time_high = v;
+ *                            have_th = 1.
+ *     0xA EXT_TRIGGER        ignored, counted in ext_triggers
+ *     every other type (0xE OTHERS, 0xF CONTINUED included): ignored, counted in ignored_words
+ *   EVT 2.1: 64-bit words W; type = W >> 60, ts6 = (W >> 54) & 0x3F, x0 = (W >> 43) & 0x7FF, y = (W >> 32) & 0x7FF,
+ *   valid = W & 0xFFFFFFFF:
+ *     0x0 EVT_NEG, 0x1 EVT_POS  for i = 0..31 ascending with bit i of valid set: event (x0 + i, y, t, type).  x0 need not be a multiple
+ *                            of 32; x0 + i fits 16 bits.  The word emits iff have_th; otherwise dropped_events += popcount(valid).
+ *     0x8 EVT_TIME_HIGH      v = (W >> 32) & 0x0FFFFFFF, the rule of EVT 2.0
+ *     0xA / every other type: as in EVT 2.0
+ *     In memory a word is two little-endian uint32: ESVO_EVT_2_1: W = (u64)second << 32 | first, a plain little-endian uint64;
+ *     ESVO_EVT_2_1_LEGACY: W = (u64)first << 32 | second, the upper half stored first.
+ *   t_us = loops << 34 | time_high << 6 | ts6; loops >= 2^18 makes the stamp invalid (it would lie outside the range anyway, and the
+ *   arithmetic stays inside 64 bits).  stamp_ns = (t_us + t_offset_us) * 1000, by the conversion of ESVO_T_US_I64 columns above: a stamp
+ *   outside [0, 2^32 * 10^9) makes the call fail and esvo_last_error names the first bad EVENT index.  x and y are not checked against
+ *   the sensor: the scatter skips events outside the image, as for every other source.  A stream starts with all state zero.
+ *   PARITY UNPINNED: no Prophesee decoder or document was at hand; the tables follow the published description as recalled, and
+ *   nothing third-party pins them.  Three points in particular: the time-loop threshold (a TIME_HIGH step back of 2^27 units or more
+ *   is a loop, a smaller one is not); the half order of EVT 2.1 (ESVO_EVT_2_1 reads a word as one little-endian uint64,
+ *   ESVO_EVT_2_1_LEGACY with the upper half first); and a "% evt 2.1" header without an endianness field, which esvo_raw_header takes
+ *   for ESVO_EVT_2_1 (only "endianness=legacy" on the format line selects the legacy order).  Out of scope: delivery of EXT_TRIGGER
+ *   events, AEDAT4, the Prophesee DAT format.
+ *   esvo_ts_push_evt2 behaves sentence for sentence as esvo_ts_push_evt3 above: exactly as esvo_ts_push_events handed the decoded
+ *   records, in everything a later call can observe (the in-order fast path; the out-of-order merge with its late marks and
+ *   stats.late_events; the queue mode's second copies; the routed band path and its refusals; the same capacity and state errors);
+ *   ALL OR NOTHING: any failure stages nothing and leaves the decoder state and the totals as they were; a packet that emits no event
+ *   still advances the state and the totals; synchronous; for ESVO_MEM_DEVICE the first and last byte are checked with
+ *   hipPointerGetAttributes before any launch or copy.  The state is per camera, carried across calls, cleared by esvo_reset; ONE state
+ *   serves the three formats.  ESVO_ERR_INVALID_ARG: an unknown format (ESVO_EVT_3_0 included: that is esvo_ts_push_evt3's), n_bytes
+ *   not a multiple of 4 (EVT 2.0) or 8 (EVT 2.1), a base that is not 4-byte aligned (4 bytes suffice for EVT 2.1 as well: a slice of an
+ *   int32 tensor is a legal argument), more than 2^31 - 1 words.
+ *   In-order packets on an unrouted handle are decoded by three dependent launches over tiles of 2048 words (the newest TIME_HIGH in
+ *   front of every word by a max scan; the event and time-loop counts; the expansion into the column staging, where a wave writes two
+ *   EVT 2.1 words per step, lane = bit index, so that stamps / x / y / p go out coalesced) and one 64-byte read-back decides before
+ *   anything touches the ring.  Packets on a routed handle, out-of-order packets, packets below the host / device bound and packets
+ *   above the tile limit are decoded on the host by esvo_evt2_to_events. */
+enum { ESVO_EVT_2_0 = 20, ESVO_EVT_2_1 = 21, ESVO_EVT_2_1_LEGACY = 121, ESVO_EVT_3_0 = 30 };
+typedef struct esvo_evt2_state_t { uint32_t flags /* bit0 have_th */, time_high, loops, reserved; } esvo_evt2_state_t;
+typedef esvo_evt3_counts_t esvo_evt2_counts_t;   /* words (32- or 64-bit, by format), events, dropped_events, ignored_words, ext_triggers, time_loops */
+int esvo_ts_push_evt2(esvo_handle h, int cam, const void* words, size_t n_bytes, int format /* ESVO_EVT_2_0 | ESVO_EVT_2_1 | ESVO_EVT_2_1_LEGACY */,
+                      int memory /* ESVO_MEM_HOST | ESVO_MEM_DEVICE */, int64_t t_offset_us, size_t* n_events /* nullable */);
+/* get (nullable) receives the camera's decoder state, then set (nullable) replaces it (flags masked to bit 0, time_high to 28 bits) */
+int esvo_ts_evt2_state(esvo_handle h, int cam, esvo_evt2_state_t* get, const esvo_evt2_state_t* set);
+/* running totals of the camera's successful esvo_ts_push_evt2 calls; cleared by esvo_reset */
+int esvo_ts_evt2_stats(esvo_handle h, int cam, esvo_evt2_counts_t* totals);
+/* The decoder alone: host only, no handle, no GPU; the contract of esvo_evt3_to_events (out == NULL counts; *st advances only on
+ * ESVO_OK; a bad stamp: ESVO_ERR_INVALID_ARG with *n_out the index of the first bad event; more events than cap: ESVO_ERR_CAPACITY) */
+int esvo_evt2_to_events(esvo_evt2_state_t* st, const void* words, size_t n_bytes, int format, int64_t t_offset_us,
+                        esvo_event_t* out, size_t cap, size_t* n_out, esvo_evt2_counts_t* counts);
+/* The general form of esvo_evt3_raw_header: *format (nullable) receives ESVO_EVT_2_0 for "% evt 2.0" / "% format EVT2;...",
+ * ESVO_EVT_2_1 for "% evt 2.1" / "% format EVT21;...", ESVO_EVT_2_1_LEGACY where the format line carries "endianness=legacy",
+ * ESVO_EVT_3_0 for 3.0 / EVT3, 0 if no line names a format.  Any other named format: ESVO_ERR_UNSUPPORTED. */
+int esvo_raw_header(const uint8_t* file, size_t n_bytes, size_t* data_offset, int* width, int* height, int* format);
+/* sizeof(esvo_evt2_state_t), sizeof(esvo_evt2_counts_t), 0, 0 */
+void esvo_evt2_sizes(size_t out[4]);
 /* rosbag (format 2.0) ingest, SURVEY.md §8(f).2: the reading side of events_repacking_helper
  * (events_repacking_helper/src/EventMessageEditor.cpp:66-119: rosbag::Bag::open, rosbag::View over an event topic,
  * MessageInstance::instantiate<dvs_msgs::EventArray>).  Chunks (compression none / bz2 / lz4) are walked in file order;

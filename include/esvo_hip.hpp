@@ -120,6 +120,12 @@ class TimeSurface {
     ctx_->check(esvo_ts_push_evt3(ctx_->handle(), cam_, words, n_bytes, memory, t_offset_us, &n_events), "esvo_ts_push_evt3");
     return n_events;
   }
+  // the same from EVT 2.0 / 2.1 words (format: ESVO_EVT_2_0, ESVO_EVT_2_1 or ESVO_EVT_2_1_LEGACY): esvo_ts_push_evt2
+  size_t evt2Words(const void* words, size_t n_bytes, int format, int memory = ESVO_MEM_HOST, int64_t t_offset_us = 0) {
+    size_t n_events = 0;
+    ctx_->check(esvo_ts_push_evt2(ctx_->handle(), cam_, words, n_bytes, format, memory, t_offset_us, &n_events), "esvo_ts_push_evt2");
+    return n_events;
+  }
   // TimeSurface::createTimeSurfaceAtTime: the rectified mono8 Time Surface at the sync time
   void createTimeSurfaceAtTime(uint64_t external_sync_time_ns, uint8_t* out_mono8 /*nullable*/) {
     ctx_->check(esvo_ts_render(ctx_->handle(), cam_, external_sync_time_ns, out_mono8), "esvo_ts_render");
