@@ -742,6 +742,59 @@ def make_bm_cases():
     print("ref_bm_cases.npz", os.path.getsize(path) // 1024, "KiB")
 
 
+
+def run_ts_case(c):
+    """the reference's TimeSurface class on one crafted case (tests/ts_cases.py): per camera a node with the case's decay, polarity
+    switch and queue length (20 where the device keeps one stamp per pixel), fed the script's pushes; the f64 image handed to
+    convertTo for every render / forward step, in script order"""
+    import ts_cases as TC
+    nodes = [R.RefTS(c["W"], c["H"], c["decay_ms"], bool(c["ignore_polarity"]), c["L"] or 20) for _ in (0, 1)]
+    if any(op[0] == "forward" for op in c["script"]):
+        for node, cam in zip(nodes, TC.cams(c)):
+            node.set_forward(cam.rect_lut)
+    out = []
+    for op in c["script"]:
+        if op[0] == "push":
+            nodes[op[1]].push(op[2])
+        elif op[0] in ("render", "forward"):
+            out.append(nodes[op[1]].render(op[2]))
+    return out
+
+
+def pack_plane(img, c):
+    """one f64 image in compact form: the flat indices of the pixels that are not background (0, or 127.5 with polarity), their
+    values rounded as cv::Mat::convertTo(CV_8U) rounds, and the sha-256 of the f64 bytes"""
+    import hashlib
+    flat = np.ascontiguousarray(img, np.float64).reshape(-1)
+    lit = np.flatnonzero(flat != (0.0 if c["ignore_polarity"] else 127.5)).astype(np.uint16)
+    u8 = np.clip(np.rint(flat[lit]), 0, 255).astype(np.uint8)
+    return lit, u8, np.frombuffer(hashlib.sha256(flat.tobytes()).digest(), np.uint8).copy()
+
+
+def pack_case(imgs, c):
+    """the outputs of a case in four arrays: lit pixels per output, and all outputs' pack_plane results end to end"""
+    packed = [pack_plane(img, c) for img in imgs]
+    return dict(n=np.array([len(p[0]) for p in packed], np.uint32), lit=np.concatenate([p[0] for p in packed]),
+                u8=np.concatenate([p[1] for p in packed]), f64sha=np.stack([p[2] for p in packed]))
+
+
+def make_ts_cases():
+    """tests/ts_cases.py: crafted stamps at the crossings of the quantised value, per-pixel queues at their switch points and
+    FORWARD look-up tables, rendered by the reference's own TimeSurface class.  Recorded results only: per case a digest of the
+    inputs and the lit pixels of every render in compact form."""
+    import ts_cases as TC
+    out = {}
+    for name in TC.PINNED:
+        c = TC.case(name)
+        out[f"{name}_sha"] = TC.input_digest(c)
+        for f, a in pack_case(run_ts_case(c), c).items():
+            out[f"{name}_{f}"] = a
+        print("ts case", name, len(out[f"{name}_n"]), "outputs", len(out[f"{name}_lit"]), "lit pixels")
+    path = os.path.join(HERE, "ref_ts_cases.npz")
+    np.savez_compressed(path, **out)
+    print("ref_ts_cases.npz", os.path.getsize(path) // 1024, "KiB")
+
+
 if __name__ == "__main__":
     assert R.available(), "needs /root/reference (build container only)"
     if "--bm-cases" in sys.argv:   # only the crafted block-matching cases: ref_bm_cases.npz
@@ -749,6 +802,9 @@ if __name__ == "__main__":
         sys.exit(0)
     if "--lm-cases" in sys.argv:   # only the crafted refinement cases: ref_lm_cases.npz
         make_lm_cases()
+        sys.exit(0)
+    if "--ts-cases" in sys.argv:   # only the crafted Time-Surface cases: ref_ts_cases.npz
+        make_ts_cases()
         sys.exit(0)
     if "--fuse-cases" in sys.argv:   # only the crafted back-stage cases: ref_fuse_cases.npz
         make_fuse_cases()
@@ -780,3 +836,4 @@ if __name__ == "__main__":
     make_fuse_cases()
     make_lm_cases()
     make_bm_cases()
+    make_ts_cases()

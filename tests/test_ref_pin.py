@@ -490,6 +490,39 @@ def test_forward_time_surface_equals_reference_source():
     assert n == 16 and int(g["p0_k4_b0"].max()) == 255 and not np.array_equal(g["p0_k4_b0"], g["p1_k4_b0"])
 
 
+def _ts_case_names():
+    import ts_cases as TC
+    return TC.PINNED
+
+
+@pytest.mark.parametrize("name", _ts_case_names())
+def test_time_surface_on_crafted_cases_equals_reference_source(name):
+    """the oracle against the reference's TimeSurface class on the crafted stamps, queues and look-up tables of tests/ts_cases.py
+    (tests/golden/ref_ts_cases.npz) -- stamps on the crossings of the quantised value and just beside the guard band of the
+    device's float shortcut, ages beyond 2^32 ns, queues of 1, 3, 20 and 32 events at their switch points, FORWARD splats whose
+    clamp decides: the criterion of test_time_surface_raster_equals_reference_source and of
+    test_forward_time_surface_equals_reference_source.  BACKWARD: the u8 image after convertTo's rounding, before the OpenCV
+    stages, pixel for pixel (the fixture lists the pixels that are not background).  FORWARD: that, and the f64 image bit for bit
+    (sha-256)."""
+    import hashlib
+    import ts_cases as TC
+    g = np.load(os.path.join(GOLDEN, "ref_ts_cases.npz"))
+    c = TC.case(name)
+    assert np.array_equal(TC.input_digest(c), g[f"{name}_sha"])
+    outs = TC.oracle(name)
+    n, lit, u8, sha = (g[f"{name}_{f}"] for f in ("n", "lit", "u8", "f64sha"))
+    assert len(outs) == len(n) and c["median_k"] == 0
+    start = 0
+    for i, o in enumerate(outs):
+        plane = o["pre"] if o["op"] == "render" else o["img"]      # (median_k = 0: FORWARD's image is the rounded f64 image)
+        ref = np.full(c["W"] * c["H"], 0 if c["ignore_polarity"] else 128, np.uint8)
+        ref[lit[start:start + n[i]]] = u8[start:start + n[i]]
+        start += int(n[i])
+        assert np.array_equal(plane.reshape(-1), ref), (name, i, int(np.count_nonzero(plane.reshape(-1) != ref)))
+        if o["op"] == "forward":
+            assert np.array_equal(np.frombuffer(hashlib.sha256(np.ascontiguousarray(o["f64"]).tobytes()).digest(), np.uint8), sha[i]), (name, i)
+
+
 def test_live_reference_time_surface_reproduces_fixture():
     from oracle import ref as R
     if not os.path.isdir(os.path.join(R.REFERENCE, "esvo_core", "src")):
