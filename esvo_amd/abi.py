@@ -341,6 +341,36 @@ class Evt2State(C.Structure):
 Evt2Counts = Evt3Counts   # esvo_evt2_counts_t; `words` counts 32- or 64-bit words, by format
 
 
+# esvo_event_filter_host / esvo_ts_filter_*: the verdicts of the event filter (include/esvo_hip.h)
+FILTER_KEPT, FILTER_OUTSIDE, FILTER_MASKED, FILTER_REFRACTORY, FILTER_UNSUPPORTED = 0, 1, 2, 3, 4
+
+
+class EventFilterStruct(C.Structure):
+    """esvo_event_filter_t"""
+    _fields_ = [("refractory_ns", C.c_uint64), ("support_ns", C.c_uint64), ("mask", C.c_void_p), ("reserved", C.c_uint32 * 4)]
+
+
+class EventFilterCounts(C.Structure):
+    """esvo_event_filter_counts_t"""
+    _fields_ = [(k, C.c_uint64) for k in ("events_in", "kept", "outside", "masked", "refractory", "unsupported")]
+
+    def as_dict(self):
+        return {k: int(getattr(self, k)) for k, _ in self._fields_}
+
+
+def event_filter_struct(refractory_ns, support_ns, mask, width, height):
+    """(EventFilterStruct, the array its mask points into or None): mask is None or (height, width), non-zero = masked"""
+    s = EventFilterStruct()
+    s.refractory_ns, s.support_ns = int(refractory_ns), int(support_ns)
+    keep = None
+    if mask is not None:
+        keep = np.ascontiguousarray((np.asarray(mask) != 0).astype(np.uint8))
+        if keep.shape != (int(height), int(width)):
+            raise ValueError(f"event filter mask: expected shape {(int(height), int(width))}, got {keep.shape}")
+        s.mask = keep.ctypes.data
+    return s, keep
+
+
 class Evt2Error(ValueError):
     """an event of the words has no valid stamp; `first_bad` is its index among the events"""
 

@@ -62,6 +62,7 @@ int zero_session_buffers(esvo_context* h, hipStream_t st) {
   HIPCHK(hipMemsetAsync(h->d_tile_count, 0, sizeof(u32) * fuse_front_tiles(h), st));  // zero between ticks: fuse_turn_kernel clears what was read
   HIPCHK(hipMemsetAsync(h->d_fuse_ctr, 0, sizeof(u32) * 2112, st));
   if (h->d_rank_kept) HIPCHK(hipMemsetAsync(h->d_rank_kept, 0, sizeof(u32) * esvo_context::SHARD_MAX_RANKS, st));  // (band mode: allocated by its configuration)
+  { int rcf = filter_zero_state(h, st); if (rcf) return rcf; }  // (the event filter's `last` images, where one is configured)
   h->d_map_cur = h->d_map;
   return ESVO_OK;
 }
@@ -83,6 +84,7 @@ void read_dev_switches(esvo_context* h) {
   if ((e = esvo_dev_switch("ESVO_BM_DEDUPE_MIN"))) h->bm_dedupe_min = (u32)std::max(1L, std::atol(e));
   if ((e = esvo_dev_switch("ESVO_CLK_PROBE"))) h->clk_probe = std::atoi(e) != 0;
   h->n_pose_slots = (e = esvo_dev_switch("ESVO_POSE_SLOTS0")) ? (u32)std::max(1, std::atoi(e)) : 1024u;  // tests: a smaller first allocation (alloc_window_and_map)
+  if ((e = esvo_dev_switch("ESVO_FLT_TILE_CAP"))) h->flt_tcap = (u32)std::min<long>(std::max(1L, std::atol(e)), (long)FLT_TILE_CAP_MAX);  // tests: force the packet-reading route
   if ((e = esvo_dev_switch("ESVO_FUSE_TILE_CAP"))) h->fuse_tile_cap = (u32)std::max(1L, std::atol(e));
   if ((e = esvo_dev_switch("ESVO_FUSE_PMAX"))) h->fuse_pmax_plus1 = (u32)std::max(0L, std::atol(e)) + 1u;
   if ((e = esvo_dev_switch("ESVO_FUSE_TILE_REC"))) h->fuse_tile_rec = (u32)std::max(1L, std::atol(e));

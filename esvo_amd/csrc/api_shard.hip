@@ -292,6 +292,7 @@ int esvo_shard_set_routing(esvo_handle h, int mode, int ts_halo_rows) {
   if (!h->sharded) FAIL(ESVO_ERR_STATE, "call esvo_shard_set_band first");
   if (!rings_empty(h)) FAIL(ESVO_ERR_STATE, "events are already staged: choose the routing before the first esvo_ts_push_events (or esvo_reset)");
   if (mode == ESVO_ROUTE_BROADCAST) { h->routed = false; return ESVO_OK; }
+  if (h->flt[0].on || h->flt[1].on) FAIL(ESVO_ERR_UNSUPPORTED, "an event filter is configured (esvo_ts_filter_configure): it needs the whole stream, row routing filters packets on the host -- use ESVO_ROUTE_BROADCAST");
   const esvo_params_t& p = h->prm;
   if (h->tsq_len) FAIL(ESVO_ERR_UNSUPPORTED, "per-pixel event queues (max_event_queue_len) are not routed: use ESVO_ROUTE_BROADCAST");
   if (p.bm_updown) FAIL(ESVO_ERR_UNSUPPORTED, "up-down stereo searches along y, across the bands: use ESVO_ROUTE_BROADCAST");

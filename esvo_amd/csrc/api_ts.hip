@@ -491,11 +491,77 @@ int push_unsorted(esvo_context* h, int cam, size_t n, GetEv get) {
   return ESVO_OK;
 }
 
+// ---- the event filter (esvo_ts_filter_configure; api_filter.hip) -------------------------------------------------------------------
+// With a filter on, every source becomes a device-resident column packet (src.columns(): the camera's column staging, or device
+// columns where they lie), the filter leaves the kept events in its twin staging and their stamps on the host, and the twin is
+// packed into the ring as a column packet is.  Order and ring room are judged first, on the unfiltered packet; the filter's state
+// changes only behind a push that succeeded.  Caller holds mu_push[cam].
+int columns_staging(esvo_context* h, int cam, size_t n);
+struct KeptPacket {
+  static constexpr bool in_flight = false;
+  esvo_context* h; int cam; FilterPacket k; const u64* stamps; size_t n;
+  StampArray stamp_fn() const { return {stamps}; }
+  int enqueue(const PushTicket& tk) {
+    launch_ts_pack_columns(k.d_x, k.d_y, k.d_t, k.d_p, k.p_type, n, h->d_ring[cam], tk.slot, h->ring_cap, h->stream_i);
+    HIPCHK(hipGetLastError());
+    return ESVO_OK;
+  }
+};
+template <typename Src>
+int push_filtered(esvo_context* h, int cam, Src& src) {
+  const char* const out_of_order = "event filter: out-of-order packet (not sorted by time stamp, or older than the newest staged event)";
+  const bool host_stamps = src.stamps_on_host();  // (else the filter's last kernel looks at stamps and order: they never come down)
+  u64 newest = 0;
+  {
+    std::lock_guard<std::mutex> lr(h->mu_ring);
+    newest = h->ts_host[cam].empty() ? 0 : h->ts_host[cam].back();
+    if (h->ring_next[cam] + src.n - h->scattered[cam] > h->ring_cap)  // on the UNFILTERED count: a refusal must come before the filter's state moves
+      FAIL(ESVO_ERR_CAPACITY, "event ring full: render (scatter) before staging more events");
+  }
+  if (host_stamps && (!src.sorted() || src.stamp_fn()(0) < newest)) FAIL(ESVO_ERR_UNSUPPORTED, out_of_order);
+  FilterPacket in{}, twin{};
+  { int rc = src.columns(in); if (rc) return rc; }
+  const u64* kept_stamps = nullptr;
+  esvo_event_filter_counts_t counts{};
+  bool unsorted = false;
+  u32 first_bad = 0xffffffffu;
+  { int rc = filter_run(h, cam, in, newest, &twin, &kept_stamps, &counts, &unsorted, &first_bad); if (rc) return rc; }
+  if (first_bad != 0xffffffffu) FAIL(ESVO_ERR_INVALID_ARG, src.bad_stamp_message(first_bad));
+  if (unsorted) FAIL(ESVO_ERR_UNSUPPORTED, out_of_order);
+  KeptPacket kept{h, cam, twin, kept_stamps, twin.n};
+  { int rc = push_staged(h, cam, kept, [](size_t) {}); if (rc) return rc; }
+  filter_commit(h, cam, counts);
+  return ESVO_OK;
+}
+// records on the host (get(i): normalised) split into columns by a plain loop and uploaded into the camera's column staging
+template <typename GetEv>
+int records_to_columns(esvo_context* h, int cam, size_t n, GetEv get, FilterPacket& out) {
+  { int rc = columns_staging(h, cam, n); if (rc) return rc; }
+  const size_t cap = h->col_cap[cam];
+  uint8_t* const d = h->d_col[cam];
+  u64* const stamps = h->h_col_stamps[cam];
+  std::vector<uint16_t> xy(2 * n);
+  std::vector<uint8_t> p(n);
+  for (size_t i = 0; i < n; ++i) {
+    const esvo_event_t e = get(i);
+    stamps[i] = event_stamp(e); xy[i] = e.x; xy[n + i] = e.y; p[i] = e.polarity;
+  }
+  HIPCHK(hipMemcpyAsync(d, stamps, sizeof(u64) * n, hipMemcpyHostToDevice, h->stream_i));
+  HIPCHK(hipMemcpyAsync(d + 8 * cap, xy.data(), 2 * n, hipMemcpyHostToDevice, h->stream_i));
+  HIPCHK(hipMemcpyAsync(d + 10 * cap, xy.data() + n, 2 * n, hipMemcpyHostToDevice, h->stream_i));
+  HIPCHK(hipMemcpyAsync(d + 12 * cap, p.data(), n, hipMemcpyHostToDevice, h->stream_i));
+  HIPCHK(hipStreamSynchronize(h->stream_i));  // (pageable sources that end with this call)
+  out = FilterPacket{reinterpret_cast<const u64*>(d), reinterpret_cast<const uint16_t*>(d + 8 * cap), reinterpret_cast<const uint16_t*>(d + 10 * cap),
+                     d + 12 * cap, ESVO_P_U8, n};
+  return ESVO_OK;
+}
+
 // ---- one staging driver for every packet format --------------------------------------------------------------------------------
 // A packet source supplies, beside what push_staged asks for,
 //   sorted()       the packet is in order in itself
 //   materialise()  makes record(i) valid: the normalised esvo_event_t, which only the paths that filter or sort on the host read
 //   prepare()      staging memory of its own, before anything is reserved
+//   columns()      the packet as device-resident columns (the event filter's input); stamps_on_host(): false where they exist there only
 // lp: mu_push[cam] where the source needed its staging for the stamps already; else it is taken here.
 template <typename Derived>
 struct PacketDefaults {
@@ -514,10 +580,19 @@ struct PacketDefaults {
   }
   int materialise() { return ESVO_OK; }
   int prepare() { return ESVO_OK; }
+  bool stamps_on_host() const { return true; }  // stamp_fn() and sorted() can be asked (else the event filter decides on the device)
+  std::string bad_stamp_message(size_t i) const { return "event " + std::to_string(i) + " has no valid time stamp"; }
 };
 template <typename Src>
 int push_packet(esvo_context* h, int cam, Src& src, std::unique_lock<std::mutex> lp = {}) {
   const auto record = [&](size_t i) { return src.record(i); };
+  if (h->flt[cam].on.load(std::memory_order_relaxed)) {  // the event filter (esvo_ts_filter_configure): every packet of the camera
+    if (!lp.owns_lock()) {
+      lp = std::unique_lock<std::mutex>(h->mu_push[cam]);
+      HIPCHK(hipSetDevice(h->device));
+    }
+    if (h->flt[cam].on) return push_filtered(h, cam, src);
+  }
   // sorted, and not older than what is staged: the fast path; anything else is sorted in as the reference's callbacks do
   bool in_order = src.sorted();
   if (in_order) {
@@ -546,6 +621,7 @@ struct RecordPacket : PacketDefaults<RecordPacket> {  // esvo_event_t records in
   esvo_context* h; int cam; const esvo_event_t* ev; size_t n; bool in_flight;
   auto stamp_fn() const { return [ev = ev](size_t i) { return event_stamp(ev[i]); }; }
   esvo_event_t record(size_t i) const { return event_normalised(ev[i]); }
+  int columns(FilterPacket& out) { return records_to_columns(h, cam, n, [this](size_t i) { return record(i); }, out); }
   int enqueue(const PushTicket& tk) {
     HIPCHK(copy_into_ring(h, h->d_ring[cam].get(), tk.slot, ev, n));
     return ESVO_OK;
@@ -568,6 +644,7 @@ struct WirePacket : PacketDefaults<WirePacket> {
     e.polarity = r[12];
     return event_normalised(e);
   }
+  int columns(FilterPacket& out) { return records_to_columns(h, cam, n, [this](size_t i) { return record(i); }, out); }
   int prepare() {
     if (n * 13 > h->d_wire[cam].cap())  // this camera's staging buffer: its pusher is the only user (mu_push)
       HIPCHK(h->d_wire[cam].alloc(std::max<size_t>(n * 13, (size_t)1 << 20)));
@@ -679,6 +756,9 @@ struct ColumnsPacket : PacketDefaults<ColumnsPacket> {
   esvo_context* h; int cam; const esvo_event_columns_t* c; size_t n; const u64* stamps; bool in_itself;
   bool sorted() const { return in_itself; }
   std::vector<esvo_event_t>* E;  // the slow paths take records: what esvo_ts_push_events does with them, nothing of it twice
+  bool host_stamps = true;       // false: a device-resident packet under the event filter, whose stamps stay on the device
+  bool stamps_on_host() const { return host_stamps; }
+  std::string bad_stamp_message(size_t i) const { return columns_bad_element(i); }
   StampArray stamp_fn() const { return {stamps}; }
   esvo_event_t record(size_t i) const { return (*E)[i]; }
   int materialise() {
@@ -697,7 +777,7 @@ struct ColumnsPacket : PacketDefaults<ColumnsPacket> {
     for (size_t i = 0; i < n; ++i) (*E)[i] = columns_event(x, y, p, c->p_type, stamps[i], i);
     return ESVO_OK;
   }
-  int enqueue(const PushTicket& tk) {
+  int columns(FilterPacket& out) {
     const size_t cap = h->col_cap[cam];
     uint8_t* const d = h->d_col[cam];
     u64* const d_stamps = reinterpret_cast<u64*>(d);
@@ -713,7 +793,13 @@ struct ColumnsPacket : PacketDefaults<ColumnsPacket> {
       ky = reinterpret_cast<const uint16_t*>(d + 10 * cap);
       if (c->p) kp = d + 12 * cap;
     }
-    launch_ts_pack_columns(kx, ky, d_stamps, kp, c->p_type, n, h->d_ring[cam], tk.slot, h->ring_cap, h->stream_i);
+    out = FilterPacket{d_stamps, kx, ky, kp, c->p_type, n};
+    return ESVO_OK;
+  }
+  int enqueue(const PushTicket& tk) {
+    FilterPacket k{};
+    { int rc = columns(k); if (rc) return rc; }
+    launch_ts_pack_columns(k.d_x, k.d_y, k.d_t, k.d_p, k.p_type, n, h->d_ring[cam], tk.slot, h->ring_cap, h->stream_i);
     HIPCHK(hipGetLastError());
     return ESVO_OK;
   }
@@ -763,6 +849,14 @@ int esvo_ts_push_event_columns(esvo_handle h, int cam, const esvo_event_columns_
   }
   { int rc = columns_staging(h, cam, n); if (rc) return rc; }
   u64* const stamps = h->h_col_stamps[cam];
+  if (on_device && h->flt[cam].on) {  // under the event filter validity and order are judged by its last kernel: the stamps stay on the device
+    launch_ts_columns_stamps(c->t, c->t_type, c->t_offset, n, reinterpret_cast<u64*>(h->d_col[cam].get()), h->stream_i);
+    HIPCHK(hipGetLastError());
+    std::vector<esvo_event_t> none;
+    ColumnsPacket judged{{}, h, cam, c, n, stamps, true, &none};
+    judged.host_stamps = false;
+    return push_packet(h, cam, judged, std::move(lp));
+  }
   if (on_device) {  // t -> stamps on the device, down once
     u64* const d_stamps = reinterpret_cast<u64*>(h->d_col[cam].get());
     launch_ts_columns_stamps(c->t, c->t_type, c->t_offset, n, d_stamps, h->stream_i);
@@ -1029,15 +1123,19 @@ int push_words(esvo_handle h, int cam, const F& f, const void* words_v, size_t n
     const size_t cap = h->col_cap[cam];
     uint8_t* const d = h->d_col[cam];
     u64* const stamps = h->h_col_stamps[cam];
-    HIPCHK(hipMemcpyAsync(stamps, d, sizeof(u64) * n, hipMemcpyDeviceToHost, h->stream_i));
-    HIPCHK(hipStreamSynchronize(h->stream_i));
+    const bool judged_on_device = h->flt[cam].on;  // under the event filter the order is judged by its last kernel: one read-back, the kept stamps
     bool in_order = true;
-    for (size_t i = 1; i < n && in_order; ++i) in_order = stamps[i] >= stamps[i - 1];
+    if (!judged_on_device) {
+      HIPCHK(hipMemcpyAsync(stamps, d, sizeof(u64) * n, hipMemcpyDeviceToHost, h->stream_i));
+      HIPCHK(hipStreamSynchronize(h->stream_i));
+      for (size_t i = 1; i < n && in_order; ++i) in_order = stamps[i] >= stamps[i - 1];
+    }
     esvo_event_columns_t c{};
     c.x = d + 8 * cap; c.y = d + 10 * cap; c.p = d + 12 * cap; c.t = d;
     c.t_type = ESVO_T_NS_I64; c.p_type = ESVO_P_U8; c.memory = ESVO_MEM_DEVICE;
     std::vector<esvo_event_t> E;
     WordsPacket<F> src{{{}, h, cam, &c, n, stamps, in_order, &E}, f, words_v, n_words, on_device, st0, t_offset_us};
+    src.host_stamps = !judged_on_device;
     rc = push_packet(h, cam, src, std::move(lp));
   }
   if (rc) return rc;

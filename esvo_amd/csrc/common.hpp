@@ -255,6 +255,28 @@ __host__ __device__ inline uint4 columns_record(uint16_t x, uint16_t y, u64 stam
 void launch_ts_columns_stamps(const void* t, int t_type, int64_t t_offset, size_t n, u64* stamps, hipStream_t s);
 void launch_ts_pack_columns(const uint16_t* x, const uint16_t* y, const u64* stamps, const void* p, int p_type, size_t n,
                             esvo_event_t* ring, u64 first_slot, u64 ring_cap, hipStream_t s);
+// The event filter (esvo_ts_filter_configure, include/esvo_hip.h; kernels_filter.hip): a packet of column events, the camera's
+// filter state and the tile lists.  hdr: FLT_HDR_WORDS words in front of the twin staging's stamps, cleared by the launch.
+constexpr u32 FLT_TILE_CAP_MAX = 1024u;  // entries of a tile's list the walk can sort in LDS (a power of two)
+constexpr u32 FLT_HDR_WORDS = 16u;       // 64 bytes: the twin's stamps stay 8-byte aligned behind it
+constexpr u32 FLT_H_VERDICT0 = 0u;       // hdr[FLT_H_VERDICT0 + v]: events of verdict v (ESVO_FILTER_*), v = 0..4
+constexpr u32 FLT_H_UNSORTED = 5u;       // non-zero: a stamp below its predecessor's (the first one's: FilterArgs::newest)
+constexpr u32 FLT_H_FIRST_BAD = 6u;      // index of the first COL_BAD_STAMP, 0xffffffff: none
+struct FilterArgs {
+  const u64* t; const uint16_t* x; const uint16_t* y; u32 n;
+  int W, H;
+  u64 refractory_ns, support_ns;
+  u64 newest;               // the newest staged stamp: what the packet's first stamp is checked against
+  const uint8_t* mask;      // [H * W], null: none
+  const u64* last_in;       // [H * W]
+  u64* last_out;            // [H * W], the other image of the pair
+  u32* tcount; u32* tlist; u32 tcap;  // per 8x8 tile: entries (running beyond tcap), the first tcap event indices
+  uint8_t* code;            // [n] verdict << 1 | kept
+  u32* hdr;
+};
+size_t filter_tiles(int W, int H);
+void launch_event_filter(const FilterArgs& a, u32* scan_tmp, const void* p, int p_type, u64* out_t, uint16_t* out_x, uint16_t* out_y,
+                         uint8_t* out_p, hipStream_t s);
 // EVT 3.0 ingest (esvo_ts_push_evt3, include/esvo_hip.h): ONE function per rule of the format, shared by the host decoder
 // (esvo_evt3_to_events) and the device decode (kernels_ts.hip), so both produce the same bytes.
 enum { EVT3_ADDR_Y = 0x0, EVT3_ADDR_X = 0x2, EVT3_VECT_BASE_X = 0x3, EVT3_VECT_12 = 0x4, EVT3_VECT_8 = 0x5, EVT3_TIME_LOW = 0x6,

@@ -78,6 +78,9 @@ struct IngestSession {  // under mu_ring: the event rings
   // the same of EVT 2.0 / 2.1 ingest (esvo_ts_push_evt2): one state serves the three formats
   esvo_evt2_state_t evt2_state[2] = {};
   esvo_evt2_counts_t evt2_totals[2] = {};
+  // the event filter (esvo_ts_filter_configure): the totals of a camera's successful pushes, under its mu_push.  (The `last` image
+  // is device memory: esvo_reset zeroes it beside the other session buffers, EventFilter below.)
+  esvo_event_filter_counts_t flt_totals[2] = {};
 };
 struct TsSession {  // under mu_ts (the right camera's flag: mapper group only)
   bool ts_valid[2] = {false, false};  // d_ts[cam] holds a render
@@ -314,6 +317,23 @@ struct esvo_context : IngestSession, TsSession, SchedSession, MapSession, CloudS
   // ~20 000 events of EVT 2.0 and ~29 000 one-event words of EVT 2.1 (profiles/evt2_ingest_ab.txt);
   // esvo_debug_evt2_device_min moves both
   size_t evt2_device_min[2] = {20480 * 4, 28672 * 8};
+  // The event filter of a camera (esvo_ts_filter_configure; api_filter.hip, kernels_filter.hip), under its mu_push; configuration:
+  // it survives a reset, which zeroes d_last.  d_last: [2][W * H], a pair -- a packet reads image `cur` and writes the other, and
+  // only a push that succeeded makes that one current.  d_twin: [FLT_HDR_WORDS u32 | cap u64 stamps | cap u16 x | cap u16 y | cap u8 p],
+  // the kept events of a packet behind the verdict counts; h_twin: the pinned copy of its header and stamps; d_code / d_scan: a
+  // verdict code per event, their exclusive scan and its scratch.  The staging grows with the packets (cap: a multiple of 256).
+  struct EventFilter {
+    std::atomic<bool> on{false};  // (read without a lock by push_packet: a handle without a filter takes no new lock)
+    u64 refractory_ns = 0, support_ns = 0;
+    bool has_mask = false;
+    int cur = 0;
+    DevBuf<u64> d_last;
+    DevBuf<uint8_t> d_mask, d_twin, d_code;
+    DevBuf<u32> d_tcount, d_tlist, d_scan;
+    PinBuf<u64> h_twin;
+    size_t cap = 0;
+  } flt[2];
+  u32 flt_tcap = FLT_TILE_CAP_MAX;  // ESVO_FLT_TILE_CAP (tests): entries of a tile's list; beyond it the tile reads the packet
   u64 ring_cap = 0;
   // esvo_ts_push_events_async: the newest enqueued (not awaited) copy of a camera; consumers of the ring on the front stream
   // queue behind it (ingest_fence, api_ts.hip) -- under mu_ring, with IngestSession::ingest_pending
@@ -540,6 +560,16 @@ void ingest_fence(esvo_context* h, int cam);  // caller holds mu_ring
 int ts_scatter_ahead(esvo_context* h, uint64_t t_ns);
 void resident_write_begin(esvo_context* h, int cam);
 int ts_render_pair(esvo_context* h, uint64_t t_ns, uint8_t* const obs_out[2]);
+// api_filter.hip
+struct FilterPacket { const u64* d_t; const uint16_t *d_x, *d_y; const void* d_p; int p_type; size_t n; };
+// runs the camera's filter over a device-resident column packet on the ingest stream and waits: *kept events lie in the twin
+// staging (twin: its columns as a packet), their stamps in *kept_stamps (pinned), the packet's counts in *counts.  Caller holds
+// mu_push[cam]; nothing of the handle's state has changed until filter_commit.
+// newest: the newest staged stamp; *unsorted: the packet is not in order behind it; *first_bad: its first invalid stamp (0xffffffff: none)
+int filter_run(esvo_context* h, int cam, const FilterPacket& in, u64 newest, FilterPacket* twin, const u64** kept_stamps, esvo_event_filter_counts_t* counts,
+               bool* unsorted, u32* first_bad);
+void filter_commit(esvo_context* h, int cam, const esvo_event_filter_counts_t& counts);
+int filter_zero_state(esvo_context* h, hipStream_t st);  // esvo_reset: the `last` images of both cameras
 // api_history.hip
 int hist_store(esvo_context* h, int cam, uint64_t t_ns, const uint8_t* src, bool from_host);  // caller holds mu_ts
 void hist_clear(esvo_context* h);                                                             // caller holds mu_ts

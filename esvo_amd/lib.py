@@ -10,7 +10,7 @@ import subprocess
 
 import numpy as np
 
-from .abi import (MEM_DEVICE, MEM_HOST, P_U8, ColumnsError, EventColumnsStruct, Evt2Counts, Evt2State, Evt3Counts, Evt3State, evt2_words, evt3_words, check_t_offset, column_p_type, column_t_type,
+from .abi import (MEM_DEVICE, MEM_HOST, P_U8, ColumnsError, EventColumnsStruct, EventFilterCounts, EventFilterStruct, event_filter_struct, Evt2Counts, Evt2State, Evt3Counts, Evt3State, evt2_words, evt3_words, check_t_offset, column_p_type, column_t_type,
                   DEPTH_POINT_DTYPE, EM_POSE_FN, ERR_CAPACITY, ERR_INVALID_ARG, ERR_STATE, EVENT_DTYPE, MATCH_DTYPE, CalibStruct, EmSelectionStruct,
                   EmStatsStruct, GpcParamsStruct, GpcStatsStruct, LmStatsStruct, ParamsStruct, SgmStatsStruct, StatsStruct, TRACK_ITER_DTYPE, TRACK_SOLVE_MAX_ITERATIONS,
                   TrackSolveInfoStruct, TrackSolveParamsStruct)
@@ -18,7 +18,7 @@ from .abi import (MEM_DEVICE, MEM_HOST, P_U8, ColumnsError, EventColumnsStruct, 
 _CSRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc")
 # ESVO_HIP_LIB: another build of the same library (A/B measurements of kernel variants, tools/ab_build.py); never a fallback
 _LIB_PATH = os.environ.get("ESVO_HIP_LIB") or os.path.join(_CSRC, "libesvo_hip.so")
-_SOURCES = ["api_core.hip", "api_ts.hip", "api_map.hip", "api_window.hip", "api_modes.hip", "api_shard.hip", "api_out.hip", "api_comm.hip", "api_bag.hip", "api_track.hip", "scan.hip", "kernels_ts.hip", "kernels_bm.hip", "kernels_lm.hip", "kernels_lm_any.hip", "kernels_fuse.hip", "kernels_shard.hip", "kernels_track.hip", "kernels_track_viz.hip", "kernels_viz.hip", "kernels_sgm.hip", "api_em.hip", "kernels_em.hip", "kernels_cloud.hip", "api_dev.hip", "api_gpc.hip", "kernels_voxel.hip", "api_history.hip"]
+_SOURCES = ["api_core.hip", "api_ts.hip", "api_map.hip", "api_window.hip", "api_modes.hip", "api_shard.hip", "api_out.hip", "api_comm.hip", "api_bag.hip", "api_track.hip", "scan.hip", "kernels_ts.hip", "kernels_bm.hip", "kernels_lm.hip", "kernels_lm_any.hip", "kernels_fuse.hip", "kernels_shard.hip", "kernels_track.hip", "kernels_track_viz.hip", "kernels_viz.hip", "kernels_sgm.hip", "api_em.hip", "kernels_em.hip", "kernels_cloud.hip", "api_dev.hip", "api_gpc.hip", "kernels_voxel.hip", "api_history.hip", "api_filter.hip", "kernels_filter.hip"]
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared",
                "-Wno-unused-value", "-Wno-unused-result", "-ldl"]
 
@@ -45,6 +45,7 @@ SYMBOLS = [
     "esvo_track_reprojection_map", "esvo_track_reprojection_map_device",
     "esvo_ts_history_configure", "esvo_ts_history_list", "esvo_ts_history_get", "esvo_ts_history_put", "esvo_map_set_observation_at",
     "esvo_track_set_current_at", "esvo_ts_history_select", "esvo_ts_history_select_observation",
+    "esvo_ts_filter_configure", "esvo_ts_filter_stats", "esvo_ts_filter_state", "esvo_event_filter_host", "esvo_event_filter_sizes",
 ]
 # the EVT 3.0 entry points, listed apart: their names carry a digit (SYMBOLS is compared with a scan of the header for [a-z_] names)
 SYMBOLS_EVT3 = ["esvo_ts_push_evt3", "esvo_ts_evt3_state", "esvo_ts_evt3_stats", "esvo_evt3_to_events", "esvo_evt3_raw_header", "esvo_evt3_sizes",
@@ -275,9 +276,15 @@ def load():
     lib.esvo_track_set_current_at.argtypes = [vp, u64, i32]
     lib.esvo_ts_history_select.argtypes = [vp, sz, i32, EM_POSE_FN, vp, psz, vp]
     lib.esvo_ts_history_select_observation.argtypes = [vp, i32, EM_POSE_FN, vp, C.POINTER(C.c_uint64), vp]
+    lib.esvo_ts_filter_configure.argtypes = [vp, i32, vp]
+    lib.esvo_ts_filter_stats.argtypes = [vp, i32, vp]
+    lib.esvo_ts_filter_state.argtypes = [vp, i32, vp, vp]
+    lib.esvo_event_filter_host.argtypes = [vp, i32, i32, vp, vp, sz, vp, vp, sz, psz, vp]
+    lib.esvo_event_filter_sizes.argtypes = [vp]
+    lib.esvo_event_filter_sizes.restype = None
     for s in SYMBOLS + SYMBOLS_EVT3:
         if s not in ("esvo_default_params", "esvo_last_error", "esvo_abi_sizes", "esvo_bag_last_error", "esvo_em_sizes", "esvo_lm_sizes", "esvo_sgm_sizes",
-                     "esvo_track_sizes", "esvo_gpc_sizes", "esvo_event_columns_sizes", "esvo_evt3_sizes", "esvo_evt2_sizes"):
+                     "esvo_track_sizes", "esvo_gpc_sizes", "esvo_event_columns_sizes", "esvo_evt3_sizes", "esvo_evt2_sizes", "esvo_event_filter_sizes"):
             getattr(lib, s).restype = C.c_int
     lib.esvo_abi_sizes.argtypes = [vp]
     lib.esvo_abi_sizes.restype = None
@@ -759,6 +766,32 @@ def evt2_sizes():
     return list(out)
 
 
+def event_filter_sizes():
+    """sizeof(esvo_event_filter_t), sizeof(esvo_event_filter_counts_t), 0, 0 (esvo_event_filter_sizes)"""
+    out = (C.c_size_t * 4)()
+    load().esvo_event_filter_sizes(out)
+    return list(out)
+
+
+def event_filter_host(events, width, height, refractory_ns=0, support_ns=0, mask=None, last=None, cap=None, want_verdicts=True):
+    """esvo_event_filter_host: the filter's rule on the host -> (verdicts uint8 [n], kept records, last (height, width) uint64, counts
+    dict).  last: the state to resume from (None: all zero), not modified -- the returned image is the advanced copy.  cap: room of
+    the output (None: n; 0 with no output: count only)."""
+    ev = np.ascontiguousarray(events, EVENT_DTYPE)
+    n = len(ev)
+    f, _keep = event_filter_struct(refractory_ns, support_ns, mask, width, height)
+    L = np.zeros((int(height), int(width)), np.uint64) if last is None else np.array(last, np.uint64).reshape(int(height), int(width)).copy()
+    verdict = np.zeros(n, np.uint8)
+    room = n if cap is None else int(cap)
+    out = np.zeros(max(room, 1), EVENT_DTYPE)
+    n_out, cnt = C.c_size_t(0), EventFilterCounts()
+    rc = load().esvo_event_filter_host(C.addressof(f), int(width), int(height), L.ctypes.data, ev.ctypes.data if n else None, n,
+                                       verdict.ctypes.data if want_verdicts and n else None, out.ctypes.data, room, C.byref(n_out), C.addressof(cnt))
+    if rc != 0:
+        raise EsvoError(f"esvo_event_filter_host failed ({rc}): {load().esvo_last_error(None).decode(errors='replace')}", code=rc)
+    return verdict, out[:n_out.value].copy(), L, cnt.as_dict()
+
+
 def abi_sizes():
     out = (C.c_size_t * 8)()
     load().esvo_abi_sizes(out)
@@ -942,6 +975,30 @@ class Esvo:
         self._ck(self.lib.esvo_ts_push_evt2(self.h, int(cam), addr or None, dt.itemsize * n, int(format), MEM_DEVICE if on_device else MEM_HOST,
                                             check_t_offset(t_offset_us), C.byref(n_ev)))
         return int(n_ev.value)
+
+    def ts_filter_configure(self, cam, refractory_ns=0, support_ns=0, mask=None, off=False):
+        """the camera's event filter (esvo_ts_filter_configure): hot-pixel mask ((H, W), non-zero = masked, copied), refractory period
+        and neighbour support in ns (0: that test is off); zeroes the camera's `last` image, keeps the totals.  off=True switches the
+        filter off and frees its memory.  From then on every ts_push_* call of the camera stages only the events the filter keeps."""
+        if off:
+            self._ck(self.lib.esvo_ts_filter_configure(self.h, int(cam), None))
+            return
+        f, _keep = event_filter_struct(refractory_ns, support_ns, mask, self.rig.width, self.rig.height)
+        self._ck(self.lib.esvo_ts_filter_configure(self.h, int(cam), C.addressof(f)))
+
+    def ts_filter_stats(self, cam):
+        """totals of the camera's filter since create / reset as a dict: events_in = kept + outside + masked + refractory + unsupported"""
+        tot = EventFilterCounts()
+        self._ck(self.lib.esvo_ts_filter_stats(self.h, int(cam), C.addressof(tot)))
+        return tot.as_dict()
+
+    def ts_filter_state(self, cam, set=None):
+        """the camera's `last` image, (H, W) uint64 ns stamps (esvo_ts_filter_state); set: an image that replaces it afterwards"""
+        H, W = self.rig.height, self.rig.width
+        got = np.zeros((H, W), np.uint64)
+        new = None if set is None else np.ascontiguousarray(np.asarray(set, np.uint64).reshape(H, W))
+        self._ck(self.lib.esvo_ts_filter_state(self.h, int(cam), got.ctypes.data, None if new is None else new.ctypes.data))
+        return got
 
     def evt2_state(self, cam, set=None):
         """the camera's EVT 2.x decoder state (an abi.Evt2State); set: an Evt2State that replaces it (a reader seeks or resumes)"""

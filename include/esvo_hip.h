@@ -463,6 +463,71 @@ int esvo_evt2_to_events(esvo_evt2_state_t* st, const void* words, size_t n_bytes
 int esvo_raw_header(const uint8_t* file, size_t n_bytes, size_t* data_offset, int* width, int* height, int* format);
 /* sizeof(esvo_evt2_state_t), sizeof(esvo_evt2_counts_t), 0, 0 */
 void esvo_evt2_sizes(size_t out[4]);
+/* Event filter on the device: hot-pixel mask, per-pixel refractory period and nearest-neighbour background-activity filter, applied
+ * to a raw sensor stream between decode and the event ring.  Off unless configured; a handle without it takes the paths above
+ * unchanged.  Each camera has its own state: one uint64 per RAW pixel, last[y][x], the ns stamp of the newest event at that pixel
+ * that passed the mask and the refractory test (0: none; an event stamped 0 never counts).  Events are judged one by one in stream
+ * order (t: the event's stamp in ns; the stream is time-sorted; differences are taken as integers, so a planted `last` ahead of
+ * the stream gives a negative one):
+ *   verdict(e):
+ *     if e.x >= W or e.y >= H:            ESVO_FILTER_OUTSIDE      (1)  touches nothing
+ *     if mask[e.y][e.x] != 0:             ESVO_FILTER_MASKED       (2)  touches nothing
+ *     L = last[e.y][e.x]
+ *     if refractory_ns > 0 and L != 0 and t - L < refractory_ns:
+ *                                         ESVO_FILTER_REFRACTORY   (3)  touches nothing
+ *     sup = any(last[n] != 0 and t - last[n] <= support_ns
+ *               for n in the up-to-8 neighbours of (x, y) inside the image)    -- read BEFORE the next line
+ *     last[e.y][e.x] = t
+ *     if support_ns > 0 and not sup:      ESVO_FILTER_UNSUPPORTED  (4)
+ *     else:                               ESVO_FILTER_KEPT         (0)
+ *   So a refractory-dropped or masked event neither supports a neighbour nor restarts the refractory period; an unsupported event does
+ *   both; an earlier event of the same packet with the same stamp supports, a later one does not; the pixel never supports itself.
+ *   Polarity plays no part.  PINNED TO NOTHING THIRD-PARTY: the whole rule is this library's own, in particular `<` for the refractory
+ *   test, `<=` for support, and unsupported events updating `last`.
+ * Only KEPT events are staged: the ring, the stamp mirror, stats.events_staged, the Time Surface and the mapper's selection are those
+ * of esvo_ts_push_events given just the kept events, in the same order.  With a filter configured EVERY push call of the camera goes
+ * through it: esvo_ts_push_events, _async (then synchronous, as in routed mode), _event_array, _bag, _event_columns, _evt3, _evt2.
+ * What those calls report about their INPUT is unchanged (*n_events and the EVT decoder totals count decoded events); how many were
+ * staged is the `kept` delta of esvo_ts_filter_stats.  A packet of which nothing is kept returns ESVO_OK, stages nothing and still
+ * advances `last`.  An out-of-order packet -- not sorted in itself, or starting before the newest staged stamp -- is refused with
+ * ESVO_ERR_UNSUPPORTED: a raw sensor stream is monotone, the late-event rules of the unfiltered path are not extended.  Every refusal
+ * (bad arguments, a bad stamp, ESVO_ERR_CAPACITY, ESVO_ERR_UNSUPPORTED) leaves ring, mirror, `last` and totals as they were; RING ROOM
+ * IS THEREFORE JUDGED ON THE UNFILTERED COUNT, before the filter runs: a packet whose decoded events would not fit is refused even
+ * if its kept events would.  esvo_reset zeroes `last` and the totals and keeps the configuration; esvo_destroy frees everything.
+ * Every source reaches the ring through the column form (u64 stamp, u16 x, u16 y, polarity): a record handed in with nsec >= 10^9 or
+ * a polarity byte above 1 is staged as sec * 10^9 + nsec re-split and polarity 0 / 1, padding 0.
+ * The filter runs on the camera's column staging on the ingest stream: the packet's events are binned by 8x8-pixel tile (each also
+ * into the neighbouring tiles whose one-pixel halo holds it), one wave per tile sorts its list into stream order and applies the
+ * rule with the tile's 10x10 patch of `last` and of the mask in LDS -- the chains of the halo pixels are recomputed there, which
+ * makes the tiles independent -- a scan over the verdicts compacts the columns, and the existing column pack writes the ring.  A
+ * tile whose list overflows reads the packet itself instead: same answers, bounded cost.  A device-resident packet (device columns,
+ * decoded words) is judged for order and stamp validity by the compaction kernel: its unfiltered stamps never come down, the one
+ * read-back of the push carries the verdict counts and the kept stamps. */
+enum { ESVO_FILTER_KEPT = 0, ESVO_FILTER_OUTSIDE = 1, ESVO_FILTER_MASKED = 2, ESVO_FILTER_REFRACTORY = 3, ESVO_FILTER_UNSUPPORTED = 4 };
+typedef struct esvo_event_filter_t {
+  uint64_t refractory_ns, support_ns;   /* 0: that test is off */
+  const uint8_t* mask;                  /* [H * W], non-zero = masked; NULL: none.  Copied by esvo_ts_filter_configure. */
+  uint32_t reserved[4];                 /* 0 */
+} esvo_event_filter_t;
+typedef struct esvo_event_filter_counts_t { uint64_t events_in, kept, outside, masked, refractory, unsupported; } esvo_event_filter_counts_t;  /* events_in: the sum of the other five */
+/* f == NULL switches the camera's filter off and frees its memory; otherwise the mask is copied, the camera's `last` image is zeroed
+ * and the totals stay.  ESVO_ERR_UNSUPPORTED on a row-routed band handle (esvo_shard_set_routing with ESVO_ROUTE_Y_RECT filters
+ * packets on the host), and esvo_shard_set_routing to such a routing is refused on a handle with a filter on; broadcast band mode
+ * and tick-interleaved handles are fine (every rank sees the whole stream and reaches the same verdicts).  ESVO_ERR_INVALID_ARG: a
+ * non-zero reserved word.  Ingest group: not while another thread pushes to the same camera. */
+int esvo_ts_filter_configure(esvo_handle h, int cam, const esvo_event_filter_t* f);
+/* totals of the camera's successful push calls since esvo_create / esvo_reset (all zero while no filter has run) */
+int esvo_ts_filter_stats(esvo_handle h, int cam, esvo_event_filter_counts_t* totals);
+/* get_last (nullable, [H * W]) receives the camera's `last` image, then set_last (nullable, [H * W]) replaces it: a stream can be
+ * resumed, a test can plant a state.  ESVO_ERR_STATE while no filter is configured. */
+int esvo_ts_filter_state(esvo_handle h, int cam, uint64_t* get_last, const uint64_t* set_last);
+/* The rule alone: host only, no handle, no GPU.  last: [height * width], in / out (it advances only on ESVO_OK).  verdict (nullable,
+ * [n]) receives ESVO_FILTER_*; the kept events go to out[0 .. *n_out) in order (out == NULL counts; more kept than cap:
+ * ESVO_ERR_CAPACITY); *add (nullable) is INCREMENTED by this call's counts.  The events are taken as sorted; f->reserved must be 0. */
+int esvo_event_filter_host(const esvo_event_filter_t* f, int width, int height, uint64_t* last, const esvo_event_t* ev, size_t n,
+                           uint8_t* verdict, esvo_event_t* out, size_t cap, size_t* n_out, esvo_event_filter_counts_t* add);
+/* sizeof(esvo_event_filter_t), sizeof(esvo_event_filter_counts_t), 0, 0 */
+void esvo_event_filter_sizes(size_t out[4]);
 /* rosbag (format 2.0) ingest, SURVEY.md §8(f).2: the reading side of events_repacking_helper
  * (events_repacking_helper/src/EventMessageEditor.cpp:66-119: rosbag::Bag::open, rosbag::View over an event topic,
  * MessageInstance::instantiate<dvs_msgs::EventArray>).  Chunks (compression none / bz2 / lz4) are walked in file order;

@@ -126,6 +126,23 @@ class TimeSurface {
     ctx_->check(esvo_ts_push_evt2(ctx_->handle(), cam_, words, n_bytes, format, memory, t_offset_us, &n_events), "esvo_ts_push_evt2");
     return n_events;
   }
+  // the camera's event filter (esvo_ts_filter_configure): hot-pixel mask ([H * W], non-zero = masked, copied; null: none), refractory
+  // period and neighbour support in ns (0: that test is off); from then on every call above stages only the events it keeps
+  void setEventFilter(uint64_t refractory_ns, uint64_t support_ns, const uint8_t* mask = nullptr) {
+    esvo_event_filter_t f{};
+    f.refractory_ns = refractory_ns; f.support_ns = support_ns; f.mask = mask;
+    ctx_->check(esvo_ts_filter_configure(ctx_->handle(), cam_, &f), "esvo_ts_filter_configure");
+  }
+  void clearEventFilter() { ctx_->check(esvo_ts_filter_configure(ctx_->handle(), cam_, nullptr), "esvo_ts_filter_configure"); }
+  esvo_event_filter_counts_t eventFilterStats() {
+    esvo_event_filter_counts_t c{};
+    ctx_->check(esvo_ts_filter_stats(ctx_->handle(), cam_, &c), "esvo_ts_filter_stats");
+    return c;
+  }
+  // get_last / set_last: [H * W] ns stamps, either may be null (esvo_ts_filter_state)
+  void eventFilterState(uint64_t* get_last, const uint64_t* set_last = nullptr) {
+    ctx_->check(esvo_ts_filter_state(ctx_->handle(), cam_, get_last, set_last), "esvo_ts_filter_state");
+  }
   // TimeSurface::createTimeSurfaceAtTime: the rectified mono8 Time Surface at the sync time
   void createTimeSurfaceAtTime(uint64_t external_sync_time_ns, uint8_t* out_mono8 /*nullable*/) {
     ctx_->check(esvo_ts_render(ctx_->handle(), cam_, external_sync_time_ns, out_mono8), "esvo_ts_render");
