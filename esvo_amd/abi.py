@@ -371,6 +371,52 @@ def event_filter_struct(refractory_ns, support_ns, mask, width, height):
     return s, keep
 
 
+# esvo_ts_survey_* / esvo_event_survey_host / esvo_hot_pixel_mask_host: the event survey and its hot-pixel rule (include/esvo_hip.h)
+SURVEY_COUNT_ONLY = 1
+MASK_KEEP, MASK_REPLACE, MASK_UNION = 0, 1, 2
+
+
+class _DictStruct(C.Structure):
+    def as_dict(self):
+        return {k: int(getattr(self, k)) for k, t in self._fields_ if not k.startswith("pad") and k != "reserved"}
+
+
+class EventSurveyStruct(C.Structure):
+    """esvo_event_survey_t"""
+    _fields_ = [("flags", C.c_uint32), ("reserved", C.c_uint32 * 3)]
+
+
+class EventSurveyStats(_DictStruct):
+    """esvo_event_survey_stats_t"""
+    _fields_ = [(k, C.c_uint64) for k in ("events_in", "outside", "packets", "t_first", "t_last")]
+
+
+class HotPixelRule(_DictStruct):
+    """esvo_hot_pixel_rule_t"""
+    _fields_ = [("min_count", C.c_uint32), ("factor", C.c_uint32), ("rank_permille", C.c_uint32), ("max_rate_hz", C.c_uint32), ("reserved", C.c_uint32 * 4)]
+
+
+class HotPixelReport(_DictStruct):
+    """esvo_hot_pixel_report_t"""
+    _fields_ = [("baseline", C.c_uint32), ("rate_count", C.c_uint32), ("n_hot", C.c_uint32), ("max_count", C.c_uint32), ("max_pixel", C.c_uint32),
+                ("pad_", C.c_uint32), ("events_hot", C.c_uint64)]
+
+
+def event_survey_stats(stats):
+    """an EventSurveyStats from a dict (missing keys: 0) or None"""
+    s = EventSurveyStats()
+    for k, v in (stats or {}).items():
+        setattr(s, k, int(v))
+    return s
+
+
+def hot_pixel_rule(min_count=1, factor=0, rank_permille=500, max_rate_hz=0, reserved=(0, 0, 0, 0)):
+    r = HotPixelRule()
+    r.min_count, r.factor, r.rank_permille, r.max_rate_hz = int(min_count), int(factor), int(rank_permille), int(max_rate_hz)
+    r.reserved[:] = [int(v) for v in reserved]
+    return r
+
+
 class Evt2Error(ValueError):
     """an event of the words has no valid stamp; `first_bad` is its index among the events"""
 

@@ -63,6 +63,7 @@ int zero_session_buffers(esvo_context* h, hipStream_t st) {
   HIPCHK(hipMemsetAsync(h->d_fuse_ctr, 0, sizeof(u32) * 2112, st));
   if (h->d_rank_kept) HIPCHK(hipMemsetAsync(h->d_rank_kept, 0, sizeof(u32) * esvo_context::SHARD_MAX_RANKS, st));  // (band mode: allocated by its configuration)
   { int rcf = filter_zero_state(h, st); if (rcf) return rcf; }  // (the event filter's `last` images, where one is configured)
+  { int rcs = survey_zero_state(h, st); if (rcs) return rcs; }  // (the event survey's counts and stats, where one is open)
   h->d_map_cur = h->d_map;
   return ESVO_OK;
 }

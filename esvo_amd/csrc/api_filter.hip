@@ -88,6 +88,7 @@ int esvo_ts_filter_configure(esvo_handle h, int cam, const esvo_event_filter_t* 
     (void)F.d_last.release(); (void)F.d_mask.release(); (void)F.d_twin.release(); (void)F.d_code.release(); (void)F.d_tcount.release();
     (void)F.d_tlist.release(); (void)F.d_scan.release(); (void)F.h_twin.release();
   };
+  if (!f && h->srv[cam].on) FAIL(ESVO_ERR_STATE, "esvo_ts_filter_configure: an event survey of this camera is open (esvo_ts_survey_end first)");
   if (!f) { release(); return ESVO_OK; }
   const size_t npx = (size_t)h->W * h->H, tiles = filter_tiles(h->W, h->H);
   hipError_t e = hipSuccess;

@@ -511,6 +511,18 @@ template <typename Src>
 int push_filtered(esvo_context* h, int cam, Src& src) {
   const char* const out_of_order = "event filter: out-of-order packet (not sorted by time stamp, or older than the newest staged event)";
   const bool host_stamps = src.stamps_on_host();  // (else the filter's last kernel looks at stamps and order: they never come down)
+  const bool survey = h->srv[cam].on;  // (esvo_ts_survey_begin; api_survey.hip)
+  if (survey) {
+    { int rc = survey_admit(h, cam, src.n); if (rc) return rc; }
+    if (h->srv[cam].count_only) {  // the packet is decoded and counted: nothing is staged, no order and no ring room is asked for
+      FilterPacket raw{};
+      { int rc = src.columns(raw); if (rc) return rc; }
+      u32 bad = 0xffffffffu;
+      { int rc = survey_count_only(h, cam, raw, !src.stamps_on_host(), &bad); if (rc) return rc; }
+      if (bad != 0xffffffffu) FAIL(ESVO_ERR_INVALID_ARG, src.bad_stamp_message(bad));
+      return ESVO_OK;
+    }
+  }
   u64 newest = 0;
   {
     std::lock_guard<std::mutex> lr(h->mu_ring);
@@ -528,9 +540,12 @@ int push_filtered(esvo_context* h, int cam, Src& src) {
   { int rc = filter_run(h, cam, in, newest, &twin, &kept_stamps, &counts, &unsorted, &first_bad); if (rc) return rc; }
   if (first_bad != 0xffffffffu) FAIL(ESVO_ERR_INVALID_ARG, src.bad_stamp_message(first_bad));
   if (unsorted) FAIL(ESVO_ERR_UNSUPPORTED, out_of_order);
+  // the survey counts the raw packet behind the last refusal, on the stream the staging below waits for (it stages nothing: nobody waits)
+  if (survey) { int rc = survey_count(h, cam, in, twin.n == 0); if (rc) return rc; }
   KeptPacket kept{h, cam, twin, kept_stamps, twin.n};
   { int rc = push_staged(h, cam, kept, [](size_t) {}); if (rc) return rc; }
   filter_commit(h, cam, counts);
+  if (survey) survey_commit(h, cam, src.n);
   return ESVO_OK;
 }
 // records on the host (get(i): normalised) split into columns by a plain loop and uploaded into the camera's column staging

@@ -277,6 +277,27 @@ struct FilterArgs {
 size_t filter_tiles(int W, int H);
 void launch_event_filter(const FilterArgs& a, u32* scan_tmp, const void* p, int p_type, u64* out_t, uint16_t* out_x, uint16_t* out_y,
                          uint8_t* out_p, hipStream_t s);
+// The event survey (esvo_ts_survey_begin, include/esvo_hip.h; kernels_survey.hip): per-pixel counts of a column packet, and the hot-pixel
+// mask derived from them.  counts: [2][H * W], plane = polarity; stats: SRV_STAT_WORDS u64 (SRV_S_*).
+constexpr u32 SRV_CHUNK = 1024u;  // events a workgroup combines in LDS before global memory hears of them
+constexpr u32 SRV_STAT_WORDS = 4u;
+constexpr u32 SRV_S_IN = 0u, SRV_S_OUTSIDE = 1u, SRV_S_T_FIRST = 2u /* ~0: no counted event yet */, SRV_S_T_LAST = 3u;
+// the select's words (u32): the baseline's known high bits, the rank left below them, the first bad stamp of a count-only packet, a
+// 256-bin histogram
+constexpr u32 SRV_SEL_PREFIX = 0u, SRV_SEL_RANK = 1u, SRV_SEL_FIRST_BAD = 2u, SRV_SEL_HIST = 4u, SRV_SEL_WORDS = SRV_SEL_HIST + 256u;
+// the report's words (u64): hot pixels, their events, max count << 32 | ~(its smallest pixel), the baseline
+constexpr u32 SRV_R_HOT = 0u, SRV_R_EVENTS = 1u, SRV_R_MAX = 2u, SRV_R_BASELINE = 3u, SRV_REPORT_WORDS = 4u;
+struct SurveyArgs {
+  const u64* t; const uint16_t* x; const uint16_t* y; const void* p; int p_type; u32 n;
+  int W, H;
+  u32* counts; u64* stats;
+};
+void launch_survey_count(const SurveyArgs& a, hipStream_t s);
+void launch_survey_first_bad(const u64* t, u32 n, u32* sel, hipStream_t s);  // sel[SRV_SEL_FIRST_BAD]: index of the first COL_BAD_STAMP, 0xffffffff: none
+// B = the rank-th smallest c (radix select into sel), then the mask bytes and the report; rate_on: the test c > rate_count applies
+void launch_survey_mask(const u32* counts, u32 npx, u32 rank, u32 min_count, u32 factor, bool rate_on, u32 rate_count, u32* sel, uint8_t* mask,
+                        u64* report, hipStream_t s);
+void launch_survey_mask_or(uint8_t* into, const uint8_t* from, u32 npx, hipStream_t s);
 // EVT 3.0 ingest (esvo_ts_push_evt3, include/esvo_hip.h): ONE function per rule of the format, shared by the host decoder
 // (esvo_evt3_to_events) and the device decode (kernels_ts.hip), so both produce the same bytes.
 enum { EVT3_ADDR_Y = 0x0, EVT3_ADDR_X = 0x2, EVT3_VECT_BASE_X = 0x3, EVT3_VECT_12 = 0x4, EVT3_VECT_8 = 0x5, EVT3_TIME_LOW = 0x6,

@@ -15,6 +15,7 @@
 //   api_em.hip     event-to-event matching (modes 0 and 2)     api_gpc.hip    the global point cloud
 //   api_track.hip  tracker residual / Jacobian evaluation      api_bag.hip, api_dev.hip  bag reader, development hooks
 //   api_history.hip  Time-Surface history: frames by stamp, the mapper's and the tracker's pick
+//   api_filter.hip, api_survey.hip  the ingest path's event filter; per-pixel counts of the pushed stream and the mask learnt from them
 #pragma once
 #include <algorithm>
 #include <array>
@@ -81,6 +82,10 @@ struct IngestSession {  // under mu_ring: the event rings
   // the event filter (esvo_ts_filter_configure): the totals of a camera's successful pushes, under its mu_push.  (The `last` image
   // is device memory: esvo_reset zeroes it beside the other session buffers, EventFilter below.)
   esvo_event_filter_counts_t flt_totals[2] = {};
+  // the event survey (esvo_ts_survey_begin), under the camera's mu_push: what the host knows of an open survey without a read-back --
+  // events of its accepted packets (events_in + outside of its stats: the bound that keeps every counter below 2^32) and the packets.
+  // (The counts are device memory: esvo_reset zeroes them beside the other session buffers, EventSurvey below.)
+  u64 srv_events[2] = {0, 0}, srv_packets[2] = {0, 0};
 };
 struct TsSession {  // under mu_ts (the right camera's flag: mapper group only)
   bool ts_valid[2] = {false, false};  // d_ts[cam] holds a render
@@ -333,6 +338,16 @@ struct esvo_context : IngestSession, TsSession, SchedSession, MapSession, CloudS
     PinBuf<u64> h_twin;
     size_t cap = 0;
   } flt[2];
+  // The event survey of a camera (esvo_ts_survey_begin; api_survey.hip, kernels_survey.hip), under its mu_push; open or not survives a
+  // reset, which zeroes the counts.  d_counts: [2][W * H], plane = polarity; d_stats: SRV_STAT_WORDS; d_sel / d_report / d_mask: the
+  // radix select's words, the report and the mask bytes of esvo_ts_survey_mask.
+  struct EventSurvey {
+    std::atomic<bool> on{false};
+    bool count_only = false;
+    DevBuf<u32> d_counts, d_sel;
+    DevBuf<u64> d_stats, d_report;
+    DevBuf<uint8_t> d_mask;
+  } srv[2];
   u32 flt_tcap = FLT_TILE_CAP_MAX;  // ESVO_FLT_TILE_CAP (tests): entries of a tile's list; beyond it the tile reads the packet
   u64 ring_cap = 0;
   // esvo_ts_push_events_async: the newest enqueued (not awaited) copy of a camera; consumers of the ring on the front stream
@@ -570,6 +585,15 @@ int filter_run(esvo_context* h, int cam, const FilterPacket& in, u64 newest, Fil
                bool* unsorted, u32* first_bad);
 void filter_commit(esvo_context* h, int cam, const esvo_event_filter_counts_t& counts);
 int filter_zero_state(esvo_context* h, hipStream_t st);  // esvo_reset: the `last` images of both cameras
+// api_survey.hip: the hook of push_filtered (api_ts.hip) while a camera's survey is open; caller holds mu_push[cam]
+int survey_admit(esvo_context* h, int cam, size_t n);  // ESVO_ERR_CAPACITY where n more events would take a counter beyond 2^32 - 1
+// counts the packet on the ingest stream, behind the verdicts that accepted it; wait: nothing else of the push waits for the stream
+int survey_count(esvo_context* h, int cam, const FilterPacket& in, bool wait);
+void survey_commit(esvo_context* h, int cam, size_t n);
+// count-only mode: the whole push.  check_stamps: the packet's stamps never reached the host; *first_bad: its first invalid one
+// (0xffffffff: none, and the packet is counted)
+int survey_count_only(esvo_context* h, int cam, const FilterPacket& in, bool check_stamps, u32* first_bad);
+int survey_zero_state(esvo_context* h, hipStream_t st);  // esvo_reset: the counts and stats of both cameras
 // api_history.hip
 int hist_store(esvo_context* h, int cam, uint64_t t_ns, const uint8_t* src, bool from_host);  // caller holds mu_ts
 void hist_clear(esvo_context* h);                                                             // caller holds mu_ts

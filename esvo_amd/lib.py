@@ -10,7 +10,7 @@ import subprocess
 
 import numpy as np
 
-from .abi import (MEM_DEVICE, MEM_HOST, P_U8, ColumnsError, EventColumnsStruct, EventFilterCounts, EventFilterStruct, event_filter_struct, Evt2Counts, Evt2State, Evt3Counts, Evt3State, evt2_words, evt3_words, check_t_offset, column_p_type, column_t_type,
+from .abi import (MEM_DEVICE, MEM_HOST, P_U8, ColumnsError, EventColumnsStruct, EventFilterCounts, EventFilterStruct, event_filter_struct, EventSurveyStats, EventSurveyStruct, HotPixelReport, event_survey_stats, hot_pixel_rule, Evt2Counts, Evt2State, Evt3Counts, Evt3State, evt2_words, evt3_words, check_t_offset, column_p_type, column_t_type,
                   DEPTH_POINT_DTYPE, EM_POSE_FN, ERR_CAPACITY, ERR_INVALID_ARG, ERR_STATE, EVENT_DTYPE, MATCH_DTYPE, CalibStruct, EmSelectionStruct,
                   EmStatsStruct, GpcParamsStruct, GpcStatsStruct, LmStatsStruct, ParamsStruct, SgmStatsStruct, StatsStruct, TRACK_ITER_DTYPE, TRACK_SOLVE_MAX_ITERATIONS,
                   TrackSolveInfoStruct, TrackSolveParamsStruct)
@@ -18,7 +18,7 @@ from .abi import (MEM_DEVICE, MEM_HOST, P_U8, ColumnsError, EventColumnsStruct, 
 _CSRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc")
 # ESVO_HIP_LIB: another build of the same library (A/B measurements of kernel variants, tools/ab_build.py); never a fallback
 _LIB_PATH = os.environ.get("ESVO_HIP_LIB") or os.path.join(_CSRC, "libesvo_hip.so")
-_SOURCES = ["api_core.hip", "api_ts.hip", "api_map.hip", "api_window.hip", "api_modes.hip", "api_shard.hip", "api_out.hip", "api_comm.hip", "api_bag.hip", "api_track.hip", "scan.hip", "kernels_ts.hip", "kernels_bm.hip", "kernels_lm.hip", "kernels_lm_any.hip", "kernels_fuse.hip", "kernels_shard.hip", "kernels_track.hip", "kernels_track_viz.hip", "kernels_viz.hip", "kernels_sgm.hip", "api_em.hip", "kernels_em.hip", "kernels_cloud.hip", "api_dev.hip", "api_gpc.hip", "kernels_voxel.hip", "api_history.hip", "api_filter.hip", "kernels_filter.hip"]
+_SOURCES = ["api_core.hip", "api_ts.hip", "api_map.hip", "api_window.hip", "api_modes.hip", "api_shard.hip", "api_out.hip", "api_comm.hip", "api_bag.hip", "api_track.hip", "scan.hip", "kernels_ts.hip", "kernels_bm.hip", "kernels_lm.hip", "kernels_lm_any.hip", "kernels_fuse.hip", "kernels_shard.hip", "kernels_track.hip", "kernels_track_viz.hip", "kernels_viz.hip", "kernels_sgm.hip", "api_em.hip", "kernels_em.hip", "kernels_cloud.hip", "api_dev.hip", "api_gpc.hip", "kernels_voxel.hip", "api_history.hip", "api_filter.hip", "kernels_filter.hip", "api_survey.hip", "kernels_survey.hip"]
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared",
                "-Wno-unused-value", "-Wno-unused-result", "-ldl"]
 
@@ -46,6 +46,8 @@ SYMBOLS = [
     "esvo_ts_history_configure", "esvo_ts_history_list", "esvo_ts_history_get", "esvo_ts_history_put", "esvo_map_set_observation_at",
     "esvo_track_set_current_at", "esvo_ts_history_select", "esvo_ts_history_select_observation",
     "esvo_ts_filter_configure", "esvo_ts_filter_stats", "esvo_ts_filter_state", "esvo_event_filter_host", "esvo_event_filter_sizes",
+    "esvo_ts_survey_begin", "esvo_ts_survey_end", "esvo_ts_survey_stats", "esvo_ts_survey_state", "esvo_ts_survey_mask",
+    "esvo_event_survey_host", "esvo_hot_pixel_mask_host", "esvo_event_survey_sizes",
 ]
 # the EVT 3.0 entry points, listed apart: their names carry a digit (SYMBOLS is compared with a scan of the header for [a-z_] names)
 SYMBOLS_EVT3 = ["esvo_ts_push_evt3", "esvo_ts_evt3_state", "esvo_ts_evt3_stats", "esvo_evt3_to_events", "esvo_evt3_raw_header", "esvo_evt3_sizes",
@@ -282,9 +284,18 @@ def load():
     lib.esvo_event_filter_host.argtypes = [vp, i32, i32, vp, vp, sz, vp, vp, sz, psz, vp]
     lib.esvo_event_filter_sizes.argtypes = [vp]
     lib.esvo_event_filter_sizes.restype = None
+    lib.esvo_ts_survey_begin.argtypes = [vp, i32, vp]
+    lib.esvo_ts_survey_end.argtypes = [vp, i32]
+    lib.esvo_ts_survey_stats.argtypes = [vp, i32, vp]
+    lib.esvo_ts_survey_state.argtypes = [vp, i32, vp, vp, vp]
+    lib.esvo_ts_survey_mask.argtypes = [vp, i32, vp, vp, i32, vp]
+    lib.esvo_event_survey_host.argtypes = [i32, i32, vp, vp, vp, sz]
+    lib.esvo_hot_pixel_mask_host.argtypes = [vp, i32, i32, vp, vp, vp, vp]
+    lib.esvo_event_survey_sizes.argtypes = [vp]
+    lib.esvo_event_survey_sizes.restype = None
     for s in SYMBOLS + SYMBOLS_EVT3:
         if s not in ("esvo_default_params", "esvo_last_error", "esvo_abi_sizes", "esvo_bag_last_error", "esvo_em_sizes", "esvo_lm_sizes", "esvo_sgm_sizes",
-                     "esvo_track_sizes", "esvo_gpc_sizes", "esvo_event_columns_sizes", "esvo_evt3_sizes", "esvo_evt2_sizes", "esvo_event_filter_sizes"):
+                     "esvo_track_sizes", "esvo_gpc_sizes", "esvo_event_columns_sizes", "esvo_evt3_sizes", "esvo_evt2_sizes", "esvo_event_filter_sizes", "esvo_event_survey_sizes"):
             getattr(lib, s).restype = C.c_int
     lib.esvo_abi_sizes.argtypes = [vp]
     lib.esvo_abi_sizes.restype = None
@@ -792,6 +803,39 @@ def event_filter_host(events, width, height, refractory_ns=0, support_ns=0, mask
     return verdict, out[:n_out.value].copy(), L, cnt.as_dict()
 
 
+def event_survey_sizes():
+    """sizeof() of esvo_event_survey_t, esvo_event_survey_stats_t, esvo_hot_pixel_rule_t, esvo_hot_pixel_report_t (esvo_event_survey_sizes)"""
+    out = (C.c_size_t * 4)()
+    load().esvo_event_survey_sizes(out)
+    return list(out)
+
+
+def event_survey_host(events, width, height, counts=None, stats=None):
+    """esvo_event_survey_host: the survey's counting on the host -> (counts (2, height, width) uint32, stats dict).  counts / stats:
+    what to resume from (None: zero), not modified -- the returned ones are the advanced copies."""
+    ev = np.ascontiguousarray(events, EVENT_DTYPE)
+    shape = (2, int(height), int(width))
+    cnt = np.zeros(shape, np.uint32) if counts is None else np.array(counts, np.uint32).reshape(shape).copy()
+    st = event_survey_stats(stats)
+    rc = load().esvo_event_survey_host(int(width), int(height), cnt.ctypes.data, C.addressof(st), ev.ctypes.data if len(ev) else None, len(ev))
+    if rc != 0:
+        raise EsvoError(f"esvo_event_survey_host failed ({rc}): {load().esvo_last_error(None).decode(errors='replace')}", code=rc)
+    return cnt, st.as_dict()
+
+
+def hot_pixel_mask_host(counts, stats, width, height, **rule):
+    """esvo_hot_pixel_mask_host: the hot-pixel rule on the host -> (mask (height, width) uint8, report dict).  counts: (2, height, width);
+    stats: a dict with t_first / t_last / events_in (the rate test's duration); rule: the fields of esvo_hot_pixel_rule_t."""
+    shape = (2, int(height), int(width))
+    cnt = np.ascontiguousarray(np.asarray(counts, np.uint32).reshape(shape))
+    st, r, rep = event_survey_stats(stats), hot_pixel_rule(**rule), HotPixelReport()
+    mask = np.zeros(shape[1:], np.uint8)
+    rc = load().esvo_hot_pixel_mask_host(C.addressof(r), int(width), int(height), cnt.ctypes.data, C.addressof(st), mask.ctypes.data, C.addressof(rep))
+    if rc != 0:
+        raise EsvoError(f"esvo_hot_pixel_mask_host failed ({rc}): {load().esvo_last_error(None).decode(errors='replace')}", code=rc)
+    return mask, rep.as_dict()
+
+
 def abi_sizes():
     out = (C.c_size_t * 8)()
     load().esvo_abi_sizes(out)
@@ -999,6 +1043,42 @@ class Esvo:
         new = None if set is None else np.ascontiguousarray(np.asarray(set, np.uint64).reshape(H, W))
         self._ck(self.lib.esvo_ts_filter_state(self.h, int(cam), got.ctypes.data, None if new is None else new.ctypes.data))
         return got
+
+    def ts_survey_begin(self, cam, count_only=False, flags=None, reserved=(0, 0, 0)):
+        """opens the camera's event survey (esvo_ts_survey_begin): per-pixel counts of every packet its push calls accept, kept on the
+        device.  The camera's filter must be configured.  count_only: packets are decoded and counted and nothing is staged."""
+        s = EventSurveyStruct()
+        s.flags = int(flags) if flags is not None else (1 if count_only else 0)
+        s.reserved[:] = [int(v) for v in reserved]
+        self._ck(self.lib.esvo_ts_survey_begin(self.h, int(cam), C.addressof(s)))
+
+    def ts_survey_end(self, cam):
+        self._ck(self.lib.esvo_ts_survey_end(self.h, int(cam)))
+
+    def ts_survey_stats(self, cam):
+        """the survey's stats as a dict: events_in, outside, packets, t_first, t_last"""
+        st = EventSurveyStats()
+        self._ck(self.lib.esvo_ts_survey_stats(self.h, int(cam), C.addressof(st)))
+        return st.as_dict()
+
+    def ts_survey_state(self, cam, set=None, stats=None):
+        """the survey's counts, (2, H, W) uint32, plane = polarity (esvo_ts_survey_state); set: counts that replace them afterwards,
+        stats: a dict that replaces the stats with them"""
+        shape = (2, self.rig.height, self.rig.width)
+        got = np.zeros(shape, np.uint32)
+        new = None if set is None else np.ascontiguousarray(np.asarray(set, np.uint32).reshape(shape))
+        st = None if stats is None else event_survey_stats(stats)
+        self._ck(self.lib.esvo_ts_survey_state(self.h, int(cam), got.ctypes.data, None if new is None else new.ctypes.data,
+                                               None if st is None else C.addressof(st)))
+        return got
+
+    def ts_survey_mask(self, cam, install=0, want_mask=True, **rule):
+        """esvo_ts_survey_mask: the hot-pixel rule on the survey's counts, on the device -> (mask (H, W) uint8 or None, report dict).
+        install: abi.MASK_KEEP / MASK_REPLACE / MASK_UNION puts the mask into the camera's filter, device to device."""
+        r, rep = hot_pixel_rule(**rule), HotPixelReport()
+        mask = np.zeros((self.rig.height, self.rig.width), np.uint8) if want_mask else None
+        self._ck(self.lib.esvo_ts_survey_mask(self.h, int(cam), C.addressof(r), None if mask is None else mask.ctypes.data, int(install), C.addressof(rep)))
+        return mask, rep.as_dict()
 
     def evt2_state(self, cam, set=None):
         """the camera's EVT 2.x decoder state (an abi.Evt2State); set: an Evt2State that replaces it (a reader seeks or resumes)"""

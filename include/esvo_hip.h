@@ -528,6 +528,92 @@ int esvo_event_filter_host(const esvo_event_filter_t* f, int width, int height, 
                            uint8_t* verdict, esvo_event_t* out, size_t cap, size_t* n_out, esvo_event_filter_counts_t* add);
 /* sizeof(esvo_event_filter_t), sizeof(esvo_event_filter_counts_t), 0, 0 */
 void esvo_event_filter_sizes(size_t out[4]);
+/* Event survey on the device: per-pixel event counts kept while a stream is pushed, and a hot-pixel mask learnt from them -- the
+ * filter's mask without a host loop over events the host may never see (device columns, device-resident words).  Off unless begun;
+ * a handle that never opens a survey takes the paths above unchanged.  Each camera has its own survey: counts[2][H][W] uint32, plane
+ * 0 = polarity 0 (off), plane 1 = polarity 1 (on), and the stats below.
+ * WHAT IS COUNTED: while a survey is open every packet that a push call of the camera ACCEPTS (esvo_ts_push_events, _async,
+ * _event_array, _bag, _event_columns, _evt3, _evt2): each decoded event with x < W and y < H adds 1 to counts[polarity][y][x], polarity
+ * normalised to 0 / 1 as the ring holds it; every other event adds 1 to stats.outside.  The RAW packet is counted, before the mask,
+ * refractory and support tests: a masked pixel keeps being counted, so a refreshed mask does not forget it.  The camera's filter must
+ * be configured (ESVO_ERR_STATE otherwise): with it every source reaches one place as a device-resident column packet, and the
+ * survey reads that packet and nothing else.  A filter with both periods 0 and no mask passes every in-sensor event: the way to
+ * survey a stream that is to stay unfiltered.  (Row-routed band handles cannot have a filter, so they cannot have a survey.)
+ * flags == 0: ring, stamp mirror, esvo_get_stats, the filter's `last` and totals, rendered Time Surfaces and every return value are
+ * those of the same pushes without a survey.  The survey is transactional as the filter is: counts and stats advance only behind a
+ * push that returned ESVO_OK; bad arguments, a bad stamp, ESVO_ERR_CAPACITY and the filter's ESVO_ERR_UNSUPPORTED leave them as they
+ * were.  An open survey adds no read-back to a push and no wait, except to a packet of which the filter keeps nothing (that push
+ * waits for nothing else, and the packet may lie in the caller's memory); counts and stats come down only in the calls below.
+ * ESVO_SURVEY_COUNT_ONLY (a dark recording): the packet is decoded and counted and NOTHING ELSE happens -- nothing is staged, no ring
+ * room is needed, the filter's `last` and totals stay, no order is demanded (counting is order-free).  A packet with an invalid
+ * stamp is still refused with ESVO_ERR_INVALID_ARG and nothing of it is counted; the EVT decoder states and totals advance as by a
+ * normal push and *n_events reports the decoded count.
+ * No counter may wrap: a push that would take events_in + outside beyond 2^32 - 1 is refused with ESVO_ERR_CAPACITY before anything
+ * runs, judged on the host from the packet's unfiltered size.  esvo_reset zeroes counts and stats and keeps the survey open;
+ * esvo_destroy frees everything; esvo_ts_filter_configure(h, cam, NULL) while a survey is open: ESVO_ERR_STATE (end it first), a
+ * non-NULL reconfiguration keeps the survey and its counts.  Ingest group: not while another thread pushes to the same camera.
+ * The counting kernel combines on chip first: a workgroup sorts the keys pixel << 1 | polarity of 1024 consecutive events in LDS and
+ * issues one atomic add per run of equal keys, so a stuck pixel costs global memory one update per chunk, not one per event. */
+enum { ESVO_SURVEY_COUNT_ONLY = 1 };
+typedef struct esvo_event_survey_t { uint32_t flags; uint32_t reserved[3]; /* 0 */ } esvo_event_survey_t;
+typedef struct esvo_event_survey_stats_t {
+  uint64_t events_in;        /* events of accepted packets with x < W and y < H: the sum of all counters */
+  uint64_t outside;          /* events of accepted packets with x >= W or y >= H (counted nowhere else) */
+  uint64_t packets;          /* accepted packets */
+  uint64_t t_first, t_last;  /* smallest / largest ns stamp among the counted events; 0, 0 while events_in == 0 */
+} esvo_event_survey_stats_t;
+/* counts and stats start at zero.  ESVO_ERR_STATE: no filter configured, or a survey is open already; ESVO_ERR_INVALID_ARG: an unknown
+ * flag or a non-zero reserved word. */
+int esvo_ts_survey_begin(esvo_handle h, int cam, const esvo_event_survey_t* s);
+/* frees the survey's memory (ESVO_ERR_STATE: none is open; so for the three calls below) */
+int esvo_ts_survey_end(esvo_handle h, int cam);
+int esvo_ts_survey_stats(esvo_handle h, int cam, esvo_event_survey_stats_t* out);
+/* counts: [2][H][W] uint32.  get (nullable) receives them, then set (nullable) replaces them; stats_set (nullable, only with set)
+ * replaces the stats: a survey can be resumed, a test can plant one.  The two planes of a pixel must not add up beyond 2^32 - 1, nor
+ * stats_set's events_in + outside (ESVO_ERR_INVALID_ARG). */
+int esvo_ts_survey_state(esvo_handle h, int cam, uint32_t* get, const uint32_t* set, const esvo_event_survey_stats_t* stats_set);
+/* The hot-pixel rule, all of it in integers on the survey's counts:
+ *   c[px] = counts[0][px] + counts[1][px]
+ *   k     = floor(rank_permille * (W * H - 1) / 1000)
+ *   B     = the k-th smallest (0-based) of the W * H values c, zeros included
+ *   R     = min(2^32 - 1, floor(max_rate_hz * (t_last - t_first) / 10^9)), computed once on the host in 128-bit arithmetic; with
+ *           t_last == t_first the rate test contributes nothing
+ *   hot(px) = c >= min_count and ((factor > 0 and c > factor * B) or (rate test on and c > R))      -- both strict, factor * B in 64 bits
+ * PINNED TO NOTHING THIRD-PARTY: the whole rule is this library's own, as the filter's is; nothing in the reference corresponds to it.
+ * ESVO_ERR_INVALID_ARG: both tests off (factor == 0 and max_rate_hz == 0), min_count == 0, rank_permille > 1000, a non-zero
+ * reserved word, an unknown `install`.  The report: baseline = B; rate_count = R (0 with the rate test off or contributing nothing);
+ * n_hot; events_hot = the sum of c over the hot pixels; max_count and max_pixel = the largest c and the smallest y * W + x holding it.
+ * Everything runs on the device from the resident counts: B from an exact radix select (four histogram passes over the 32-bit values,
+ * LDS histograms merged per workgroup), no sort and no download of the count image; only mask_out and the report come down (and,
+ * first, the 32 bytes of device stats that R is computed from).
+ * install: ESVO_MASK_KEEP leaves the filter alone; ESVO_MASK_REPLACE makes the mask the camera's filter mask, ESVO_MASK_UNION ORs it
+ * into the one in force -- device to device, from the next push on, the filter's `last` image, periods and totals untouched (which
+ * esvo_ts_filter_configure cannot do: it zeroes `last`).  The survey stays open and keeps its counts.  The calibration flow: begin
+ * count-only, push the dark recording, take the mask with install, end, push the real stream. */
+typedef struct esvo_hot_pixel_rule_t {
+  uint32_t min_count;      /* >= 1: a pixel with fewer events is never hot (so a pixel with none never is) */
+  uint32_t factor;         /* baseline test: c > factor * B.  0: test off */
+  uint32_t rank_permille;  /* 0..1000: which order statistic of the counts is the baseline B; 500 = the median */
+  uint32_t max_rate_hz;    /* rate test: c > R.  0: test off */
+  uint32_t reserved[4];    /* 0 */
+} esvo_hot_pixel_rule_t;
+typedef struct esvo_hot_pixel_report_t {
+  uint32_t baseline, rate_count, n_hot, max_count, max_pixel, pad_;
+  uint64_t events_hot;
+} esvo_hot_pixel_report_t;
+enum { ESVO_MASK_KEEP = 0, ESVO_MASK_REPLACE = 1, ESVO_MASK_UNION = 2 };
+/* mask_out: nullable, [H * W], 0 / 1; report: nullable */
+int esvo_ts_survey_mask(esvo_handle h, int cam, const esvo_hot_pixel_rule_t* rule, uint8_t* mask_out, int install, esvo_hot_pixel_report_t* report);
+/* The same rules on the host: no handle, no GPU.  counts: [2][height][width], in / out; *stats in / out (a call with n > 0 is one
+ * packet).  ESVO_ERR_CAPACITY, and nothing changes, where the call would take events_in + outside beyond 2^32 - 1. */
+int esvo_event_survey_host(int width, int height, uint32_t* counts, esvo_event_survey_stats_t* stats, const esvo_event_t* ev, size_t n);
+/* mask (nullable, [height * width]) and report (nullable) of `rule` on counts and stats (its t_first / t_last) */
+int esvo_hot_pixel_mask_host(const esvo_hot_pixel_rule_t* rule, int width, int height, const uint32_t* counts, const esvo_event_survey_stats_t* stats,
+                             uint8_t* mask, esvo_hot_pixel_report_t* report);
+/* sizeof(esvo_event_survey_t), sizeof(esvo_event_survey_stats_t), sizeof(esvo_hot_pixel_rule_t), sizeof(esvo_hot_pixel_report_t) */
+void esvo_event_survey_sizes(size_t out[4]);
+/* Still out of scope: Prophesee's STC / trail filters, polarity-aware support, event-rate control, reading decoded events back to
+ * the caller. */
 /* rosbag (format 2.0) ingest, SURVEY.md §8(f).2: the reading side of events_repacking_helper
  * (events_repacking_helper/src/EventMessageEditor.cpp:66-119: rosbag::Bag::open, rosbag::View over an event topic,
  * MessageInstance::instantiate<dvs_msgs::EventArray>).  Chunks (compression none / bz2 / lz4) are walked in file order;

@@ -143,6 +143,26 @@ class TimeSurface {
   void eventFilterState(uint64_t* get_last, const uint64_t* set_last = nullptr) {
     ctx_->check(esvo_ts_filter_state(ctx_->handle(), cam_, get_last, set_last), "esvo_ts_filter_state");
   }
+  // the camera's event survey (esvo_ts_survey_begin): per-pixel counts of every packet the calls above accept, kept on the device; the
+  // filter must be set (setEventFilter(0, 0) passes everything).  count_only: packets are decoded and counted, nothing is staged
+  void beginSurvey(bool count_only = false) {
+    esvo_event_survey_t s{};
+    s.flags = count_only ? ESVO_SURVEY_COUNT_ONLY : 0;
+    ctx_->check(esvo_ts_survey_begin(ctx_->handle(), cam_, &s), "esvo_ts_survey_begin");
+  }
+  void endSurvey() { ctx_->check(esvo_ts_survey_end(ctx_->handle(), cam_), "esvo_ts_survey_end"); }
+  esvo_event_survey_stats_t surveyStats() {
+    esvo_event_survey_stats_t s{};
+    ctx_->check(esvo_ts_survey_stats(ctx_->handle(), cam_, &s), "esvo_ts_survey_stats");
+    return s;
+  }
+  // the hot-pixel rule on the survey's counts (esvo_ts_survey_mask): mask_out ([H * W], 0 / 1) may be null; install: ESVO_MASK_KEEP,
+  // ESVO_MASK_REPLACE or ESVO_MASK_UNION puts the mask into the camera's filter, device to device
+  esvo_hot_pixel_report_t learnHotPixelMask(const esvo_hot_pixel_rule_t& rule, uint8_t* mask_out = nullptr, int install = ESVO_MASK_REPLACE) {
+    esvo_hot_pixel_report_t r{};
+    ctx_->check(esvo_ts_survey_mask(ctx_->handle(), cam_, &rule, mask_out, install, &r), "esvo_ts_survey_mask");
+    return r;
+  }
   // TimeSurface::createTimeSurfaceAtTime: the rectified mono8 Time Surface at the sync time
   void createTimeSurfaceAtTime(uint64_t external_sync_time_ns, uint8_t* out_mono8 /*nullable*/) {
     ctx_->check(esvo_ts_render(ctx_->handle(), cam_, external_sync_time_ns, out_mono8), "esvo_ts_render");
