@@ -795,8 +795,54 @@ def make_ts_cases():
     print("ref_ts_cases.npz", os.path.getsize(path) // 1024, "KiB")
 
 
+def run_track_case(c, motion):
+    """the reference's RegProblemLM on one crafted tracker problem (tests/track_cases.py) under one motion, without the points on
+    which the reference itself is undefined (track_cases.UNPINNED_KINDS): the order its shuffle produced, (R, t) as setProblem
+    derived them, per norm the residuals at x = 0 and at track_cases.PIN_X with the warping transformation of each, the Jacobian"""
+    import track_cases as TC
+    keep, _ = TC.pinned(c, motion)
+    assert keep.mean() >= 0.8, (c["variant"], c["W"], c["H"], motion, keep.mean())   # at least 80 % of a problem stays pinned
+    xyz = c["xyz"][keep]
+    neg, du, dv = c["images0"]
+    T_left = np.eye(4)
+    T_left[:3, :3], T_left[:3, 3] = TC.MOTIONS[motion]
+    out = {}
+    for norm, huber in (("huber", True), ("l2", False)):
+        rt = R.RefTracker(c["rig"], huber=huber, huber_threshold=50.0, max_points=len(xyz))
+        order, Rm, tv = rt.set_problem(neg, du, dv, xyz, TC.I4, T_left, seed=3)
+        assert rt.n == len(xyz)
+        out["order"], out["R"], out["t"] = order, Rm, tv
+        for i, x in enumerate((np.zeros(6), TC.PIN_X)):
+            out[f"{norm}_f{i}"], out[f"{norm}_T{i}"] = rt.residuals(0, rt.n, x)
+        out[f"{norm}_J"] = rt.jacobian(0, rt.n)
+    return out
+
+
+def make_track_cases():
+    """tests/track_cases.py: crafted reference points at the switch points of the tracker's reprojection, interpolation, mask,
+    Jacobian and Huber weight, evaluated by the reference's own RegProblemLM.  Recorded results only: per problem and motion a
+    digest of the inputs, the shuffle's order and the functor's outputs."""
+    import track_cases as TC
+    out = {}
+    for variant in TC.VARIANTS:
+        for W, H in TC.SIZES:
+            c = TC.problem(variant, W, H)
+            for motion in TC.MOTIONS:
+                key = f"{variant}_{W}x{H}_{motion}"
+                out[f"{key}_sha"] = TC.input_digest(c, motion)
+                for f, a in run_track_case(c, motion).items():
+                    out[f"{key}_{f}"] = a
+                print("track case", key, len(out[f"{key}_order"]), "of", len(c["xyz"]), "points pinned")
+    path = os.path.join(HERE, "ref_track_cases.npz")
+    np.savez_compressed(path, **out)
+    print("ref_track_cases.npz", os.path.getsize(path) // 1024, "KiB")
+
+
 if __name__ == "__main__":
     assert R.available(), "needs /root/reference (build container only)"
+    if "--track-cases" in sys.argv:   # only the crafted tracker cases: ref_track_cases.npz
+        make_track_cases()
+        sys.exit(0)
     if "--bm-cases" in sys.argv:   # only the crafted block-matching cases: ref_bm_cases.npz
         make_bm_cases()
         sys.exit(0)
@@ -837,3 +883,4 @@ if __name__ == "__main__":
     make_lm_cases()
     make_bm_cases()
     make_ts_cases()
+    make_track_cases()
