@@ -319,7 +319,7 @@ int esvo_map_tick_em(esvo_handle h, const esvo_em_params_t* em, int mode, uint64
   if (rc) return rc;
   // ---- the selected events into the matcher's buffers.  Under mu_ring again: the selection is re-validated, the gather is
   // ENQUEUED on the front stream before the lock is released and both cameras' selected ranges are registered with the ingest
-  // side (esvo_context::em_guard_lo): a push that would evict them drains the front stream first (push_begin, api_ts.hip), so
+  // side (esvo_context::em_guard_lo): a push that would evict them drains the front stream first (push_begin, api_ingest.hip), so
   // the copies always read the events that were selected.  The guard is lifted once the copies have completed.
   EmGuard guard(h);
   {

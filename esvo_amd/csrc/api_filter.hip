@@ -1,7 +1,7 @@
 // api_filter.hip — the event filter of the ingest path (include/esvo_hip.h, esvo_ts_filter_configure): its configuration and
 // state, the launch sequence over a column packet (kernels_filter.hip) and the rule itself on the host (esvo_event_filter_host).
-// The push calls reach it through push_packet (api_ts.hip).
-#include "context.hpp"
+// The push calls reach it through push_packet (ingest.hpp).
+#include "ingest.hpp"
 
 namespace esvo_host {
 
@@ -29,8 +29,8 @@ int filter_run(esvo_context* h, int cam, const FilterPacket& in, u64 newest, Fil
   auto& F = h->flt[cam];
   if (in.n > 0x7fffffffull) FAIL(ESVO_ERR_UNSUPPORTED, "event filter: more than 2^31 - 1 events in one packet");
   { int rc = filter_staging(h, cam, in.n); if (rc) return rc; }
-  const size_t npx = (size_t)h->W * h->H, cap = F.cap;
-  uint8_t* const d = F.d_twin.get() + sizeof(u32) * FLT_HDR_WORDS;
+  const size_t npx = (size_t)h->W * h->H;
+  const ColumnBlock b = column_block(F.d_twin.get() + sizeof(u32) * FLT_HDR_WORDS, F.cap);  // the twin staging behind its header
   FilterArgs a{};
   a.t = in.d_t; a.x = in.d_x; a.y = in.d_y; a.n = (u32)in.n;
   a.W = h->W; a.H = h->H;
@@ -39,10 +39,7 @@ int filter_run(esvo_context* h, int cam, const FilterPacket& in, u64 newest, Fil
   a.last_in = F.d_last + (size_t)F.cur * npx; a.last_out = F.d_last + (size_t)(F.cur ^ 1) * npx;
   a.tcount = F.d_tcount; a.tlist = F.d_tlist; a.tcap = h->flt_tcap;
   a.code = F.d_code; a.hdr = reinterpret_cast<u32*>(F.d_twin.get());
-  twin->d_t = reinterpret_cast<u64*>(d); twin->d_x = reinterpret_cast<uint16_t*>(d + 8 * cap); twin->d_y = reinterpret_cast<uint16_t*>(d + 10 * cap);
-  twin->d_p = d + 12 * cap; twin->p_type = ESVO_P_U8;
-  launch_event_filter(a, F.d_scan, in.d_p, in.p_type, reinterpret_cast<u64*>(d), reinterpret_cast<uint16_t*>(d + 8 * cap),
-                      reinterpret_cast<uint16_t*>(d + 10 * cap), d + 12 * cap, h->stream_i);
+  launch_event_filter(a, F.d_scan, in.d_p, in.p_type, b.t, b.x, b.y, b.p, h->stream_i);
   HIPCHK(hipGetLastError());
   // the verdict counts and the kept stamps (at most n of them) with one copy
   HIPCHK(hipMemcpyAsync(F.h_twin, F.d_twin, sizeof(u32) * FLT_HDR_WORDS + sizeof(u64) * in.n, hipMemcpyDeviceToHost, h->stream_i));
@@ -54,7 +51,7 @@ int filter_run(esvo_context* h, int cam, const FilterPacket& in, u64 newest, Fil
                                        hdr[ESVO_FILTER_UNSUPPORTED]};
   if (counts->kept + counts->outside + counts->masked + counts->refractory + counts->unsupported != counts->events_in)
     FAIL(ESVO_ERR_STATE, "event filter: the verdict counts do not add up to the packet");
-  twin->n = (size_t)counts->kept;
+  *twin = b.packet((size_t)counts->kept);
   *kept_stamps = F.h_twin.get() + FLT_HDR_WORDS / 2;
   return ESVO_OK;
 }

@@ -1,7 +1,7 @@
 // api_survey.hip — the event survey of the ingest path (include/esvo_hip.h, esvo_ts_survey_begin): its state, the hook push_filtered
-// (api_ts.hip) calls while a survey is open, the mask call and its installation into the camera's filter, and both rules on the host
+// (ingest.hpp) calls while a survey is open, the mask call and its installation into the camera's filter, and both rules on the host
 // (esvo_event_survey_host, esvo_hot_pixel_mask_host).  The kernels are in kernels_survey.hip.
-#include "context.hpp"
+#include "ingest.hpp"
 
 namespace {
 constexpr u64 SRV_MAX_EVENTS = 0xffffffffull;  // events_in + outside of a survey: no counter can wrap below it

@@ -8,13 +8,14 @@
 // -- buffers, flags, stage events -- sits in one slot struct (front[fpar], back[par], pose[pose_buf]).  Each entry point replays, on
 // the handle's HIP streams, the call sequence of the reference seam it replaces (cited in include/esvo_hip.h); nothing
 // computes on the CPU except bookkeeping (time-stamp binary searches, window policy, output ordering).
-//   api_core.hip   lifecycle, parameters, self-tests           api_ts.hip     event ingest, Time-Surface render
+//   api_core.hip   lifecycle, parameters, self-tests           api_ts.hip     Time-Surface render: scatter, queue mode
 //   api_map.hip    mapper: stage launches, the tick pipeline   api_window.hip fusion window, back stage, map export
 //   api_modes.hip  synchronous MVStereo modes 1 and 4, SGM     api_shard.hip  band mode: routed front, phases, configuration
 //   api_out.hip    DepthMap / cloud / image outputs, stats     api_comm.hip   tick-interleaved multi-GPU exchange
 //   api_em.hip     event-to-event matching (modes 0 and 2)     api_gpc.hip    the global point cloud
 //   api_track.hip  tracker residual / Jacobian evaluation      api_bag.hip, api_dev.hip  bag reader, development hooks
 //   api_history.hip  Time-Surface history: frames by stamp, the mapper's and the tracker's pick
+//   api_ingest.hip, api_words.hip   event ingest (ingest.hpp: what the two share): records, EventArray messages, columns; EVT 2 / EVT 3 words
 //   api_filter.hip, api_survey.hip  the ingest path's event filter; per-pixel counts of the pushed stream and the mask learnt from them
 #pragma once
 #include <algorithm>
@@ -69,7 +70,7 @@ struct IngestSession {  // under mu_ring: the event rings
   std::deque<u64> own_before;   // how many OWN events (floor(y_rect) in the band) were kept before this one: the count of a
   u64 own_total = 0;            //   selection's own events bounds its LM launch (the ring also holds the raster's halo events)
   u64 last_stamp[2] = {0, 0};   // newest stamp seen per camera (kept or not): the order check of the push calls
-  // queue mode, out-of-order packets (api_ts.hip, push_unsorted): the copies of the then-newest event that take a late event's place
+  // queue mode, out-of-order packets (api_ingest.hip, push_unsorted): the copies of the then-newest event that take a late event's place
   // in the per-pixel queues, inserted with the next batch
   std::vector<esvo_event_t> tsq_dup[2];
   // EVT 3.0 ingest (esvo_ts_push_evt3): the decoder state a camera's stream is in, and the totals of its successful calls -- under
@@ -450,7 +451,7 @@ struct esvo_context : IngestSession, TsSession, SchedSession, MapSession, CloudS
   PinBuf<esvo_event_t> h_route_ev[2];  // pinned staging of the kept events of one push, per camera
   PinBuf<u32> h_route_gidx;
   size_t route_cap[2] = {0, 0};
-  // out-of-order packets (api_ts.hip, push_unsorted): scratch of the ring merge; queue mode: the device copy of tsq_dup
+  // out-of-order packets (api_ingest.hip, push_unsorted): scratch of the ring merge; queue mode: the device copy of tsq_dup
   DevBuf<esvo_event_t> d_merge_a, d_merge_b;
   DevBuf<u32> d_merge_plan;
   DevBuf<esvo_event_t> d_tsq_dup;
@@ -575,24 +576,8 @@ void ingest_fence(esvo_context* h, int cam);  // caller holds mu_ring
 int ts_scatter_ahead(esvo_context* h, uint64_t t_ns);
 void resident_write_begin(esvo_context* h, int cam);
 int ts_render_pair(esvo_context* h, uint64_t t_ns, uint8_t* const obs_out[2]);
-// api_filter.hip
-struct FilterPacket { const u64* d_t; const uint16_t *d_x, *d_y; const void* d_p; int p_type; size_t n; };
-// runs the camera's filter over a device-resident column packet on the ingest stream and waits: *kept events lie in the twin
-// staging (twin: its columns as a packet), their stamps in *kept_stamps (pinned), the packet's counts in *counts.  Caller holds
-// mu_push[cam]; nothing of the handle's state has changed until filter_commit.
-// newest: the newest staged stamp; *unsorted: the packet is not in order behind it; *first_bad: its first invalid stamp (0xffffffff: none)
-int filter_run(esvo_context* h, int cam, const FilterPacket& in, u64 newest, FilterPacket* twin, const u64** kept_stamps, esvo_event_filter_counts_t* counts,
-               bool* unsorted, u32* first_bad);
-void filter_commit(esvo_context* h, int cam, const esvo_event_filter_counts_t& counts);
+// api_filter.hip, api_survey.hip (their hooks in the push path: ingest.hpp)
 int filter_zero_state(esvo_context* h, hipStream_t st);  // esvo_reset: the `last` images of both cameras
-// api_survey.hip: the hook of push_filtered (api_ts.hip) while a camera's survey is open; caller holds mu_push[cam]
-int survey_admit(esvo_context* h, int cam, size_t n);  // ESVO_ERR_CAPACITY where n more events would take a counter beyond 2^32 - 1
-// counts the packet on the ingest stream, behind the verdicts that accepted it; wait: nothing else of the push waits for the stream
-int survey_count(esvo_context* h, int cam, const FilterPacket& in, bool wait);
-void survey_commit(esvo_context* h, int cam, size_t n);
-// count-only mode: the whole push.  check_stamps: the packet's stamps never reached the host; *first_bad: its first invalid one
-// (0xffffffff: none, and the packet is counted)
-int survey_count_only(esvo_context* h, int cam, const FilterPacket& in, bool check_stamps, u32* first_bad);
 int survey_zero_state(esvo_context* h, hipStream_t st);  // esvo_reset: the counts and stats of both cameras
 // api_history.hip
 int hist_store(esvo_context* h, int cam, uint64_t t_ns, const uint8_t* src, bool from_host);  // caller holds mu_ts

@@ -59,7 +59,7 @@ void launch_ts_scatter_segs(const TsScatterSegs& g, int n_seg, int W, int H, hip
   hipLaunchKernelGGL(ts_scatter_segs_kernel, dim3((u32)blocks, (u32)n_seg), dim3(256), 0, s, g, W, H);
 }
 
-// ---- out-of-order packets (api_ts.hip, push_unsorted): the staged tail of the ring merged with a late packet -----------------
+// ---- out-of-order packets (api_ingest.hip, push_unsorted): the staged tail of the ring merged with a late packet -----------------
 // plan[j]: source of merged position j -- bit 31 clear: staged[idx] (a copy of the ring's tail), set: packet[idx]
 __global__ void __launch_bounds__(256) ts_merge_kernel(const uint4* __restrict__ staged, const uint4* __restrict__ packet,
                                                        const u32* __restrict__ plan, size_t n, uint4* __restrict__ ring, u64 first_slot,
@@ -100,7 +100,7 @@ __global__ void __launch_bounds__(256) tsq_bin_kernel(TsQueueArgs a, int W, int 
       const uint4 e = ev[i];
       const u32 x = e.x & 0xffffu, y = e.x >> 16;
       if (x >= (u32)W || y >= (u32)H) continue;  // EventQueueMat::insideImage
-      if (ev_is_late(e.w)) continue;  // (its place in the queues is taken by a copy of the then-newest event: api_ts.hip, push_unsorted)
+      if (ev_is_late(e.w)) continue;  // (its place in the queues is taken by a copy of the then-newest event: api_ingest.hip, push_unsorted)
       const u64 t_ns = (u64)e.y * 1000000000ull + (u64)e.z;
       const u64 key = (t_ns << 1) | (u64)((e.w & 0xffu) ? 1u : 0u);
       if (key <= 1ull) continue;  // a zero stamp never renders (TimeSurface.cpp:73) and would read as an empty slot

@@ -1,4 +1,4 @@
-"""Every ingest format and every scatter walk where the event ring wraps (esvo_amd/csrc/api_ts.hip): handles that are fed the
+"""Every ingest format and every scatter walk where the event ring wraps (esvo_amd/csrc/api_ingest.hip, api_words.hip; the scatter: api_ts.hip): handles that are fed the
 same events by different routes, or hold them in rings of different size, must end in the same state.  Built like
 tests/test_gpu_event_columns.py (whose packets and state comparison are used here): upenn rig, a ring of 1024 slots, crafted
 packets in a small pixel box so that the median filter keeps them, the state read through esvo_debug_ts_ring."""

@@ -4,6 +4,7 @@ usage: python tools/ab_build.py <name> [--rev <git rev> file ... | --rev <git re
   --rev R f1 f2 : take these source files (relative to esvo_amd/csrc) from git revision R instead of the working tree
   --rev R ALL   : the whole library (esvo_amd/csrc + include) as of revision R
 writes tools/ab/libesvo_hip_<name>.so; run with ESVO_HIP_LIB=tools/ab/libesvo_hip_<name>.so"""
+import ast
 import os
 import shutil
 import subprocess
@@ -36,7 +37,11 @@ def main():
         shutil.copytree(csrc, src, ignore=shutil.ignore_patterns("*.so"))
         shutil.copytree(os.path.join(ROOT, "include"), os.path.join(d, "include"))
         shutil.copytree(os.path.join(ROOT, "tools", "dev_hooks"), os.path.join(d, "tools", "dev_hooks"))   # (dev_hooks.hpp includes ../../tools/dev_hooks/ under -D flags)
+        sources = lib._SOURCES
         if files == ["ALL"]:
+            # the revision's own source list: files come and go between revisions
+            lib_py = subprocess.check_output(["git", "-C", ROOT, "show", f"{rev}:esvo_amd/lib.py"]).decode()
+            sources = ast.literal_eval(next(ln for ln in lib_py.splitlines() if ln.startswith("_SOURCES = ")).split("=", 1)[1].strip())
             for sub in ("esvo_amd/csrc", "include"):
                 shutil.rmtree(os.path.join(d, sub))
                 os.makedirs(os.path.join(d, sub))
@@ -52,7 +57,7 @@ def main():
         os.makedirs(out_dir, exist_ok=True)
         out = os.path.join(out_dir, f"libesvo_hip_{name}.so")
         cmd = ["/opt/rocm/bin/hipcc"] + lib.HIPCC_FLAGS + flags + ["-I", os.path.join(d, "include"), "-o", out] + \
-              [os.path.join(src, s) for s in lib._SOURCES if os.path.exists(os.path.join(src, s))]
+              [os.path.join(src, s) for s in sources if os.path.exists(os.path.join(src, s))]
         subprocess.check_call(cmd)
         print(out)
 
