@@ -371,6 +371,31 @@ def event_filter_struct(refractory_ns, support_ns, mask, width, height):
     return s, keep
 
 
+# esvo_ts_burst_* / esvo_event_burst_filter_host: the burst stage of the event filter (include/esvo_hip.h)
+BURST_OFF, BURST_TRAIL, BURST_STC_CUT_TRAIL, BURST_STC_KEEP_TRAIL = 0, 1, 2, 3
+FILTER_BURST = 5
+
+
+class EventBurstStruct(C.Structure):
+    """esvo_event_burst_t"""
+    _fields_ = [("burst_ns", C.c_uint64), ("mode", C.c_uint32), ("reserved", C.c_uint32 * 3)]
+
+
+class EventBurstCounts(C.Structure):
+    """esvo_event_burst_counts_t"""
+    _fields_ = [(k, C.c_uint64) for k in ("judged", "passed", "dropped")]
+
+    def as_dict(self):
+        return {k: int(getattr(self, k)) for k, _ in self._fields_}
+
+
+def event_burst_struct(mode, burst_ns, reserved=(0, 0, 0)):
+    s = EventBurstStruct()
+    s.mode, s.burst_ns = int(mode), int(burst_ns)
+    s.reserved[:] = [int(v) for v in reserved]
+    return s
+
+
 # esvo_ts_survey_* / esvo_event_survey_host / esvo_hot_pixel_mask_host: the event survey and its hot-pixel rule (include/esvo_hip.h)
 SURVEY_COUNT_ONLY = 1
 MASK_KEEP, MASK_REPLACE, MASK_UNION = 0, 1, 2

@@ -262,6 +262,15 @@ constexpr u32 FLT_HDR_WORDS = 16u;       // 64 bytes: the twin's stamps stay 8-b
 constexpr u32 FLT_H_VERDICT0 = 0u;       // hdr[FLT_H_VERDICT0 + v]: events of verdict v (ESVO_FILTER_*), v = 0..4
 constexpr u32 FLT_H_UNSORTED = 5u;       // non-zero: a stamp below its predecessor's (the first one's: FilterArgs::newest)
 constexpr u32 FLT_H_FIRST_BAD = 6u;      // index of the first COL_BAD_STAMP, 0xffffffff: none
+constexpr u32 FLT_H_BURST = 7u;          // events of verdict ESVO_FILTER_BURST (the burst stage, esvo_ts_burst_configure; 0 while it is off)
+// The burst stage of the filter (esvo_ts_burst_configure): mode ESVO_BURST_OFF = the stage is not there, nothing below is read.
+// The state is a pair of images as `last` is: a packet reads *_in and writes every pixel of *_out.
+struct BurstArgs {
+  u32 mode; u64 burst_ns;
+  const void* p; int p_type;                           // the packet's polarity column (columns_polarity)
+  const u64* stamp_in; u64* stamp_out;                 // [H * W]
+  const uint8_t* flags_in; uint8_t* flags_out;         // [H * W]
+};
 struct FilterArgs {
   const u64* t; const uint16_t* x; const uint16_t* y; u32 n;
   int W, H;
@@ -275,8 +284,8 @@ struct FilterArgs {
   u32* hdr;
 };
 size_t filter_tiles(int W, int H);
-void launch_event_filter(const FilterArgs& a, u32* scan_tmp, const void* p, int p_type, u64* out_t, uint16_t* out_x, uint16_t* out_y,
-                         uint8_t* out_p, hipStream_t s);
+void launch_event_filter(const FilterArgs& a, const BurstArgs& b, u32* scan_tmp, const void* p, int p_type, u64* out_t, uint16_t* out_x,
+                         uint16_t* out_y, uint8_t* out_p, hipStream_t s);
 // The event survey (esvo_ts_survey_begin, include/esvo_hip.h; kernels_survey.hip): per-pixel counts of a column packet, and the hot-pixel
 // mask derived from them.  counts: [2][H * W], plane = polarity; stats: SRV_STAT_WORDS u64 (SRV_S_*).
 constexpr u32 SRV_CHUNK = 1024u;  // events a workgroup combines in LDS before global memory hears of them

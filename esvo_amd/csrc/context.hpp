@@ -83,6 +83,8 @@ struct IngestSession {  // under mu_ring: the event rings
   // the event filter (esvo_ts_filter_configure): the totals of a camera's successful pushes, under its mu_push.  (The `last` image
   // is device memory: esvo_reset zeroes it beside the other session buffers, EventFilter below.)
   esvo_event_filter_counts_t flt_totals[2] = {};
+  // the filter's burst stage (esvo_ts_burst_configure): the same of its totals (the state images: EventBurst below)
+  esvo_event_burst_counts_t bst_totals[2] = {};
   // the event survey (esvo_ts_survey_begin), under the camera's mu_push: what the host knows of an open survey without a read-back --
   // events of its accepted packets (events_in + outside of its stats: the bound that keeps every counter below 2^32) and the packets.
   // (The counts are device memory: esvo_reset zeroes them beside the other session buffers, EventSurvey below.)
@@ -339,6 +341,16 @@ struct esvo_context : IngestSession, TsSession, SchedSession, MapSession, CloudS
     PinBuf<u64> h_twin;
     size_t cap = 0;
   } flt[2];
+  // The burst stage of a camera's filter (esvo_ts_burst_configure; api_filter.hip, flt_burst_kernel), under its mu_push; the
+  // configuration survives a reset, which zeroes the state.  d_stamp / d_flags: [2][W * H], pairs as d_last is, with an index of
+  // their own (a filter reconfiguration restarts the filter's pair and leaves this one alone).
+  struct EventBurst {
+    u32 mode = 0;  // ESVO_BURST_OFF: no stage, no memory
+    u64 burst_ns = 0;
+    int cur = 0;
+    DevBuf<u64> d_stamp;
+    DevBuf<uint8_t> d_flags;
+  } bst[2];
   // The event survey of a camera (esvo_ts_survey_begin; api_survey.hip, kernels_survey.hip), under its mu_push; open or not survives a
   // reset, which zeroes the counts.  d_counts: [2][W * H], plane = polarity; d_stats: SRV_STAT_WORDS; d_sel / d_report / d_mask: the
   // radix select's words, the report and the mask bytes of esvo_ts_survey_mask.

@@ -172,9 +172,10 @@ int require_memory_place(esvo_context* h, const void* base, size_t bytes, bool o
 // staging (twin: its columns as a packet), their stamps in *kept_stamps (pinned), the packet's counts in *counts.  Caller holds
 // mu_push[cam]; nothing of the handle's state has changed until filter_commit.
 // newest: the newest staged stamp; *unsorted: the packet is not in order behind it; *first_bad: its first invalid stamp (0xffffffff: none)
+// *burst_dropped: the events the burst stage dropped (esvo_ts_burst_configure; 0 while it is off): counts->events_in + *burst_dropped = in.n
 int filter_run(esvo_context* h, int cam, const FilterPacket& in, u64 newest, FilterPacket* twin, const u64** kept_stamps, esvo_event_filter_counts_t* counts,
-               bool* unsorted, u32* first_bad);
-void filter_commit(esvo_context* h, int cam, const esvo_event_filter_counts_t& counts);
+               u64* burst_dropped, bool* unsorted, u32* first_bad);
+void filter_commit(esvo_context* h, int cam, const esvo_event_filter_counts_t& counts, u64 burst_dropped);
 // api_survey.hip: the hook of push_filtered while a camera's survey is open; caller holds mu_push[cam]
 int survey_admit(esvo_context* h, int cam, size_t n);  // ESVO_ERR_CAPACITY where n more events would take a counter beyond 2^32 - 1
 // counts the packet on the ingest stream, behind the verdicts that accepted it; wait: nothing else of the push waits for the stream
@@ -226,14 +227,15 @@ int push_filtered(esvo_context* h, int cam, Src& src) {
   esvo_event_filter_counts_t counts{};
   bool unsorted = false;
   u32 first_bad = 0xffffffffu;
-  { int rc = filter_run(h, cam, in, newest, &twin, &kept_stamps, &counts, &unsorted, &first_bad); if (rc) return rc; }
+  u64 burst_dropped = 0;
+  { int rc = filter_run(h, cam, in, newest, &twin, &kept_stamps, &counts, &burst_dropped, &unsorted, &first_bad); if (rc) return rc; }
   if (first_bad != 0xffffffffu) FAIL(ESVO_ERR_INVALID_ARG, src.bad_stamp_message(first_bad));
   if (unsorted) FAIL(ESVO_ERR_UNSUPPORTED, out_of_order);
   // the survey counts the raw packet behind the last refusal, on the stream the staging below waits for (it stages nothing: nobody waits)
   if (survey) { int rc = survey_count(h, cam, in, twin.n == 0); if (rc) return rc; }
   KeptPacket kept{h, cam, twin, kept_stamps, twin.n};
   { int rc = push_staged(h, cam, kept, [](size_t) {}); if (rc) return rc; }
-  filter_commit(h, cam, counts);
+  filter_commit(h, cam, counts, burst_dropped);
   if (survey) survey_commit(h, cam, src.n);
   return ESVO_OK;
 }

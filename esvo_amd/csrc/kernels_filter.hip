@@ -21,6 +21,20 @@
 //                and kept stamps come down with one copy -- and with them whether the packet was in order and its stamps valid,
 //                for packets whose unfiltered stamps never reach the host (device columns, decoded words).
 // Per event the code byte is verdict << 1 | kept.
+//
+// The burst stage (esvo_ts_burst_configure: trail / STC with polarity, between the mask and the refractory test) is a fourth kernel,
+// launched between flt_bin and flt_walk only while the stage is on:
+//   flt_burst    one wave / tile over the tile's OWN-pixel entries (the stage's rule needs no halo): an event's burst verdict depends
+//                on the previous two raw events of its own pixel and on nothing else, so the entries, sorted by (pixel in tile,
+//                packet index) in LDS (bitonic, 64-bit keys), are judged all at once -- entry i reads entry i - 1 for `linked` and
+//                entry i - 2 for the `linked` bit of its predecessor, the first one or two entries of a pixel read the state the
+//                packet found, the last entry of a pixel writes the state it leaves.  Every own entry gets a code here: MASKED,
+//                ESVO_FILTER_BURST for the dropped ones, FLT_CODE_PENDING for those the walk still has to judge.  A tile whose
+//                count exceeds the capacity reads the packet, 64 events per step, collects its own events in the same LDS array and
+//                judges a batch whenever the array is nearly full, the state carried in LDS from batch to batch: the same rule on
+//                the same events in the same order.  The state is a pair of images as `last` is.
+// flt_walk<true> then leaves out every entry whose code says ESVO_FILTER_BURST, own pixels and halo alike (a burst-dropped event
+// never reaches `last`); flt_walk<false>, the stage off, is the kernel as it was.
 #include "common.hpp"
 
 namespace esvo {
@@ -29,6 +43,10 @@ namespace {
 constexpr int FLT_TILE = 8, FLT_PATCH = FLT_TILE + 2, FLT_CELLS = FLT_PATCH * FLT_PATCH;
 
 __device__ inline uint8_t flt_code(u32 verdict) { return (uint8_t)((verdict << 1) | (verdict == ESVO_FILTER_KEPT ? 1u : 0u)); }
+
+constexpr u32 FLT_CODE_BURST = (u32)ESVO_FILTER_BURST << 1;  // flt_code(ESVO_FILTER_BURST)
+constexpr u32 FLT_CODE_PENDING = 0xfeu;  // passed the burst stage, the walk's to judge (verdict 7: nothing counts it, so the counts would not add up)
+constexpr u64 BST_NONE = ~0ull;          // padding of the burst kernel's key array: behind every entry
 
 // lane j's 64-bit value, j uniform
 __device__ inline u64 lane_u64(u64 v, int j) {
@@ -55,6 +73,104 @@ __global__ void __launch_bounds__(256) flt_bin_kernel(FilterArgs a) {
   }
 }
 
+// `linked` of the burst stage: the event (t, p) continues the burst of the event (T, P) judged before it at the same pixel
+__device__ inline bool bst_linked(u64 T, u32 P, u64 t, u32 p, u64 burst_ns) { return T != 0ull && p == P && (T > t || t - T <= burst_ns); }
+
+__global__ void __launch_bounds__(64) flt_burst_kernel(FilterArgs a, BurstArgs b) {
+  __shared__ u64 s_key[FLT_TILE_CAP_MAX];  // pixel of the tile << 32 | packet index
+  __shared__ u64 s_t[FLT_TILE_CAP_MAX];    // the sorted entries' stamps and polarities
+  __shared__ uint8_t s_p[FLT_TILE_CAP_MAX];
+  __shared__ u64 s_st[2][FLT_TILE * FLT_TILE];  // the tile's state, [0] in front of the batch being judged, [1] behind it
+  __shared__ uint8_t s_fl[2][FLT_TILE * FLT_TILE];
+  const int lane = threadIdx.x;
+  const u32 tile = blockIdx.x;
+  const int tiles_x = (a.W + FLT_TILE - 1) / FLT_TILE;
+  const int tx0 = (int)(tile % (u32)tiles_x) * FLT_TILE, ty0 = (int)(tile / (u32)tiles_x) * FLT_TILE;
+  const u32 cnt = a.tcount[tile];  // (own and halo entries: the walk, which runs behind this kernel, clears it)
+  const int ox = tx0 + lane % FLT_TILE, oy = ty0 + lane / FLT_TILE;
+  const bool o_in = ox < a.W && oy < a.H;
+  const size_t o_px = (size_t)oy * a.W + ox;
+  s_st[0][lane] = o_in ? b.stamp_in[o_px] : 0ull;
+  s_fl[0][lane] = o_in ? b.flags_in[o_px] : (uint8_t)0;
+  __syncthreads();
+  // One batch: the m entries of s_key (m uniform, 1 .. FLT_TILE_CAP_MAX), any order.
+  const auto judge = [&](u32 m) {
+    u32 N = 64;  // padded to a power of two
+    while (N < m) N <<= 1;
+    for (u32 k = m + lane; k < N; k += 64) s_key[k] = BST_NONE;
+    __syncthreads();
+    for (u32 k = 2; k <= N; k <<= 1)
+      for (u32 j = k >> 1; j > 0; j >>= 1) {
+        for (u32 q = lane; q < N / 2; q += 64) {
+          const u32 lo = 2u * q - (q & (j - 1u)), hi = lo + j;
+          const u64 va = s_key[lo], vb = s_key[hi];
+          if ((va > vb) == ((lo & k) == 0u)) { s_key[lo] = vb; s_key[hi] = va; }
+        }
+        __syncthreads();
+      }
+    for (u32 k = lane; k < m; k += 64) {
+      const u32 idx = (u32)s_key[k];
+      s_t[k] = a.t[idx];
+      s_p[k] = (uint8_t)columns_polarity(b.p, idx, b.p_type);
+    }
+    s_st[1][lane] = s_st[0][lane]; s_fl[1][lane] = s_fl[0][lane];
+    __syncthreads();
+    for (u32 k = lane; k < m; k += 64) {
+      const u64 key = s_key[k];
+      const u32 pix = (u32)(key >> 32), idx = (u32)key;
+      const u64 t = s_t[k];
+      const u32 p = s_p[k];
+      const u32 k1 = k >= 1u ? k - 1u : 0u, k2 = k >= 2u ? k - 2u : 0u;
+      const bool has1 = k >= 1u && (u32)(s_key[k1] >> 32) == pix, has2 = k >= 2u && (u32)(s_key[k2] >> 32) == pix;  // (sorted: has2 implies has1)
+      const u64 T0 = s_st[0][pix];
+      const u32 F0 = s_fl[0][pix];
+      const u64 T1 = has1 ? s_t[k1] : T0;
+      const u32 P1 = has1 ? (u32)s_p[k1] : (F0 & 1u);
+      const bool linked = bst_linked(T1, P1, t, p, b.burst_ns);
+      const u64 T2 = has2 ? s_t[k2] : T0;
+      const u32 P2 = has2 ? (u32)s_p[k2] : (F0 & 1u);
+      const bool K = has1 ? bst_linked(T2, P2, T1, P1, b.burst_ns) : ((F0 >> 1) & 1u) != 0u;  // `linked` of the event before
+      const bool pass = b.mode == ESVO_BURST_TRAIL ? !linked : (b.mode == ESVO_BURST_STC_CUT_TRAIL ? linked && !K : linked);
+      a.code[idx] = (uint8_t)(pass ? FLT_CODE_PENDING : FLT_CODE_BURST);
+      const bool newest = k + 1u >= m || (u32)(s_key[k + 1u] >> 32) != pix;  // (k + 1 < m: an entry)
+      if (newest) { s_st[1][pix] = t; s_fl[1][pix] = (uint8_t)(p | (linked ? 2u : 0u)); }
+    }
+    __syncthreads();
+    s_st[0][lane] = s_st[1][lane]; s_fl[0][lane] = s_fl[1][lane];
+    __syncthreads();
+  };
+  // the lane's event (have: there is one) into the batch if it lies at an unmasked pixel of the tile; -> the batch's new length (uniform)
+  const auto collect = [&](u32 m, bool have, u32 idx) -> u32 {
+    const int ex = have ? (int)a.x[idx] : -1, ey = have ? (int)a.y[idx] : -1;
+    const bool own = have && ex < a.W && ey < a.H && ex >= tx0 && ex < tx0 + FLT_TILE && ey >= ty0 && ey < ty0 + FLT_TILE;
+    const bool masked = own && a.mask && a.mask[(size_t)ey * a.W + ex];
+    if (masked) a.code[idx] = flt_code(ESVO_FILTER_MASKED);  // (the walk says so again: every own entry has a code of this packet before it runs)
+    const bool valid = own && !masked;
+    const u64 ball = __ballot(valid);
+    if (valid) s_key[m + (u32)__popcll(ball & ((1ull << lane) - 1ull))] = ((u64)(u32)((ey - ty0) * FLT_TILE + (ex - tx0)) << 32) | (u64)idx;
+    return m + (u32)__popcll(ball);
+  };
+  if (cnt != 0u) {
+    u32 m = 0;
+    if (cnt <= a.tcap) {
+      for (u32 base = 0; base < cnt; base += 64) {
+        const bool have = base + lane < cnt;
+        m = collect(m, have, have ? a.tlist[(size_t)tile * a.tcap + base + lane] : 0u);
+      }
+    } else {
+      for (u32 base = 0; base < a.n; base += 64) {
+        m = collect(m, base + lane < a.n, base + lane);
+        if (m + 64u > FLT_TILE_CAP_MAX) { __syncthreads(); judge(m); m = 0; }
+      }
+    }
+    __syncthreads();
+    if (m) judge(m);
+  }
+  if (o_in) { b.stamp_out[o_px] = s_st[0][lane]; b.flags_out[o_px] = s_fl[0][lane]; }
+}
+
+// BURST: the burst stage ran in front (flt_burst_kernel): entries it dropped are left out
+template <bool BURST>
 __global__ void __launch_bounds__(64) flt_walk_kernel(FilterArgs a) {
   __shared__ u64 s_last[FLT_CELLS];
   __shared__ uint8_t s_mask[FLT_CELLS];
@@ -130,14 +246,17 @@ __global__ void __launch_bounds__(64) flt_walk_kernel(FilterArgs a) {
       const u32 m = min(64u, cnt - base);
       const bool have = (u32)lane < m;
       const u32 idx = have ? s_list[base + lane] : 0u;
-      walk(m == 64u ? ~0ull : (1ull << m) - 1ull, idx, have ? (int)a.x[idx] : 0, have ? (int)a.y[idx] : 0, have ? a.t[idx] : 0ull);
+      u64 todo = m == 64u ? ~0ull : (1ull << m) - 1ull;
+      if constexpr (BURST) todo = __ballot(have && a.code[idx] != FLT_CODE_BURST);
+      walk(todo, idx, have ? (int)a.x[idx] : 0, have ? (int)a.y[idx] : 0, have ? a.t[idx] : 0ull);
     }
   } else {
     for (u32 base = 0; base < a.n; base += 64) {
       const u32 idx = base + lane;
       const bool have = idx < a.n;
       const int ex = have ? (int)a.x[idx] : 0, ey = have ? (int)a.y[idx] : 0;
-      const bool mine = have && ex < a.W && ey < a.H && ex >= x0 && ex < x0 + FLT_PATCH && ey >= y0 && ey < y0 + FLT_PATCH;
+      bool mine = have && ex < a.W && ey < a.H && ex >= x0 && ex < x0 + FLT_PATCH && ey >= y0 && ey < y0 + FLT_PATCH;
+      if constexpr (BURST) mine = mine && a.code[idx] != FLT_CODE_BURST;
       const u64 todo = __ballot(mine);
       if (!todo) continue;
       walk(todo, idx, ex, ey, mine ? a.t[idx] : 0ull);
@@ -151,8 +270,8 @@ __global__ void __launch_bounds__(64) flt_walk_kernel(FilterArgs a) {
 __global__ void __launch_bounds__(256) flt_compact_kernel(FilterArgs a, const u32* __restrict__ prefix, const void* __restrict__ p, int p_type,
                                                           u64* __restrict__ out_t, uint16_t* __restrict__ out_x, uint16_t* __restrict__ out_y,
                                                           uint8_t* __restrict__ out_p) {
-  __shared__ u32 s_cnt[8];
-  if (threadIdx.x < 8) s_cnt[threadIdx.x] = 0u;
+  __shared__ u32 s_cnt[9];  // per verdict 0..7; [8]: the packet is not in order
+  if (threadIdx.x < 9) s_cnt[threadIdx.x] = 0u;
   __syncthreads();
   const u32 i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i < a.n) {
@@ -160,7 +279,7 @@ __global__ void __launch_bounds__(256) flt_compact_kernel(FilterArgs a, const u3
     atomicAdd(&s_cnt[(c >> 1) & 7u], 1u);
     // the packet's order and the validity of its stamps, for packets whose stamps never reach the host: decided here, read with the counts
     const u64 t = a.t[i], before = i ? a.t[i - 1] : a.newest;
-    if (t < before) s_cnt[5] = 1u;
+    if (t < before) s_cnt[8] = 1u;
     if (t == COL_BAD_STAMP) atomicMin(&a.hdr[FLT_H_FIRST_BAD], i);
     if (c & 1u) {
       const u32 pos = prefix[i];
@@ -170,20 +289,28 @@ __global__ void __launch_bounds__(256) flt_compact_kernel(FilterArgs a, const u3
   }
   __syncthreads();
   if (threadIdx.x < 5 && s_cnt[threadIdx.x]) atomicAdd(&a.hdr[FLT_H_VERDICT0 + threadIdx.x], s_cnt[threadIdx.x]);
-  if (threadIdx.x == 5 && s_cnt[5]) atomicOr(&a.hdr[FLT_H_UNSORTED], 1u);
+  if (threadIdx.x == ESVO_FILTER_BURST && s_cnt[ESVO_FILTER_BURST]) atomicAdd(&a.hdr[FLT_H_BURST], s_cnt[ESVO_FILTER_BURST]);
+  if (threadIdx.x == 8 && s_cnt[8]) atomicOr(&a.hdr[FLT_H_UNSORTED], 1u);
 }
 }  // namespace
 
 size_t filter_tiles(int W, int H) { return (size_t)((W + FLT_TILE - 1) / FLT_TILE) * ((H + FLT_TILE - 1) / FLT_TILE); }
 
-// bin -> walk -> scan -> compact on `s`.  scan_tmp: a.n + scan_scratch_elems(a.n) words (the prefix, the scan's sums);
-// a.hdr[FLT_H_VERDICT0 + v] receives the count of verdict v (v = 0: the kept events, the twin's length).
-void launch_event_filter(const FilterArgs& a, u32* scan_tmp, const void* p, int p_type, u64* out_t, uint16_t* out_x, uint16_t* out_y,
-                         uint8_t* out_p, hipStream_t s) {
+// bin -> (burst ->) walk -> scan -> compact on `s`.  scan_tmp: a.n + scan_scratch_elems(a.n) words (the prefix, the scan's sums);
+// a.hdr[FLT_H_VERDICT0 + v] receives the count of verdict v (v = 0: the kept events, the twin's length), a.hdr[FLT_H_BURST] that of
+// ESVO_FILTER_BURST.
+void launch_event_filter(const FilterArgs& a, const BurstArgs& b, u32* scan_tmp, const void* p, int p_type, u64* out_t, uint16_t* out_x,
+                         uint16_t* out_y, uint8_t* out_p, hipStream_t s) {
   if (a.n == 0) return;
   const u32 blocks = (a.n + 255u) / 256u;
   hipLaunchKernelGGL(flt_bin_kernel, dim3(min(blocks, 2048u)), dim3(256), 0, s, a);
-  hipLaunchKernelGGL(flt_walk_kernel, dim3((u32)filter_tiles(a.W, a.H)), dim3(64), 0, s, a);
+  const dim3 tiles((u32)filter_tiles(a.W, a.H));
+  if (b.mode != ESVO_BURST_OFF) {
+    hipLaunchKernelGGL(flt_burst_kernel, tiles, dim3(64), 0, s, a, b);
+    hipLaunchKernelGGL(flt_walk_kernel<true>, tiles, dim3(64), 0, s, a);
+  } else {
+    hipLaunchKernelGGL(flt_walk_kernel<false>, tiles, dim3(64), 0, s, a);
+  }
   launch_exclusive_scan_code_bit0(a.code, scan_tmp, nullptr, scan_tmp + a.n, a.n, nullptr, s);
   hipLaunchKernelGGL(flt_compact_kernel, dim3(blocks), dim3(256), 0, s, a, scan_tmp, p, p_type, out_t, out_x, out_y, out_p);
 }

@@ -10,7 +10,7 @@ import subprocess
 
 import numpy as np
 
-from .abi import (MEM_DEVICE, MEM_HOST, P_U8, ColumnsError, EventColumnsStruct, EventFilterCounts, EventFilterStruct, event_filter_struct, EventSurveyStats, EventSurveyStruct, HotPixelReport, event_survey_stats, hot_pixel_rule, Evt2Counts, Evt2State, Evt3Counts, Evt3State, evt2_words, evt3_words, check_t_offset, column_p_type, column_t_type,
+from .abi import (MEM_DEVICE, MEM_HOST, P_U8, ColumnsError, EventColumnsStruct, EventFilterCounts, EventFilterStruct, event_filter_struct, EventBurstCounts, event_burst_struct, EventSurveyStats, EventSurveyStruct, HotPixelReport, event_survey_stats, hot_pixel_rule, Evt2Counts, Evt2State, Evt3Counts, Evt3State, evt2_words, evt3_words, check_t_offset, column_p_type, column_t_type,
                   DEPTH_POINT_DTYPE, EM_POSE_FN, ERR_CAPACITY, ERR_INVALID_ARG, ERR_STATE, EVENT_DTYPE, MATCH_DTYPE, CalibStruct, EmSelectionStruct,
                   EmStatsStruct, GpcParamsStruct, GpcStatsStruct, LmStatsStruct, ParamsStruct, SgmStatsStruct, StatsStruct, TRACK_ITER_DTYPE, TRACK_SOLVE_MAX_ITERATIONS,
                   TrackSolveInfoStruct, TrackSolveParamsStruct)
@@ -46,6 +46,7 @@ SYMBOLS = [
     "esvo_ts_history_configure", "esvo_ts_history_list", "esvo_ts_history_get", "esvo_ts_history_put", "esvo_map_set_observation_at",
     "esvo_track_set_current_at", "esvo_ts_history_select", "esvo_ts_history_select_observation",
     "esvo_ts_filter_configure", "esvo_ts_filter_stats", "esvo_ts_filter_state", "esvo_event_filter_host", "esvo_event_filter_sizes",
+    "esvo_ts_burst_configure", "esvo_ts_burst_stats", "esvo_ts_burst_state", "esvo_event_burst_filter_host", "esvo_event_burst_sizes",
     "esvo_ts_survey_begin", "esvo_ts_survey_end", "esvo_ts_survey_stats", "esvo_ts_survey_state", "esvo_ts_survey_mask",
     "esvo_event_survey_host", "esvo_hot_pixel_mask_host", "esvo_event_survey_sizes",
 ]
@@ -284,6 +285,12 @@ def load():
     lib.esvo_event_filter_host.argtypes = [vp, i32, i32, vp, vp, sz, vp, vp, sz, psz, vp]
     lib.esvo_event_filter_sizes.argtypes = [vp]
     lib.esvo_event_filter_sizes.restype = None
+    lib.esvo_ts_burst_configure.argtypes = [vp, i32, vp]
+    lib.esvo_ts_burst_stats.argtypes = [vp, i32, vp]
+    lib.esvo_ts_burst_state.argtypes = [vp, i32, vp, vp, vp, vp]
+    lib.esvo_event_burst_filter_host.argtypes = [vp, vp, i32, i32, vp, vp, vp, vp, sz, vp, vp, sz, psz, vp, vp]
+    lib.esvo_event_burst_sizes.argtypes = [vp]
+    lib.esvo_event_burst_sizes.restype = None
     lib.esvo_ts_survey_begin.argtypes = [vp, i32, vp]
     lib.esvo_ts_survey_end.argtypes = [vp, i32]
     lib.esvo_ts_survey_stats.argtypes = [vp, i32, vp]
@@ -295,7 +302,7 @@ def load():
     lib.esvo_event_survey_sizes.restype = None
     for s in SYMBOLS + SYMBOLS_EVT3:
         if s not in ("esvo_default_params", "esvo_last_error", "esvo_abi_sizes", "esvo_bag_last_error", "esvo_em_sizes", "esvo_lm_sizes", "esvo_sgm_sizes",
-                     "esvo_track_sizes", "esvo_gpc_sizes", "esvo_event_columns_sizes", "esvo_evt3_sizes", "esvo_evt2_sizes", "esvo_event_filter_sizes", "esvo_event_survey_sizes"):
+                     "esvo_track_sizes", "esvo_gpc_sizes", "esvo_event_columns_sizes", "esvo_evt3_sizes", "esvo_evt2_sizes", "esvo_event_filter_sizes", "esvo_event_burst_sizes", "esvo_event_survey_sizes"):
             getattr(lib, s).restype = C.c_int
     lib.esvo_abi_sizes.argtypes = [vp]
     lib.esvo_abi_sizes.restype = None
@@ -803,6 +810,37 @@ def event_filter_host(events, width, height, refractory_ns=0, support_ns=0, mask
     return verdict, out[:n_out.value].copy(), L, cnt.as_dict()
 
 
+def event_burst_sizes():
+    """sizeof(esvo_event_burst_t), sizeof(esvo_event_burst_counts_t), 0, 0 (esvo_event_burst_sizes)"""
+    out = (C.c_size_t * 4)()
+    load().esvo_event_burst_sizes(out)
+    return list(out)
+
+
+def event_burst_filter_host(events, width, height, mode=0, burst_ns=0, refractory_ns=0, support_ns=0, mask=None, bstamp=None, bflags=None, last=None,
+                            cap=None, reserved=(0, 0, 0)):
+    """esvo_event_burst_filter_host: the filter's rule with its burst stage on the host -> (verdicts uint8 [n], kept records, bstamp
+    (height, width) uint64, bflags (height, width) uint8, last (height, width) uint64, burst counts dict, filter counts dict).
+    bstamp / bflags / last: the state to resume from (None: all zero), not modified -- the returned images are the advanced copies."""
+    ev = np.ascontiguousarray(events, EVENT_DTYPE)
+    n, shape = len(ev), (int(height), int(width))
+    b = event_burst_struct(mode, burst_ns, reserved)
+    f, _keep = event_filter_struct(refractory_ns, support_ns, mask, width, height)
+    S = np.zeros(shape, np.uint64) if bstamp is None else np.array(bstamp, np.uint64).reshape(shape).copy()
+    G = np.zeros(shape, np.uint8) if bflags is None else np.array(bflags, np.uint8).reshape(shape).copy()
+    L = np.zeros(shape, np.uint64) if last is None else np.array(last, np.uint64).reshape(shape).copy()
+    verdict = np.zeros(n, np.uint8)
+    room = n if cap is None else int(cap)
+    out = np.zeros(max(room, 1), EVENT_DTYPE)
+    n_out, bc, fc = C.c_size_t(0), EventBurstCounts(), EventFilterCounts()
+    rc = load().esvo_event_burst_filter_host(C.addressof(b), C.addressof(f), shape[1], shape[0], S.ctypes.data, G.ctypes.data, L.ctypes.data,
+                                             ev.ctypes.data if n else None, n, verdict.ctypes.data if n else None, out.ctypes.data, room,
+                                             C.byref(n_out), C.addressof(bc), C.addressof(fc))
+    if rc != 0:
+        raise EsvoError(f"esvo_event_burst_filter_host failed ({rc}): {load().esvo_last_error(None).decode(errors='replace')}", code=rc)
+    return verdict, out[:n_out.value].copy(), S, G, L, bc.as_dict(), fc.as_dict()
+
+
 def event_survey_sizes():
     """sizeof() of esvo_event_survey_t, esvo_event_survey_stats_t, esvo_hot_pixel_rule_t, esvo_hot_pixel_report_t (esvo_event_survey_sizes)"""
     out = (C.c_size_t * 4)()
@@ -1043,6 +1081,30 @@ class Esvo:
         new = None if set is None else np.ascontiguousarray(np.asarray(set, np.uint64).reshape(H, W))
         self._ck(self.lib.esvo_ts_filter_state(self.h, int(cam), got.ctypes.data, None if new is None else new.ctypes.data))
         return got
+
+    def ts_burst_configure(self, cam, mode=0, burst_ns=0, reserved=(0, 0, 0)):
+        """the burst stage of the camera's filter (esvo_ts_burst_configure): abi.BURST_TRAIL keeps the first event of every same-polarity
+        burst of a pixel, BURST_STC_CUT_TRAIL the second, BURST_STC_KEEP_TRAIL all but the first; burst_ns: the largest gap inside a
+        burst.  Zeroes the stage's state, keeps its totals; abi.BURST_OFF switches it off and frees its memory.  The camera's filter
+        must be configured (ts_filter_configure(cam) with no arguments passes everything)."""
+        b = event_burst_struct(mode, burst_ns, reserved)
+        self._ck(self.lib.esvo_ts_burst_configure(self.h, int(cam), C.addressof(b)))
+
+    def ts_burst_stats(self, cam):
+        """totals of the camera's burst stage since create / reset as a dict: judged = passed + dropped"""
+        tot = EventBurstCounts()
+        self._ck(self.lib.esvo_ts_burst_stats(self.h, int(cam), C.addressof(tot)))
+        return tot.as_dict()
+
+    def ts_burst_state(self, cam, set=None):
+        """the stage's state (esvo_ts_burst_state) -> (bstamp (H, W) uint64, bflags (H, W) uint8); set: a (bstamp, bflags) pair that
+        replaces it afterwards"""
+        H, W = self.rig.height, self.rig.width
+        st, fl = np.zeros((H, W), np.uint64), np.zeros((H, W), np.uint8)
+        new = None if set is None else (np.ascontiguousarray(np.asarray(set[0], np.uint64).reshape(H, W)), np.ascontiguousarray(np.asarray(set[1], np.uint8).reshape(H, W)))
+        self._ck(self.lib.esvo_ts_burst_state(self.h, int(cam), st.ctypes.data, fl.ctypes.data, None if new is None else new[0].ctypes.data,
+                                              None if new is None else new[1].ctypes.data))
+        return st, fl
 
     def ts_survey_begin(self, cam, count_only=False, flags=None, reserved=(0, 0, 0)):
         """opens the camera's event survey (esvo_ts_survey_begin): per-pixel counts of every packet its push calls accept, kept on the

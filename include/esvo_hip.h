@@ -528,6 +528,73 @@ int esvo_event_filter_host(const esvo_event_filter_t* f, int width, int height, 
                            uint8_t* verdict, esvo_event_t* out, size_t cap, size_t* n_out, esvo_event_filter_counts_t* add);
 /* sizeof(esvo_event_filter_t), sizeof(esvo_event_filter_counts_t), 0, 0 */
 void esvo_event_filter_sizes(size_t out[4]);
+/* Burst stage of the event filter: trail and STC (spatio-temporal-contrast) filtering with polarity, on the device.  A Gen4 / IMX636
+ * pixel answers one contrast edge with a burst of same-polarity events; the trailing ones keep the pixel bright in the Time Surface
+ * after the edge has moved on and spend the mapper's event budget on one pixel.  The refractory test cannot remove them: it ignores
+ * polarity and so swallows the opposite-polarity event of an object's other edge as well.  The stage is a SECOND STAGE of a camera's
+ * filter, after the mask test and before the refractory test, with its own configuration, state and totals.  Off unless configured;
+ * a handle that never configures it takes the paths above unchanged.  State per camera and RAW pixel:
+ *   bstamp[y][x]  uint64: the ns stamp of the newest event the stage judged at that pixel (0: none)
+ *   bflags[y][x]  uint8:  bit 0 that event's polarity, normalised to 0 / 1 as the ring holds it; bit 1 `linked`: that event continued a
+ *                         burst; the other bits 0
+ * The filter's rule with the stage in it (p: the event's polarity 0 / 1; the lines marked + are the stage):
+ *   verdict(e):
+ *     if e.x >= W or e.y >= H:            ESVO_FILTER_OUTSIDE      (1)  touches nothing
+ *     if mask[e.y][e.x] != 0:             ESVO_FILTER_MASKED       (2)  touches nothing (no burst state either)
+ *   + if mode != ESVO_BURST_OFF:
+ *   +   T = bstamp[px]; P = bflags[px] & 1; K = bflags[px] >> 1 & 1
+ *   +   linked = T != 0 and p == P and t - T <= burst_ns      -- integer difference: a planted T ahead of the stream gives a negative one
+ *   +   pass   = ESVO_BURST_TRAIL:          not linked         -- the first event of every burst
+ *   +            ESVO_BURST_STC_CUT_TRAIL:  linked and not K   -- the second event of every burst, and only that one
+ *   +            ESVO_BURST_STC_KEEP_TRAIL: linked             -- every event of a burst but its first
+ *   +   bstamp[px] = t; bflags[px] = p | linked << 1           -- ALWAYS, whatever the verdict
+ *   +   if not pass:                      ESVO_FILTER_BURST        (5)  touches nothing else
+ *     L = last[px] ... refractory test, support test, last[px] = t: as above
+ *   So a burst-dropped event neither updates `last`, nor supports a neighbour, nor restarts the refractory period; equal stamps at one
+ *   pixel link (difference 0); a polarity change always ends a burst; an isolated event passes TRAIL and is dropped by both STC modes;
+ *   stamp 0 means "none", as for `last`.  PINNED TO NOTHING THIRD-PARTY, as the filter's rule: the three modes follow the published
+ *   description of Metavision's trail / STC algorithms as recalled; `<=`, the state updating on every judged event and the stage's
+ *   place between mask and refractory test are this library's choices.
+ * The camera's filter must be configured (ESVO_ERR_STATE otherwise; a filter with both periods 0 and no mask passes everything: the
+ * way to run the stage alone).  esvo_ts_filter_configure(h, cam, NULL) while the stage is on: ESVO_ERR_STATE; a non-NULL
+ * reconfiguration keeps the stage, its state and its totals.  Row-routed band handles cannot have a filter, so they cannot have the
+ * stage.  Transactional as the filter is: bstamp, bflags and the totals advance only behind a push that returned ESVO_OK; ring room is
+ * still judged on the unfiltered count.  Burst-dropped events appear in NONE of esvo_event_filter_counts_t's fields (its events_in
+ * stays the sum of its other five): packet size = the filter's events_in delta + the stage's `dropped` delta.  *n_events, the EVT decoder
+ * totals, the survey (it counts the raw packet) and stats.events_staged (the kept events) keep their meaning.  A packet of which the
+ * stage drops everything returns ESVO_OK, stages nothing and advances the state.
+ * On the device the stage is one kernel between the filter's binning and its walk: one wave per 8x8 tile takes the tile's own-pixel
+ * entries (the rule needs no halo), sorts them by (pixel, packet index) in LDS and judges them all at once -- an event's verdict
+ * depends on the previous two raw events of its own pixel and on nothing else, which after the sort are its two left neighbours or
+ * the planted state.  The walk then skips every entry the stage dropped, own pixels and halo alike.  A tile whose list overflows
+ * reads the packet, collects its own events in LDS and judges them in batches by the same code, the state carried in LDS. */
+enum { ESVO_BURST_OFF = 0, ESVO_BURST_TRAIL = 1, ESVO_BURST_STC_CUT_TRAIL = 2, ESVO_BURST_STC_KEEP_TRAIL = 3 };
+enum { ESVO_FILTER_BURST = 5 };
+typedef struct esvo_event_burst_t {
+  uint64_t burst_ns;      /* > 0 with a mode other than ESVO_BURST_OFF */
+  uint32_t mode;          /* ESVO_BURST_* */
+  uint32_t reserved[3];   /* 0 */
+} esvo_event_burst_t;
+typedef struct esvo_event_burst_counts_t { uint64_t judged, passed, dropped; } esvo_event_burst_counts_t;  /* judged = passed + dropped */
+/* b == NULL or mode ESVO_BURST_OFF switches the stage off and frees its memory; a mode zeroes bstamp / bflags and keeps the totals.
+ * ESVO_ERR_STATE: the camera has no filter.  ESVO_ERR_INVALID_ARG: an unknown mode, burst_ns == 0 with a mode other than OFF, a
+ * non-zero reserved word.  Ingest group: not while another thread pushes to the same camera. */
+int esvo_ts_burst_configure(esvo_handle h, int cam, const esvo_event_burst_t* b);
+/* totals of the camera's successful push calls since esvo_create / esvo_reset (esvo_reset zeroes state and totals and keeps the configuration) */
+int esvo_ts_burst_stats(esvo_handle h, int cam, esvo_event_burst_counts_t* totals);
+/* get_stamp / get_flags (nullable, [H * W]) receive the state, then set_stamp / set_flags ([H * W], both or neither) replace it.
+ * ESVO_ERR_STATE while the stage is off; ESVO_ERR_INVALID_ARG: only one of the two set arrays, or a flag byte above 3. */
+int esvo_ts_burst_state(esvo_handle h, int cam, uint64_t* get_stamp, uint8_t* get_flags, const uint64_t* set_stamp, const uint8_t* set_flags);
+/* The whole two-stage rule on the host: esvo_event_filter_host with the stage in it.  bstamp, bflags: [height * width], in / out
+ * like `last` (all three advance only on ESVO_OK; required unless the stage is off); verdict receives ESVO_FILTER_* including
+ * ESVO_FILTER_BURST; *add_burst and *add_filter (nullable) are INCREMENTED.  With b == NULL or mode ESVO_BURST_OFF it is
+ * esvo_event_filter_host, bit for bit. */
+int esvo_event_burst_filter_host(const esvo_event_burst_t* b, const esvo_event_filter_t* f, int width, int height,
+                                 uint64_t* bstamp, uint8_t* bflags, uint64_t* last, const esvo_event_t* ev, size_t n,
+                                 uint8_t* verdict, esvo_event_t* out, size_t cap, size_t* n_out,
+                                 esvo_event_burst_counts_t* add_burst, esvo_event_filter_counts_t* add_filter);
+/* sizeof(esvo_event_burst_t), sizeof(esvo_event_burst_counts_t), 0, 0 */
+void esvo_event_burst_sizes(size_t out[4]);
 /* Event survey on the device: per-pixel event counts kept while a stream is pushed, and a hot-pixel mask learnt from them -- the
  * filter's mask without a host loop over events the host may never see (device columns, device-resident words).  Off unless begun;
  * a handle that never opens a survey takes the paths above unchanged.  Each camera has its own survey: counts[2][H][W] uint32, plane
@@ -612,8 +679,7 @@ int esvo_hot_pixel_mask_host(const esvo_hot_pixel_rule_t* rule, int width, int h
                              uint8_t* mask, esvo_hot_pixel_report_t* report);
 /* sizeof(esvo_event_survey_t), sizeof(esvo_event_survey_stats_t), sizeof(esvo_hot_pixel_rule_t), sizeof(esvo_hot_pixel_report_t) */
 void esvo_event_survey_sizes(size_t out[4]);
-/* Still out of scope: Prophesee's STC / trail filters, polarity-aware support, event-rate control, reading decoded events back to
- * the caller. */
+/* Still out of scope: polarity-aware support, event-rate control, reading decoded events back to the caller. */
 /* rosbag (format 2.0) ingest, SURVEY.md §8(f).2: the reading side of events_repacking_helper
  * (events_repacking_helper/src/EventMessageEditor.cpp:66-119: rosbag::Bag::open, rosbag::View over an event topic,
  * MessageInstance::instantiate<dvs_msgs::EventArray>).  Chunks (compression none / bz2 / lz4) are walked in file order;

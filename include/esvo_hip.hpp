@@ -143,6 +143,24 @@ class TimeSurface {
   void eventFilterState(uint64_t* get_last, const uint64_t* set_last = nullptr) {
     ctx_->check(esvo_ts_filter_state(ctx_->handle(), cam_, get_last, set_last), "esvo_ts_filter_state");
   }
+  // the burst stage of the camera's filter (esvo_ts_burst_configure): mode ESVO_BURST_TRAIL keeps the first event of every same-polarity
+  // burst of a pixel, ESVO_BURST_STC_CUT_TRAIL the second, ESVO_BURST_STC_KEEP_TRAIL all but the first; burst_ns: the largest gap inside
+  // a burst.  The filter must be set (setEventFilter(0, 0) passes everything: the stage alone)
+  void setBurstFilter(uint32_t mode, uint64_t burst_ns) {
+    esvo_event_burst_t b{};
+    b.mode = mode; b.burst_ns = burst_ns;
+    ctx_->check(esvo_ts_burst_configure(ctx_->handle(), cam_, &b), "esvo_ts_burst_configure");
+  }
+  void clearBurstFilter() { ctx_->check(esvo_ts_burst_configure(ctx_->handle(), cam_, nullptr), "esvo_ts_burst_configure"); }
+  esvo_event_burst_counts_t burstFilterStats() {
+    esvo_event_burst_counts_t c{};
+    ctx_->check(esvo_ts_burst_stats(ctx_->handle(), cam_, &c), "esvo_ts_burst_stats");
+    return c;
+  }
+  // get_* / set_*: [H * W] ns stamps and flag bytes (bit 0 polarity, bit 1 linked); the get pair may be null, the set pair goes together
+  void burstFilterState(uint64_t* get_stamp, uint8_t* get_flags, const uint64_t* set_stamp = nullptr, const uint8_t* set_flags = nullptr) {
+    ctx_->check(esvo_ts_burst_state(ctx_->handle(), cam_, get_stamp, get_flags, set_stamp, set_flags), "esvo_ts_burst_state");
+  }
   // the camera's event survey (esvo_ts_survey_begin): per-pixel counts of every packet the calls above accept, kept on the device; the
   // filter must be set (setEventFilter(0, 0) passes everything).  count_only: packets are decoded and counted, nothing is staged
   void beginSurvey(bool count_only = false) {
